@@ -21,6 +21,12 @@ float-atomic mode is reported beside it (`fast_mode`) with its measured distance
 parent that never touches the GPU) and relays rank 0's line; the driver's own `python -m torch.distributed.run ... bench.py
 --gpus N` form is taken as it comes.
 
+A plain run sets up, warms up, times --steps impulse responses and prints the headline line (ms_per_step = wall clock of one
+timed step).  --full adds everything else the line used to carry, each in passes of its own: one-IR latencies, per-kernel
+durations and rooflines, the check of the timed histograms against an IR generated alone, the other binning mode, the other
+driver, the attenuate probe, the API-flow leg and the CPU baseline.  --dump-outputs DIR writes what the timed path returned
+for its last step (see dump_outputs).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -56,9 +62,11 @@ def parse():
     p.add_argument("--triangles", type=int, default=75000)
     p.add_argument("--sample-rate", type=float, default=44100.0)
     p.add_argument("--mode", choices=["fast", "exact"], default="exact")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-extras", action="store_true", help="only the timed region and the per-kernel pass (profiling runs): no fast-mode leg, "
-                   "no fast-vs-exact comparison, no API-flow leg, no attenuate probe")
+    p.add_argument("--full", action="store_true", help="also measure and check everything beside the headline figure (see the module docstring)")
+    p.add_argument("--dump-outputs", metavar="DIR", help="write the timed path's last histogram and its scalars to DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    p.add_argument("--no-extras", action="store_true", help="with --full: only the timed region and the per-kernel pass (profiling runs): no "
+                   "fast-mode leg, no fast-vs-exact comparison, no API-flow leg, no attenuate probe")
     p.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsals)")
     p.add_argument("--share-gpu", action="store_true", help="rehearsal: every rank uses cuda:0 (needs --backend gloo)")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the baseline sample")
@@ -127,6 +135,25 @@ def fast_vs_exact(fast, exact):
     return {"max_abs_err_over_band_max": float((err / band_max).max()), "claimed_tolerance": 1e-5,
             "fraction_band_bins_outside_1e-5_relative": float(outside.double().mean()),
             "band_bins": int(err.numel()), "band_bins_differing": int((err > 0).sum())}
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(directory, hist, predelay, images):
+    """What the timed path handed its caller for its last step: the histogram [channels][8][nbins] (float32, as returned) as
+    histogram.npy, its predelay in seconds and its image-source count (float64).  A histogram over DUMP_LIMIT_BYTES is written as
+    histogram_sample.npy instead: the band-bins at the sorted flat indices np.unique(default_rng(0).integers(0, size, n))."""
+    os.makedirs(directory, exist_ok=True)
+    hist = np.ascontiguousarray(hist, dtype=np.float32)
+    arrays = {"predelay_s": np.array([predelay], np.float64), "image_sources": np.array([images], np.float64)}
+    if hist.nbytes <= DUMP_LIMIT_BYTES:
+        arrays["histogram"] = hist
+    else:
+        index = np.unique(np.random.default_rng(0).integers(0, hist.size, DUMP_LIMIT_BYTES // 8))
+        arrays["histogram_sample"] = hist.reshape(-1)[index]
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def launch_ranks(args):
@@ -296,41 +323,43 @@ def main():
             elapsed = float(t[0])
         return elapsed
 
-    # untimed: every context allocates its buffers, then a few IRs strictly alone for the per-kernel "solo" durations and the
-    # latency of one IR — to the histogram in HBM (ir_gen_wall_ms) and on to pinned host memory (ir_gen_to_host_ms)
+    # untimed: every context allocates its buffers (set-up: the timed region must not pay for first touches)
     for c in contexts:
         keep(*distributed.generate_ir(c, *trace_args, **ir_kwargs(None)), c)      # (the histogram stays alive until its export has landed)
     fence()
-    for c in contexts:
-        c.set_concurrent_traces(1)                  # alone on the GPU: what a caller with one IR gets (the pipeline announced its group)
-    solo_irs = 4
-    t0 = time.perf_counter()
-    for _ in range(solo_irs):
-        keep(*distributed.generate_ir(ctx, *trace_args, **ir_kwargs(solo_ms)), ctx)
-        ctx.synchronize()
-        ctx.synchronize_exports()
-    solo_latency_ms = (time.perf_counter() - t0) * 1e3 / solo_irs
-    in_hbm = dict(ir_kwargs(None), host_out=None)
-    for _ in range(solo_irs):
-        distributed.generate_ir(ctx, *trace_args, **in_hbm)
-    fence()
-    t0 = time.perf_counter()
-    for _ in range(solo_irs):
-        distributed.generate_ir(ctx, *trace_args, **in_hbm)
-        ctx.synchronize()
-    hbm_latency_ms = (time.perf_counter() - t0) * 1e3 / solo_irs
-    to_host_latency_ms, solo_latency_ms = solo_latency_ms, hbm_latency_ms      # (the first solo pass above ran with the host copy)
-    for c in contexts:
-        c.set_concurrent_traces(pipeline.group_size(len(contexts)))
-    if pipeline.group_size(len(contexts)) > 1:
-        # the path kernel the pipeline's contexts use (two lanes per ray when two traces are in flight), also alone on the GPU
-        pair_solo = {}
-        for _ in range(2):
-            keep(*distributed.generate_ir(ctx, *trace_args, **ir_kwargs(pair_solo)), ctx)
+    if args.full:
+        # a few IRs strictly alone for the per-kernel "solo" durations and the latency of one IR — to the histogram in HBM
+        # (ir_gen_wall_ms) and on to pinned host memory (ir_gen_to_host_ms)
+        for c in contexts:
+            c.set_concurrent_traces(1)                  # alone on the GPU: what a caller with one IR gets (the pipeline announced its group)
+        solo_irs = 4
+        t0 = time.perf_counter()
+        for _ in range(solo_irs):
+            keep(*distributed.generate_ir(ctx, *trace_args, **ir_kwargs(solo_ms)), ctx)
             ctx.synchronize()
-        for k, v in pair_solo.items():
-            if k not in solo_ms:
-                solo_ms[k] = v
+            ctx.synchronize_exports()
+        solo_latency_ms = (time.perf_counter() - t0) * 1e3 / solo_irs
+        in_hbm = dict(ir_kwargs(None), host_out=None)
+        for _ in range(solo_irs):
+            distributed.generate_ir(ctx, *trace_args, **in_hbm)
+        fence()
+        t0 = time.perf_counter()
+        for _ in range(solo_irs):
+            distributed.generate_ir(ctx, *trace_args, **in_hbm)
+            ctx.synchronize()
+        hbm_latency_ms = (time.perf_counter() - t0) * 1e3 / solo_irs
+        to_host_latency_ms, solo_latency_ms = solo_latency_ms, hbm_latency_ms      # (the first solo pass above ran with the host copy)
+        for c in contexts:
+            c.set_concurrent_traces(pipeline.group_size(len(contexts)))
+        if pipeline.group_size(len(contexts)) > 1:
+            # the path kernel the pipeline's contexts use (two lanes per ray when two traces are in flight), also alone on the GPU
+            pair_solo = {}
+            for _ in range(2):
+                keep(*distributed.generate_ir(ctx, *trace_args, **ir_kwargs(pair_solo)), ctx)
+                ctx.synchronize()
+            for k, v in pair_solo.items():
+                if k not in solo_ms:
+                    solo_ms[k] = v
 
     def timed_native(steps, warmup, native_mode):
         """The same region through rvb_pipeline_* (csrc/pipeline.hip): jobs submitted a few ahead of the results taken, every histogram
@@ -368,10 +397,11 @@ def main():
         elapsed, native_hist, native_info = timed_native(args.steps, args.warmup, mode)
         state.update(host=native_hist, hist=native_hist, nbins=native_info["nbins"], images=native_info["images"], predelay=native_info["predelay"])
         host_ring[:] = []                                   # (the ring check below is the Python pipeline's)
-        # per-kernel elapsed times of the timed region are the Python pipeline's hook: one short pass for the report
-        pipeline.run(4, trace_args, ir_kwargs(kernel_ms), keep)
-        state.update(host=native_hist, hist=native_hist, nbins=native_info["nbins"], images=native_info["images"], predelay=native_info["predelay"])
-        host_ring[:] = []
+        if args.full:
+            # per-kernel elapsed times of the timed region are the Python pipeline's hook: one short pass for the report
+            pipeline.run(4, trace_args, ir_kwargs(kernel_ms), keep)
+            state.update(host=native_hist, hist=native_hist, nbins=native_info["nbins"], images=native_info["images"], predelay=native_info["predelay"])
+            host_ring[:] = []
     else:
         pipeline.run(args.warmup, trace_args, ir_kwargs(None), keep)
         elapsed = timed(args.steps, ir_kwargs(kernel_ms))
@@ -379,10 +409,47 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     bounces_per_step = world * rays_per_gpu * nrefl
     value = bounces_per_step / (elapsed / args.steps)
-    executed = ctx.executed_bounces()
 
     if rank == 0:
         print("bench.py: timed region %.3f ms per step" % ms_per_step, file=sys.stderr)
+    if rank == 0 and args.dump_outputs:          # what the caller of the timed path received for its last step
+        dump_outputs(args.dump_outputs, (state["host"] if to_host else state["hist"].cpu()).numpy(), state["predelay"], state["images"])
+
+    def headline():
+        return {
+            "metric": "ray_bounces_per_sec", "value": value, "unit": "ray-bounces/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "cathedral stand-in (Sibenik unavailable offline), %d triangles, %d rays/GPU x %d bounces x 8 bands, "
+                                   "2 cardioid speakers, %.0f Hz, trim_predelay, output_mode all, histogram mode %s%s"
+                                   % (scene[0].shape[0], rays_per_gpu, nrefl, sr, args.mode,
+                                      "" if world == 1 else " (BASELINE configs[2]'s shape: %d rays over %d GPUs)" % (rays_per_gpu * world, world)),
+                       "triangles": int(scene[0].shape[0]), "rays_per_gpu": rays_per_gpu, "reflections": nrefl,
+                       "histogram_mode": args.mode + ((": the reference's serial float sum over all impulses, bit for bit" if world == 1 or args.exact_chain else
+                                                       ": every rank's histogram is the serial float sum over ITS impulses; the ranks' histograms are then "
+                                                       "added by one all-reduce, so the result is within 1e-5 of each band's maximum of the single-GPU "
+                                                       "serial sum, not bit-equal to it (the bit-equal chain over devices is rvb_multi_*, csrc/multi.hip)")
+                                                      if args.mode == "exact" else ": float atomics, order-dependent in the last bits"),
+                       "histogram_seconds": state["nbins"] / sr,
+                       "sharding": "ray-range shards, replicated scene, one all-reduce(sum) of [2][8][nbins] histograms",
+                       "pipelining": "%d contexts per GPU take turns: traces are enqueued %d at a time, the next group before the current one is finished; "
+                                     "the timed impulse responses are IDENTICAL jobs (same microphone, source and rays every step; jobs that differ — "
+                                     "the 64 pairs of config C5 — run in tests/test_gpu_decomposition.py and tests/cpp/test_pipeline.cpp)"
+                                     % (len(contexts), max(1, len(contexts) // 2))},
+            "result_on_host_in_timed_region": to_host, "contexts_per_gpu": len(contexts),
+            "driver": ("rvb_pipeline_* (csrc/pipeline.hip, the C-ABI's own pipeline, through ctypes)" if args.native and world == 1 and not grouped
+                       else "distributed.IrPipeline (Python over the C-ABI; the N > 1 form with torch.distributed collectives)"),
+        }
+
+    if not args.full:
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(real_stdout, (json.dumps(headline()) + "\n").encode())
+        if grouped:
+            dist.destroy_process_group()
+        return
+
+    executed = ctx.executed_bounces()
     # What the timed region produced must be what one IR generated strictly alone produces: the last histogram of the pipelined,
     # fused (two traces per path-kernel launch) region — as it landed on the host — against a solo IR of the same arguments.
     # Exact mode on one rank: bit for bit (the serial-order sum has one value).  Several ranks add their serial sums with an
@@ -564,43 +631,23 @@ def main():
             stream["attenuate_kernel"] = {"bound": "hbm", "achieved": a, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": a / HBM_PEAK_GBS,
                                           "avg_launch_ms": attenuate_probe["ms"], "traffic": None,
                                           "note": "materialised attenuate of the workload's %d traced impulses, HBM to HBM, 64 B read + 64 B written each" % attenuate_probe["impulses"]}
-        out = {
-            "metric": "ray_bounces_per_sec", "value": value, "unit": "ray-bounces/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "cathedral stand-in (Sibenik unavailable offline), %d triangles, %d rays/GPU x %d bounces x 8 bands, "
-                                   "2 cardioid speakers, %.0f Hz, trim_predelay, output_mode all, histogram mode %s%s"
-                                   % (scene[0].shape[0], rays_per_gpu, nrefl, sr, args.mode,
-                                      "" if world == 1 else " (BASELINE configs[2]'s shape: %d rays over %d GPUs)" % (rays_per_gpu * world, world)),
-                       "triangles": int(scene[0].shape[0]), "rays_per_gpu": rays_per_gpu, "reflections": nrefl,
-                       "histogram_mode": args.mode + ((": the reference's serial float sum over all impulses, bit for bit" if world == 1 or args.exact_chain else
-                                                       ": every rank's histogram is the serial float sum over ITS impulses; the ranks' histograms are then "
-                                                       "added by one all-reduce, so the result is within 1e-5 of each band's maximum of the single-GPU "
-                                                       "serial sum, not bit-equal to it (the bit-equal chain over devices is rvb_multi_*, csrc/multi.hip)")
-                                                      if args.mode == "exact" else ": float atomics, order-dependent in the last bits"),
-                       "histogram_seconds": state["nbins"] / sr,
-                       "sharding": "ray-range shards, replicated scene, one all-reduce(sum) of [2][8][nbins] histograms",
-                       "pipelining": "%d contexts per GPU take turns: traces are enqueued %d at a time, the next group before the current one is finished; "
-                                     "the timed impulse responses are IDENTICAL jobs (same microphone, source and rays every step; jobs that differ — "
-                                     "the 64 pairs of config C5 — run in tests/test_gpu_decomposition.py and tests/cpp/test_pipeline.cpp)"
-                                     % (len(contexts), max(1, len(contexts) // 2))},
+        out = headline()
+        out.update({
             "lanes_per_ray": {"path_kernel_in_timed_region": 2 if "path_pair_kernel" in avg else 4,
                               "path_kernel_one_ir_alone": 4 if "path_kernel" in solo else 2, "shadow_kernel": 2 if "shadow_pair_kernel" in solo else 4,
                               "rule": "rvb_path_lanes_for (csrc/trace_kernels.hip): two lanes per ray when rays per launch x traces in flight >= 196 608"},
             # one IR strictly alone, wall clock incl. the Python host path: until [channels][8][nbins] is on the host /
             # with the histogram left in HBM
             "ir_gen_wall_ms": to_host_latency_ms, "ir_gen_to_host_ms": to_host_latency_ms, "ir_gen_wall_ms_histogram_in_hbm": solo_latency_ms,
-            "result_on_host_in_timed_region": to_host, "timed_region_check": timed_check, "contexts_per_gpu": len(contexts),
+            "timed_region_check": timed_check,
             "fast_mode" if args.mode == "exact" else "exact_mode": other_mode, "fast_vs_exact": comparison, "api_flow": api_flow,
-            "driver": ("rvb_pipeline_* (csrc/pipeline.hip, the C-ABI's own pipeline, through ctypes)" if args.native and world == 1 and not grouped
-                       else "distributed.IrPipeline (Python over the C-ABI; the N > 1 form with torch.distributed collectives)"),
             "native_pipeline": native_leg, "python_pipeline": python_leg,
             "trace_only_ray_bounces_per_sec": (nrays * nrefl) / (trace_ms * 1e-3) if trace_ms else None,
             "executed_bounces_rank0": int(executed), "nominal_bounces_rank0": nrays * nrefl,
             "kernel_elapsed_ms_timed_region": avg, "kernel_ms": solo, "nbins": state["nbins"], "image_sources": state["images"], "predelay_s": state["predelay"],
             "scene_build_upload_ms": scene_ms, "bvh": ctx.scene_info(),
             "roofline": roofline, "roofline_stream": stream, "roofline_valu": valu,
-        }
+        })
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(scene, mic, src, nrefl, args.cpu_seconds)
         else:

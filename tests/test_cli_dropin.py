@@ -1,7 +1,8 @@
 """the post-processing chain and the drop-in CLI surface.
 
 * the reference's own cmd/main.cpp must compile and link UNCHANGED against include/rayverb +
-  include/shims + librayverb.so (build container only: the reference does not travel);
+  include/shims + librayverb.so (build() does that into oracle/_ref/ where the reference checkout is
+  present, oracle/ref/build_ref.sh; its demo inputs are fixtures under tests/golden/assets);
 * process() / RayverbFiltering against an independent numpy/scipy restatement of reference
   rayverb/filters.cpp + rayverb.cpp:79-149 (the reference has no tests or fixtures for these:
   parity unpinned, SURVEY §8(c) gap 3 — the restatement below is the stated algorithm);
@@ -18,7 +19,10 @@ from conftest import ROOT
 
 PKG = os.path.join(ROOT, "parallel-reverb-raytracer_amd")
 BUILD = os.path.join(ROOT, "tests", "cpp", "_build")
-REFERENCE_CLI = "/root/reference/cmd/main.cpp"
+ASSETS = os.path.join(ROOT, "tests", "golden", "assets")
+REFERENCE_CLI = os.path.join(ROOT, "oracle", "_ref", "parallel_raytrace")
+REFERENCE_CLI_DIAG = os.path.join(ROOT, "oracle", "_ref", "parallel_raytrace_diag")
+NOT_BUILT = "oracle/_ref/parallel_raytrace not built (build() compiles it where the reference checkout is present)"
 INC = ["-I" + os.path.join(ROOT, "include", "rayverb"), "-I" + os.path.join(ROOT, "include", "shims"), "-I" + os.path.join(ROOT, "include")]
 LINK = ["-L" + PKG, "-lrayverb", "-lrvb_hip", "-Wl,-rpath," + PKG]
 
@@ -30,26 +34,24 @@ def _compile(src, out, std="-std=c++11", extra=()):
     return out
 
 
-@pytest.mark.skipif(not os.path.exists(REFERENCE_CLI), reason="reference checkout not present (GPU box)")
+@pytest.mark.skipif(not os.path.exists(REFERENCE_CLI), reason=NOT_BUILT)
 def test_reference_cli_compiles_unchanged_and_fails_like_the_reference_without_gpu(tmp_path):
     import torch
-    exe = _compile(REFERENCE_CLI, str(tmp_path / "parallel_raytrace"), std="-std=c++1y")   # never kept in the repo
-    assets = "/root/reference/demo/assets"
-    args = [exe, assets + "/configs/near_c.json", assets + "/test_models/echo_tunnel.obj", assets + "/materials/mat.json", str(tmp_path / "o.aif")]
+    args = [REFERENCE_CLI, os.path.join(ASSETS, "near_c.json"), os.path.join(ASSETS, "echo_tunnel.obj"), os.path.join(ASSETS, "mat.json"),
+            str(tmp_path / "o.aif")]
     if not torch.cuda.is_available():
         r = subprocess.run(args, capture_output=True, text=True)
         assert r.returncode == 1 and "encountered opencl error" in r.stderr and "no CPU path" in r.stderr
     # a demo config the reference itself rejects ("hipass": false is not a number, config.h:143-146)
-    args[1] = assets + "/configs/tunnel.json"
+    args[1] = os.path.join(ASSETS, "tunnel.json")
     r = subprocess.run(args, capture_output=True, text=True)
     assert r.returncode == 1 and "invalid value" in r.stderr
 
 
-@pytest.mark.skipif(not os.path.exists(REFERENCE_CLI), reason="reference checkout not present (GPU box)")
+@pytest.mark.skipif(not os.path.exists(REFERENCE_CLI), reason=NOT_BUILT)
 def test_reference_cli_diagnostic_build_links(tmp_path):
     """-DDIAGNOSTIC makes cmd/main.cpp:270-278 call print_diagnostic (the impulse.dump writer, helpers.cpp:19-59)."""
-    exe = _compile(REFERENCE_CLI, str(tmp_path / "parallel_raytrace_diag"), std="-std=c++1y", extra=["-DDIAGNOSTIC"])
-    assert os.path.exists(exe)
+    assert os.path.exists(REFERENCE_CLI_DIAG)
 
 
 # ---- independent restatement of the post-processing chain ---------------------------------------------

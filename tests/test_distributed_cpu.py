@@ -11,6 +11,20 @@ import pytest
 from conftest import ROOT
 
 
+@pytest.fixture(autouse=True)
+def _rendezvous_environment_is_restored():
+    """The single-process legs below run the workers in the test process, and the workers set the rendezvous variables: keep
+    them from reaching later tests (a `bench.py --gpus N` started with WORLD_SIZE set would not start its own ranks)."""
+    keys = ("MASTER_ADDR", "MASTER_PORT", "RANK", "WORLD_SIZE")
+    saved = {k: os.environ.get(k) for k in keys}
+    yield
+    for k, v in saved.items():
+        if v is None:
+            os.environ.pop(k, None)
+        else:
+            os.environ[k] = v
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))

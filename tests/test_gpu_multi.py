@@ -207,7 +207,7 @@ def test_two_processes_chained_exact_mode_equals_one_context(tmp_path):
     from conftest import ROOT
     from parallel_reverb_raytracer_amd import capi, distributed
     args = ["--gpus", "2", "--backend", "gloo", "--share-gpu", "--rays", "3000", "--reflections", "24", "--triangles", "6000",
-            "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-extras"]
+            "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras"]
     env = dict(os.environ, RVB_BENCH_CRC="1")
     found = {}
     for label, extra in (("chain", ["--exact-chain"]), ("allreduce", [])):
