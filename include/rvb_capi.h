@@ -343,6 +343,40 @@ int rvb_pipeline_submit_oriented(rvb_pipeline * p, const float mic[3], const flo
 uint64_t rvb_pipeline_pending(const rvb_pipeline * p);
 int rvb_pipeline_next(rvb_pipeline * p, rvb_pipeline_result * out);
 
+/* The same pipeline over LANES — several GPUs of a node, or several schedules on one — and several pairs per path-kernel launch: what a
+ * caller with many (source, listener) pairs of one hall does (BASELINE config C5: 64 pairs on 8 GPUs).  A lane is a run of consecutive
+ * contexts of `ctxs`, lane_sizes[l] of them (they add up to `count`); the contexts of one lane share one device, different lanes may sit
+ * on different devices or on the same one, a context appears once.  Every lane runs the schedule above (groups, early traces, staged
+ * binning, its own zero-fill stream and ring) from a host thread of its own: that thread makes every HIP and rvb_* call on the lane's
+ * contexts, from set-up in rvb_pipeline_create_lanes to tear-down in rvb_pipeline_destroy, so the caller does not touch them either
+ * while the pipeline exists.
+ *   options->pairs_per_launch  P = 1: one trace per job, as above.  P = 2 .. RVB_PIPELINE_MAX_PAIRS: a UNIT of P consecutive jobs is
+ *                              traced by ONE rvb_trace_pairs launch on one context, then staged pair by pair (rvb_ir_select_pair, the
+ *                              pair's own image-source candidates, its own facing), each pair into a device histogram of its own
+ *   options->group             contexts per path-kernel launch inside a lane, as `group` above (0 = default); with P > 1 a unit is a
+ *                              launch of its own and a group above 1 is refused
+ *   options == NULL            group 0, P = 1
+ * WHERE A JOB RUNS (deterministic): job i belongs to unit u = i / P; unit u goes to lane u % nlanes; inside the lane, the lane's k-th unit
+ * (k = u / nlanes) runs on its context k % lane_sizes[l].  An incomplete last unit is traced with the pairs it has when
+ * rvb_pipeline_next waits for one of its jobs.
+ *   rvb_pipeline_configure_*, _submit, _submit_oriented, _pending, _next, _destroy work as above, with
+ *   - the pending limit 2 x count x P (RVB_ERR_CAPACITY above it; submit never blocks);
+ *   - results in submission order; `histogram` stays valid until count x P further results have been taken (or the pipeline is
+ *     destroyed); the rings hold pending limit + that window buffers in all, allocated as they are first used;
+ *   - a failing stage (e.g. RVB_ERR_STATE from rvb_trace on a context without a scene) fails its LANE: rvb_pipeline_next returns the
+ *     code for that job and for every later job of the lane (each counts as taken), rvb_pipeline_last_error names the lane and the call
+ *     ("lane 1: rvb_pipeline: trace: ..."); results of other lanes, and of earlier jobs, are unaffected.  A failed lane stays failed;
+ *   - rvb_pipeline_destroy joins the lane threads, also after a failure.
+ * Results are bit for bit those of rvb_trace + rvb_merge_images + rvb_ir_configure_* + rvb_ir_download on one context in RVB_IR_EXACT
+ * (tests/cpp/test_pipeline_lanes.cpp), whatever the lanes and P.  Not thread-safe: one caller thread per pipeline. */
+#define RVB_PIPELINE_MAX_PAIRS 8
+typedef struct {
+    uint64_t group;              /* contexts per path-kernel launch inside a lane (0 = default; must be 0 or 1 with pairs_per_launch > 1) */
+    uint64_t pairs_per_launch;   /* 1 .. RVB_PIPELINE_MAX_PAIRS */
+} rvb_pipeline_options;
+int rvb_pipeline_create_lanes(rvb_pipeline ** out, rvb_ctx ** ctxs, uint64_t count, const uint64_t * lane_sizes, uint64_t nlanes,
+                              const rvb_pipeline_options * options);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------
  * Durations in milliseconds of the kernels of the last rvb_trace / rvb_ir_accumulate, taken with
  * HIP events on the context's stream; names is a ';'-separated list matching ms[]. */

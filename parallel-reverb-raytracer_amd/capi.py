@@ -37,7 +37,10 @@ SYMBOLS = [
     "rvb_multi_ir_speakers", "rvb_multi_ir_hrtf",
     "rvb_device_index", "rvb_pipeline_create", "rvb_pipeline_destroy", "rvb_pipeline_last_error", "rvb_pipeline_configure_speakers",
     "rvb_pipeline_configure_hrtf", "rvb_pipeline_submit", "rvb_pipeline_submit_oriented", "rvb_pipeline_pending", "rvb_pipeline_next",
+    "rvb_pipeline_create_lanes",
 ]
+
+PIPELINE_MAX_PAIRS = 8      # RVB_PIPELINE_MAX_PAIRS
 
 _vp = ctypes.c_void_p
 _u64 = ctypes.c_uint64
@@ -526,20 +529,43 @@ class PipelineResult(ctypes.Structure):
                 ("predelay", ctypes.c_float), ("max_time", ctypes.c_float), ("nimages", ctypes.c_uint64)]
 
 
+class PipelineOptions(ctypes.Structure):
+    """rvb_pipeline_options of include/rvb_capi.h."""
+    _fields_ = [("group", ctypes.c_uint64), ("pairs_per_launch", ctypes.c_uint64)]
+
+
 class Pipeline:
     """Impulse responses back to back behind the C-ABI (rvb_pipeline_*, csrc/pipeline.hip): the native form of
     distributed.IrPipeline — groups of traces in one path-kernel launch, the next groups' traces enqueued ahead, the binning stages of a
     group enqueued together, histograms exported to a ring of pinned buffers.  `contexts`: capi.Context objects of one GPU with the
-    same scene and rays set."""
+    same scene and rays set.
 
-    def __init__(self, contexts, group=0):
+    lanes = [[Context, ...], ...] (rvb_pipeline_create_lanes): that schedule per lane, each lane on one device and driven by a host thread
+    of its own; unit u of `pairs_per_launch` consecutive jobs goes to lane u % len(lanes) and is traced by ONE rvb_trace_pairs launch.
+    `contexts` is then ignored.  lanes=None with pairs_per_launch=1 is rvb_pipeline_create."""
+
+    def __init__(self, contexts, group=0, lanes=None, pairs_per_launch=1):
         self.lib = load_library()
-        self.contexts = list(contexts)
         self.handle = _vp()
+        if lanes is None and int(pairs_per_launch) == 1:
+            self.contexts = list(contexts)
+            handles = (_vp * len(self.contexts))(*[c.handle for c in self.contexts])
+            rc = self.lib.rvb_pipeline_create(ctypes.byref(self.handle), handles, _u64(len(self.contexts)), _u64(int(group)))
+            if rc:
+                raise RvbError(rc, "rvb_pipeline_create failed")
+            self.limit, self.valid_for = 4 * len(self.contexts), len(self.contexts)
+            return
+        lanes = [list(contexts)] if lanes is None else [list(l) for l in lanes]
+        self.contexts = [c for l in lanes for c in l]
         handles = (_vp * len(self.contexts))(*[c.handle for c in self.contexts])
-        rc = self.lib.rvb_pipeline_create(ctypes.byref(self.handle), handles, _u64(len(self.contexts)), _u64(int(group)))
+        sizes = (_u64 * len(lanes))(*[len(l) for l in lanes])
+        opts = PipelineOptions(int(group), int(pairs_per_launch))
+        rc = self.lib.rvb_pipeline_create_lanes(ctypes.byref(self.handle), handles, _u64(len(self.contexts)), sizes, _u64(len(lanes)),
+                                                ctypes.byref(opts))
         if rc:
-            raise RvbError(rc, "rvb_pipeline_create failed")
+            raise RvbError(rc, "rvb_pipeline_create_lanes failed")
+        # pending limit and how many further results a histogram view outlives (include/rvb_capi.h)
+        self.limit, self.valid_for = 2 * len(self.contexts) * int(pairs_per_launch), len(self.contexts) * int(pairs_per_launch)
 
     def close(self):
         if self.handle:
@@ -582,7 +608,7 @@ class Pipeline:
 
     def next(self, copy=True):
         """The oldest pending job: (histogram [nchannels][8][nbins] — a copy, or a view of the pipeline's pinned buffer that stays valid
-        until len(contexts) further results have been taken —, info dict)."""
+        until `valid_for` further results have been taken —, info dict)."""
         res = PipelineResult()
         self._check(self.lib.rvb_pipeline_next(self.handle, ctypes.byref(res)))
         view = np.ctypeslib.as_array(res.histogram, shape=(int(res.nchannels), 8, int(res.nbins)))

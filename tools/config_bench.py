@@ -123,10 +123,11 @@ def pairs_pipelined(scene, src, mic, nrays, nrefl, npairs):
     return out
 
 
-def native_pipeline(name, scene, jobs, nrays, nrefl, hrtf, contexts=4, repeats=3):
+def native_pipeline(name, scene, jobs, nrays, nrefl, hrtf, contexts=4, repeats=3, lanes=None, pairs_per_launch=1):
     """The configuration's impulse responses back to back through the pipeline behind the C-ABI (rvb_pipeline_*, csrc/pipeline.hip):
     jobs = [(mic, source)] (HRTF: every listener faces its source), each `repeats` times; ms per impulse response with the histogram
-    in the pipeline's pinned ring."""
+    in the pipeline's pinned ring.  lanes = [contexts per lane] (and pairs_per_launch): rvb_pipeline_create_lanes over the same
+    contexts, the caller keeping the pipeline's pending limit filled; the warm-up then goes once round every lane's ring."""
     dirs = torch.from_numpy(np.ascontiguousarray(scenes.sphere_directions(nrays, seed=1))).cuda()
     torch.cuda.synchronize()
     ctxs = []
@@ -138,7 +139,15 @@ def native_pipeline(name, scene, jobs, nrays, nrefl, hrtf, contexts=4, repeats=3
             c.set_scene(scene)
         c.set_directions_device(dirs.data_ptr(), nrays)
         ctxs.append(c)
-    pipe = capi.Pipeline(ctxs)
+    if lanes is None:
+        pipe = capi.Pipeline(ctxs)
+        keep, warm = 2 * contexts, contexts
+    else:
+        assert sum(lanes) == contexts
+        split = [ctxs[sum(lanes[:i]):sum(lanes[:i + 1])] for i in range(len(lanes))]
+        pipe = capi.Pipeline(None, lanes=split, pairs_per_launch=pairs_per_launch)
+        keep, warm = pipe.limit, pipe.limit + pipe.valid_for
+        warm = (warm + len(jobs) - 1) // len(jobs) * len(jobs)
     if hrtf:
         pipe.configure_hrtf(scenes.hrtf_synthetic_table(), (0, 0, 1), (0, 1, 0), nrefl, dtypes.AIR_COEFFICIENTS, 44100.0, True, MODE)
     else:
@@ -148,7 +157,7 @@ def native_pipeline(name, scene, jobs, nrays, nrefl, hrtf, contexts=4, repeats=3
         sent = taken = 0
         nbins = 0
         while taken < len(todo):
-            while sent < len(todo) and pipe.pending() < 2 * contexts:
+            while sent < len(todo) and pipe.pending() < keep:
                 mic, src = todo[sent]
                 if hrtf:
                     f = np.asarray(src, np.float64) - np.asarray(mic, np.float64)
@@ -160,7 +169,7 @@ def native_pipeline(name, scene, jobs, nrays, nrefl, hrtf, contexts=4, repeats=3
             nbins = info["nbins"]
             taken += 1
         return nbins
-    run(jobs[:contexts])
+    run((jobs * warm)[:warm])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     nbins = run(jobs * repeats)
@@ -169,12 +178,40 @@ def native_pipeline(name, scene, jobs, nrays, nrefl, hrtf, contexts=4, repeats=3
     pipe.close()
     for c in ctxs:
         c.close()
-    return {"config": name + " — native pipeline, %d contexts" % contexts, "triangles": int(scene[0].shape[0]), "rays": nrays, "reflections": nrefl,
+    shape = "" if lanes is None else ", lanes %s, %d pairs per launch" % (list(lanes), pairs_per_launch)
+    return {"config": name + " — native pipeline, %d contexts%s" % (contexts, shape), "triangles": int(scene[0].shape[0]), "rays": nrays, "reflections": nrefl,
             "model": "hrtf" if hrtf else "speakers", "ms_per_ir": ms, "ray_bounces_per_sec": nrays * nrefl / (ms * 1e-3), "nbins_last": int(nbins), "kernel_ms": {}}
+
+
+def c5_lanes(rounds=3, repeats=25):
+    """C5's per-GPU share (the first 8 of the 64 pairs, 100k rays x 128, HRTF facing the source) through rvb_pipeline_create_lanes: one
+    lane of 2 and of 4 contexts with 1, 2, 4 pairs per launch, and two lanes of 2 against one of 4 (same GPU) — against the
+    rvb_pipeline_create leg with 4 contexts; the shapes alternate, `rounds` times.  ms per pair over 8 x `repeats` pairs (25: a window of
+    about a second; 3 windows of 0.1 s read up to 10 % apart on the same build)."""
+    hall, _ = scenes.concert_hall(30000)
+    src, mic = scenes.source_mic_pairs(64, seed=0)
+    jobs = [(tuple(map(float, mic[p])), tuple(map(float, src[p]))) for p in range(8)]
+    shapes = [("create_4", None, 4, 1)] + [("lane_%d_ppl_%d" % (n, ppl), [n], n, ppl) for n in (2, 4) for ppl in (1, 2, 4)] + \
+             [("lanes_2_2_ppl_%d" % ppl, [2, 2], 4, ppl) for ppl in (1, 4)]
+    if os.environ.get("CONFIG_BENCH_SHAPES"):                # e.g. "create_4,lane_2_ppl_4": one process per shape
+        shapes = [s for s in shapes if s[0] in os.environ["CONFIG_BENCH_SHAPES"].split(",")]
+    out = {}
+    for _ in range(rounds):
+        for key, lanes, nctx, ppl in shapes:
+            r = native_pipeline("C5 per-GPU share: 8 pairs, 100k rays x 128, HRTF", hall, jobs, 100000, 128, True, contexts=nctx, repeats=repeats,
+                                lanes=lanes, pairs_per_launch=ppl)
+            out.setdefault(key, {"config": r["config"], "ms_per_pair": []})["ms_per_pair"].append(r["ms_per_ir"])
+            print("%-18s %.3f ms per pair" % (key, r["ms_per_ir"]), file=sys.stderr, flush=True)
+    for v in out.values():
+        v["median"] = float(np.median(v["ms_per_pair"]))
+    return out
 
 
 def main():
     results = []
+    if os.environ.get("CONFIG_BENCH_ONLY") == "c5_lanes":     # the C5 legs through the pipeline over lanes, pairs per launch 1 / 2 / 4
+        print(json.dumps(c5_lanes(int(os.environ.get("CONFIG_BENCH_ROUNDS", "3"))), indent=1))
+        return
     if os.environ.get("CONFIG_BENCH_ONLY") == "c5":      # the C5 pipeline leg alone, a few times (CONFIG_BENCH_OWN_SCENES=1: a scene copy per context)
         hall, _ = scenes.concert_hall(30000)
         src, mic = scenes.source_mic_pairs(64, seed=0)
