@@ -196,6 +196,16 @@ int rvb_flatten(rvb_ctx * ctx, const rvb_attenuated_impulse * in, uint64_t n, fl
 enum { RVB_IR_DIFFUSE = 1, RVB_IR_IMAGES = 2, RVB_IR_ALL = 3 };   /* OutputMode, config.h:19-23 */
 enum { RVB_IR_FAST = 0, RVB_IR_EXACT = 1 };
 
+/* Speaker layouts: 1 .. RVB_MAX_SPEAKERS channels (a 22.2 layout is 24, a spherical microphone array 32); 0 or more than that is
+ * RVB_ERR_INVALID at rvb_ir_configure_speakers, rvb_pipeline_configure_speakers and rvb_multi_ir_speakers.  Channel c of every
+ * [nchannels][8][nbins] histogram is speaker c.  Up to 8 channels run the kernels of csrc/stream_kernels.hip; above 8 the speaker table
+ * is uploaded to the device at configure time (in stream order) and ONE sort and ONE fold serve all channels, every impulse record
+ * gathered from HBM once (csrc/wide_kernels.hip).  Above 8 channels RVB_IR_FAST runs that sorted fold as well — per channel count it is
+ * faster than float atomics, which pay 32 bytes of adds per live impulse and channel (profiles/speaker_arrays_n1.txt) — so there
+ * both modes return the exact mode's sums; RVB_IR_FAST promises its rounding bound only, not a mechanism.
+ * MEMORY: a histogram is nchannels x 8 x nbins floats — at workload C2's 846 741 bins 27 MB per channel, 1.73 GB at 64 channels — in
+ * device memory per context (rvb_ir_download; the caller's own with rvb_ir_accumulate), and again in pinned host memory per exported copy. */
+#define RVB_MAX_SPEAKERS 64
 int rvb_ir_configure_speakers(rvb_ctx * ctx, const float mic[3], const rvb_speaker * speakers, uint64_t nspeakers,
                               int which, const rvb_impulse * images, uint64_t nimages);
 /* table == NULL: the table of this context's previous rvb_ir_configure_hrtf call stays on the device (many listeners, one table: 4 MB
@@ -297,7 +307,9 @@ int rvb_multi_trace(rvb_multi * m, const float mic[3], const float source[3], ui
 /* getRawDiffuse / getRawImages over all shards: ray-major [nrays * nreflections]; merged image sources in std::map key order. */
 int rvb_multi_get_diffuse(rvb_multi * m, rvb_impulse * out);
 int rvb_multi_get_images(rvb_multi * m, int remove_direct, rvb_impulse * out, uint64_t capacity, uint64_t * count);
-/* attenuate -> fixPredelay -> flattenImpulses over all shards; out (host) is [nchannels][8][*nbins]; out == NULL reports *nbins. */
+/* attenuate -> fixPredelay -> flattenImpulses over all shards; out (host) is [nchannels][8][*nbins]; out == NULL reports *nbins.
+ * 1 .. RVB_MAX_SPEAKERS speakers, in both modes.  The exact mode's chain moves nchannels x 8 rows per block: on distinct devices that
+ * is one peer copy per row and block — 512 of them per block for a 64-channel layout — which this entry point does not batch. */
 int rvb_multi_ir_speakers(rvb_multi * m, const float mic[3], const rvb_speaker * speakers, uint64_t nspeakers, int which, int remove_direct,
                           int trim_predelay, float sample_rate, int mode, float * out, uint64_t capacity_bins, uint64_t * nbins);
 int rvb_multi_ir_hrtf(rvb_multi * m, const float mic[3], const float * table /* [2][360*180*8] */, const float facing[3], const float up[3],
@@ -320,7 +332,12 @@ int rvb_multi_ir_hrtf(rvb_multi * m, const float mic[3], const float * table /* 
  *                              `histogram` points into the pipeline's ring of pinned buffers and stays valid until `count` further
  *                              results have been taken (or the pipeline is destroyed)
  * Results are those of rvb_trace + rvb_merge_images + rvb_ir_configure_* + rvb_ir_download on one context, bit for bit in
- * RVB_IR_EXACT (tests/cpp/test_pipeline.cpp).  Not thread-safe. */
+ * RVB_IR_EXACT (tests/cpp/test_pipeline.cpp).  Not thread-safe.
+ * MEMORY with wide speaker layouts (1 .. RVB_MAX_SPEAKERS channels): every context keeps one device histogram per pair of a unit, and
+ * the ring of pinned host buffers holds 2 x count histograms here, and "pending limit + validity window" = 3 x count x P of them with
+ * lanes (rvb_pipeline_create_lanes below), once all are in use.  A histogram is nchannels x 8 x nbins floats (27 MB per channel at workload C2's 846 741 bins, 1.73 GB at 64 channels),
+ * so a caller with wide layouts uses fewer contexts.  There is no limit of its own: a pinned or device allocation that fails surfaces
+ * as RVB_ERR_HIP with the runtime's text. */
 #define RVB_PIPELINE_MAX_GROUP 4
 typedef struct rvb_pipeline rvb_pipeline;
 typedef struct {

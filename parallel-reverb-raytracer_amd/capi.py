@@ -41,6 +41,7 @@ SYMBOLS = [
 ]
 
 PIPELINE_MAX_PAIRS = 8      # RVB_PIPELINE_MAX_PAIRS
+MAX_SPEAKERS = 64           # RVB_MAX_SPEAKERS
 
 _vp = ctypes.c_void_p
 _u64 = ctypes.c_uint64

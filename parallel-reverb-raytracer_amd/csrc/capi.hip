@@ -4,6 +4,9 @@
 #include "../../include/rvb_capi.h"
 #include "kernels.h"
 
+#define RVB_STR_(x) #x
+#define RVB_STR(x) RVB_STR_(x)      // RVB_MAX_SPEAKERS in error texts
+
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -122,6 +125,8 @@ struct rvb_ctx {
     DevBuf own_sort_temp, own_sort_keys, own_sort_values;      // csrc/radix_sort.hip: tile counters, the intermediate (key, value) pair
     uint64_t nimages = 0;
     std::vector<rvb_impulse> images_host;
+    DevBuf speakers;                             // more than 8 speakers: AttenuationModel::speaker_table, uploaded in stream order at configure
+    std::vector<float4> speakers_host;
     // exact mode in two steps (rvb_ir_exact_prepare / rvb_ir_exact_fold): what the sorted list in keys_b / vals_b / bin_starts was prepared for
     struct ExactState { bool valid = false; bool hrtf_combined = false; uint64_t nbins = 0, n = 0, ndiffuse = 0, nimages = 0; } exact;
 
@@ -275,7 +280,7 @@ void rvb_destroy(rvb_ctx * ctx)
     for (DevBuf * b : {&ctx->sort_keys, &ctx->sort_scratch, &ctx->sort_order, &ctx->group_temp, &ctx->directions_own, &ctx->impulses, &ctx->image_items,
                        &ctx->early, &ctx->candidates, &ctx->small, &ctx->stamps, &ctx->images, &ctx->hrtf_table, &ctx->acc, &ctx->keys_a,
                        &ctx->keys_b, &ctx->vals_a, &ctx->vals_b, &ctx->sort_temp, &ctx->scratch_in, &ctx->scratch_out, &ctx->flat_in, &ctx->hist, &ctx->bin_starts, &ctx->own_sort_temp, &ctx->own_sort_keys, &ctx->own_sort_values,
-                       &ctx->pair_geom, &ctx->pair_direct, &ctx->pair_range})
+                       &ctx->pair_geom, &ctx->pair_direct, &ctx->pair_range, &ctx->speakers})
         b->release();
     for (rvb_ctx::CopyLane & l : ctx->copy_lanes) {
         for (int i = 0; i < 2; ++i) { if (l.pinned[i]) (void) hipHostFree(l.pinned[i]); if (l.done[i]) (void) hipEventDestroy(l.done[i]); }
@@ -1372,16 +1377,27 @@ int rvb_ir_configure_speakers(rvb_ctx * ctx, const float mic[3], const rvb_speak
                               int which, const rvb_impulse * images, uint64_t nimages)
 {
     if (!ctx) return RVB_ERR_INVALID;
-    if (!mic || !speakers || nspeakers == 0 || nspeakers > 8)
-        return fail(ctx, RVB_ERR_INVALID, "rvb_ir_configure_speakers: 1..8 speakers required");
+    if (!mic || !speakers || nspeakers == 0 || nspeakers > RVB_MAX_SPEAKERS)
+        return fail(ctx, RVB_ERR_INVALID, "rvb_ir_configure_speakers: 1.." RVB_STR(RVB_MAX_SPEAKERS) " speakers required");
     RVB_BIND(ctx);
     AttenuationModel m;
     m.hrtf = 0;
     m.nchannels = (uint32_t) nspeakers;
     for (int i = 0; i < 3; ++i) m.mic[i] = mic[i];
-    for (uint64_t s = 0; s < nspeakers; ++s) {
+    for (uint64_t s = 0; s < nspeakers && s < 8; ++s) {
         for (int i = 0; i < 3; ++i) m.speaker_dir[s][i] = speakers[s].direction[i];
         m.speaker_coeff[s] = speakers[s].coefficient;
+    }
+    if (nspeakers > 8) {
+        // the wide kernels read their speakers from device memory: uploaded in stream order like the images (kernels of an earlier
+        // configuration that read the old table run before the copy; the source is the context's own copy, alive until the next configure)
+        if (nspeakers * sizeof(float4) > ctx->speakers.cap)
+            RVB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the buffer is about to be replaced
+        RVB_HIP(ctx, ctx->speakers.ensure(RVB_MAX_SPEAKERS * sizeof(float4)));
+        ctx->speakers_host.resize(nspeakers);
+        rvb_make_speaker_table(speakers, nspeakers, ctx->speakers_host.data());
+        RVB_HIP(ctx, hipMemcpyAsync(ctx->speakers.p, ctx->speakers_host.data(), nspeakers * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+        m.speaker_table = ctx->speakers.as<const float4>();
     }
     ctx->model = m;
     return configure_common(ctx, which, images, nimages);
@@ -1564,6 +1580,9 @@ static int exact_fold(rvb_ctx * ctx, uint64_t b0, uint64_t b1, float * hist)
         const uint64_t nkeys = 2 * (e.nbins + 1);
         rvb_launch_ordered_sum_hrtf(m, ir_diffuse(ctx), e.ndiffuse, ctx->images.as<rvb_impulse>(), ctx->vals_b.as<uint32_t>(),
                                     ctx->bin_starts.as<uint32_t>(), ctx->bin_starts.as<uint32_t>() + nkeys, e.nbins, hist, ctx->stream, b0, b1);
+    } else if (m.nchannels > 8) {
+        rvb_launch_ordered_sum_wide(m, ir_diffuse(ctx), e.ndiffuse, ctx->images.as<rvb_impulse>(), ctx->vals_b.as<uint32_t>(),
+                                    ctx->bin_starts.as<uint32_t>(), ctx->bin_starts.as<uint32_t>() + e.nbins, e.n, e.nbins, hist, ctx->stream, b0, b1);
     } else {
         rvb_launch_ordered_sum(m, 0, m.nchannels, ir_diffuse(ctx), e.ndiffuse, ctx->images.as<rvb_impulse>(), e.nimages, ctx->vals_b.as<uint32_t>(),
                                ctx->bin_starts.as<uint32_t>(), ctx->bin_starts.as<uint32_t>() + e.nbins, e.n, e.nbins, hist, ctx->stream, b0, b1);
@@ -1611,7 +1630,12 @@ static int ir_accumulate_impl(rvb_ctx * ctx, float predelay, float sample_rate, 
     const uint64_t nimages = (ctx->which & RVB_IR_IMAGES) ? ctx->nimages : 0;
     float * hist = reinterpret_cast<float *>(d_histogram);
     ctx->reset_timings();
-    if (mode == RVB_IR_FAST) {
+    // More than 8 speakers: RVB_IR_FAST runs the sorted fold too.  An atomic histogram adds 32 bytes per live impulse and channel at
+    // the chip-wide float-atomic rate (about 6.5 ms for 32 channels at workload C2 before its transpose); the fold gathers each record
+    // once for all channels and writes with plain stores (profiles/speaker_arrays_n1.txt).  Its sums are the exact mode's, which meet
+    // the fast mode's bound trivially.
+    const bool wide = !m.hrtf && m.nchannels > 8;
+    if (mode == RVB_IR_FAST && !wide) {
         const size_t acc_bytes = (size_t) nbins * m.nchannels * 8 * sizeof(float);
         RVB_HIP(ctx, ctx->acc.ensure(acc_bytes));
         RVB_HIP(ctx, hipMemsetAsync(ctx->acc.p, 0, acc_bytes, ctx->stream));
@@ -1622,10 +1646,10 @@ static int ir_accumulate_impl(rvb_ctx * ctx, float predelay, float sample_rate, 
         ctx->begin_timing("histogram_transpose_kernel");
         rvb_launch_histogram_transpose(ctx->acc.as<float>(), hist, m.nchannels, nbins, ctx->stream);
         ctx->end_timing();
-    } else if (mode == RVB_IR_EXACT) {
+    } else if (mode == RVB_IR_EXACT || mode == RVB_IR_FAST) {
         const char * split_env = getenv("RVB_HRTF_SPLIT_EARS");     // measurement / test switch (read per call): one list per ear, as in round 2
         const bool split_ears = m.hrtf && split_env && split_env[0] == '1';
-        ctx->begin_timing("exact_mode");
+        ctx->begin_timing(mode == RVB_IR_FAST ? "sorted_fold_wide" : "exact_mode");
         if (!split_ears) {
             // one sorted list (speaker channels share it; the two HRTF ears are keyed into one list of 2 n entries), then the fold —
             // bin range by bin range when the histogram leaves for the host as it becomes final

@@ -84,10 +84,14 @@ hipError_t rvb_group_records16(void * temp, size_t temp_bytes, const uint16_t * 
 // ---- streaming kernels (stream_kernels.hip) ---------------------------------------------------
 struct AttenuationModel {
     int hrtf = 0;                       // 0: speakers, 1: hrtf
-    uint32_t nchannels = 0;             // speakers: <= 8; hrtf: 2
+    uint32_t nchannels = 0;             // speakers: <= RVB_MAX_SPEAKERS; hrtf: 2
     float mic[3] = {0, 0, 0};
     float speaker_dir[8][3] = {};       // normalised on device exactly as kernel.cpp:511 does
     float speaker_coeff[8] = {};
+    // more than 8 speakers (wide_kernels.hip): the table in device memory, one 16-byte entry per channel — the direction normalised
+    // on the host with normalize3 exactly as make_model does for the eight above, then the coefficient.  speaker_dir / speaker_coeff
+    // then hold the first eight only (the kernels that take them never run for a wide layout).
+    const float4 * speaker_table = nullptr;
     const float * hrtf_table = nullptr; // device [2][360*180+1][8]
     float facing[3] = {0, 0, 0}, up[3] = {0, 0, 0};
 };
@@ -111,6 +115,12 @@ void rvb_launch_ordered_sum(const AttenuationModel & m, uint32_t first_channel, 
                             uint64_t ndiffuse, const rvb_impulse * images, uint64_t nimages,
                             const uint32_t * sorted_values, const uint32_t * starts, const uint32_t * ends, uint64_t n,
                             uint64_t nbins, float * hist, hipStream_t s, uint64_t bin_begin = 0, uint64_t bin_end = ~0ull);   // bins [bin_begin, bin_end) only
+// The same fold for more than 8 speaker channels (wide_kernels.hip): ALL m.nchannels channels of bins [bin_begin, bin_end) in one
+// launch, the speaker table read from m.speaker_table, every record gathered from HBM once.
+void rvb_make_speaker_table(const rvb_speaker * speakers, uint64_t nspeakers, float4 * table);      // host: the entries of speaker_table
+void rvb_launch_ordered_sum_wide(const AttenuationModel & m, const rvb_impulse * diffuse, uint64_t ndiffuse, const rvb_impulse * images,
+                                 const uint32_t * sorted_values, const uint32_t * starts, const uint32_t * ends, uint64_t n,
+                                 uint64_t nbins, float * hist, hipStream_t s, uint64_t bin_begin = 0, uint64_t bin_end = ~0ull);
 // HRTF model, both ears at once: ONE list of 2 n (key, value) entries — ear e's entry of impulse j at e * n + j, key e * (nbins + 1) + bin
 // (sentinel e * (nbins + 1) + nbins) — and the ordered sum of both ears over its sorted form (starts / ends indexed by that key)
 void rvb_launch_bin_keys_hrtf(const AttenuationModel & m, const rvb_impulse * in, uint64_t count, uint64_t index_base, uint64_t n,

@@ -17,6 +17,9 @@
 //                 listed twice, as the single-GPU tests do) are summed with peer copies and an add kernel instead.
 #include "../../include/rvb_capi.h"
 
+#define RVB_STR_(x) #x
+#define RVB_STR(x) RVB_STR_(x)      // RVB_MAX_SPEAKERS in error texts
+
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -493,7 +496,7 @@ int rvb_multi_ir_speakers(rvb_multi * m, const float mic[3], const rvb_speaker *
                           int trim_predelay, float sample_rate, int mode, float * out, uint64_t capacity_bins, uint64_t * nbins)
 {
     if (!m) return RVB_ERR_INVALID;
-    if (!mic || !speakers || nspeakers == 0 || nspeakers > 8) return mfail(m, RVB_ERR_INVALID, "rvb_multi_ir_speakers: 1..8 speakers required");
+    if (!mic || !speakers || nspeakers == 0 || nspeakers > RVB_MAX_SPEAKERS) return mfail(m, RVB_ERR_INVALID, "rvb_multi_ir_speakers: 1.." RVB_STR(RVB_MAX_SPEAKERS) " speakers required");
     return multi_ir(m, mic, speakers, nspeakers, nullptr, nullptr, nullptr, which, remove_direct, trim_predelay, sample_rate, mode, out, capacity_bins, nbins);
 }
 

@@ -20,6 +20,9 @@
 // Nothing but the public C-ABI underneath (plus HIP for the histogram buffers, their zero fill and a few events).
 #include "../../include/rvb_capi.h"
 
+#define RVB_STR_(x) #x
+#define RVB_STR(x) RVB_STR_(x)      // RVB_MAX_SPEAKERS in error texts
+
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -643,7 +646,7 @@ int rvb_pipeline_configure_speakers(rvb_pipeline * p, const rvb_speaker * speake
                                     int trim_predelay, float sample_rate, int mode, uint64_t nreflections, const float air_coefficient[8])
 {
     if (!p) return RVB_ERR_INVALID;
-    if (!speakers || nspeakers == 0 || nspeakers > 8) return pfail(p, RVB_ERR_INVALID, "rvb_pipeline_configure_speakers: 1..8 speakers required");
+    if (!speakers || nspeakers == 0 || nspeakers > RVB_MAX_SPEAKERS) return pfail(p, RVB_ERR_INVALID, "rvb_pipeline_configure_speakers: 1.." RVB_STR(RVB_MAX_SPEAKERS) " speakers required");
     std::lock_guard<std::mutex> lk(p->mu);        // (the lane threads read the configuration while jobs are pending: none are)
     const int rc = configure_common(p, which, remove_direct, trim_predelay, sample_rate, mode, nreflections, air_coefficient);
     if (rc != RVB_OK) return rc;
