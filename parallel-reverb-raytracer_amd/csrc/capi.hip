@@ -582,9 +582,8 @@ static int trace_prepare(rvb_ctx * ctx, const float * mics, const float * source
         // slots of escaped rays get key 0xFFFFFFFF from path_kernel: they land in the last bucket and the
         // shadow kernel skips them by their valid flag
         // 16-bit keys in 64-byte runs (trace_kernels.hip, flush_key_run) whenever a ray's row divides into whole runs and rocPRIM sorts;
-        // 32-bit keys, one store per record, otherwise (and for RVB_SORT=own, RVB_KEY_RUNS=0)
-        static const bool runs_off = getenv("RVB_KEY_RUNS") && getenv("RVB_KEY_RUNS")[0] == '0';
-        if (nreflections % 32 == 0 && !own_sort_enabled() && !runs_off) {
+        // 32-bit keys, one store per record, otherwise (and for RVB_SORT=own)
+        if (nreflections % 32 == 0 && !own_sort_enabled()) {
             a.sort_keys16 = ctx->sort_keys.as<uint16_t>();
             a.key_shift = (uint32_t) std::max(0, key_bits - 16);
         } else {
@@ -595,7 +594,6 @@ static int trace_prepare(rvb_ctx * ctx, const float * mics, const float * source
     a.nreflections = (uint32_t) nreflections;
     a.stack_entries = ctx->stack_need;
     a.lds_surfaces = rvb_lds_surfaces(ctx->stack_need, ctx->nsurfaces);
-    a.scene_nodes = (uint32_t) ctx->nnodes;
     // (rays_in_flight: what a group launch carries in all; 0 = this trace alone, times the caller's hint)
     a.path_lanes = ctx->path_lanes ? ctx->path_lanes : (rays_in_flight ? rvb_path_lanes_for(rays_in_flight, 1) : rvb_path_lanes_for(nrays, ctx->concurrent_traces));
     a.ray_offset = ray_offset;
@@ -611,13 +609,6 @@ static int trace_prepare(rvb_ctx * ctx, const float * mics, const float * source
         ctx->stamps_cleared = true;
     }
     a.scene.stamps = ctx->stamps.as<unsigned long long>();
-
-    // diagnostic only (timing probes whose path kernel leaves records unwritten, -DRVB_PROBE_NO_STORES): start from invalid records
-    static const bool probe_zero = getenv("RVB_PROBE_ZERO_RECORDS") != nullptr;
-    if (probe_zero) {
-        RVB_HIP(ctx, hipMemsetAsync(ctx->impulses.p, 0, imp_bytes, ctx->stream));
-        if (a.sort_keys || a.sort_keys16) RVB_HIP(ctx, hipMemsetAsync(ctx->sort_keys.p, 0xFF, nrecords * (a.sort_keys ? 4 : 2), ctx->stream));
-    }
 
     ctx->reset_timings();
     plan.npairs = npairs;
@@ -1601,14 +1592,8 @@ static int export_bin_range(rvb_ctx * ctx, float * pinned_dst, const float * his
     if (b0 == 0 && b1 == nbins) {
         RVB_HIP(ctx, hipMemcpyAsync(pinned_dst, hist, rows * nbins * sizeof(float), hipMemcpyDeviceToHost, ctx->export_stream));
     } else {
-        static const bool by_rows = getenv("RVB_EXPORT_ROWS") && getenv("RVB_EXPORT_ROWS")[0] == '1';      // measurement: one copy per [channel][band] row
-        if (by_rows) {
-            for (uint64_t r = 0; r < rows; ++r)
-                RVB_HIP(ctx, hipMemcpyAsync(pinned_dst + r * nbins + b0, hist + r * nbins + b0, (b1 - b0) * sizeof(float), hipMemcpyDeviceToHost, ctx->export_stream));
-        } else {
-            RVB_HIP(ctx, hipMemcpy2DAsync(pinned_dst + b0, nbins * sizeof(float), hist + b0, nbins * sizeof(float), (b1 - b0) * sizeof(float), rows,
-                                          hipMemcpyDeviceToHost, ctx->export_stream));
-        }
+        RVB_HIP(ctx, hipMemcpy2DAsync(pinned_dst + b0, nbins * sizeof(float), hist + b0, nbins * sizeof(float), (b1 - b0) * sizeof(float), rows,
+                                      hipMemcpyDeviceToHost, ctx->export_stream));
     }
     return RVB_OK;
 }

@@ -43,7 +43,6 @@ struct TraceArgs {
     uint32_t nreflections;
     uint32_t stack_entries;             // LDS traversal stack entries per lane (BuiltScene::stack_need)
     uint32_t lds_surfaces;              // surfaces staged in LDS behind the stack by the quad kernels (rvb_lds_surfaces), 0 = none
-    uint32_t scene_nodes;               // number of BVH nodes (experiments that stage the top of the tree)
     uint32_t path_lanes;                // lanes per ray in the path kernel: 4 (path_kernel) or 2 (path_pair_kernel), rvb_path_lanes_for
     // Several (source, microphone) pairs in ONE launch (rvb_trace_pairs): ray r belongs to pair r / rays_per_pair and uses
     // direction r % rays_per_pair; its records, early ids, candidates follow the global ray number.  npairs == 1: mic / source below.

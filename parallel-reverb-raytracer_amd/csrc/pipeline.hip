@@ -376,10 +376,8 @@ int lane_next(Lane * l, rvb_pipeline_result * out)
             if ((rc = stage_bin(l, job_at(l, id))) != RVB_OK) return rc;
         // ... then for their binning (not for their histograms' way to the host): with it done, the group's contexts take the traces of
         // the group after next — enqueued before this call waits for the link, so the copy runs beside them
-        // (measured: enqueuing those traces in stream order behind the binning, BEFORE this wait — RVB_PIPELINE_EARLY_TRACES=1 — costs 4.45 -> 5.6 ms per
+        // (measured: enqueuing those traces in stream order behind the binning, BEFORE this wait, costs 4.45 -> 5.6 ms per
         // IR at workload C2: a third group's path kernel then competes with this group's binning for the SIMDs)
-        static const bool early = getenv("RVB_PIPELINE_EARLY_TRACES") && getenv("RVB_PIPELINE_EARLY_TRACES")[0] == '1';
-        if (early && (rc = begin_upto(l, std::min(group_first + l->group + n, l->submitted / l->group * l->group))) != RVB_OK) return rc;
         for (uint64_t id = j.id; id < last; ++id) {
             rvb_ctx * cx = l->slots[(size_t) (id % n)].ctx;
             if ((rc = rvb_synchronize(cx)) != RVB_OK) return cfail(l, rc, cx, "rvb_pipeline_next: wait");

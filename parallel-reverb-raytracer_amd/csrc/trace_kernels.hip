@@ -29,18 +29,8 @@
 #include <algorithm>
 #include <cstdlib>
 
-#ifndef RVB_PATH_JOBS
-#define RVB_PATH_JOBS 2     // 2: majority-vote job loop (traverse_jobs_vote), 1: while-while job loop, 0: one query at a time
-#endif
-#ifndef RVB_PROBE_NO_STORES
-#define RVB_PROBE_NO_STORES 0
-#endif
-#ifndef RVB_QUAD_SELECT
-#define RVB_QUAD_SELECT 1      // slab_select (near / far plane by the direction's sign) in the four-lane path kernel as well
-#endif
-#ifndef RVB_SHADOW_JOBS
-#define RVB_SHADOW_JOBS 0
-#endif
+// ---- build knobs: single numbers (tools/build_variant.sh runs set them) and the two diagnostic builds; everything else is the shipped form ----
+// step thresholds of the path kernels' schedule (traverse_jobs_cycle, traverse_pairs_cycle: "THE SCHEDULE")
 #ifndef RVB_CYCLE_LEAF_NUM
 #define RVB_CYCLE_LEAF_NUM 3       // a leaf step when NUM x (lanes at a leaf) >= DEN x (live lanes)
 #define RVB_CYCLE_LEAF_DEN 1
@@ -49,11 +39,22 @@
 #define RVB_CYCLE_DONE_NUM 4       // a shading step when NUM x (lanes with a finished query) >= DEN x (live lanes)
 #define RVB_CYCLE_DONE_DEN 1
 #endif
-#ifndef RVB_LDS_NODES
-#define RVB_LDS_NODES 0        // experiment: top nodes of the BVH staged in LDS per workgroup (path_kernel); 21 = levels 0-2
+// waves per SIMD the register budget of a kernel allows (its __launch_bounds__)
+#ifndef RVB_PAIR_WAVES
+#define RVB_PAIR_WAVES 6            // path_pair_group_kernel: 80 VGPRs, so that six waves fit a SIMD beside the other kernels' (see the node step of traverse_pairs_cycle);
+                                    // 7 (72 VGPRs) spills ten registers: pipeline 4.52-4.54 ms against 4.37-4.40, and 4.70 against 4.47 when LDS
+                                    // allows the seventh wave too (no key runs: profiles/r04c_occupancy_n1.txt); 8 (64 VGPRs): 5.9 ms
 #endif
-
-// tools/isa_mix.py: -DRVB_ISA_MARKS=1 leaves comment lines in the ISA at the borders of the step kinds of the vote loops (never in the shipped build)
+#ifndef RVB_SHADOW_PAIR_WAVES
+#define RVB_SHADOW_PAIR_WAVES 5     // shadow_pair_kernel
+#endif
+#ifndef RVB_SHADOW_WAVES
+#define RVB_SHADOW_WAVES 8          // shadow_kernel: 64 VGPRs (8 waves/SIMD): 1.845 -> 1.807 ms against 7
+#endif
+#ifndef RVB_LANE_WAVES
+#define RVB_LANE_WAVES 4            // path_lane_group_kernel, shadow_lane_kernel: 128 VGPRs
+#endif
+// tools/isa_mix.py: -DRVB_ISA_MARKS=1 leaves comment lines in the ISA at the borders of the step kinds of the path loops (never in the shipped build)
 #ifndef RVB_ISA_MARKS
 #define RVB_ISA_MARKS 0
 #endif
@@ -61,6 +62,10 @@
 #define RVB_MARK(name) asm volatile("; RVB_MARK " name)
 #else
 #define RVB_MARK(name)
+#endif
+// tools/pair_stamps.py: -DRVB_STAMPS=1 (never shipped) stamps the traversal loops with s_memtime, see STAMP below
+#ifndef RVB_STAMPS
+#define RVB_STAMPS 0
 #endif
 
 #define WAVE 64
@@ -71,9 +76,6 @@ namespace {
 
 // Diagnostic build only (-DRVB_STAMPS=1, never shipped): per-wave s_memtime shares of the traversal
 // loop, written to a side buffer that no other code reads (cdna_hip_programming.md §7 "In-kernel stamps").
-#ifndef RVB_STAMPS
-#define RVB_STAMPS 0
-#endif
 #if RVB_STAMPS
 #define STAMP(var) { __builtin_amdgcn_sched_barrier(0); var = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); }
 struct Stamps {
@@ -86,26 +88,15 @@ struct Stamps {
 
 struct Hit { float t; uint32_t tri; };
 
-// Streaming accesses to the 64-byte work records / Impulses (written once, read once by a later kernel).
-// RVB_STREAM_STORE picks the cache policy of the stores: 0 = nt (stays in the XCD's L2 until evicted),
-// 1 = sc1, 2 = sc0 sc1 (write-through, the line is DROPPED from L2 — MI355X_MICROARCH.md "stores of each
-// flavour"), so that the 819 MB record stream does not push the ~6 MB scene out of the 4 MiB per-XCD L2s.
-#ifndef RVB_STREAM_STORE
-#define RVB_STREAM_STORE 0
-#endif
+// Streaming accesses to the 64-byte work records / Impulses (written once, read once by a later kernel): non-temporal, the lines stay in
+// the XCD's L2 until evicted (the write-through forms sc1 / sc0 sc1 of the stores were measured and are no faster: DESIGN.md §3).
 typedef float nt_float4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) uint32_t * lds_u32_ptr;
 typedef __attribute__((address_space(3))) const nt_float4 * lds_float4_ptr;  // keeps ds_read: a generic pointer would load flat
 __device__ __forceinline__ void store_stream(float4 * p, const float4 v)
 {
     nt_float4 t = {v.x, v.y, v.z, v.w};
-#if RVB_STREAM_STORE == 1
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(t) : "memory");
-#elif RVB_STREAM_STORE == 2
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" :: "v"(p), "v"(t) : "memory");
-#else
     __builtin_nontemporal_store(t, reinterpret_cast<nt_float4 *>(p));
-#endif
 }
 __device__ __forceinline__ float4 load_stream(const float4 * p)
 {
@@ -242,14 +233,14 @@ __device__ __forceinline__ void traverse_jobs(const SceneDev & sc, uint32_t * __
     STAMP(st.t0)
 #endif
     bool active = job.next(o, d, tmax);
-#define RVB_RESET_QUERY()                                                         \
-    {                                                                             \
-        ix = clamp_inv(d.x); iy = clamp_inv(d.y); iz = clamp_inv(d.z);            \
-        oix = o.x * ix; oiy = o.y * iy; oiz = o.z * iz;                           \
-        best_t = ANY ? tmax : __builtin_inff();                                   \
-        best_i = NONE; sp = 0; ref = 0;                                           \
+#define RESET_QUERY_JOBS()                                                \
+    {                                                                     \
+        ix = clamp_inv(d.x); iy = clamp_inv(d.y); iz = clamp_inv(d.z);    \
+        oix = o.x * ix; oiy = o.y * iy; oiz = o.z * iz;                   \
+        best_t = ANY ? tmax : __builtin_inff();                           \
+        best_i = NONE; sp = 0; ref = 0;                                   \
     }
-    if (active) RVB_RESET_QUERY()
+    if (active) RESET_QUERY_JOBS()
     while (active) {
         while (!(ref & RVB_BVH_LEAF)) {
             STAMP(ta)
@@ -347,7 +338,7 @@ __device__ __forceinline__ void traverse_jobs(const SceneDev & sc, uint32_t * __
             h.tri = best_i;
             job.done(ANY ? found : best_i != NONE, h);
             active = job.next(o, d, tmax);
-            if (active) RVB_RESET_QUERY()
+            if (active) RESET_QUERY_JOBS()
 #if RVB_STAMPS
             STAMP(tb)
             st.done_calls += 1; st.done_cycles += tb - ta;
@@ -370,18 +361,14 @@ __device__ __forceinline__ void traverse_jobs(const SceneDev & sc, uint32_t * __
         if ((threadIdx.x & 63u) == 0) atomicAdd(sc.stamps + 9, 1ull);
     }
 #endif
-#undef RVB_RESET_QUERY
+#undef RESET_QUERY_JOBS
 }
 
 // min of two unsigned 64-bit keys.  The compiler's form is v_cmp_lt_u64 -> VCC and two v_cndmask_b32 that read VCC; the SECOND
 // select on one VCC value issues far slower than the first (tools/inst_probe.hip "cmpsel2_vcc": 3.0 ns against 0.9 ns for the
 // same select on an SGPR-pair mask at 8 waves per SIMD, and 5-10x that at low occupancy).  Here the mask lives in an SGPR pair.
-#ifndef RVB_MIN64_SGPR
-#define RVB_MIN64_SGPR 1
-#endif
 __device__ __forceinline__ unsigned long long min_u64(unsigned long long a, unsigned long long b)
 {
-#if RVB_MIN64_SGPR
     unsigned long long mask;
     uint32_t lo, hi;
     // (s_nop 1: a VALU-written SGPR needs two wait states before a VALU reads it as a mask)
@@ -389,9 +376,6 @@ __device__ __forceinline__ unsigned long long min_u64(unsigned long long a, unsi
         : "=&s"(mask), "=&v"(lo), "=&v"(hi)
         : "v"(a), "v"(b), "v"((uint32_t) a), "v"((uint32_t) b), "v"((uint32_t) (a >> 32)), "v"((uint32_t) (b >> 32)));
     return ((unsigned long long) hi << 32) | lo;
-#else
-    return a < b ? a : b;
-#endif
 }
 
 // Population count of a wave mask as a 32-bit scalar (the builtin's 64-bit result drags the comparisons that follow
@@ -403,7 +387,7 @@ __device__ __forceinline__ int scalar_popcount(unsigned long long mask)
     return n;
 }
 
-// Closest-hit job loop with SCHEDULED step kinds over the wave's 16 quads (path_kernel, RVB_PATH_JOBS=2).
+// Closest-hit job loop with SCHEDULED step kinds over the wave's 16 quads (path_kernel).
 // A quad is in one of four states, all encoded in `ref`: at a node (bit 31 clear), at a leaf (bit 31 set), query
 // finished (NONE), out of jobs (IDLE).  The while-while loop above runs node steps until the LAST quad has reached a
 // leaf, so on incoherent rays (every bounce after the first) only ~7 of 16 quads do useful work in a node step.  Here
@@ -411,11 +395,10 @@ __device__ __forceinline__ int scalar_popcount(unsigned long long mask)
 // majority vote per iteration (host replay on workload C2, tools/travsim.cpp: wave-level node steps per bounce 37 -> 28,
 // quads active per node step 6.7 -> 8.9, wave instructions per bounce -13 %); round 4 replaced the vote by a fixed
 // cycle with thresholds (node step, leaf step if a third of the live lanes wait for one, shading step if a quarter do:
-// 27.6 + 4.8 + 2.4 -> 22.0 + 5.7 + 3.8 steps per 16 ray-bounces, tools/travforms.cpp) — see traverse_pairs_vote,
-// "THE SCHEDULE", for the measurements.  (The function names keep the word `vote`.)
+// 27.6 + 4.8 + 2.4 -> 22.0 + 5.7 + 3.8 steps per 16 ray-bounces, tools/travforms.cpp) — see traverse_pairs_cycle,
+// "THE SCHEDULE", for the measurements.
 template <class Job>
-__device__ __forceinline__ void traverse_jobs_vote(const SceneDev & sc, uint32_t * __restrict__ stack, Job & job,
-                                                   lds_float4_ptr lds_nodes = nullptr)
+__device__ __forceinline__ void traverse_jobs_cycle(const SceneDev & sc, uint32_t * __restrict__ stack, Job & job)
 {
     const uint32_t IDLE = 0xFFFFFFFEu;
     const uint32_t c = threadIdx.x & 3u;
@@ -431,22 +414,15 @@ __device__ __forceinline__ void traverse_jobs_vote(const SceneDev & sc, uint32_t
     float ix = 0.0f, iy = 0.0f, iz = 0.0f, oix = 0.0f, oiy = 0.0f, oiz = 0.0f;
     unsigned long long best_key = NO_HIT_KEY;                              // (distance bits, triangle index) of the closest hit so far
     uint32_t sp = 0, ref = IDLE;
-#if RVB_QUAD_SELECT
-    uint32_t selx = 0, sely = 0, selz = 0;
-#define RVB_QUAD_SEL_SET() selx = slab_selector(ix); sely = slab_selector(iy); selz = slab_selector(iz);
-#define RVB_QUAD_SLAB(n, tn) slab_select(n, ix, iy, iz, oix, oiy, oiz, selx, sely, selz, limit, neg_cull, job.skip_ref(), tn)
-#else
-#define RVB_QUAD_SEL_SET()
-#define RVB_QUAD_SLAB(n, tn) slab(n, ix, iy, iz, oix, oiy, oiz, limit, neg_cull, job.skip_ref(), tn)
-#endif
-#define RVB_RESET_QUERY()                                                         \
-    {                                                                             \
-        ix = clamp_inv(d.x); iy = clamp_inv(d.y); iz = clamp_inv(d.z);            \
-        oix = o.x * ix; oiy = o.y * iy; oiz = o.z * iz;                           \
-        RVB_QUAD_SEL_SET()                                                        \
-        best_key = NO_HIT_KEY; sp = 0; ref = 0;                                   \
+    uint32_t selx = 0, sely = 0, selz = 0;       // slab_select (near / far plane by the direction's sign) here as well
+#define RESET_QUERY_QUADS()                                                              \
+    {                                                                                    \
+        ix = clamp_inv(d.x); iy = clamp_inv(d.y); iz = clamp_inv(d.z);                   \
+        oix = o.x * ix; oiy = o.y * iy; oiz = o.z * iz;                                  \
+        selx = slab_selector(ix); sely = slab_selector(iy); selz = slab_selector(iz);    \
+        best_key = NO_HIT_KEY; sp = 0; ref = 0;                                          \
     }
-    if (job.next(o, d, tmax)) RVB_RESET_QUERY()
+    if (job.next(o, d, tmax)) RESET_QUERY_QUADS()
     int n_active = 0;                    // lanes that carry a ray (not IDLE): changes in shading steps only
     auto leaf_step = [&]() {
         if ((int32_t) ref < (int32_t) IDLE) {
@@ -480,22 +456,16 @@ __device__ __forceinline__ void traverse_jobs_vote(const SceneDev & sc, uint32_t
             h.tri = (uint32_t) best_key;
             job.done(h.tri != NONE, h);
             ref = IDLE;
-            if (job.next(o, d, tmax)) RVB_RESET_QUERY()
+            if (job.next(o, d, tmax)) RESET_QUERY_QUADS()
         }
         n_active = scalar_popcount(__builtin_amdgcn_ballot_w64(ref != IDLE));
     };
     auto node_step = [&]() {
         if ((int32_t) ref >= 0) {
-#if RVB_LDS_NODES
-            uint4 n;
-            if (ref < RVB_LDS_NODES * 64u) { const nt_float4 t = lds_nodes[(ref | child_off) >> 4]; n = make_uint4(__float_as_uint(t.x), __float_as_uint(t.y), __float_as_uint(t.z), __float_as_uint(t.w)); }
-            else n = *reinterpret_cast<const uint4 *>(node_base + (ref | child_off));
-#else
             const uint4 n = *reinterpret_cast<const uint4 *>(node_base + (ref | child_off));
-#endif
             const float limit = fmaf(__uint_as_float((uint32_t) (best_key >> 32)), cull_scale, sc.cull_abs);
             float tn;
-            const bool ok = RVB_QUAD_SLAB(n, tn);
+            const bool ok = slab_select(n, ix, iy, iz, oix, oiy, oiz, selx, sely, selz, limit, neg_cull, job.skip_ref(), tn);
             const uint32_t cref = n.w;
             const uint32_t key = ok ? ((__float_as_uint(fmaxf(tn, 0.0f)) & ~3u) | c) : NONE;
             uint32_t kmin = min(key, dpp_u<QP_SWAP1>(key));
@@ -516,7 +486,7 @@ __device__ __forceinline__ void traverse_jobs_vote(const SceneDev & sc, uint32_t
         }
     };
     n_active = scalar_popcount(__builtin_amdgcn_ballot_w64(ref != IDLE));
-    // (the schedule of traverse_pairs_vote: no vote — node step, leaf step if a third of the live lanes wait for one, shading step if a quarter do)
+    // (the schedule of traverse_pairs_cycle: node step, leaf step if a third of the live lanes wait for one, shading step if a quarter do)
     for (;;) {
         if (n_active == 0)
             break;
@@ -531,22 +501,18 @@ __device__ __forceinline__ void traverse_jobs_vote(const SceneDev & sc, uint32_t
         if (n_done && (RVB_CYCLE_DONE_NUM * n_done >= RVB_CYCLE_DONE_DEN * n_active || !ran))
             shading_step();
     }
-#undef RVB_RESET_QUERY
+#undef RESET_QUERY_QUADS
 }
 
 // TWO LANES PER RAY (path_kernel at RVB_PATH_LANES = 2): a lane owns two children of a node and two triangles of a leaf, a wave
-// carries 32 rays.  The vote, the stack handling, the reductions and the loads' addressing are per-RAY work that every lane of
+// carries 32 rays.  The schedule, the stack handling, the reductions and the loads' addressing are per-RAY work that every lane of
 // the ray repeats: with two lanes instead of four a node step costs ~1.45x the instructions for twice the rays.  (One lane per
 // ray would be cheaper still per ray, but 100 k rays are then 1.5 waves per SIMD, too few to cover a node fetch.)
 // stack: this pair's column of the LDS stack, entries PAIRS_PER_BLOCK words apart.
 #define PAIRS_PER_BLOCK 32
-#ifndef RVB_PAIR_SELECT
-#define RVB_PAIR_SELECT 1          // bit 0: path_pair_kernel, bit 1: shadow_pair_kernel use slab_select (near / far plane by the direction's sign)
-                                   // instead of slab (min / max).  Measured at C2: path pairs 3.92 -> 3.80 ms, shadow pairs 1.28 -> 1.34 ms
-#endif
-// The node step of traverse_pairs_vote is written for ISSUE COST (round 4; measured as the build flag RVB_PAIR_PUSH_COUNTS against the
-// hit-mask form it replaced, like the short vote — RVB_PAIR_SHORT_VOTE — and the chained node step — RVB_PAIR_CHAIN — further down: the
-// flags were folded in once the measurements were committed, tools/r04*_*.sh name them).  In the pipeline (traces of the
+// The node step of traverse_pairs_cycle is written for ISSUE COST (round 4; measured as the build flag RVB_PAIR_PUSH_COUNTS against the
+// hit-mask form it replaced, like the short vote — RVB_PAIR_SHORT_VOTE — and the chained node step — RVB_PAIR_CHAIN — that led to
+// THE SCHEDULE further down: the flags exist in the commits of those measurements only).  In the pipeline (traces of the
 // next group beside the binning of this one) the SIMDs issue vector instructions three quarters of the time, and the node step is two
 // thirds of the path kernel's instructions; tools/inst_probe.hip measures two classes of them on gfx950 — v_fma / v_add / v_mul_f32,
 // v_mov, two-operand integer add / and / or / xor / right shift and v_bitop3 issue at the full rate, everything else (comparisons,
@@ -562,11 +528,8 @@ __device__ __forceinline__ void traverse_jobs_vote(const SceneDev & sc, uint32_t
 // VGPRs (RVB_PAIR_WAVES = 6); uncapped it takes 84, loses a wave per SIMD to the kernels beside it and the pipeline is 8 % SLOWER
 // (4.82-4.87 ms) — the register count of the path kernel matters more than its instruction count.  Alone (one trace of 100 k rays,
 // bound by the latency of its chains) the kernel takes 3.49 ms either way.
-#define RVB_PAIR_SLAB(SEL, n, tn, skip) ((SEL) ? slab_select(n, ix, iy, iz, oix, oiy, oiz, selx, sely, selz, limit, neg_cull, skip, tn) \
-                                               : slab(n, ix, iy, iz, oix, oiy, oiz, limit, neg_cull, skip, tn))
 template <class Job>
-__device__ __forceinline__ void traverse_pairs_vote(const SceneDev & sc, uint32_t * __restrict__ stack, Job & job,
-                                                    lds_float4_ptr lds_nodes = nullptr)
+__device__ __forceinline__ void traverse_pairs_cycle(const SceneDev & sc, uint32_t * __restrict__ stack, Job & job)
 {
     const uint32_t IDLE = 0xFFFFFFFEu;
     const uint32_t h = threadIdx.x & 1u;
@@ -596,15 +559,15 @@ __device__ __forceinline__ void traverse_pairs_vote(const SceneDev & sc, uint32_
     uint32_t selx = 0, sely = 0, selz = 0;
     float limit = 0.0f;                  // culling distance of the best hit so far: changes in leaf steps, is read in node steps
 #define RVB_PAIR_LIMIT() limit = fmaf(__uint_as_float((uint32_t) (best_key >> 32)), cull_scale, sc.cull_abs)
-#define RVB_RESET_QUERY()                                                         \
-    {                                                                             \
-        ix = clamp_inv(d.x); iy = clamp_inv(d.y); iz = clamp_inv(d.z);            \
-        oix = o.x * ix; oiy = o.y * iy; oiz = o.z * iz;                           \
-        selx = slab_selector(ix); sely = slab_selector(iy); selz = slab_selector(iz); \
-        best_key = NO_HIT_KEY; RVB_PAIR_EMPTY(); ref = 0; RVB_PAIR_LIMIT();       \
+#define RESET_QUERY_PAIRS()                                                              \
+    {                                                                                    \
+        ix = clamp_inv(d.x); iy = clamp_inv(d.y); iz = clamp_inv(d.z);                   \
+        oix = o.x * ix; oiy = o.y * iy; oiz = o.z * iz;                                  \
+        selx = slab_selector(ix); sely = slab_selector(iy); selz = slab_selector(iz);    \
+        best_key = NO_HIT_KEY; RVB_PAIR_EMPTY(); ref = 0; RVB_PAIR_LIMIT();              \
     }
 #if RVB_STAMPS
-    // diagnostic builds.  -DRVB_STAMPS=1: where a wave's cycles go — [0] vote, [1] node step until its two loads are back, [2] the rest of the
+    // diagnostic builds.  -DRVB_STAMPS=1: where a wave's cycles go — [0] the schedule's ballots and branches, [1] node step until its two loads are back, [2] the rest of the
     // node step (incl. the wait for the popped entry), [3] / [4] the same for leaf steps, [5] shading steps; [6..8] step counts.  Any RVB_STAMPS
     // (2 = these alone, the loop runs at its own pace): [9] shader cycles and [11] 100-MHz ticks of the whole loop — their quotient is the
     // clock the chip holds under this load (MI355X_MICROARCH.md "DVFS give-back") —, [10] waves
@@ -613,7 +576,7 @@ __device__ __forceinline__ void traverse_pairs_vote(const SceneDev & sc, uint32_
     { __builtin_amdgcn_sched_barrier(0); r_loop = __builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); }
     t_c = t_loop;
 #endif
-    if (job.next(o, d, tmax)) RVB_RESET_QUERY()
+    if (job.next(o, d, tmax)) RESET_QUERY_PAIRS()
     int n_active = 0;                    // lanes that carry a ray (not IDLE): changes in shading steps only
     // the three step kinds of the loop (inlined where the schedule below calls them)
     auto leaf_step = [&]() {
@@ -663,7 +626,7 @@ __device__ __forceinline__ void traverse_pairs_vote(const SceneDev & sc, uint32_
             hit.tri = (uint32_t) best_key;
             job.done(hit.tri != NONE, hit);
             ref = IDLE;
-            if (job.next(o, d, tmax)) RVB_RESET_QUERY()
+            if (job.next(o, d, tmax)) RESET_QUERY_PAIRS()
         }
         n_active = scalar_popcount(__builtin_amdgcn_ballot_w64(ref != IDLE));
 #if RVB_STAMPS == 1
@@ -684,23 +647,11 @@ __device__ __forceinline__ void traverse_pairs_vote(const SceneDev & sc, uint32_
         sv[1] += t_b - t_a; sn[0] += 1;
 #endif
         if ((int32_t) ref >= 0) {
-#if RVB_LDS_NODES
-            uint4 n0, n1;
-            if (ref < RVB_LDS_NODES * 64u) {
-                const nt_float4 t0 = lds_nodes[(ref | child_off) >> 4], t1 = lds_nodes[((ref | child_off) >> 4) + 1];
-                n0 = make_uint4(__float_as_uint(t0.x), __float_as_uint(t0.y), __float_as_uint(t0.z), __float_as_uint(t0.w));
-                n1 = make_uint4(__float_as_uint(t1.x), __float_as_uint(t1.y), __float_as_uint(t1.z), __float_as_uint(t1.w));
-            } else {
-                const uint4 * np = reinterpret_cast<const uint4 *>(node_base + (ref | child_off));
-                n0 = np[0]; n1 = np[1];
-            }
-#else
             const uint4 * np = reinterpret_cast<const uint4 *>(node_base + (ref | child_off));
             const uint4 n0 = np[0], n1 = np[1];
-#endif
             float tn0, tn1;
-            const bool ok0 = RVB_PAIR_SLAB(RVB_PAIR_SELECT & 1, n0, tn0, job.skip_ref());
-            const bool ok1 = RVB_PAIR_SLAB(RVB_PAIR_SELECT & 1, n1, tn1, job.skip_ref());
+            const bool ok0 = slab_select(n0, ix, iy, iz, oix, oiy, oiz, selx, sely, selz, limit, neg_cull, job.skip_ref(), tn0);
+            const bool ok1 = slab_select(n1, ix, iy, iz, oix, oiy, oiz, selx, sely, selz, limit, neg_cull, job.skip_ref(), tn1);
             // the hit children's keys: entry distance (its two low bits give way to the child number), compared as SIGNED integers —
             // negative distances (the origin is inside the box, or the box a rounding behind it) come before all others, in any
             // order; tools/travforms.cpp replays the same number of node visits as with keys of max(distance, 0)
@@ -752,7 +703,7 @@ __device__ __forceinline__ void traverse_pairs_vote(const SceneDev & sc, uint32_
     // node requested a step ahead (a third L1 access per step costs more than its head start: 3.40 -> 3.81 ms), two node steps per iteration.
     n_active = scalar_popcount(__builtin_amdgcn_ballot_w64(ref != IDLE));
     for (;;) {
-        RVB_MARK("vote");
+        RVB_MARK("vote");               // (the schedule's block; tools/isa_mix.py knows it by this name)
         if (n_active == 0)
             break;
         bool ran = __builtin_amdgcn_ballot_w64((int32_t) ref >= 0) != 0ull;
@@ -791,7 +742,7 @@ __device__ __forceinline__ void traverse_pairs_vote(const SceneDev & sc, uint32_
         }
     }
 #endif
-#undef RVB_RESET_QUERY
+#undef RESET_QUERY_PAIRS
 #undef RVB_PAIR_POP
 #undef RVB_PAIR_EMPTY
 #undef ref
@@ -817,15 +768,14 @@ __device__ __forceinline__ bool traverse_pair_any(const SceneDev & sc, const v3 
     const float limit = fmaf(tmax, 1.0f + sc.cull_rel, sc.cull_abs);
     const float ix = clamp_inv(d.x), iy = clamp_inv(d.y), iz = clamp_inv(d.z);
     const float oix = o.x * ix, oiy = o.y * iy, oiz = o.z * iz;
-    const uint32_t selx = slab_selector(ix), sely = slab_selector(iy), selz = slab_selector(iz);
     uint32_t sp = 0, ref = 0;
     for (;;) {
         while (!(ref & RVB_BVH_LEAF)) {
             const uint4 * np = reinterpret_cast<const uint4 *>(node_base + (ref | child_off));
             const uint4 n0 = np[0], n1 = np[1];
             float tn0, tn1;
-            const bool ok0 = RVB_PAIR_SLAB(RVB_PAIR_SELECT & 2, n0, tn0, skip);
-            const bool ok1 = RVB_PAIR_SLAB(RVB_PAIR_SELECT & 2, n1, tn1, skip);
+            const bool ok0 = slab(n0, ix, iy, iz, oix, oiy, oiz, limit, neg_cull, skip, tn0);      // (slab_select: shadow pairs 1.28 -> 1.34 ms)
+            const bool ok1 = slab(n1, ix, iy, iz, oix, oiy, oiz, limit, neg_cull, skip, tn1);
             uint32_t okmask = (ok0 ? bit0 : 0u) | (ok1 ? bit1 : 0u);
             okmask |= dpp_u<QP_SWAP1>(okmask);
             if (okmask == 0u) {
@@ -922,19 +872,8 @@ __device__ __forceinline__ lds_float4_ptr stage_surfaces(const TraceArgs & a, ui
 }
 
 // LANES = 4: quad lane c stores chunk c.  LANES = 2: lane c of the pair stores chunks c and c + 2.
-// COLD (the two-lane kernel): what only the shading step touches — the lane's four band volumes and the path length so far — lives
-// in LDS between bounces ([5][64] words behind the surface table, one column per lane) instead of in five registers that the
-// compiler would otherwise keep through every node and leaf step: with them the kernel fits the 72-register budget of seven
-// waves per SIMD without scratch spills (the compiler's own choice at that budget spills two values the LEAF step reloads).
-// Measured at workload C2 (round 3, profiles/r03_pair_cold_state_n1.txt): with COLD the group kernel needs 72 registers and no
-// scratch, all 6 250 waves of two 100 k-ray traces are resident at once (80 registers: 6 144 slots, and the 106 waves that start
-// when the first ones finish run a whole 128-bounce chain almost alone: 196 608 rays 4.97 ms, 200 000 rays 6.15 ms), and the launch
-// takes 5.36 instead of 6.15 ms.  In the bench pipeline it LOSES (4.81 against 4.59 ms per IR): the other group's sort, shadow and
-// binning kernels used to run in that long thin tail and now stretch by what the path kernel gained (chain per context 16.7 against
-// 16.6 ms).  Off by default; -DRVB_PAIR_COLD=1 for callers whose path launches run alone.
-#ifndef RVB_PAIR_COLD
-#define RVB_PAIR_COLD 0
-#endif
+// (The lane's band volumes and path length kept in LDS between bounces instead of in registers — "cold ray state" — lose in the
+// pipeline: DESIGN.md §3.)
 #define RVB_KEY_RUN 32u      // grouping keys per run: 32 x 2 bytes = one 64-byte segment
 __device__ __forceinline__ uint32_t lane_id_here()
 {
@@ -942,21 +881,20 @@ __device__ __forceinline__ uint32_t lane_id_here()
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
     return lane;
 }
-template <bool SURF_LDS, int LANES = 4, bool COLD = false>
+template <bool SURF_LDS, int LANES = 4>
 struct PathJob {
     const TraceArgs & a;
     uint32_t ray;                        // < 2^32 / 9 (rvb_trace checks)
     uint32_t c;
     v3 o, d;
-    float distance;                      // (COLD: in LDS)
-    float4 vol;                          // lane 0 (and 2): bands 0-3, lane 1 (and 3): bands 4-7 — the chunk the lane stores (COLD: in LDS)
+    float distance;
+    float4 vol;                          // lane 0 (and 2): bands 0-3, lane 1 (and 3): bands 4-7 — the chunk the lane stores
     uint32_t index;
     bool alive;
     lds_float4_ptr surf_lds;             // the surface table staged in LDS (stage_surfaces); unused when !SURF_LDS
     uint32_t pair_tag;                   // (source, microphone) pair of this ray + 1: what marks its work records as valid
     uint32_t skip;                       // own-plane subtree of the triangle the current segment starts on (TriShade, bvh.h)
     bool unit;                           // the ray's direction has unit length (the own-plane rule is derived for |d| = 1)
-    float * cold;                        // COLD: this workgroup's [5][64] words in LDS
     uint16_t * key_rows;                 // key runs (TraceArgs::sort_keys16): this workgroup's [rays][RVB_KEY_RUN] 16-bit keys in LDS
 
     // Record-grouping keys as 64-byte RUNS.  The grouping key of a record (the leaf position of the triangle hit, 16 significant
@@ -1002,12 +940,6 @@ struct PathJob {
         float4 sp;
         if (SURF_LDS) sp = lds_load4(surf_lds, 4 * surface + half);
         else sp = reinterpret_cast<const float4 *>(a.scene.surfaces + surface)[half];
-        float * mine = nullptr;
-        if (COLD) {
-            mine = cold + lane_id_here();
-            vol = make_float4(mine[0], mine[64], mine[128], mine[192]);
-            distance = mine[256];
-        }
         const v3 p = o + d * h.t;                                    // kernel.cpp:459
         const float new_dist = distance + h.t;                       // kernel.cpp:460
         vol = make_float4(-vol.x * sp.x, -vol.y * sp.y, -vol.z * sp.z, -vol.w * sp.w);   // kernel.cpp:461
@@ -1029,9 +961,6 @@ struct PathJob {
         uint32_t ray_here = ray;
         asm volatile("" : "+v"(ray_here));
         const uint64_t record = (uint64_t) ray_here * a.nreflections + index;
-#if RVB_PROBE_NO_STORES          // diagnostic build (wrong output): what the record stores cost the bounce chain
-        if (new_dist == 1.2345f) {
-#endif
         store_stream(reinterpret_cast<float4 *>(a.impulses + record) + c, chunk);
         if (LANES == 2)
             store_stream(reinterpret_cast<float4 *>(a.impulses + record) + c + 2, c == 0 ? make_float4(p.x, p.y, p.z, diff) : tail);
@@ -1048,16 +977,9 @@ struct PathJob {
         } else if (c == 1 && a.sort_keys) {
             a.sort_keys[record] = __float_as_uint(sk.w);
         }
-#if RVB_PROBE_NO_STORES
-        }
-#endif
-        if (COLD) {
-            mine[0] = vol.x; mine[64] = vol.y; mine[128] = vol.z; mine[192] = vol.w;
-            mine[256] = new_dist;
-        }
         d = reflect3(normal, d);                                     // kernel.cpp:492-499
         o = p;
-        if (!COLD) distance = new_dist;
+        distance = new_dist;
         ++index;
     }
 };
@@ -1110,18 +1032,6 @@ __global__ __launch_bounds__(WAVE, WAVES) void path_kernel(TraceArgs a)
     const uint32_t q = threadIdx.x >> 2;
     const uint64_t ray = (uint64_t) blockIdx.x * QUADS_PER_BLOCK + q;
     const lds_float4_ptr surf_lds = stage_surfaces(a, stack_lds + a.stack_entries * QUADS_PER_BLOCK);
-#if RVB_LDS_NODES
-    lds_float4_ptr lds_nodes;
-    {
-        uint4 * dst = reinterpret_cast<uint4 *>(stack_lds + a.stack_entries * QUADS_PER_BLOCK) + 4u * a.lds_surfaces;
-        const uint4 * src = reinterpret_cast<const uint4 *>(a.scene.nodes);
-        const uint32_t count = 4u * (RVB_LDS_NODES < a.scene_nodes ? RVB_LDS_NODES : a.scene_nodes);
-        for (uint32_t i = threadIdx.x; i < 4u * RVB_LDS_NODES; i += WAVE)
-            dst[i] = i < count ? src[i] : make_uint4(0xFC007C00u, 0xFC007C00u, 0xFC007C00u, RVB_BVH_EMPTY);
-        __syncthreads();
-        lds_nodes = (lds_float4_ptr) dst;
-    }
-#endif
     if (ray >= a.nrays)
         return;                                   // whole quads leave together
     uint32_t pair = 0, local = (uint32_t) ray;
@@ -1135,58 +1045,22 @@ __global__ __launch_bounds__(WAVE, WAVES) void path_kernel(TraceArgs a)
     const float4 d4 = a.directions[local];
     const float len2 = d4.x * d4.x + d4.y * d4.y + d4.z * d4.z;
     PathJob<SURF_LDS> job = {a, (uint32_t) ray, threadIdx.x & 3u, source, mk3(d4.x, d4.y, d4.z), 0.0f,
-                   make_float4(1.0f, 1.0f, 1.0f, 1.0f), 0u, true, surf_lds, pair + 1u, RVB_BVH_EMPTY, fabsf(len2 - 1.0f) < 1e-3f, nullptr,
-                   reinterpret_cast<uint16_t *>(stack_lds + a.stack_entries * QUADS_PER_BLOCK + 16u * a.lds_surfaces + (RVB_LDS_NODES * 16u))};
-#if RVB_PATH_JOBS == 2
-#if RVB_LDS_NODES
-    traverse_jobs_vote(a.scene, stack_lds + q, job, lds_nodes);
-#else
-    traverse_jobs_vote(a.scene, stack_lds + q, job);
-#endif
-#elif RVB_PATH_JOBS
-    traverse_jobs<false>(a.scene, stack_lds + q, job);
-#else
-    v3 o, d;
-    float tmax;
-    while (job.next(o, d, tmax)) {
-        Hit h;
-        const bool hit = traverse_quad<false>(a.scene, o, d, tmax, stack_lds + q, h, job.skip);
-        job.done(hit, h);
-    }
-#endif
+                   make_float4(1.0f, 1.0f, 1.0f, 1.0f), 0u, true, surf_lds, pair + 1u, RVB_BVH_EMPTY, fabsf(len2 - 1.0f) < 1e-3f,
+                   reinterpret_cast<uint16_t *>(stack_lds + a.stack_entries * QUADS_PER_BLOCK + 16u * a.lds_surfaces)};
+    traverse_jobs_cycle(a.scene, stack_lds + q, job);
     finish_escaped_ray<PathJob<SURF_LDS>, 4>(a, job, ray);
     if (job.c == 0)
         atomicAdd(a.executed, (unsigned long long) job.index);
 }
 
-// path_kernel with two lanes per ray (traverse_pairs_vote): 32 rays per single-wave workgroup.
-#ifndef RVB_PAIR_WAVES
-#define RVB_PAIR_WAVES 6            // register cap: 80 VGPRs, so that six waves fit a SIMD beside the other kernels' (see the node step of traverse_pairs_vote);
-                                    // 7 (72 VGPRs) spills ten registers: pipeline 4.52-4.54 ms against 4.37-4.40, and 4.70 against 4.47 when LDS
-                                    // allows the seventh wave too (no key runs: profiles/r04c_occupancy_n1.txt); 8 (64 VGPRs): 5.9 ms
-#endif
+// path_kernel with two lanes per ray (traverse_pairs_cycle): 32 rays per single-wave workgroup.
 template <bool SURF_LDS>
 __device__ __forceinline__ void path_pair_body(const TraceArgs & a, const uint32_t block)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t stack_lds[];   // [stack_entries][PAIRS_PER_BLOCK]
-#if RVB_PATH_PRIO
-    __builtin_amdgcn_s_setprio(RVB_PATH_PRIO);
-#endif
     const uint32_t q = threadIdx.x >> 1;
     const uint64_t ray = (uint64_t) block * PAIRS_PER_BLOCK + q;
     const lds_float4_ptr surf_lds = stage_surfaces(a, stack_lds + a.stack_entries * PAIRS_PER_BLOCK);
-#if RVB_LDS_NODES
-    lds_float4_ptr lds_nodes;
-    {
-        uint4 * dst = reinterpret_cast<uint4 *>(stack_lds + a.stack_entries * PAIRS_PER_BLOCK) + 4u * a.lds_surfaces;
-        const uint4 * src = reinterpret_cast<const uint4 *>(a.scene.nodes);
-        const uint32_t count = 4u * (RVB_LDS_NODES < a.scene_nodes ? RVB_LDS_NODES : a.scene_nodes);
-        for (uint32_t i = threadIdx.x; i < 4u * RVB_LDS_NODES; i += WAVE)
-            dst[i] = i < count ? src[i] : make_uint4(0xFC007C00u, 0xFC007C00u, 0xFC007C00u, RVB_BVH_EMPTY);
-        __syncthreads();
-        lds_nodes = (lds_float4_ptr) dst;
-    }
-#endif
     if (ray >= a.nrays)
         return;                                   // whole pairs leave together
     uint32_t pair = 0, local = (uint32_t) ray;
@@ -1199,21 +1073,12 @@ __device__ __forceinline__ void path_pair_body(const TraceArgs & a, const uint32
     }
     const float4 d4 = a.directions[local];
     const float len2 = d4.x * d4.x + d4.y * d4.y + d4.z * d4.z;
-    // the cold words sit behind the stack and the surface table (rvb_pair_lds_bytes)
-    float * cold = reinterpret_cast<float *>(stack_lds + a.stack_entries * PAIRS_PER_BLOCK + 16u * a.lds_surfaces + (RVB_LDS_NODES * 16u));
-    if (RVB_PAIR_COLD) {
-        cold[threadIdx.x] = 1.0f; cold[64 + threadIdx.x] = 1.0f; cold[128 + threadIdx.x] = 1.0f; cold[192 + threadIdx.x] = 1.0f;
-        cold[256 + threadIdx.x] = 0.0f;
-    }
-    PathJob<SURF_LDS, 2, RVB_PAIR_COLD != 0> job = {a, (uint32_t) ray, threadIdx.x & 1u, source, mk3(d4.x, d4.y, d4.z), 0.0f,
-                   make_float4(1.0f, 1.0f, 1.0f, 1.0f), 0u, true, surf_lds, pair + 1u, RVB_BVH_EMPTY, fabsf(len2 - 1.0f) < 1e-3f, cold,
-                   reinterpret_cast<uint16_t *>(cold + (RVB_PAIR_COLD ? 5u * WAVE : 0u))};
-#if RVB_LDS_NODES
-    traverse_pairs_vote(a.scene, stack_lds + q, job, lds_nodes);
-#else
-    traverse_pairs_vote(a.scene, stack_lds + q, job);
-#endif
-    finish_escaped_ray<PathJob<SURF_LDS, 2, RVB_PAIR_COLD != 0>, 2>(a, job, ray);
+    // the key runs sit behind the stack and the surface table (rvb_pair_lds_bytes)
+    PathJob<SURF_LDS, 2> job = {a, (uint32_t) ray, threadIdx.x & 1u, source, mk3(d4.x, d4.y, d4.z), 0.0f,
+                   make_float4(1.0f, 1.0f, 1.0f, 1.0f), 0u, true, surf_lds, pair + 1u, RVB_BVH_EMPTY, fabsf(len2 - 1.0f) < 1e-3f,
+                   reinterpret_cast<uint16_t *>(stack_lds + a.stack_entries * PAIRS_PER_BLOCK + 16u * a.lds_surfaces)};
+    traverse_pairs_cycle(a.scene, stack_lds + q, job);
+    finish_escaped_ray<PathJob<SURF_LDS, 2>, 2>(a, job, ray);
     if (job.c == 0)
         atomicAdd(a.executed, (unsigned long long) job.index);
 }
@@ -1237,7 +1102,7 @@ __global__ __launch_bounds__(WAVE, RVB_PAIR_WAVES) void path_pair_group_kernel(T
 
 // ONE LANE PER RAY (path_lane_group_kernel, round 4): 64 rays per single-wave workgroup, every lane walks its own ray — it tests the
 // four children of its node and the up-to-four triangles of its leaf itself, nothing is exchanged between lanes, and the stack is the
-// lane's own column in LDS.  What the lanes of a pair (or quad) repeat per ray — the vote's state, the stack pointer, the child
+// lane's own column in LDS.  What the lanes of a pair (or quad) repeat per ray — the schedule's state, the stack pointer, the child
 // keys, the lane exchange, the 64-bit key reductions — is paid once per ray, and a wave step serves 64 rays: tools/travforms.cpp
 // replays C2 at 29.3 node + 5.4 leaf + 2.7 shading wave steps per 64 ray-bounces (pairs: 28.5 + 5.2 + 2.6 per 32), i.e. a quarter to
 // a third fewer wave instructions per ray-bounce with the step costs of this kernel's ISA.  The price is half the waves again (100 k
@@ -1245,27 +1110,8 @@ __global__ __launch_bounds__(WAVE, RVB_PAIR_WAVES) void path_pair_group_kernel(T
 // in flight: rvb_path_lanes_for picks it for group launches of that size only.  Same arithmetic, same records, same bytes as the
 // other two path kernels (tests/test_gpu_parity.py runs every trace case with all three).
 #define LANE_RAYS 64
-typedef __attribute__((address_space(3))) void * lds_void_ptr;
-typedef const __attribute__((address_space(1))) void * global_void_ptr;
-#ifndef RVB_LANE_WAVES
-#define RVB_LANE_WAVES 4            // waves per SIMD the register budget allows (128 VGPRs)
-#endif
-// Node fetch of the one-lane kernel.  A lane that reads the 64 bytes of ITS node with four 16-byte loads makes four L1 accesses per
-// node visit (the texture addresser coalesces the lanes of ONE instruction, not the instructions of one lane): PMC at 800 k rays —
-// 87 L1 accesses per ray-bounce against 50 (pairs) and 33 (quads), TA stalled by the L1 a quarter of its busy time, and the kernel
-// slower than the pairs although it issues 27 % fewer vector instructions (profiles/r04_path_pmc_by_lanes_800k_rays_n1.txt).
-// RVB_LANE_COOP = 1: the four lanes of a QUAD fetch each other's nodes — in load s every lane of the quad reads "its" child (16 bytes)
-// of the node of the quad's lane s, one contiguous 64-byte access per quad like the quad kernel's — straight into LDS
-// (global_load_lds_dwordx4: no registers in between), and each lane then reads its own node's four children back with four
-// ds_read_b128.  Load s of the wave lands at stage + s * RVB_LANE_STAGE_STRIDE + lane * 16 (the extra 16 bytes per load put the four
-// reads of a quad's lanes on different banks).
-// MEASURED, and slower still (profiles/r04_rays_sweep_by_lanes_n1.txt): 800 k rays 3.02 ms per 100 k rays against 2.35 with the plain
-// loads (pairs 2.07), 100 k rays 4.48 against 3.94 — the detour through LDS adds a dependent round trip to every node step and its 4 KB
-// of LDS per wave cost a fifth of the occupancy.  Off; the shipped kernels stay the pair / quad kernels.
-#ifndef RVB_LANE_COOP
-#define RVB_LANE_COOP 0
-#endif
-#define RVB_LANE_STAGE_STRIDE 1040u
+// (A cooperative node fetch — the four lanes of a quad load each other's nodes straight into LDS, one 64-byte access per node — was
+// measured and is slower than the four 16-byte loads per lane below: DESIGN.md §3.)
 template <bool SURF_LDS>
 __device__ __forceinline__ void path_lane_body(const TraceArgs & a, const uint32_t block)
 {
@@ -1278,17 +1124,9 @@ __device__ __forceinline__ void path_lane_body(const TraceArgs & a, const uint32
     uint32_t * const after_stack = stack_lds + (a.stack_entries + 1u) * LANE_RAYS;
     const lds_float4_ptr surf_lds = stage_surfaces(a, after_stack);
     uint16_t * const key_row = reinterpret_cast<uint16_t *>(after_stack + 16u * a.lds_surfaces) + lane * RVB_KEY_RUN;
-    // (behind the key runs when there are any: rvb_lane_lds_bytes) the landing area of the cooperative node fetch
-#if RVB_LANE_COOP
-    uint32_t * const stage = after_stack + 16u * a.lds_surfaces + (a.sort_keys16 ? LANE_RAYS * RVB_KEY_RUN / 2u : 0u);
-#endif
-    const bool in_range = ray < a.nrays;
-#if !RVB_LANE_COOP
-    if (!in_range)
+    if (ray >= a.nrays)
         return;
-#endif
-    // (with the cooperative fetch the lanes behind the last ray stay: they carry no ray, but fetch for their quad's other lanes)
-    uint32_t pair = 0, local = in_range ? (uint32_t) ray : 0u;
+    uint32_t pair = 0, local = (uint32_t) ray;
     v3 o = ld3(a.source);
     if (a.npairs > 1) {
         pair = (uint32_t) ray / a.rays_per_pair;
@@ -1314,14 +1152,14 @@ __device__ __forceinline__ void path_lane_body(const TraceArgs & a, const uint32
     uint32_t selx = 0, sely = 0, selz = 0;
     unsigned long long best_key = NO_HIT_KEY;
     uint32_t ref = IDLE;
-#define RVB_RESET_QUERY()                                                         \
-    {                                                                             \
-        ix = clamp_inv(d.x); iy = clamp_inv(d.y); iz = clamp_inv(d.z);            \
-        oix = o.x * ix; oiy = o.y * iy; oiz = o.z * iz;                           \
-        selx = slab_selector(ix); sely = slab_selector(iy); selz = slab_selector(iz); \
-        best_key = NO_HIT_KEY; sp = bottom; ref = 0;                              \
+#define RESET_QUERY_LANE()                                                               \
+    {                                                                                    \
+        ix = clamp_inv(d.x); iy = clamp_inv(d.y); iz = clamp_inv(d.z);                   \
+        oix = o.x * ix; oiy = o.y * iy; oiz = o.z * iz;                                  \
+        selx = slab_selector(ix); sely = slab_selector(iy); selz = slab_selector(iz);    \
+        best_key = NO_HIT_KEY; sp = bottom; ref = 0;                                     \
     }
-    if (in_range && index < a.nreflections) RVB_RESET_QUERY()
+    if (index < a.nreflections) RESET_QUERY_LANE()
     for (;;) {
         RVB_MARK("vote");
         const unsigned long long m_node = __builtin_amdgcn_ballot_w64((int32_t) ref >= 0);
@@ -1332,30 +1170,8 @@ __device__ __forceinline__ void path_lane_body(const TraceArgs & a, const uint32
             break;
         if (n_node >= n_leaf && n_node >= n_done) {
             RVB_MARK("node");
-#if RVB_LANE_COOP
-            {
-                // every lane of the wave is here (the branch is wave-uniform): load s fetches the node of each quad's lane s, if that lane
-                // is at a node (the condition is quad-uniform: whole quads skip the load)
-                const uint32_t child = 16u * (lane & 3u);
-#define RVB_COOP_LOAD(S)                                                                                                         \
-                {                                                                                                                \
-                    const uint32_t ref_s = quad_bcast_u<S>(ref);                                                                 \
-                    if ((int32_t) ref_s >= 0)                                                                                    \
-                        __builtin_amdgcn_global_load_lds((global_void_ptr) (node_base + (ref_s | child)),                        \
-                                                         (lds_void_ptr) (stage + S * (RVB_LANE_STAGE_STRIDE / 4u)), 16, 0, 0);   \
-                }
-                RVB_COOP_LOAD(0) RVB_COOP_LOAD(1) RVB_COOP_LOAD(2) RVB_COOP_LOAD(3)
-#undef RVB_COOP_LOAD
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the LDS-DMA loads are not in the compiler's books
-            }
-#endif
             if ((int32_t) ref >= 0) {
-#if RVB_LANE_COOP
-                // this lane's node: load (lane & 3) of the wave, this quad's 64 bytes
-                const uint4 * np = reinterpret_cast<const uint4 *>(stage + (lane & 3u) * (RVB_LANE_STAGE_STRIDE / 4u) + (lane & ~3u) * 4u);
-#else
                 const uint4 * np = reinterpret_cast<const uint4 *>(node_base + ref);
-#endif
                 const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
                 const float limit = fmaf(__uint_as_float((uint32_t) (best_key >> 32)), cull_scale, a.scene.cull_abs);
                 float tn0, tn1, tn2, tn3;
@@ -1456,15 +1272,13 @@ __device__ __forceinline__ void path_lane_body(const TraceArgs & a, const uint32
                     o = p;
                     distance = new_dist;
                     ++index;
-                    if (index < a.nreflections) RVB_RESET_QUERY()
+                    if (index < a.nreflections) RESET_QUERY_LANE()
                 }
             }
         }
         RVB_MARK("loop_end");
     }
-#undef RVB_RESET_QUERY
-    if (!in_range)
-        return;
+#undef RESET_QUERY_LANE
     // an escaped ray leaves its remaining slots zero-filled and their grouping keys "no record" (finish_escaped_ray)
     if (index < a.nreflections) {
         const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -1746,6 +1560,30 @@ __global__ __launch_bounds__(WAVE) void image_check_kernel(TraceArgs a)
     }
 }
 
+// Arrival-time range of the non-zero diffuse impulses, the inputs of findPredelay / MAX_SAMPLE (rayverb.h:49-74, rayverb.cpp:54-57), in
+// a.time_range as float bits (non-negative floats order like their bit patterns).  An atomic is skipped when a plain read says it cannot
+// move the result (stale reads are harmless).
+// Several pairs per launch: one range per pair, updated record by record.
+__device__ __forceinline__ void time_range_of_pair(const TraceArgs & a, const uint32_t pair, const float t)
+{
+    const volatile uint32_t * seen = a.time_range + 2u * pair;
+    if (t != 0.0f && __float_as_uint(t) < seen[0]) atomicMin(a.time_range + 2u * pair, __float_as_uint(t));
+    if (__float_as_uint(t) > seen[1]) atomicMax(a.time_range + 2u * pair + 1u, __float_as_uint(t));
+}
+// One pair: every lane keeps its own range, the wave folds them at the kernel's end.
+__device__ __forceinline__ void time_range_of_wave(const TraceArgs & a, float tmin, float tmax_seen)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        tmin = fminf(tmin, __shfl_xor(tmin, off));
+        tmax_seen = fmaxf(tmax_seen, __shfl_xor(tmax_seen, off));
+    }
+    if (threadIdx.x == 0 && a.npairs <= 1) {
+        const volatile uint32_t * seen = a.time_range;
+        if (tmin != __builtin_inff() && __float_as_uint(tmin) < seen[0]) atomicMin(a.time_range + 0, __float_as_uint(tmin));
+        if (__float_as_uint(tmax_seen) > seen[1]) atomicMax(a.time_range + 1, __float_as_uint(tmax_seen));
+    }
+}
+
 // The shadow rays as Jobs: a quad walks the work records g, g + stride, ...; next() loads a record
 // (the quad reads its 64 bytes as one line, lane c = chunk c) and aims at the microphone
 // (kernel.cpp:463-469), done() finishes the Impulse in place (kernel.cpp:471-490).
@@ -1839,12 +1677,7 @@ struct ShadowJob {
         if (nonzero) {
             const float t = seconds_per_meter() * dist;
             if (a.npairs > 1) {
-                // one range per pair: a quad's lane 0 updates it, and only when a plain read says the value can still move
-                if (c == 0) {
-                    const volatile uint32_t * seen = a.time_range + 2u * pair;
-                    if (t != 0.0f && __float_as_uint(t) < seen[0]) atomicMin(a.time_range + 2u * pair, __float_as_uint(t));
-                    if (__float_as_uint(t) > seen[1]) atomicMax(a.time_range + 2u * pair + 1u, __float_as_uint(t));
-                }
+                if (c == 0) time_range_of_pair(a, pair, t);
             } else {
                 if (t != 0.0f) tmin = fminf(tmin, t);
                 tmax_seen = fmaxf(tmax_seen, t);
@@ -1853,18 +1686,6 @@ struct ShadowJob {
     }
 };
 
-#ifndef RVB_SHADOW_PAIR_WAVES
-#define RVB_SHADOW_PAIR_WAVES 5
-#endif
-#ifndef RVB_SHADOW_PRIO
-#define RVB_SHADOW_PRIO 0
-#endif
-#ifndef RVB_PATH_PRIO
-#define RVB_PATH_PRIO 0
-#endif
-#ifndef RVB_SHADOW_WAVES
-#define RVB_SHADOW_WAVES 8     // 64 VGPRs (8 waves/SIMD): 1.845 -> 1.807 ms against 7
-#endif
 template <bool SURF_LDS>
 __global__ __launch_bounds__(WAVE, RVB_SHADOW_WAVES) void shadow_kernel(TraceArgs a)
 {
@@ -1884,9 +1705,6 @@ __global__ __launch_bounds__(WAVE, RVB_SHADOW_WAVES) void shadow_kernel(TraceArg
     job.tmax_seen = 0.0f;
     job.surf_lds = stage_surfaces(a, stack_lds + a.stack_entries * QUADS_PER_BLOCK);
     job.skip = RVB_BVH_EMPTY;
-#if RVB_SHADOW_JOBS
-    traverse_jobs<true>(a.scene, stack_lds + q, job);
-#else
     // one record per quad per pass: the 16 quads of the wave start and finish a pass together
     v3 o, d;
     float tmax;
@@ -1895,17 +1713,7 @@ __global__ __launch_bounds__(WAVE, RVB_SHADOW_WAVES) void shadow_kernel(TraceArg
         const bool blocked = traverse_quad<true>(a.scene, o, d, tmax, stack_lds + q, h, job.skip);
         job.done(blocked, h);
     }
-#endif
-    float tmin = job.tmin, tmax_seen = job.tmax_seen;
-    for (int off = 32; off > 0; off >>= 1) {
-        tmin = fminf(tmin, __shfl_xor(tmin, off));
-        tmax_seen = fmaxf(tmax_seen, __shfl_xor(tmax_seen, off));
-    }
-    if (threadIdx.x == 0 && a.npairs <= 1) {      // non-negative floats order like their bit patterns
-        const volatile uint32_t * seen = a.time_range;    // skip the atomic when it cannot move the result (stale reads are harmless)
-        if (tmin != __builtin_inff() && __float_as_uint(tmin) < seen[0]) atomicMin(a.time_range + 0, __float_as_uint(tmin));
-        if (__float_as_uint(tmax_seen) > seen[1]) atomicMax(a.time_range + 1, __float_as_uint(tmax_seen));
-    }
+    time_range_of_wave(a, job.tmin, job.tmax_seen);
 }
 
 // shadow_kernel with two lanes per record: lane 0 carries chunks 0 and 2 of the 64-byte record (bands 0-3; hit point, DIFF), lane 1
@@ -1914,9 +1722,6 @@ template <bool SURF_LDS>
 __global__ __launch_bounds__(WAVE, RVB_SHADOW_PAIR_WAVES) void shadow_pair_kernel(TraceArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t stack_lds[];   // [stack_entries][PAIRS_PER_BLOCK]
-#if RVB_SHADOW_PRIO
-    __builtin_amdgcn_s_setprio(RVB_SHADOW_PRIO);      // experiment: the shadow waves win the issue arbitration against resident path waves of the other group
-#endif
     const uint32_t h = threadIdx.x & 1u;
     const uint32_t q = threadIdx.x >> 1;
     uint32_t * stack = stack_lds + q;
@@ -1969,7 +1774,7 @@ __global__ __launch_bounds__(WAVE, RVB_SHADOW_PAIR_WAVES) void shadow_pair_kerne
         nonzero |= dpp_u<QP_SWAP1>(nonzero);
         if (nonzero) {
             if (a.npairs > 1) {
-                if (h == 0) {
+                if (h == 0) {       // time_range_of_pair, written out: through the helper this kernel's registers are allocated differently
                     const volatile uint32_t * seen = a.time_range + 2u * pair;
                     if (t != 0.0f && __float_as_uint(t) < seen[0]) atomicMin(a.time_range + 2u * pair, __float_as_uint(t));
                     if (__float_as_uint(t) > seen[1]) atomicMax(a.time_range + 2u * pair + 1u, __float_as_uint(t));
@@ -1980,15 +1785,7 @@ __global__ __launch_bounds__(WAVE, RVB_SHADOW_PAIR_WAVES) void shadow_pair_kerne
             }
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        tmin = fminf(tmin, __shfl_xor(tmin, off));
-        tmax_seen = fmaxf(tmax_seen, __shfl_xor(tmax_seen, off));
-    }
-    if (threadIdx.x == 0 && a.npairs <= 1) {
-        const volatile uint32_t * seen = a.time_range;
-        if (tmin != __builtin_inff() && __float_as_uint(tmin) < seen[0]) atomicMin(a.time_range + 0, __float_as_uint(tmin));
-        if (__float_as_uint(tmax_seen) > seen[1]) atomicMax(a.time_range + 1, __float_as_uint(tmax_seen));
-    }
+    time_range_of_wave(a, tmin, tmax_seen);
 }
 
 // shadow_pair_kernel with ONE lane per record (round 4, RVB_SHADOW_LANES=1): 64 records per wave pass, every lane walks its own any-hit
@@ -2115,24 +1912,14 @@ __global__ __launch_bounds__(WAVE, RVB_LANE_WAVES) void shadow_lane_kernel(Trace
                           || o_hi.x != 0.0f || o_hi.y != 0.0f || o_hi.z != 0.0f || o_hi.w != 0.0f;
         if (nonzero) {
             if (a.npairs > 1) {
-                const volatile uint32_t * seen = a.time_range + 2u * pair;
-                if (t != 0.0f && __float_as_uint(t) < seen[0]) atomicMin(a.time_range + 2u * pair, __float_as_uint(t));
-                if (__float_as_uint(t) > seen[1]) atomicMax(a.time_range + 2u * pair + 1u, __float_as_uint(t));
+                time_range_of_pair(a, pair, t);
             } else {
                 if (t != 0.0f) tmin = fminf(tmin, t);
                 tmax_seen = fmaxf(tmax_seen, t);
             }
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        tmin = fminf(tmin, __shfl_xor(tmin, off));
-        tmax_seen = fmaxf(tmax_seen, __shfl_xor(tmax_seen, off));
-    }
-    if (threadIdx.x == 0 && a.npairs <= 1) {
-        const volatile uint32_t * seen = a.time_range;
-        if (tmin != __builtin_inff() && __float_as_uint(tmin) < seen[0]) atomicMin(a.time_range + 0, __float_as_uint(tmin));
-        if (__float_as_uint(tmax_seen) > seen[1]) atomicMax(a.time_range + 1, __float_as_uint(tmax_seen));
-    }
+    time_range_of_wave(a, tmin, tmax_seen);
 }
 
 }  // namespace
@@ -2140,22 +1927,30 @@ __global__ __launch_bounds__(WAVE, RVB_LANE_WAVES) void shadow_lane_kernel(Trace
 // LDS of a quad kernel's single-wave workgroup: the traversal stack, then (optionally) the surface table, then — path kernel only — the key runs
 static size_t quad_kernel_lds_bytes(const TraceArgs & a, bool key_runs = false)
 {
-    return a.stack_entries * QUADS_PER_BLOCK * sizeof(uint32_t) + (size_t) a.lds_surfaces * sizeof(rvb_surface) + RVB_LDS_NODES * 64u
+    return a.stack_entries * QUADS_PER_BLOCK * sizeof(uint32_t) + (size_t) a.lds_surfaces * sizeof(rvb_surface)
            + (key_runs && a.sort_keys16 ? QUADS_PER_BLOCK * RVB_KEY_RUN * sizeof(uint16_t) : 0u);
 }
 
-// LDS of the two-lane path kernel's single-wave workgroup: stack, surface table, (experiment: top nodes), the lanes' cold words
+// LDS of the two-lane path kernel's single-wave workgroup: stack, surface table, key runs
 static size_t rvb_pair_lds_bytes(const TraceArgs & a)
 {
-    return a.stack_entries * PAIRS_PER_BLOCK * sizeof(uint32_t) + (size_t) a.lds_surfaces * sizeof(rvb_surface) + RVB_LDS_NODES * 64u
-           + (RVB_PAIR_COLD ? 5u * WAVE * sizeof(float) : 0u) + (a.sort_keys16 ? PAIRS_PER_BLOCK * RVB_KEY_RUN * sizeof(uint16_t) : 0u);
+    return a.stack_entries * PAIRS_PER_BLOCK * sizeof(uint32_t) + (size_t) a.lds_surfaces * sizeof(rvb_surface)
+           + (a.sort_keys16 ? PAIRS_PER_BLOCK * RVB_KEY_RUN * sizeof(uint16_t) : 0u);
 }
 
 // LDS of the one-lane path kernel's single-wave workgroup: a stack column per lane (one slack row), surface table, a key run per lane
 static size_t rvb_lane_lds_bytes(const TraceArgs & a)
 {
     return (a.stack_entries + 1u) * LANE_RAYS * sizeof(uint32_t) + (size_t) a.lds_surfaces * sizeof(rvb_surface)
-           + (a.sort_keys16 ? LANE_RAYS * RVB_KEY_RUN * sizeof(uint16_t) : 0u) + (RVB_LANE_COOP ? 4u * RVB_LANE_STAGE_STRIDE : 0u);
+           + (a.sort_keys16 ? LANE_RAYS * RVB_KEY_RUN * sizeof(uint16_t) : 0u);
+}
+
+// KERNEL<true> when the launch stages the surface table in LDS, KERNEL<false> otherwise: single-wave workgroups
+template <class Args>
+static void launch_by_surfaces(void (*staged)(Args), void (*plain)(Args), uint32_t lds_surfaces, uint64_t blocks, size_t lds, hipStream_t s,
+                               const Args & args)
+{
+    hipLaunchKernelGGL(lds_surfaces ? staged : plain, dim3((unsigned) blocks), dim3(WAVE), lds, s, args);
 }
 
 uint32_t rvb_lds_surfaces(uint32_t stack_entries, uint64_t nsurfaces)
@@ -2164,17 +1959,16 @@ uint32_t rvb_lds_surfaces(uint32_t stack_entries, uint64_t nsurfaces)
     static const bool off = getenv("RVB_LDS_SURFACES") && getenv("RVB_LDS_SURFACES")[0] == '0';
     const size_t budget = (160u * 1024u) / 32u;
     const size_t stack = (size_t) stack_entries * QUADS_PER_BLOCK * sizeof(uint32_t) + QUADS_PER_BLOCK * RVB_KEY_RUN * sizeof(uint16_t);
-    // ... and the two-lane kernels (twice the stack and key runs per workgroup, the cold words) want 5 waves/SIMD = 20 workgroups per CU
+    // ... and the two-lane kernels (twice the stack and key runs per workgroup) want 5 waves/SIMD = 20 workgroups per CU
     const size_t pair_budget = (160u * 1024u) / 20u;
-    const size_t pair_stack = (size_t) stack_entries * PAIRS_PER_BLOCK * sizeof(uint32_t) + PAIRS_PER_BLOCK * RVB_KEY_RUN * sizeof(uint16_t)
-                              + (RVB_PAIR_COLD ? 5u * WAVE * sizeof(float) : 0u);
+    const size_t pair_stack = (size_t) stack_entries * PAIRS_PER_BLOCK * sizeof(uint32_t) + PAIRS_PER_BLOCK * RVB_KEY_RUN * sizeof(uint16_t);
     if (off || nsurfaces == 0 || stack + nsurfaces * sizeof(rvb_surface) > budget || pair_stack + nsurfaces * sizeof(rvb_surface) > pair_budget)
         return 0;
     return (uint32_t) nsurfaces;
 }
 
 // Lanes per ray of the path kernel.  Per ray-bounce the pair kernel issues 17 % fewer VALU instructions than the quad kernel (the
-// vote, stack and reduction work is per ray and every lane of the ray repeats it), but it has half the waves: it pays when the rays
+// schedule, stack and reduction work is per ray and every lane of the ray repeats it), but it has half the waves: it pays when the rays
 // in flight fill the chip without the extra waves — one resident round of pair waves at 6 waves per SIMD is 6 x 1024 x 32 rays.
 // Measured at workload C2 sizes (path kernel alone, ms per 100 k rays, quads / pairs): 100 k rays 3.60 / 3.79, 200 k 3.12 / 3.13,
 // 400 k 2.77 / 2.49, 1 M 2.51 / 2.16; two 100 k traces in flight (the bench pipeline): 5.32 / 5.11 ms per IR.
@@ -2201,13 +1995,8 @@ void rvb_launch_path(const TraceArgs & a, hipStream_t s)
     }
     const unsigned blocks = (unsigned) ((a.nrays + QUADS_PER_BLOCK - 1) / QUADS_PER_BLOCK);
     const bool seven = a.nrays <= 7ull * 1024ull * QUADS_PER_BLOCK;      // fits in seven waves per SIMD: the 72-register build
-    if (a.lds_surfaces) {
-        if (seven) hipLaunchKernelGGL((path_kernel<true, 7>), dim3(blocks), dim3(WAVE), quad_kernel_lds_bytes(a, true), s, a);
-        else hipLaunchKernelGGL((path_kernel<true, 8>), dim3(blocks), dim3(WAVE), quad_kernel_lds_bytes(a, true), s, a);
-    } else {
-        if (seven) hipLaunchKernelGGL((path_kernel<false, 7>), dim3(blocks), dim3(WAVE), quad_kernel_lds_bytes(a, true), s, a);
-        else hipLaunchKernelGGL((path_kernel<false, 8>), dim3(blocks), dim3(WAVE), quad_kernel_lds_bytes(a, true), s, a);
-    }
+    launch_by_surfaces(seven ? path_kernel<true, 7> : path_kernel<true, 8>, seven ? path_kernel<false, 7> : path_kernel<false, 8>,
+                       a.lds_surfaces, blocks, quad_kernel_lds_bytes(a, true), s, a);
 }
 
 // (the caller checked: every trace has the same lane count, stack depth, number of surfaces staged in LDS and key form)
@@ -2227,16 +2016,8 @@ void rvb_launch_path_group(const TraceArgs * traces, uint32_t count, hipStream_t
     for (uint32_t k = count; k < RVB_MAX_GROUP; ++k) g.trace[k] = traces[0];
     size_t lds = 0;                          // (the largest of the traces', should a caller ever group traces whose layouts differ in size)
     for (uint32_t k = 0; k < count; ++k) lds = std::max(lds, a.path_lanes == 1 ? rvb_lane_lds_bytes(traces[k]) : rvb_pair_lds_bytes(traces[k]));
-    // measurement: an LDS request per workgroup that caps the path waves per CU (160 KiB / bytes), leaving wave slots and registers to other kernels
-    static const size_t lds_floor = getenv("RVB_PATH_LDS_BYTES") ? strtoull(getenv("RVB_PATH_LDS_BYTES"), nullptr, 10) : 0;
-    lds = std::max(lds, lds_floor);
-    if (a.path_lanes == 1) {
-        if (a.lds_surfaces) hipLaunchKernelGGL(path_lane_group_kernel<true>, dim3(blocks), dim3(WAVE), lds, s, g);
-        else hipLaunchKernelGGL(path_lane_group_kernel<false>, dim3(blocks), dim3(WAVE), lds, s, g);
-        return;
-    }
-    if (a.lds_surfaces) hipLaunchKernelGGL(path_pair_group_kernel<true>, dim3(blocks), dim3(WAVE), lds, s, g);
-    else hipLaunchKernelGGL(path_pair_group_kernel<false>, dim3(blocks), dim3(WAVE), lds, s, g);
+    if (a.path_lanes == 1) launch_by_surfaces(path_lane_group_kernel<true>, path_lane_group_kernel<false>, a.lds_surfaces, blocks, lds, s, g);
+    else launch_by_surfaces(path_pair_group_kernel<true>, path_pair_group_kernel<false>, a.lds_surfaces, blocks, lds, s, g);
 }
 
 void rvb_launch_images(const TraceArgs & a, hipStream_t s)
@@ -2259,27 +2040,20 @@ void rvb_launch_shadow(const TraceArgs & a, hipStream_t s)
 {
     const uint64_t total = a.nrays * (uint64_t) a.nreflections;
     if (total == 0) return;
-    uint64_t blocks = (total + QUADS_PER_BLOCK - 1) / QUADS_PER_BLOCK;
-    static const uint64_t per_cu = getenv("RVB_SHADOW_WG_PER_CU") ? strtoull(getenv("RVB_SHADOW_WG_PER_CU"), nullptr, 10) : 256;
-    if (blocks > 256u * per_cu) blocks = 256u * per_cu;     // single-wave workgroups per CU; records beyond are grid-strided
-    if (rvb_shadow_lanes() == 1) {
-        blocks = (total + LANE_RAYS - 1) / LANE_RAYS;
-        static const uint64_t lane_per_cu = getenv("RVB_SHADOW_WG_PER_CU") ? strtoull(getenv("RVB_SHADOW_WG_PER_CU"), nullptr, 10) : 128;
-        if (blocks > 256u * lane_per_cu) blocks = 256u * lane_per_cu;
-        const size_t lds = (a.stack_entries + 1u) * LANE_RAYS * sizeof(uint32_t) + (size_t) a.lds_surfaces * sizeof(rvb_surface);
-        if (a.lds_surfaces) hipLaunchKernelGGL(shadow_lane_kernel<true>, dim3((unsigned) blocks), dim3(WAVE), lds, s, a);
-        else hipLaunchKernelGGL(shadow_lane_kernel<false>, dim3((unsigned) blocks), dim3(WAVE), lds, s, a);
-        return;
-    }
-    if (rvb_shadow_lanes() == 2) {
-        blocks = (total + PAIRS_PER_BLOCK - 1) / PAIRS_PER_BLOCK;
-        static const uint64_t pair_per_cu = getenv("RVB_SHADOW_WG_PER_CU") ? strtoull(getenv("RVB_SHADOW_WG_PER_CU"), nullptr, 10) : 256;
-        if (blocks > 256u * pair_per_cu) blocks = 256u * pair_per_cu;
-        const size_t lds = a.stack_entries * PAIRS_PER_BLOCK * sizeof(uint32_t) + (size_t) a.lds_surfaces * sizeof(rvb_surface);
-        if (a.lds_surfaces) hipLaunchKernelGGL(shadow_pair_kernel<true>, dim3((unsigned) blocks), dim3(WAVE), lds, s, a);
-        else hipLaunchKernelGGL(shadow_pair_kernel<false>, dim3((unsigned) blocks), dim3(WAVE), lds, s, a);
-        return;
-    }
-    if (a.lds_surfaces) hipLaunchKernelGGL(shadow_kernel<true>, dim3((unsigned) blocks), dim3(WAVE), quad_kernel_lds_bytes(a), s, a);
-    else hipLaunchKernelGGL(shadow_kernel<false>, dim3((unsigned) blocks), dim3(WAVE), quad_kernel_lds_bytes(a), s, a);
+    // single-wave workgroups per CU (RVB_SHADOW_WG_PER_CU, else the kernel's default); records beyond are grid-strided
+    static const char * const per_cu_env = getenv("RVB_SHADOW_WG_PER_CU");
+    static const uint64_t per_cu_set = per_cu_env ? strtoull(per_cu_env, nullptr, 10) : 0;
+    const uint32_t lanes = rvb_shadow_lanes();
+    const uint32_t per_block = lanes == 1 ? LANE_RAYS : (lanes == 2 ? PAIRS_PER_BLOCK : QUADS_PER_BLOCK);     // records per workgroup
+    const uint64_t per_cu = per_cu_env ? per_cu_set : (lanes == 1 ? 128 : 256);
+    const uint64_t blocks = std::min<uint64_t>((total + per_block - 1) / per_block, 256u * per_cu);
+    const size_t surfaces = (size_t) a.lds_surfaces * sizeof(rvb_surface);
+    if (lanes == 1)
+        launch_by_surfaces(shadow_lane_kernel<true>, shadow_lane_kernel<false>, a.lds_surfaces, blocks,
+                           (a.stack_entries + 1u) * LANE_RAYS * sizeof(uint32_t) + surfaces, s, a);
+    else if (lanes == 2)
+        launch_by_surfaces(shadow_pair_kernel<true>, shadow_pair_kernel<false>, a.lds_surfaces, blocks,
+                           a.stack_entries * PAIRS_PER_BLOCK * sizeof(uint32_t) + surfaces, s, a);
+    else
+        launch_by_surfaces(shadow_kernel<true>, shadow_kernel<false>, a.lds_surfaces, blocks, quad_kernel_lds_bytes(a), s, a);
 }

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Developer tool: the instruction mix of the two-lane path kernel's vote loop by STEP KIND, from the ISA.
+"""Developer tool: the instruction mix of the two-lane path kernel's loop by STEP KIND, from the ISA.
 
     tools/isa_mix.py [node_steps leaf_steps done_steps]      (wave-level steps per bounce, default: tools/travsim.cpp on workload C2)
 
-Compiles csrc/trace_kernels.hip with -DRVB_ISA_MARKS=1 (comment lines at the borders of the vote / node / leaf / shading blocks of
-traverse_pairs_vote; the marked build is never shipped: the markers are volatile asm and pin the block order), classifies every
+Compiles csrc/trace_kernels.hip with -DRVB_ISA_MARKS=1 through the Makefile's `asm` target (comment lines at the borders of the
+schedule / node / leaf / shading blocks of traverse_pairs_cycle, the first still marked "vote"; the marked build is never shipped: the markers are volatile asm and pin the block order), classifies every
 instruction of path_pair_kernel between the markers and weights the three step kinds with the wave-level step counts of one bounce.
 Answers what the PMC class counters cannot: what the "other" VALU instructions (neither f32 add / mul / fma nor integer) ARE."""
 import collections
@@ -69,9 +69,8 @@ def issue_cost(line):
 def main():
     steps = [float(x) for x in sys.argv[1:4]] if len(sys.argv) >= 4 else [23.73, 6.30, 3.18]      # travforms (TRAVFORMS_CYCLE=34,25), C2, 32 rays per wave; the majority vote of rounds 1-3: 28.66 5.14 2.57
     asm = "/tmp/isa_mix.s"
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-                           "-fhip-fp32-correctly-rounded-divide-sqrt", "-munsafe-fp-atomics", "-fno-slp-vectorize", "--cuda-device-only",
-                           "-DRVB_ISA_MARKS=1", *os.environ.get("ISA_MIX_FLAGS", "").split(), "-S", "-o", asm, os.path.join(PKG, "csrc", "trace_kernels.hip")], cwd=PKG)
+    subprocess.check_call(["make", "-s", "asm", "SRC=csrc/trace_kernels.hip", "OUT=" + asm,
+                           "EXTRA=-DRVB_ISA_MARKS=1 " + os.environ.get("ISA_MIX_FLAGS", "")], cwd=PKG)
     text = open(asm).read()
     start = text.index("_ZN12_GLOBAL__N_122path_pair_group_kernelILb1EEEvNS_10TraceGroupE:")
     body = text[start:text.index("s_endpgm", start)]
@@ -92,7 +91,7 @@ def main():
         blocks[current][classify(op)] += 1
         cost[current] += issue_cost(line)
     weights = {"vote": steps[0], "node": steps[0], "leaf": steps[1], "done": steps[2]}      # one loop iteration per node step
-    print("static instruction counts per block of traverse_pairs_vote (path_pair_kernel<true>), and per bounce of one wave (32 rays)")
+    print("static instruction counts per block of traverse_pairs_cycle (path_pair_group_kernel<true>), and per bounce of one wave (32 rays)")
     print("weights = wave-level executions per bounce: %s" % weights)
     total = collections.Counter()
     for name, counter in blocks.items():

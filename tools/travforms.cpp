@@ -202,7 +202,7 @@ struct RayState { v3 o, d; uint32_t bounce, skip, tri; bool alive; uint32_t id; 
 
 struct Result { double ray_node, ray_leaf, wave_node, wave_leaf, wave_done, act_node, act_leaf, act_done, cost; unsigned long long bounces; unsigned long long checksum; };
 
-// one wave runs its rays for up to `bounces_here` bounces each (vote loop of traverse_pairs_vote)
+// one wave runs its rays for up to `bounces_here` bounces each (loop of traverse_pairs_cycle)
 static unsigned long long g_votes = 0;
 static const bool g_chain = getenv("TRAVFORMS_CHAIN") != nullptr;
 static const int g_double = getenv("TRAVFORMS_DOUBLE") ? atoi(getenv("TRAVFORMS_DOUBLE")) : 0;
