@@ -1,0 +1,202 @@
+// ctx.h — the context behind include/rvb_capi.h and what its translation units share:
+//   context.hip  life cycle, scene, directions, timings, diagnostics
+//   trace.hip    the trace in three steps, its results, rvb_merge_images
+//   memory.hip   caller-owned device / pinned memory, staged host copies, the export stream
+//   sort.hip     the sorts the other stages call, "sorted list and bin boundaries"
+//   ir.hip       materialised attenuate / flatten, the fused impulse-response stage
+// No compute happens in them and nothing falls back to the CPU: every entry point that produces results launches the HIP kernels
+// of trace_kernels.hip / stream_kernels.hip / wide_kernels.hip.
+#pragma once
+
+#include "../../include/rvb_capi.h"
+#include "hip_owned.h"
+#include "kernels.h"
+
+#include <cmath>
+#include <cstddef>
+#include <memory>
+#include <string>
+#include <vector>
+
+#pragma GCC visibility push(hidden)
+
+// The scene's device buffers: built and uploaded once (rvb_set_scene), read by every context that holds the store (rvb_share_scene) —
+// one copy in HBM, and ONE copy for the L2s to keep, however many contexts trace in it side by side.  Freed with its last holder.
+struct SceneStore {
+    int device = 0;
+    DevBuf nodes, tris, shade, corners, surfaces;
+    ~SceneStore() { (void) hipSetDevice(device); }
+};
+
+// The small result block of a trace: one per context on the device, fetched into its pinned host mirror once per trace (fetch_small).
+struct SmallBlock {
+    uint32_t candidate_count;           // image-source candidates (image kernels)
+    uint32_t pad0_;
+    unsigned long long executed;        // bounces executed
+    uint32_t range[2];                  // float bits: time range of the HRTF model's attenuated impulses (time_range_kernel)
+    uint32_t max_time_bits;             // rvb_flatten: latest attenuated time
+    uint32_t pad1_;
+    uint32_t trace_range[2];            // float bits: time range of the traced diffuse impulses (shadow_kernel)
+    uint32_t image_item_count;          // entries of the image-source work list (image_plan_kernel)
+    uint32_t pad2_[5];
+    rvb_impulse direct;
+};
+static_assert(offsetof(SmallBlock, candidate_count) == 0 && offsetof(SmallBlock, executed) == 8, "small block layout");
+static_assert(offsetof(SmallBlock, range) == 16 && offsetof(SmallBlock, max_time_bits) == 24, "small block layout");
+static_assert(offsetof(SmallBlock, trace_range) == 32 && offsetof(SmallBlock, image_item_count) == 40, "small block layout");
+static_assert(offsetof(SmallBlock, direct) == 64 && sizeof(SmallBlock) == 128, "small block layout");
+const size_t kFirstCandidates = 32;
+
+struct Timing { std::string name; hipEvent_t start, stop; };       // (events of the context's pool)
+
+struct rvb_ctx {
+    int device = 0;
+    // (declared first: destroyed last, after everything that work on them may use)
+    Stream stream;
+    Stream side_stream;                         // image_kernel runs here, beside the record grouping
+    Stream export_stream;                       // rvb_copy_to_pinned_host_async: results leave for the host beside the next trace
+    Event export_ready;
+    Event path_done, side_done;
+    Event prep_done, group_done;                // rvb_trace_group: this context's fills are enqueued / the group's path kernel is
+    std::string error;
+    std::string arch;
+    int compute_units = 0;
+    uint64_t hbm_bytes = 0;
+
+    // scene
+    bool have_scene = false;
+    std::shared_ptr<SceneStore> store;          // (its own after rvb_set_scene, another context's after rvb_share_scene)
+    SceneDev scene;
+    uint64_t nnodes = 0, kept = 0;
+    uint32_t depth = 0;
+    uint32_t stack_need = RVB_BVH_STACK;
+    uint64_t nsurfaces = 0;
+
+    // rays + trace results
+    DevBuf directions_own;
+    const float4 * directions = nullptr;
+    uint64_t nrays = 0;
+    uint32_t concurrent_traces = 1;             // rvb_set_concurrent_traces
+    uint32_t path_lanes = 0;                    // rvb_set_path_lanes: 0 = chosen per launch (rvb_path_lanes_for)
+    bool range_pending = false;                 // rvb_ir_time_range_begin has enqueued the HRTF time-range pass of the current configuration
+    int hrtf_table_ears = 0;                    // ears of the HRTF table on the device: 2 after rvb_ir_configure_hrtf, 1 after the one-ear attenuate calls
+    bool traced = false;
+    uint64_t nreflections = 0;
+    float mic[3] = {0, 0, 0};
+    // last trace: npairs (source, microphone) pairs x nrays rays each; the IR stage works on one pair's slice at a time
+    uint64_t npairs = 1, traced_rays = 0, ir_pair = 0;
+    std::vector<float> pair_mics_host;          // [npairs][3]
+    DevBuf pair_geom, pair_direct, pair_range;   // device: mics+sources [2*npairs] float4, direct [npairs] Impulse, ranges [npairs][2]
+    PinnedBuf pair_stage;                        // pinned staging of the per-pair geometry of a launch
+    Event pair_stage_free;
+    std::vector<rvb_impulse> pair_direct_host;
+    std::vector<uint32_t> pair_range_host;
+    DevBuf image_items;                          // work list of the image-source check kernel
+    DevBuf impulses, early, candidates, small, stamps, sort_keys, sort_scratch, sort_order, group_temp;       // small: one SmallBlock
+    // host mirror of `small`, fetched once per trace together with the first few image-source candidates (usually all of them).
+    // One PINNED block: a device-to-host copy into pageable memory is staged by the runtime and blocks the host per call (three
+    // round trips of 30-160 us between the shadow kernel and the binning stage in a kernel trace); into pinned memory the copies
+    // are asynchronous and the host waits once.
+    PinnedBuf host_block;
+    SmallBlock * small_host = nullptr;          // the start of host_block
+    rvb_image_candidate * first_candidates = nullptr;   // [kFirstCandidates], behind small_host in the same block
+    uint32_t * range_host = nullptr;            // [2] behind them: where the HRTF time-range pass lands (rvb_ir_time_range_begin)
+    bool small_valid = false;
+    bool stamps_cleared = false;
+    std::vector<Timing> timings;
+    std::vector<Event> event_pool;
+    size_t events_used = 0;
+    bool timing_failed = false;                 // an event could not be created: timings are dropped, the work itself is unaffected
+    bool timing_open = false;
+
+    // impulse-response stage
+    bool ir_configured = false;
+    AttenuationModel model;
+    int which = RVB_IR_ALL;
+    DevBuf images, hrtf_table, acc, keys_a, keys_b, vals_a, vals_b, sort_temp, scratch_in, scratch_out, hist, bin_starts;
+    DevBuf flat_in;                              // rvb_flatten's upload: a buffer of its own, so that no other entry point overwrites it between a size query and the fill
+    DevBuf own_sort_temp, own_sort_keys, own_sort_values;      // csrc/radix_sort.hip: tile counters, the intermediate (key, value) pair
+    uint64_t nimages = 0;
+    std::vector<rvb_impulse> images_host;
+    DevBuf speakers;                             // more than 8 speakers: AttenuationModel::speaker_table, uploaded in stream order at configure
+    std::vector<float4> speakers_host;
+    // exact mode in two steps (rvb_ir_exact_prepare / rvb_ir_exact_fold): what the sorted list in keys_b / vals_b / bin_starts was prepared for
+    struct ExactState { bool valid = false; bool hrtf_combined = false; uint64_t nbins = 0, n = 0, ndiffuse = 0, nimages = 0; } exact;
+
+    // staged host copies (rvb_copy_to_host / rvb_copy_to_device): per worker thread a stream and two pinned bounce buffers
+    struct CopyLane { Stream stream; PinnedBuf pinned[2]; Event done[2]; };
+    std::vector<CopyLane> copy_lanes;
+    // rvb_flatten remembers what it uploaded for a size query, so that the fill that follows does not upload and key it again.
+    // The array sits in flat_in (written by rvb_flatten only), its keys in keys_a / vals_a: every other writer of those two
+    // (rvb_ir_accumulate in exact mode, rvb_flatten_device) clears flat_host, and so does a reallocation of the sort buffers.
+    const void * flat_host = nullptr;
+    uint64_t flat_n = 0, flat_bins = 0;
+    float flat_rate = 0.0f;
+
+    ~rvb_ctx()
+    {
+        (void) hipSetDevice(device);
+        for (hipStream_t s : {stream.h, side_stream.h, export_stream.h})
+            if (s) (void) hipStreamSynchronize(s);
+    }
+
+    SmallBlock * small_dev() const { return small.as<SmallBlock>(); }
+    hipEvent_t next_event()
+    {
+        if (events_used == event_pool.size()) {
+            Event e;
+            if (hipEventCreate(&e.h) != hipSuccess) { timing_failed = true; return nullptr; }
+            event_pool.push_back(std::move(e));
+        }
+        return event_pool[events_used++];
+    }
+    void begin_timing(const char * name, hipStream_t on = nullptr)
+    {
+        Timing t;
+        t.name = name;
+        t.start = next_event();
+        t.stop = next_event();
+        timing_open = t.start && t.stop;
+        if (!timing_open) return;
+        (void) hipEventRecord(t.start, on ? on : stream.h);
+        timings.push_back(t);
+    }
+    void end_timing(hipStream_t on = nullptr) { if (timing_open) (void) hipEventRecord(timings.back().stop, on ? on : stream.h); timing_open = false; }
+    void reset_timings() { timings.clear(); events_used = 0; }
+};
+
+// ctx == NULL: the text of a failed rvb_create, per thread (rvb_last_error(NULL))
+int fail(rvb_ctx * ctx, int code, const std::string & what);
+#define RVB_BIND(ctx) RVB_HIP(fail, ctx, hipSetDevice((ctx)->device))
+
+// the diffuse impulses the IR stage works on: the slice of the pair chosen with rvb_ir_select_pair (pair 0 of 1 otherwise)
+inline const rvb_impulse * ir_diffuse(const rvb_ctx * ctx)
+{
+    return ctx->impulses.as<rvb_impulse>() + ctx->ir_pair * ctx->nrays * ctx->nreflections;
+}
+
+inline uint64_t bins_for(float max_time, float predelay, float sample_rate)
+{
+    const float t = max_time > predelay ? max_time - predelay : 0.0f;   // rayverb.h:89
+    return (uint64_t) (roundf(t * sample_rate) + 1);                    // rayverb.cpp:57
+}
+
+inline int key_bits_for(uint64_t nbins)
+{
+    int bits = 1;
+    while (bits < 32 && (1ull << bits) < nbins + 1)
+        ++bits;
+    return bits;
+}
+
+// trace.hip: one synchronising 128-byte read per trace serves candidate count, direct path, time range, bounce count
+int fetch_small(rvb_ctx * ctx);
+
+// sort.hip
+bool own_sort_enabled();
+int own_sort(rvb_ctx * ctx, const uint32_t * keys, uint32_t value_base, uint64_t n, int begin_bit, int end_bit,
+             uint32_t * keys_out, uint32_t * values_out, bool want_keys);
+int ensure_sort_buffers(rvb_ctx * ctx, uint64_t n);
+int sort_and_bin(rvb_ctx * ctx, uint64_t n, uint64_t nkeys, int key_bits, bool may_sort_own);
+
+#pragma GCC visibility pop

@@ -16,17 +16,14 @@
 //                 xGMI, loaded from librccl.so at run time; devices that RCCL cannot put in one communicator (the same GPU
 //                 listed twice, as the single-GPU tests do) are summed with peer copies and an add kernel instead.
 #include "../../include/rvb_capi.h"
-
-#define RVB_STR_(x) #x
-#define RVB_STR(x) RVB_STR_(x)      // RVB_MAX_SPEAKERS in error texts
-
-#include <hip/hip_runtime.h>
+#include "hip_owned.h"
 
 #include <dlfcn.h>
 
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -80,14 +77,20 @@ struct Shard {
     rvb_ctx * ctx = nullptr;
     int device = 0;
     uint64_t first = 0, count = 0;            // ray range
-    hipStream_t stream = nullptr;             // histogram traffic of this device
-    float * hist = nullptr;
-    size_t hist_cap = 0;
-    float * peer = nullptr;                   // landing buffer for another device's histogram (fallback sum)
-    size_t peer_cap = 0;
-    std::vector<hipEvent_t> arrived, folded;  // exact chain: block k of the histogram has landed on this device / has been folded here
+    Stream stream;                            // histogram traffic of this device
+    DevBuf hist;
+    float * histogram() const { return hist.as<float>(); }
+    DevBuf peer;                              // landing buffer for another device's histogram (fallback sum)
+    std::vector<Event> arrived, folded;       // exact chain: block k of the histogram has landed on this device / has been folded here
     int rc = RVB_OK;
     std::string error;
+    Shard() = default;
+    Shard(Shard &&) = default;
+    ~Shard()
+    {
+        (void) hipSetDevice(device);
+        if (stream) (void) hipStreamSynchronize(stream);
+    }
 };
 
 }  // namespace
@@ -104,6 +107,12 @@ struct rvb_multi {
     int peer_links = 0;                       // directed device pairs with peer access enabled (rvb_multi_create)
     float mic[3] = {0, 0, 0};
     std::vector<rvb_impulse> images;          // merged image sources of the last rvb_multi_ir_* call
+    ~rvb_multi()                              // (the contexts go first; then each shard's own stream, buffers and events)
+    {
+        for (ncclComm_t c : comms)
+            if (c) (void) rccl().CommDestroy(c);
+        for (Shard & s : shards) rvb_destroy(s.ctx);
+    }
 };
 
 namespace {
@@ -129,24 +138,6 @@ int for_each_shard(rvb_multi * m, F f)
         if (s.rc != RVB_OK) return mfail(m, s.rc, "device " + std::to_string(s.device) + ": " + s.error);
     return RVB_OK;
 }
-
-hipError_t ensure(int device, float *& p, size_t & cap, size_t bytes)
-{
-    if (bytes <= cap) return hipSuccess;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return e;
-    if (p) { (void) hipFree(p); p = nullptr; cap = 0; }
-    e = hipMalloc(reinterpret_cast<void **>(&p), bytes);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-}
-
-#define MHIP(m, call)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (call);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return mfail(m, RVB_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));            \
-    } while (0)
 
 bool distinct_devices(const rvb_multi * m)
 {
@@ -179,24 +170,16 @@ int rvb_multi_create(rvb_multi ** out, const int * devices, int ndevices, unsign
 {
     if (!out || ndevices <= 0 || ndevices > 64) return RVB_ERR_INVALID;
     *out = nullptr;
-    rvb_multi * m = new rvb_multi();
+    std::unique_ptr<rvb_multi> m(new rvb_multi());
     m->flags = flags;
+    m->shards.reserve((size_t) ndevices);
     for (int i = 0; i < ndevices; ++i) {
-        Shard s;
+        m->shards.emplace_back();
+        Shard & s = m->shards.back();
         s.device = devices ? devices[i] : i;
         const int rc = rvb_create(&s.ctx, s.device, 0);
-        if (rc != RVB_OK) {
-            for (Shard & made : m->shards) rvb_destroy(made.ctx);
-            delete m;
-            return rc;                         // rvb_last_error(NULL) holds the text
-        }
-        if (hipSetDevice(s.device) != hipSuccess || hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess) {
-            rvb_destroy(s.ctx);
-            for (Shard & made : m->shards) rvb_destroy(made.ctx);
-            delete m;
-            return RVB_ERR_HIP;
-        }
-        m->shards.push_back(s);
+        if (rc != RVB_OK) return rc;           // rvb_last_error(NULL) holds the text
+        if (hipSetDevice(s.device) != hipSuccess || hipStreamCreateWithFlags(&s.stream.h, hipStreamNonBlocking) != hipSuccess) return RVB_ERR_HIP;
     }
     // peer access between every pair of distinct devices (the chain's hops, the fallback sum's gathers): without it the runtime stages a
     // peer copy through the host.  A refusal is not an error — the copies still work, staged.
@@ -210,7 +193,7 @@ int rvb_multi_create(rvb_multi ** out, const int * devices, int ndevices, unsign
             if (e == hipSuccess || e == hipErrorPeerAccessAlreadyEnabled) ++m->peer_links;
             (void) hipGetLastError();
         }
-    *out = m;
+    *out = m.release();
     return RVB_OK;
 }
 
@@ -224,22 +207,7 @@ int rvb_multi_set_chain_blocks(rvb_multi * m, uint32_t blocks)
 
 int rvb_multi_peer_links(const rvb_multi * m) { return m ? m->peer_links : 0; }
 
-void rvb_multi_destroy(rvb_multi * m)
-{
-    if (!m) return;
-    for (ncclComm_t c : m->comms)
-        if (c) (void) rccl().CommDestroy(c);
-    for (Shard & s : m->shards) {
-        (void) hipSetDevice(s.device);
-        if (s.stream) { (void) hipStreamSynchronize(s.stream); (void) hipStreamDestroy(s.stream); }
-        for (hipEvent_t e : s.arrived) (void) hipEventDestroy(e);
-        for (hipEvent_t e : s.folded) (void) hipEventDestroy(e);
-        if (s.hist) (void) hipFree(s.hist);
-        if (s.peer) (void) hipFree(s.peer);
-        rvb_destroy(s.ctx);
-    }
-    delete m;
-}
+void rvb_multi_destroy(rvb_multi * m) { delete m; }
 
 const char * rvb_multi_last_error(const rvb_multi * m) { return m ? m->error.c_str() : rvb_last_error(nullptr); }
 
@@ -385,7 +353,7 @@ static int multi_ir(rvb_multi * m, const float mic[3], const rvb_speaker * speak
     if (!out) return RVB_OK;
     if (capacity_bins < bins) return mfail(m, RVB_ERR_CAPACITY, "rvb_multi_ir: capacity_bins too small");
     const size_t count = (size_t) bins * nch * 8, bytes = count * sizeof(float);
-    for (Shard & s : m->shards) MHIP(m, ensure(s.device, s.hist, s.hist_cap, bytes));
+    for (Shard & s : m->shards) { RVB_HIP(mfail, m, hipSetDevice(s.device)); RVB_HIP(mfail, m, s.hist.ensure(bytes)); }
     m->rccl_used_last = false;
     Shard * result = nullptr;
     if (mode == RVB_IR_EXACT) {
@@ -398,9 +366,9 @@ static int multi_ir(rvb_multi * m, const float mic[3], const rvb_speaker * speak
         const uint64_t per = ((bins + blocks - 1) / blocks + 15) & ~15ull;
         const uint64_t nblocks = (bins + per - 1) / per;
         for (Shard & s : m->shards) {
-            MHIP(m, hipSetDevice(s.device));
-            while (s.arrived.size() < nblocks) { hipEvent_t e; MHIP(m, hipEventCreateWithFlags(&e, hipEventDisableTiming)); s.arrived.push_back(e); }
-            while (s.folded.size() < nblocks) { hipEvent_t e; MHIP(m, hipEventCreateWithFlags(&e, hipEventDisableTiming)); s.folded.push_back(e); }
+            RVB_HIP(mfail, m, hipSetDevice(s.device));
+            for (std::vector<Event> * events : {&s.arrived, &s.folded})
+                while (events->size() < nblocks) { Event e; RVB_HIP(mfail, m, hipEventCreateWithFlags(&e.h, hipEventDisableTiming)); events->push_back(std::move(e)); }
         }
         const int rc_prep = for_each_shard(m, [&](Shard & s) {
             if (!(which & RVB_IR_DIFFUSE) || !s.count) return (int) RVB_OK;
@@ -411,46 +379,46 @@ static int multi_ir(rvb_multi * m, const float mic[3], const rvb_speaker * speak
         for (size_t g = 0; g < m->shards.size(); ++g) {
             Shard & s = m->shards[g];
             const bool folds = (which & RVB_IR_DIFFUSE) && s.count;
-            MHIP(m, hipSetDevice(s.device));
-            if (g == 0) MHIP(m, hipMemsetAsync(s.hist, 0, bytes, s.stream));
+            RVB_HIP(mfail, m, hipSetDevice(s.device));
+            if (g == 0) RVB_HIP(mfail, m, hipMemsetAsync(s.histogram(), 0, bytes, s.stream));
             for (uint64_t k = 0; k < nblocks; ++k) {
                 const uint64_t b0 = k * per, b1 = std::min<uint64_t>(bins, b0 + per);
                 if (g > 0) {
                     Shard & prev = m->shards[g - 1];
-                    MHIP(m, hipStreamWaitEvent(s.stream, prev.folded[k], 0));
+                    RVB_HIP(mfail, m, hipStreamWaitEvent(s.stream, prev.folded[k], 0));
                     if (prev.device == s.device) {
-                        MHIP(m, hipMemcpy2DAsync(s.hist + b0, bins * sizeof(float), prev.hist + b0, bins * sizeof(float), (b1 - b0) * sizeof(float), rows,
-                                                 hipMemcpyDeviceToDevice, s.stream));
+                        RVB_HIP(mfail, m, hipMemcpy2DAsync(s.histogram() + b0, bins * sizeof(float), prev.histogram() + b0, bins * sizeof(float), (b1 - b0) * sizeof(float), rows,
+                                                           hipMemcpyDeviceToDevice, s.stream));
                     } else {
                         for (uint64_t r = 0; r < rows; ++r)     // (a row's piece of the block is contiguous: one peer copy each)
-                            MHIP(m, hipMemcpyPeerAsync(s.hist + r * bins + b0, s.device, prev.hist + r * bins + b0, prev.device, (b1 - b0) * sizeof(float), s.stream));
+                            RVB_HIP(mfail, m, hipMemcpyPeerAsync(s.histogram() + r * bins + b0, s.device, prev.histogram() + r * bins + b0, prev.device, (b1 - b0) * sizeof(float), s.stream));
                     }
                 }
-                MHIP(m, hipEventRecord(s.arrived[k], s.stream));
+                RVB_HIP(mfail, m, hipEventRecord(s.arrived[k], s.stream));
                 if (folds) {
                     int rc = rvb_wait_for_event(s.ctx, s.arrived[k]);
-                    if (rc == RVB_OK) rc = rvb_ir_exact_fold(s.ctx, bins, b0, b1, s.hist);
+                    if (rc == RVB_OK) rc = rvb_ir_exact_fold(s.ctx, bins, b0, b1, s.histogram());
                     if (rc == RVB_OK) rc = rvb_record_event(s.ctx, s.folded[k]);
                     if (rc != RVB_OK) return mfail(m, rc, rvb_last_error(s.ctx));
                 } else {
-                    MHIP(m, hipEventRecord(s.folded[k], s.stream));          // nothing to add here: the block passes through
+                    RVB_HIP(mfail, m, hipEventRecord(s.folded[k], s.stream));          // nothing to add here: the block passes through
                 }
             }
         }
         // the last device's folds are the end of the chain (a device without impulses only passed blocks on its own stream)
-        MHIP(m, hipSetDevice(last.device));
-        MHIP(m, hipStreamSynchronize(last.stream));
+        RVB_HIP(mfail, m, hipSetDevice(last.device));
+        RVB_HIP(mfail, m, hipStreamSynchronize(last.stream));
         { const int rc = rvb_synchronize(last.ctx); if (rc != RVB_OK) return mfail(m, rc, rvb_last_error(last.ctx)); }
         result = &last;
     } else if (mode == RVB_IR_FAST) {
         // 2b. all shards at once, then one sum over the devices
         int rc = for_each_shard(m, [&](Shard & s) {
-            if (hipSetDevice(s.device) != hipSuccess || hipMemsetAsync(s.hist, 0, bytes, s.stream) != hipSuccess ||
+            if (hipSetDevice(s.device) != hipSuccess || hipMemsetAsync(s.histogram(), 0, bytes, s.stream) != hipSuccess ||
                 hipStreamSynchronize(s.stream) != hipSuccess)
                 return (int) RVB_ERR_HIP;
             if (!(which & RVB_IR_DIFFUSE) || !s.count) return (int) RVB_OK;
             int r = configure(s.ctx, RVB_IR_DIFFUSE, nullptr, 0);
-            if (r == RVB_OK) r = rvb_ir_accumulate(s.ctx, predelay, sample_rate, bins, RVB_IR_FAST, s.hist);
+            if (r == RVB_OK) r = rvb_ir_accumulate(s.ctx, predelay, sample_rate, bins, RVB_IR_FAST, s.histogram());
             return r != RVB_OK ? r : rvb_synchronize(s.ctx);
         });
         if (rc != RVB_OK) return rc;
@@ -459,24 +427,24 @@ static int multi_ir(rvb_multi * m, const float mic[3], const rvb_speaker * speak
             // RCCL over xGMI: [channels][8][nbins] floats, in place on every device (rccl.h:611)
             int e = rccl().GroupStart();
             for (size_t g = 0; g < m->shards.size() && e == 0; ++g) {
-                MHIP(m, hipSetDevice(m->shards[g].device));
-                e = rccl().AllReduce(m->shards[g].hist, m->shards[g].hist, count, kNcclFloat, kNcclSum, m->comms[g], m->shards[g].stream);
+                RVB_HIP(mfail, m, hipSetDevice(m->shards[g].device));
+                e = rccl().AllReduce(m->shards[g].histogram(), m->shards[g].histogram(), count, kNcclFloat, kNcclSum, m->comms[g], m->shards[g].stream);
             }
             const int e2 = rccl().GroupEnd();
             if (e != 0 || e2 != 0) return mfail(m, RVB_ERR_HIP, std::string("ncclAllReduce: ") + rccl().GetErrorString(e ? e : e2));
-            for (Shard & s : m->shards) { MHIP(m, hipSetDevice(s.device)); MHIP(m, hipStreamSynchronize(s.stream)); }
+            for (Shard & s : m->shards) { RVB_HIP(mfail, m, hipSetDevice(s.device)); RVB_HIP(mfail, m, hipStreamSynchronize(s.stream)); }
             m->rccl_used_last = true;
         } else if (m->shards.size() > 1) {
             // no communicator for this device list: gather on shard 0 with peer copies, add there
             Shard & root = m->shards[0];
-            MHIP(m, ensure(root.device, root.peer, root.peer_cap, bytes));
-            MHIP(m, hipSetDevice(root.device));
+            RVB_HIP(mfail, m, hipSetDevice(root.device));
+            RVB_HIP(mfail, m, root.peer.ensure(bytes));
             for (size_t g = 1; g < m->shards.size(); ++g) {
-                MHIP(m, hipMemcpyPeerAsync(root.peer, root.device, m->shards[g].hist, m->shards[g].device, bytes, root.stream));
-                hipLaunchKernelGGL(add_kernel, dim3(4096), dim3(256), 0, root.stream, root.hist, root.peer, (uint64_t) count);
-                MHIP(m, hipGetLastError());
+                RVB_HIP(mfail, m, hipMemcpyPeerAsync(root.peer.as<float>(), root.device, m->shards[g].histogram(), m->shards[g].device, bytes, root.stream));
+                hipLaunchKernelGGL(add_kernel, dim3(4096), dim3(256), 0, root.stream, root.histogram(), root.peer.as<float>(), (uint64_t) count);
+                RVB_HIP(mfail, m, hipGetLastError());
             }
-            MHIP(m, hipStreamSynchronize(root.stream));
+            RVB_HIP(mfail, m, hipStreamSynchronize(root.stream));
         }
         result = &m->shards[0];
     } else {
@@ -485,11 +453,11 @@ static int multi_ir(rvb_multi * m, const float mic[3], const rvb_speaker * speak
     // 3. the merged image sources go last (reference order: diffuse, then images — rayverb.cpp:708-714)
     if (!m->images.empty()) {
         int rc = configure(result->ctx, RVB_IR_IMAGES, m->images.data(), m->images.size());
-        if (rc == RVB_OK) rc = rvb_ir_accumulate(result->ctx, predelay, sample_rate, bins, mode, result->hist);
+        if (rc == RVB_OK) rc = rvb_ir_accumulate(result->ctx, predelay, sample_rate, bins, mode, result->histogram());
         if (rc == RVB_OK) rc = rvb_synchronize(result->ctx);
         if (rc != RVB_OK) return mfail(m, rc, rvb_last_error(result->ctx));
     }
-    return rvb_copy_to_host(result->ctx, out, result->hist, bytes) == RVB_OK ? (int) RVB_OK : mfail(m, RVB_ERR_HIP, rvb_last_error(result->ctx));
+    return rvb_copy_to_host(result->ctx, out, result->histogram(), bytes) == RVB_OK ? (int) RVB_OK : mfail(m, RVB_ERR_HIP, rvb_last_error(result->ctx));
 }
 
 int rvb_multi_ir_speakers(rvb_multi * m, const float mic[3], const rvb_speaker * speakers, uint64_t nspeakers, int which, int remove_direct,

@@ -19,11 +19,7 @@
 // own (the only thread that touches the lane's contexts); unit u goes to lane u % lanes, results come back in submission order.
 // Nothing but the public C-ABI underneath (plus HIP for the histogram buffers, their zero fill and a few events).
 #include "../../include/rvb_capi.h"
-
-#define RVB_STR_(x) #x
-#define RVB_STR(x) RVB_STR_(x)      // RVB_MAX_SPEAKERS in error texts
-
-#include <hip/hip_runtime.h>
+#include "hip_owned.h"
 
 #include <algorithm>
 #include <condition_variable>
@@ -51,13 +47,10 @@ struct Job {
 struct Slot {                                 // per context
     rvb_ctx * ctx = nullptr;
     bool has_table = false;                   // the pipeline's HRTF table is on this context's device (uploaded with its first HRTF job)
-    float * hist[RVB_PIPELINE_MAX_PAIRS] = {};     // device [nchannels][8][nbins], one per pair of a unit
-    size_t hist_cap[RVB_PIPELINE_MAX_PAIRS] = {};
-    hipEvent_t zeroed = nullptr;
-    hipEvent_t uploaded = nullptr;            // pairs > 1: behind a pair's rvb_ir_configure_* (its image upload reads the context's host copy)
+    DevBuf hist[RVB_PIPELINE_MAX_PAIRS];      // device [nchannels][8][nbins], one per pair of a unit
+    Event zeroed;
+    Event uploaded;                           // pairs > 1: behind a pair's rvb_ir_configure_* (its image upload reads the context's host copy)
 };
-
-struct HostBuffer { float * p = nullptr; size_t cap = 0; };
 
 // model + binning configuration (rvb_pipeline_configure_*): the pipeline's, read by its lanes while jobs are pending
 struct Config {
@@ -77,13 +70,13 @@ struct Lane {
     std::vector<Slot> slots;
     uint64_t group = 1, pairs = 1;
     int device = 0;
-    hipStream_t fill_stream = nullptr;        // zero fills of the histograms (the contexts' streams wait for them by an event)
+    Stream fill_stream;                       // zero fills of the histograms (the contexts' streams wait for them by an event)
     std::string error;
     // jobs: [returned, submitted); jobs.front() is the oldest not yet returned
     std::deque<Job> jobs;
     uint64_t submitted = 0, returned = 0, begun_upto = 0;
     uint64_t allow = UINT64_MAX;              // jobs [0, allow) may be traced (a lane thread holds back an incomplete last unit / group)
-    std::vector<HostBuffer> ring;             // pinned result buffers, job id % ring.size()
+    std::vector<PinnedBuf> ring;              // pinned result buffers, job id % ring.size()
     std::vector<rvb_image_candidate> candidates, pair_candidates;
     std::vector<rvb_impulse> images;
     // rvb_pipeline_create_lanes: the lane's thread and what it shares with the caller's (guarded by rvb_pipeline::mu)
@@ -97,6 +90,7 @@ struct Lane {
     bool quit = false;
     int failed = RVB_OK;                      // a stage failed: every pending and later job of the lane returns this code
     std::string failure;
+    ~Lane() { (void) hipSetDevice(device); }  // (lane_drain has run: nothing uses what the members release)
 };
 
 struct Outcome {                              // a job of rvb_pipeline_create_lanes, as its lane's thread finished it
@@ -123,26 +117,16 @@ struct rvb_pipeline {
 
 namespace {
 
-int pfail(Lane * l, int code, const std::string & what)
+template <class Owner>                        // a Lane or the pipeline: each has its own last error
+int pfail(Owner * o, int code, const std::string & what)
 {
-    if (l) l->error = what;
-    return code;
-}
-int pfail(rvb_pipeline * p, int code, const std::string & what)
-{
-    if (p) p->error = what;
+    if (o) o->error = what;
     return code;
 }
 int cfail(Lane * l, int code, rvb_ctx * ctx, const char * where)
 {
     return pfail(l, code, std::string(where) + ": " + rvb_last_error(ctx));
 }
-#define PHIP(l, call)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (call);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return pfail(l, RVB_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));            \
-    } while (0)
 
 Job & job_at(Lane * l, uint64_t id) { return l->jobs[(size_t) (id - l->returned)]; }
 // job i runs on context (i / pairs) % contexts: units go round-robin over the lane's contexts
@@ -216,6 +200,17 @@ int begin_upto(Lane * l, uint64_t limit)
     return RVB_OK;
 }
 
+// l->candidates = the image-source candidates of the context's last trace
+int fetch_candidates(Lane * l, rvb_ctx * ctx)
+{
+    uint64_t ncand = 0;
+    int rc = rvb_get_image_candidates(ctx, nullptr, 0, &ncand);
+    if (rc != RVB_OK) return cfail(l, rc, ctx, "rvb_pipeline: candidates");
+    l->candidates.resize(ncand);
+    if (ncand && (rc = rvb_get_image_candidates(ctx, l->candidates.data(), ncand, &ncand)) != RVB_OK) return cfail(l, rc, ctx, "rvb_pipeline: candidates");
+    return RVB_OK;
+}
+
 // Staging of a traced job in two phases, so that a group's jobs overlap their device work: (1) image-source merge and configuration — the
 // only host wait is the one for the trace's small result block (image-source candidates, time range of the speaker model) — and the HRTF
 // model's time-range pass ENQUEUED; (2) the time range read, the histogram sized and zeroed, binning + export enqueued.
@@ -246,11 +241,9 @@ int stage_configure(Lane * l, Job & j)
             ncand = l->pair_candidates.size();
         }
     } else {
-        rc = rvb_get_image_candidates(ctx, nullptr, 0, &ncand);
-        if (rc != RVB_OK) return cfail(l, rc, ctx, "rvb_pipeline: candidates");
-        l->candidates.resize(ncand);
-        if (ncand && (rc = rvb_get_image_candidates(ctx, l->candidates.data(), ncand, &ncand)) != RVB_OK) return cfail(l, rc, ctx, "rvb_pipeline: candidates");
+        if ((rc = fetch_candidates(l, ctx)) != RVB_OK) return rc;
         cand = l->candidates.data();
+        ncand = l->candidates.size();
     }
     l->images.clear();
     if (c.which & RVB_IR_IMAGES) {
@@ -286,28 +279,19 @@ int stage_bin(Lane * l, Job & j)
     j.nbins = rvb_ir_bins(hi, j.predelay, c.sample_rate);
     const uint64_t nch = c.hrtf ? 2 : c.speakers.size();
     const size_t bytes = (size_t) j.nbins * nch * 8 * sizeof(float);
-    PHIP(l, hipSetDevice(l->device));
+    RVB_HIP(pfail, l, hipSetDevice(l->device));
     // (each pair of a unit has a histogram of its own: pair k's export must not read what pair k + 1's zero fill and binning write)
-    const size_t k = (size_t) (j.id % l->pairs);
-    float *& hist = s.hist[k];
-    size_t & hist_cap = s.hist_cap[k];
-    if (bytes > hist_cap) {
-        // (the previous histogram of this context left for the host before its result was handed out: nothing reads it any more)
-        if (hist) { PHIP(l, hipFree(hist)); hist = nullptr; hist_cap = 0; }
-        PHIP(l, hipMalloc(reinterpret_cast<void **>(&hist), bytes + bytes / 8));
-        hist_cap = bytes + bytes / 8;
-    }
-    HostBuffer & hb = l->ring[(size_t) (j.id % l->ring.size())];
-    if (bytes > hb.cap) {
-        if (hb.p) { PHIP(l, hipHostFree(hb.p)); hb.p = nullptr; hb.cap = 0; }
-        PHIP(l, hipHostMalloc(reinterpret_cast<void **>(&hb.p), bytes + bytes / 8, hipHostMallocDefault));
-        hb.cap = bytes + bytes / 8;
-    }
-    j.host = hb.p;
-    PHIP(l, hipMemsetAsync(hist, 0, bytes, l->fill_stream));
-    PHIP(l, hipEventRecord(s.zeroed, l->fill_stream));
+    DevBuf & hist = s.hist[(size_t) (j.id % l->pairs)];
+    // (the previous histogram of this context left for the host before its result was handed out: nothing reads it any more;
+    // an eighth of head-room, so that slowly growing histograms do not reallocate every time)
+    if (bytes > hist.cap) RVB_HIP(pfail, l, hist.ensure(bytes + bytes / 8));
+    PinnedBuf & hb = l->ring[(size_t) (j.id % l->ring.size())];
+    if (bytes > hb.cap) RVB_HIP(pfail, l, hb.ensure(bytes + bytes / 8));
+    j.host = hb.as<float>();
+    RVB_HIP(pfail, l, hipMemsetAsync(hist.p, 0, bytes, l->fill_stream));
+    RVB_HIP(pfail, l, hipEventRecord(s.zeroed, l->fill_stream));
     if ((rc = rvb_wait_for_event(ctx, s.zeroed)) != RVB_OK) return cfail(l, rc, ctx, "rvb_pipeline: wait for the zero fill");
-    if ((rc = rvb_ir_accumulate_export(ctx, j.predelay, c.sample_rate, j.nbins, c.mode, hist, j.host, 0)) != RVB_OK) return cfail(l, rc, ctx, "rvb_pipeline: binning");
+    if ((rc = rvb_ir_accumulate_export(ctx, j.predelay, c.sample_rate, j.nbins, c.mode, hist.p, j.host, 0)) != RVB_OK) return cfail(l, rc, ctx, "rvb_pipeline: binning");
     j.staged = true;
     return RVB_OK;
 }
@@ -320,16 +304,11 @@ int stage_pairs(Lane * l, uint64_t first, uint64_t last)
     rvb_ctx * ctx = s.ctx;
     int rc;
     l->candidates.clear();
-    if (c.which & RVB_IR_IMAGES) {            // all pairs of the launch, global ray numbers
-        uint64_t ncand = 0;
-        if ((rc = rvb_get_image_candidates(ctx, nullptr, 0, &ncand)) != RVB_OK) return cfail(l, rc, ctx, "rvb_pipeline: candidates");
-        l->candidates.resize(ncand);
-        if (ncand && (rc = rvb_get_image_candidates(ctx, l->candidates.data(), ncand, &ncand)) != RVB_OK) return cfail(l, rc, ctx, "rvb_pipeline: candidates");
-    }
+    if ((c.which & RVB_IR_IMAGES) && (rc = fetch_candidates(l, ctx)) != RVB_OK) return rc;      // all pairs of the launch, global ray numbers
     for (uint64_t id = first; id < last; ++id) {
         // rvb_ir_configure_* uploads the merged images from the context's host copy, which the next configuration overwrites: the
         // previous pair's upload must be done (stream order protects the device buffer, not that host copy)
-        if (id > first) PHIP(l, hipEventSynchronize(s.uploaded));
+        if (id > first) RVB_HIP(pfail, l, hipEventSynchronize(s.uploaded));
         if ((rc = stage_configure(l, job_at(l, id))) != RVB_OK) return rc;
         if ((rc = rvb_record_event(ctx, s.uploaded)) != RVB_OK) return cfail(l, rc, ctx, "rvb_pipeline: record");
         if ((rc = stage_bin(l, job_at(l, id))) != RVB_OK) return rc;
@@ -416,31 +395,24 @@ int lane_init(Lane * l, rvb_ctx ** ctxs, uint64_t count, uint64_t group, uint64_
     }
     l->device = device;
     if (hipSetDevice(device) != hipSuccess) return RVB_ERR_HIP;
-    if (hipStreamCreateWithFlags(&l->fill_stream, hipStreamNonBlocking) != hipSuccess) return RVB_ERR_HIP;
+    if (hipStreamCreateWithFlags(&l->fill_stream.h, hipStreamNonBlocking) != hipSuccess) return RVB_ERR_HIP;
     for (uint64_t i = 0; i < count; ++i) {
         Slot s;
         s.ctx = ctxs[i];
-        if (hipEventCreateWithFlags(&s.zeroed, hipEventDisableTiming) != hipSuccess) return RVB_ERR_HIP;
-        if (pairs > 1 && hipEventCreateWithFlags(&s.uploaded, hipEventDisableTiming) != hipSuccess) { l->slots.push_back(s); return RVB_ERR_HIP; }
-        l->slots.push_back(s);
+        if (hipEventCreateWithFlags(&s.zeroed.h, hipEventDisableTiming) != hipSuccess) return RVB_ERR_HIP;
+        if (pairs > 1 && hipEventCreateWithFlags(&s.uploaded.h, hipEventDisableTiming) != hipSuccess) return RVB_ERR_HIP;
+        l->slots.push_back(std::move(s));
         (void) rvb_set_concurrent_traces(ctxs[i], (uint32_t) l->group);     // the traces of a group run side by side: the path kernel is sized for them
     }
     return RVB_OK;
 }
 
-void lane_destroy(Lane * l)
+// the end of a lane's work: its contexts and its fill stream idle, the contexts' hint withdrawn (~Lane then releases buffers and events)
+void lane_drain(Lane * l)
 {
     (void) hipSetDevice(l->device);
-    for (Slot & s : l->slots) {
-        if (s.ctx) { (void) rvb_synchronize(s.ctx); (void) rvb_synchronize_exports(s.ctx); (void) rvb_set_concurrent_traces(s.ctx, 1); }
-        for (float * h : s.hist)
-            if (h) (void) hipFree(h);
-        if (s.zeroed) (void) hipEventDestroy(s.zeroed);
-        if (s.uploaded) (void) hipEventDestroy(s.uploaded);
-    }
-    for (HostBuffer & h : l->ring)
-        if (h.p) (void) hipHostFree(h.p);
-    if (l->fill_stream) { (void) hipStreamSynchronize(l->fill_stream); (void) hipStreamDestroy(l->fill_stream); }
+    for (Slot & s : l->slots) { (void) rvb_synchronize(s.ctx); (void) rvb_synchronize_exports(s.ctx); (void) rvb_set_concurrent_traces(s.ctx, 1); }
+    if (l->fill_stream) (void) hipStreamSynchronize(l->fill_stream);
 }
 
 // ---- rvb_pipeline_create_lanes: one host thread per lane -------------------------------------------------------------------------------
@@ -504,7 +476,7 @@ void lane_thread(rvb_pipeline * p, Lane * l)
     }
 }
 
-// a lane's thread: sets the lane up, serves it, tears it down — every call on the lane's contexts is made here
+// a lane's thread: sets the lane up, serves it, drains it — every call on the lane's contexts is made here
 void lane_main(rvb_pipeline * p, Lane * l, uint64_t group)
 {
     const int rc = lane_init(l, l->init_ctxs.data(), l->init_ctxs.size(), group, p->pairs);
@@ -516,7 +488,7 @@ void lane_main(rvb_pipeline * p, Lane * l, uint64_t group)
         if (rc != RVB_OK) l->wake.wait(lk, [l] { return l->quit; });
     }
     if (rc == RVB_OK) lane_thread(p, l);
-    lane_destroy(l);
+    lane_drain(l);
 }
 
 int configure_common(rvb_pipeline * p, int which, int remove_direct, int trim_predelay, float sample_rate, int mode, uint64_t nreflections,
@@ -633,7 +605,7 @@ void rvb_pipeline_destroy(rvb_pipeline * p)
         for (std::unique_ptr<Lane> & l : p->lanes)
             if (l->worker.joinable()) l->worker.join();
     } else {
-        for (std::unique_ptr<Lane> & l : p->lanes) lane_destroy(l.get());
+        for (std::unique_ptr<Lane> & l : p->lanes) lane_drain(l.get());
     }
     delete p;
 }

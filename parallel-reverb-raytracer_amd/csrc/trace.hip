@@ -1,0 +1,436 @@
+// trace.hip — the trace of include/rvb_capi.h: buffers, fills and kernel arguments; the path kernel; everything after it; then what a
+// trace leaves for the host (diffuse impulses, direct path, image-source candidates) and the image-source merge.
+#include "ctx.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+
+namespace {
+
+// A trace in three steps — buffers, fills and kernel arguments; the path kernel; everything after it — so that rvb_trace_group can put
+// the path kernels of several contexts into ONE launch.
+struct TracePlan {
+    TraceArgs a;
+    uint64_t npairs = 1, nrays = 0, nreflections = 0;
+    int key_bits = 1;
+};
+
+int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint64_t npairs, uint64_t nreflections,
+                  const float air_coefficient[8], uint64_t ray_offset, uint64_t rays_in_flight, TracePlan & plan)
+{
+    if (!ctx->have_scene) return fail(ctx, RVB_ERR_STATE, "rvb_trace: rvb_set_scene has not been called");
+    if (!ctx->directions && ctx->nrays) return fail(ctx, RVB_ERR_STATE, "rvb_trace: no directions");
+    if (nreflections >= (1ull << 31) || ctx->nrays * npairs * 9 >= (1ull << 32))
+        return fail(ctx, RVB_ERR_CAPACITY, "rvb_trace: too many reflections or rays for one context");
+    const float * mic = mics, * source = sources;
+    RVB_BIND(ctx);
+    ctx->traced = false;                              // (until trace_finish: a failure below must not leave the last trace's results half reset)
+    const uint64_t nrays = ctx->nrays * npairs;       // rays of this launch
+    const size_t imp_bytes = (size_t) nrays * nreflections * sizeof(rvb_impulse);
+    const size_t early_bytes = (size_t) nrays * 9 * sizeof(uint32_t);
+    RVB_HIP(fail, ctx, ctx->impulses.ensure(imp_bytes));
+    RVB_HIP(fail, ctx, ctx->early.ensure(early_bytes));
+    RVB_HIP(fail, ctx, ctx->candidates.ensure((size_t) nrays * 9 * sizeof(rvb_image_candidate)));
+    RVB_HIP(fail, ctx, ctx->image_items.ensure(((size_t) nrays * 9 + npairs) * 3 * sizeof(uint32_t)));      // (ray, bounce) entries, then a state word each
+
+    // reference rayverb.cpp:600-616: outputs start zero-filled — path_kernel writes every slot of the
+    // impulse array itself (work record or zeros), so no 819 MB fill is needed here
+    // (a probe that skips this 3.6 MB fill — the kernel trace of the pipeline shows it stretched to 0.7 ms beside a histogram's host copy, right in
+    // front of the next path kernel — made the pipeline 2 % SLOWER, 4.52 -> 4.62 ms per IR, three alternating runs: the fills stay)
+    SmallBlock * small = ctx->small_dev();
+    if (early_bytes) RVB_HIP(fail, ctx, hipMemsetAsync(ctx->early.p, 0xFF, early_bytes, ctx->stream));
+    RVB_HIP(fail, ctx, hipMemsetAsync(small, 0, sizeof(SmallBlock), ctx->stream));
+    RVB_HIP(fail, ctx, hipMemsetAsync(&small->trace_range[0], 0xFF, 4, ctx->stream));
+
+    TraceArgs & a = plan.a;
+    a.scene = ctx->scene;
+    a.directions = ctx->directions;
+    a.impulses = ctx->impulses.as<rvb_impulse>();
+    a.early = ctx->early.as<uint32_t>();
+    a.candidates = ctx->candidates.as<rvb_image_candidate>();
+    a.candidate_count = &small->candidate_count;
+    a.image_items = reinterpret_cast<ImageItem *>(ctx->image_items.p);
+    a.image_state = ctx->image_items.as<uint32_t>() + ((size_t) nrays * 9 + npairs) * 2;
+    a.image_item_count = &small->image_item_count;
+    a.direct = &small->direct;
+    a.npairs = (uint32_t) npairs;
+    a.rays_per_pair = (uint32_t) ctx->nrays;
+    a.pair_mics = nullptr;
+    a.pair_sources = nullptr;
+    a.executed = &small->executed;
+    a.time_range = small->trace_range;
+    if (npairs > 1) {
+        // several pairs per launch: geometry, direct path and time range per pair live in arrays of their own
+        // staged through pinned memory and copied in stream order: no host synchronisation in front of the launch (the staging
+        // block is reused only after the copies of the previous launch have left it)
+        const size_t geom_floats = 8 * npairs, init_words = 2 * npairs;
+        const size_t stage_bytes = geom_floats * sizeof(float) + init_words * sizeof(uint32_t);
+        if (stage_bytes > ctx->pair_stage.cap) {
+            if (ctx->pair_stage.p) RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));      // the copies of the previous launch may still read it
+            RVB_HIP(fail, ctx, ctx->pair_stage.ensure(stage_bytes));
+        }
+        if (!ctx->pair_stage_free) RVB_HIP(fail, ctx, hipEventCreateWithFlags(&ctx->pair_stage_free.h, hipEventDisableTiming));
+        else RVB_HIP(fail, ctx, hipEventSynchronize(ctx->pair_stage_free));
+        float * geom = ctx->pair_stage.as<float>();
+        uint32_t * init = reinterpret_cast<uint32_t *>(geom + geom_floats);
+        std::memset(geom, 0, geom_floats * sizeof(float));
+        for (uint64_t p = 0; p < npairs; ++p)
+            for (int i = 0; i < 3; ++i) { geom[4 * p + i] = mics[3 * p + i]; geom[4 * (npairs + p) + i] = sources[3 * p + i]; }
+        for (uint64_t p = 0; p < npairs; ++p) { init[2 * p] = 0xFFFFFFFFu; init[2 * p + 1] = 0u; }
+        RVB_HIP(fail, ctx, ctx->pair_geom.ensure(geom_floats * sizeof(float)));
+        RVB_HIP(fail, ctx, ctx->pair_direct.ensure(npairs * sizeof(rvb_impulse)));
+        RVB_HIP(fail, ctx, ctx->pair_range.ensure(npairs * 2 * sizeof(uint32_t)));
+        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_geom.p, geom, geom_floats * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_range.p, init, init_words * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        RVB_HIP(fail, ctx, hipEventRecord(ctx->pair_stage_free, ctx->stream));
+        a.pair_mics = ctx->pair_geom.as<float4>();
+        a.pair_sources = ctx->pair_geom.as<float4>() + npairs;
+        a.direct = ctx->pair_direct.as<rvb_impulse>();
+        a.time_range = ctx->pair_range.as<uint32_t>();
+    }
+    // record bucketing for coherent shadow rays (RVB_SHADOW_SORT=0 turns it off)
+    static const bool sort_records = !(getenv("RVB_SHADOW_SORT") && getenv("RVB_SHADOW_SORT")[0] == '0');
+    const uint64_t nrecords = nrays * nreflections;
+    a.sort_keys = nullptr; a.sort_keys16 = nullptr; a.key_shift = 0; a.sort_order = nullptr;
+    int key_bits = 1;
+    while (key_bits < 32 && (1ull << key_bits) < ctx->scene.ntris) ++key_bits;
+    // The grouping only has to bring neighbouring triangles together: the top 16 bits of the leaf position are two
+    // onesweep passes instead of three (C2, 17 key bits: grouping 0.66 -> 0.51 ms beside image_kernel, shadow_kernel +0.02 ms).
+    if (sort_records && nrecords && nrecords < (1ull << 32) && ctx->scene.ntris) {
+        RVB_HIP(fail, ctx, ctx->sort_keys.ensure(nrecords * 4));
+        RVB_HIP(fail, ctx, ctx->sort_scratch.ensure(nrecords * 4));
+        RVB_HIP(fail, ctx, ctx->sort_order.ensure(nrecords * 4));
+        const size_t group_bytes = rvb_group_records_temp_bytes(ctx->nrays * nreflections);
+        if (group_bytes == 0) return fail(ctx, RVB_ERR_HIP, "rvb_trace: radix sort size query failed");
+        RVB_HIP(fail, ctx, ctx->group_temp.ensure(group_bytes));
+        // slots of escaped rays get key 0xFFFFFFFF from path_kernel: they land in the last bucket and the
+        // shadow kernel skips them by their valid flag
+        // 16-bit keys in 64-byte runs (trace_kernels.hip, flush_key_run) whenever a ray's row divides into whole runs and rocPRIM sorts;
+        // 32-bit keys, one store per record, otherwise (and for RVB_SORT=own)
+        if (nreflections % 32 == 0 && !own_sort_enabled()) {
+            a.sort_keys16 = ctx->sort_keys.as<uint16_t>();
+            a.key_shift = (uint32_t) std::max(0, key_bits - 16);
+        } else {
+            a.sort_keys = ctx->sort_keys.as<uint32_t>();
+        }
+    }
+    a.nrays = nrays;
+    a.nreflections = (uint32_t) nreflections;
+    a.stack_entries = ctx->stack_need;
+    a.lds_surfaces = rvb_lds_surfaces(ctx->stack_need, ctx->nsurfaces);
+    // (rays_in_flight: what a group launch carries in all; 0 = this trace alone, times the caller's hint)
+    a.path_lanes = ctx->path_lanes ? ctx->path_lanes : (rays_in_flight ? rvb_path_lanes_for(rays_in_flight, 1) : rvb_path_lanes_for(nrays, ctx->concurrent_traces));
+    a.ray_offset = ray_offset;
+    for (int i = 0; i < 3; ++i) { a.mic[i] = mic[i]; a.source[i] = source[i]; ctx->mic[i] = mic[i]; }
+    for (int i = 0; i < 8; ++i) a.air[i] = air_coefficient[i];
+
+    // diagnostic builds (RVB_STAMPS): [0..15] path_kernel, [16..31] shadow_kernel
+    RVB_HIP(fail, ctx, ctx->stamps.ensure(32 * sizeof(unsigned long long)));
+    // (zeroed per trace only where a diagnostic build may write them: one tiny fill kernel less on the stream of every shipped trace)
+    static const bool stamps_on = getenv("RVB_STAMPS") != nullptr;
+    if (stamps_on || !ctx->stamps_cleared) {
+        RVB_HIP(fail, ctx, hipMemsetAsync(ctx->stamps.p, 0, 32 * sizeof(unsigned long long), ctx->stream));
+        ctx->stamps_cleared = true;
+    }
+    a.scene.stamps = ctx->stamps.as<unsigned long long>();
+
+    ctx->reset_timings();
+    plan.npairs = npairs;
+    plan.nrays = nrays;
+    plan.nreflections = nreflections;
+    plan.key_bits = key_bits;
+    return RVB_OK;
+}
+
+int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
+{
+    TraceArgs & a = plan.a;
+    const uint64_t npairs = plan.npairs, nrays = plan.nrays, nreflections = plan.nreflections;
+    const int key_bits = plan.key_bits;
+    static const int group_bits = getenv("RVB_SHADOW_SORT_BITS") ? atoi(getenv("RVB_SHADOW_SORT_BITS")) : 16;
+    // image_kernel and the record grouping both depend on path_kernel only: the first (latency-bound) runs on the
+    // side stream beside the second (bandwidth-bound); shadow_kernel, which rewrites the records image_kernel
+    // reads, waits for both.
+    RVB_HIP(fail, ctx, hipEventRecord(ctx->path_done, ctx->stream));
+    RVB_HIP(fail, ctx, hipStreamWaitEvent(ctx->side_stream, ctx->path_done, 0));
+    ctx->begin_timing("image_kernel", ctx->side_stream);
+    a.scene.stamps = nullptr;
+    rvb_launch_images(a, ctx->side_stream);
+    ctx->end_timing(ctx->side_stream);
+    RVB_HIP(fail, ctx, hipEventRecord(ctx->side_done, ctx->side_stream));
+    a.scene.stamps = ctx->stamps.as<unsigned long long>() + 16;
+    if (a.sort_keys || a.sort_keys16) {
+        ctx->begin_timing("record_sort_kernels");
+        a.sort_order = ctx->sort_order.as<uint32_t>();
+        RVB_HIP(fail, ctx, hipGetLastError());
+        // one grouping per pair (a pair's shadow rays share a microphone; records are [pair][ray][bounce])
+        const uint64_t per_pair = ctx->nrays * nreflections;
+        for (uint64_t p = 0; p < npairs; ++p) {
+            if (a.sort_keys16) {
+                // key16 = leaf position >> key_shift: its top group_bits bits are bits [end - group_bits, end) with end = min(16, key_bits)
+                const int end = std::min(16, key_bits);
+                RVB_HIP(fail, ctx, rvb_group_records16(ctx->group_temp.p, ctx->group_temp.cap, a.sort_keys16 + p * per_pair,
+                                                       ctx->sort_scratch.as<uint16_t>() + p * per_pair, a.sort_order + p * per_pair, per_pair,
+                                                       (uint32_t) (p * per_pair), std::max(0, end - group_bits), end, ctx->stream));
+            } else if (own_sort_enabled()) {
+                const int rc = own_sort(ctx, a.sort_keys + p * per_pair, (uint32_t) (p * per_pair), per_pair, std::max(0, key_bits - group_bits), key_bits,
+                                        ctx->sort_scratch.as<uint32_t>() + p * per_pair, a.sort_order + p * per_pair, false);
+                if (rc != RVB_OK) return rc;
+            } else {
+                RVB_HIP(fail, ctx, rvb_group_records(ctx->group_temp.p, ctx->group_temp.cap, a.sort_keys + p * per_pair,
+                                                     ctx->sort_scratch.as<uint32_t>() + p * per_pair, a.sort_order + p * per_pair, per_pair,
+                                                     (uint32_t) (p * per_pair), std::max(0, key_bits - group_bits), key_bits, ctx->stream));
+            }
+        }
+        ctx->end_timing();
+    }
+    RVB_HIP(fail, ctx, hipStreamWaitEvent(ctx->stream, ctx->side_done, 0));
+    ctx->begin_timing(rvb_shadow_lanes() == 2 ? "shadow_pair_kernel" : (rvb_shadow_lanes() == 1 ? "shadow_lane_kernel" : "shadow_kernel"));
+    rvb_launch_shadow(a, ctx->stream);
+    ctx->end_timing();
+    RVB_HIP(fail, ctx, hipGetLastError());
+    ctx->nreflections = nreflections;
+    ctx->traced = true;
+    ctx->small_valid = false;
+    ctx->ir_configured = false;
+    ctx->exact.valid = false;
+    ctx->npairs = npairs;
+    ctx->traced_rays = nrays;
+    ctx->ir_pair = 0;
+    ctx->pair_mics_host.assign(mics, mics + 3 * npairs);
+    return RVB_OK;
+}
+
+// the name a path launch is timed under: the kernel that ran (csrc/trace_kernels.hip, rvb_path_lanes_for)
+const char * path_kernel_name(uint32_t lanes) { return lanes == 1 ? "path_lane_kernel" : (lanes == 2 ? "path_pair_kernel" : "path_kernel"); }
+
+int trace_common(rvb_ctx * ctx, const float * mics, const float * sources, uint64_t npairs, uint64_t nreflections,
+                 const float air_coefficient[8], uint64_t ray_offset)
+{
+    TracePlan plan;
+    int rc = trace_prepare(ctx, mics, sources, npairs, nreflections, air_coefficient, ray_offset, 0, plan);
+    if (rc != RVB_OK) return rc;
+    ctx->begin_timing(path_kernel_name(plan.a.path_lanes));
+    rvb_launch_path(plan.a, ctx->stream);
+    ctx->end_timing();
+    return trace_finish(ctx, plan, mics);
+}
+
+bool by_ray_and_slot(const rvb_image_candidate & x, const rvb_image_candidate & y) { return x.ray != y.ray ? x.ray < y.ray : x.slot < y.slot; }
+
+}  // namespace
+
+// one synchronising 128-byte read per trace serves candidate count, direct path, time range, bounce count
+int fetch_small(rvb_ctx * ctx)
+{
+    if (ctx->small_valid)
+        return RVB_OK;
+    RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->small_host, ctx->small.p, sizeof(SmallBlock), hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->traced_rays)      // capacity rays * 9 >= 32 entries unless there are fewer than 4 rays
+        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->first_candidates, ctx->candidates.p,
+                                          std::min(kFirstCandidates * sizeof(rvb_image_candidate), (size_t) ctx->traced_rays * 9 * sizeof(rvb_image_candidate)),
+                                          hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->npairs > 1) {     // per-pair direct paths and time ranges
+        ctx->pair_direct_host.resize(ctx->npairs);
+        ctx->pair_range_host.resize(2 * ctx->npairs);
+        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_direct_host.data(), ctx->pair_direct.p, ctx->npairs * sizeof(rvb_impulse), hipMemcpyDeviceToHost, ctx->stream));
+        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_range_host.data(), ctx->pair_range.p, ctx->npairs * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
+    ctx->small_valid = true;
+    return RVB_OK;
+}
+
+extern "C" {
+
+int rvb_trace_group(rvb_ctx ** ctxs, uint64_t count, const float * mics, const float * sources, uint64_t nreflections,
+                    const float air_coefficient[8], const uint64_t * ray_offsets)
+{
+    if (!ctxs || count == 0 || count > RVB_MAX_GROUP) return RVB_ERR_INVALID;
+    for (uint64_t i = 0; i < count; ++i)
+        if (!ctxs[i]) return RVB_ERR_INVALID;
+    if (!mics || !sources || !air_coefficient) return fail(ctxs[0], RVB_ERR_INVALID, "rvb_trace_group: null argument");
+    for (uint64_t i = 0; i < count; ++i)
+        for (uint64_t j = 0; j < i; ++j)
+            if (ctxs[i] == ctxs[j]) return fail(ctxs[0], RVB_ERR_INVALID, "rvb_trace_group: a context is listed twice");
+    uint64_t total_rays = 0;
+    for (uint64_t i = 0; i < count; ++i) total_rays += ctxs[i]->nrays;
+    TracePlan plans[RVB_MAX_GROUP];
+    for (uint64_t i = 0; i < count; ++i) {
+        const int rc = trace_prepare(ctxs[i], mics + 3 * i, sources + 3 * i, 1, nreflections, air_coefficient, ray_offsets ? ray_offsets[i] : 0,
+                                     total_rays, plans[i]);
+        if (rc != RVB_OK) return rc;
+    }
+    // one launch for all of them when they can share a kernel: one or two lanes per ray, one device, one LDS layout (stack depth, surfaces
+    // staged, key runs or not: the launch's LDS is laid out once for all its workgroups)
+    bool fused = count > 1 && plans[0].a.path_lanes <= 2;
+    for (uint64_t i = 1; i < count && fused; ++i)
+        fused = ctxs[i]->device == ctxs[0]->device && plans[i].a.path_lanes == plans[0].a.path_lanes && plans[i].a.stack_entries == plans[0].a.stack_entries
+                && plans[i].a.lds_surfaces == plans[0].a.lds_surfaces && (plans[i].a.sort_keys16 != nullptr) == (plans[0].a.sort_keys16 != nullptr);
+    for (uint64_t i = 0; i < count && fused; ++i) fused = plans[i].nrays > 0;
+    if (fused) {
+        rvb_ctx * lead = ctxs[0];
+        RVB_BIND(lead);
+        for (uint64_t i = 1; i < count; ++i) {                      // the others' fills come first
+            RVB_HIP(fail, ctxs[i], hipEventRecord(ctxs[i]->prep_done, ctxs[i]->stream));
+            RVB_HIP(fail, lead, hipStreamWaitEvent(lead->stream, ctxs[i]->prep_done, 0));
+        }
+        TraceArgs args[RVB_MAX_GROUP];
+        for (uint64_t i = 0; i < count; ++i) args[i] = plans[i].a;
+        lead->begin_timing(path_kernel_name(args[0].path_lanes));
+        rvb_launch_path_group(args, (uint32_t) count, lead->stream);
+        lead->end_timing();
+        RVB_HIP(fail, lead, hipEventRecord(lead->group_done, lead->stream));
+        for (uint64_t i = 1; i < count; ++i) {
+            ctxs[i]->begin_timing(path_kernel_name(args[0].path_lanes));   // (elapsed: from this stream's arrival to the end of the group's kernel)
+            RVB_HIP(fail, ctxs[i], hipStreamWaitEvent(ctxs[i]->stream, lead->group_done, 0));
+            ctxs[i]->end_timing();
+        }
+    } else {
+        for (uint64_t i = 0; i < count; ++i) {
+            RVB_BIND(ctxs[i]);
+            ctxs[i]->begin_timing(path_kernel_name(plans[i].a.path_lanes));
+            rvb_launch_path(plans[i].a, ctxs[i]->stream);
+            ctxs[i]->end_timing();
+        }
+    }
+    for (uint64_t i = 0; i < count; ++i) {
+        RVB_BIND(ctxs[i]);
+        const int rc = trace_finish(ctxs[i], plans[i], mics + 3 * i);
+        if (rc != RVB_OK) return rc;
+    }
+    return RVB_OK;
+}
+
+int rvb_trace(rvb_ctx * ctx, const float mic[3], const float source[3], uint64_t nreflections,
+              const float air_coefficient[8], uint64_t ray_offset)
+{
+    if (!ctx) return RVB_ERR_INVALID;
+    if (!mic || !source || !air_coefficient) return fail(ctx, RVB_ERR_INVALID, "rvb_trace: null argument");
+    return trace_common(ctx, mic, source, 1, nreflections, air_coefficient, ray_offset);
+}
+
+int rvb_trace_pairs(rvb_ctx * ctx, const float * mics, const float * sources, uint64_t npairs, uint64_t nreflections,
+                    const float air_coefficient[8], uint64_t ray_offset)
+{
+    if (!ctx) return RVB_ERR_INVALID;
+    if (!mics || !sources || !air_coefficient || npairs == 0) return fail(ctx, RVB_ERR_INVALID, "rvb_trace_pairs: null argument or no pairs");
+    return trace_common(ctx, mics, sources, npairs, nreflections, air_coefficient, ray_offset);
+}
+
+int rvb_ir_select_pair(rvb_ctx * ctx, uint64_t pair)
+{
+    if (!ctx) return RVB_ERR_INVALID;
+    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_ir_select_pair: nothing traced");
+    if (pair >= ctx->npairs) return fail(ctx, RVB_ERR_INVALID, "rvb_ir_select_pair: pair out of range");
+    ctx->ir_pair = pair;
+    ctx->ir_configured = false;
+    for (int i = 0; i < 3; ++i) ctx->mic[i] = ctx->pair_mics_host[3 * pair + i];
+    return RVB_OK;
+}
+
+int rvb_get_diffuse(rvb_ctx * ctx, rvb_impulse * out)
+{
+    if (!ctx) return RVB_ERR_INVALID;
+    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_get_diffuse: nothing traced");
+    RVB_BIND(ctx);
+    RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
+    const size_t bytes = (size_t) ctx->traced_rays * ctx->nreflections * sizeof(rvb_impulse);
+    if (bytes) {
+        if (!out) return fail(ctx, RVB_ERR_INVALID, "rvb_get_diffuse: null output");
+        return rvb_copy_to_host(ctx, out, ctx->impulses.p, bytes);
+    }
+    return RVB_OK;
+}
+
+int rvb_diffuse_device(rvb_ctx * ctx, const void ** d_impulses, uint64_t * count)
+{
+    if (!ctx) return RVB_ERR_INVALID;
+    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_diffuse_device: nothing traced");
+    if (d_impulses) *d_impulses = ctx->impulses.p;
+    if (count) *count = ctx->traced_rays * ctx->nreflections;
+    return RVB_OK;
+}
+
+int rvb_get_direct(rvb_ctx * ctx, rvb_impulse * out)
+{
+    if (!ctx || !out) return RVB_ERR_INVALID;
+    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_get_direct: nothing traced");
+    RVB_BIND(ctx);
+    int rc = fetch_small(ctx);
+    if (rc != RVB_OK) return rc;
+    if (ctx->npairs > 1) *out = ctx->pair_direct_host[ctx->ir_pair];       // of the pair chosen with rvb_ir_select_pair
+    else *out = ctx->small_host->direct;
+    return RVB_OK;
+}
+
+int rvb_get_image_candidates(rvb_ctx * ctx, rvb_image_candidate * out, uint64_t capacity, uint64_t * count)
+{
+    if (!ctx || !count) return RVB_ERR_INVALID;
+    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_get_image_candidates: nothing traced");
+    RVB_BIND(ctx);
+    int rc = fetch_small(ctx);
+    if (rc != RVB_OK) return rc;
+    const uint32_t n = ctx->small_host->candidate_count;
+    *count = n;
+    if (!out)
+        return RVB_OK;                       // size query
+    if (capacity < n)
+        return fail(ctx, RVB_ERR_CAPACITY, "rvb_get_image_candidates: capacity too small");
+    if (n) {
+        if (n <= kFirstCandidates)
+            std::memcpy(out, ctx->first_candidates, (size_t) n * sizeof(rvb_image_candidate));     // came with the small block
+        else
+            RVB_HIP(fail, ctx, hipMemcpy(out, ctx->candidates.p, (size_t) n * sizeof(rvb_image_candidate), hipMemcpyDeviceToHost));
+        std::sort(out, out + n, by_ray_and_slot);
+    }
+    return RVB_OK;
+}
+
+int rvb_merge_images(const rvb_image_candidate * candidates, uint64_t ncandidates,
+                     const rvb_impulse * direct, int remove_direct,
+                     rvb_impulse * out, uint64_t capacity, uint64_t * count)
+{
+    if (!count || (ncandidates && !candidates))
+        return RVB_ERR_INVALID;
+    // reference rayverb.cpp:654-676: for each ray j and k = 1..10 the key is the first k entries of
+    // the ray's index row; inserted if absent when k == 1 or the last entry is non-zero.  Entries
+    // are zero except where a candidate exists, so rows are rebuilt from the candidates alone.
+    std::vector<rvb_image_candidate> sorted(candidates, candidates + ncandidates);
+    std::sort(sorted.begin(), sorted.end(), by_ray_and_slot);
+    std::map<std::vector<unsigned long>, rvb_impulse> tally;
+    if (direct)
+        tally[std::vector<unsigned long>(1, 0)] = *direct;      // k == 1: key {0} from ray 0
+    size_t i = 0;
+    while (i < sorted.size()) {
+        size_t j = i;
+        unsigned long row[RVB_NUM_IMAGE_SOURCE] = {0};
+        while (j < sorted.size() && sorted[j].ray == sorted[i].ray) {
+            if (sorted[j].slot == 0 || sorted[j].slot >= RVB_NUM_IMAGE_SOURCE)
+                return RVB_ERR_INVALID;
+            row[sorted[j].slot] = sorted[j].index;
+            ++j;
+        }
+        for (size_t c = i; c < j; ++c) {
+            std::vector<unsigned long> key(row, row + sorted[c].slot + 1);
+            if (tally.find(key) == tally.end())
+                tally[key] = sorted[c].impulse;
+        }
+        i = j;
+    }
+    if (remove_direct)
+        tally.erase(std::vector<unsigned long>(1, 0));          // rayverb.cpp:695-696
+    *count = tally.size();
+    if (!out)
+        return RVB_OK;
+    if (capacity < tally.size())
+        return RVB_ERR_CAPACITY;
+    size_t w = 0;
+    for (const auto & kv : tally)
+        out[w++] = kv.second;
+    return RVB_OK;
+}
+
+}  // extern "C"
