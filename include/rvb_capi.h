@@ -198,9 +198,9 @@ enum { RVB_IR_FAST = 0, RVB_IR_EXACT = 1 };
 
 /* Speaker layouts: 1 .. RVB_MAX_SPEAKERS channels (a 22.2 layout is 24, a spherical microphone array 32); 0 or more than that is
  * RVB_ERR_INVALID at rvb_ir_configure_speakers, rvb_pipeline_configure_speakers and rvb_multi_ir_speakers.  Channel c of every
- * [nchannels][8][nbins] histogram is speaker c.  Up to 8 channels run the kernels of csrc/stream_kernels.hip; above 8 the speaker table
+ * [nchannels][8][nbins] histogram is speaker c.  Up to 8 channels run the kernels of csrc/histogram_kernels.hip and csrc/exact_kernels.hip; above 8 the speaker table
  * is uploaded to the device at configure time (in stream order) and ONE sort and ONE fold serve all channels, every impulse record
- * gathered from HBM once (csrc/wide_kernels.hip).  Above 8 channels RVB_IR_FAST runs that sorted fold as well — per channel count it is
+ * gathered from HBM once (ordered_sum_wide_kernel, csrc/exact_kernels.hip).  Above 8 channels RVB_IR_FAST runs that sorted fold as well — per channel count it is
  * faster than float atomics, which pay 32 bytes of adds per live impulse and channel (profiles/speaker_arrays_n1.txt) — so there
  * both modes return the exact mode's sums; RVB_IR_FAST promises its rounding bound only, not a mechanism.
  * MEMORY: a histogram is nchannels x 8 x nbins floats — at workload C2's 846 741 bins 27 MB per channel, 1.73 GB at 64 channels — in

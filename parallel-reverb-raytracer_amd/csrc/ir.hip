@@ -10,14 +10,14 @@ namespace {
 
 // ---- materialised attenuation / flatten ---------------------------------------------------------
 
-// device layout [ear][360*180 + 1][8]; the extra row is the zero padding behind quirk Q5.  `table` holds `ears` ears: they go to the
+// device layout [ear][RVB_HRTF_ROWS][8]; the last row is the zero padding behind quirk Q5.  `table` holds `ears` ears: they go to the
 // slots from `first_ear` on, a slot without a table is zeros.
 int upload_hrtf_table(rvb_ctx * ctx, const float * table, int first_ear, int ears)
 {
-    const size_t row = 360 * 180;
-    std::vector<float> padded((size_t) 2 * (row + 1) * 8, 0.0f);
+    const size_t rows = RVB_HRTF_ROWS - 1;                 // rows per ear of the caller's table
+    std::vector<float> padded((size_t) 2 * RVB_HRTF_ROWS * 8, 0.0f);
     for (int e = 0; e < ears; ++e)
-        std::memcpy(padded.data() + (size_t) (first_ear + e) * (row + 1) * 8, table + (size_t) e * row * 8, row * 8 * sizeof(float));
+        std::memcpy(padded.data() + (size_t) (first_ear + e) * RVB_HRTF_ROWS * 8, table + (size_t) e * rows * 8, rows * 8 * sizeof(float));
     RVB_HIP(fail, ctx, ctx->hrtf_table.ensure(padded.size() * sizeof(float)));
     RVB_HIP(fail, ctx, hipMemcpy(ctx->hrtf_table.p, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice));
     return RVB_OK;
@@ -28,8 +28,8 @@ AttenuationModel one_speaker_model(const float mic[3], const rvb_speaker & speak
     AttenuationModel m;
     m.hrtf = 0;
     m.nchannels = 1;
-    for (int i = 0; i < 3; ++i) { m.mic[i] = mic[i]; m.speaker_dir[0][i] = speaker.direction[i]; }
-    m.speaker_coeff[0] = speaker.coefficient;
+    for (int i = 0; i < 3; ++i) m.mic[i] = mic[i];
+    m.speakers[0] = speaker;
     return m;
 }
 
@@ -225,7 +225,7 @@ int exact_fold(rvb_ctx * ctx, uint64_t b0, uint64_t b1, float * hist)
         rvb_launch_ordered_sum_wide(m, ir_diffuse(ctx), e.ndiffuse, ctx->images.as<rvb_impulse>(), ctx->vals_b.as<uint32_t>(),
                                     ctx->bin_starts.as<uint32_t>(), ctx->bin_starts.as<uint32_t>() + e.nbins, e.n, e.nbins, hist, ctx->stream, b0, b1);
     } else {
-        rvb_launch_ordered_sum(m, 0, m.nchannels, ir_diffuse(ctx), e.ndiffuse, ctx->images.as<rvb_impulse>(), e.nimages, ctx->vals_b.as<uint32_t>(),
+        rvb_launch_ordered_sum(m, 0, m.nchannels, ir_diffuse(ctx), e.ndiffuse, ctx->images.as<rvb_impulse>(), ctx->vals_b.as<uint32_t>(),
                                ctx->bin_starts.as<uint32_t>(), ctx->bin_starts.as<uint32_t>() + e.nbins, e.n, e.nbins, hist, ctx->stream, b0, b1);
     }
     RVB_HIP(fail, ctx, hipGetLastError());
@@ -306,7 +306,7 @@ int ir_accumulate_impl(rvb_ctx * ctx, float predelay, float sample_rate, uint64_
             if (rc != RVB_OK) return rc;
             for (uint32_t ch = 0; ch < m.nchannels; ++ch) {
                 if ((rc = exact_list(ctx, in, ch, predelay, sample_rate, nbins, false)) != RVB_OK) return rc;      // (always rocPRIM's sort, as round 2 had it)
-                rvb_launch_ordered_sum(m, ch, 1u, ir_diffuse(ctx), ndiffuse, ctx->images.as<rvb_impulse>(), nimages,
+                rvb_launch_ordered_sum(m, ch, 1u, ir_diffuse(ctx), ndiffuse, ctx->images.as<rvb_impulse>(),
                                        ctx->vals_b.as<uint32_t>(), ctx->bin_starts.as<uint32_t>(), ctx->bin_starts.as<uint32_t>() + nbins, in.n, nbins, hist, ctx->stream);
             }
         }
@@ -429,10 +429,7 @@ int rvb_ir_configure_speakers(rvb_ctx * ctx, const float mic[3], const rvb_speak
     m.hrtf = 0;
     m.nchannels = (uint32_t) nspeakers;
     for (int i = 0; i < 3; ++i) m.mic[i] = mic[i];
-    for (uint64_t s = 0; s < nspeakers && s < 8; ++s) {
-        for (int i = 0; i < 3; ++i) m.speaker_dir[s][i] = speakers[s].direction[i];
-        m.speaker_coeff[s] = speakers[s].coefficient;
-    }
+    for (uint64_t s = 0; s < nspeakers && s < 8; ++s) m.speakers[s] = speakers[s];
     if (nspeakers > 8) {
         // the wide kernels read their speakers from device memory: uploaded in stream order like the images (kernels of an earlier
         // configuration that read the old table run before the copy; the source is the context's own copy, alive until the next configure)
@@ -534,11 +531,10 @@ int rvb_ir_accumulate_export(rvb_ctx * ctx, float predelay, float sample_rate, u
                              void * pinned_dst, uint32_t slices)
 {
     if (ctx && !pinned_dst) return fail(ctx, RVB_ERR_INVALID, "rvb_ir_accumulate_export: null destination");
-    static const uint32_t env_slices = getenv("RVB_EXPORT_SLICES") ? (uint32_t) atoi(getenv("RVB_EXPORT_SLICES")) : 0;      // measurements
     // Default: ONE piece.  Measured at workload C2 (profiles/r04_export_slices_n1.txt): 1 / 2 / 4 / 8 bin ranges leave one impulse response
     // on the host after 6.98 / 7.04 / 7.02 / 7.00 ms (5.88 ms to HBM: the 54 MB need 1.1 ms of the link whenever they start, and the fold they
     // could overlap is 0.27 ms split into launches that cost what the overlap gains) and the pipeline at 4.82 / 4.81 / 4.80 / 4.96 ms per IR.
-    return ir_accumulate_impl(ctx, predelay, sample_rate, nbins, mode, d_histogram, static_cast<float *>(pinned_dst), env_slices ? env_slices : (slices ? slices : 1u));
+    return ir_accumulate_impl(ctx, predelay, sample_rate, nbins, mode, d_histogram, static_cast<float *>(pinned_dst), slices ? slices : 1u);
 }
 
 int rvb_ir_exact_prepare(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins)

@@ -72,7 +72,7 @@ void rvb_launch_images(const TraceArgs & a, hipStream_t s);
 // Phase B: one lane per (ray, bounce): diffuse shadow ray to the microphone and the final
 // Impulse (kernel.cpp:463-490).  Overwrites the work records.
 void rvb_launch_shadow(const TraceArgs & a, hipStream_t s);
-// Grouping of the work records by the leaf position of the triangle they start from (stream_kernels.hip):
+// Grouping of the work records by the leaf position of the triangle they start from (rocprim_sort.hip):
 // order[] lists the records bucket by bucket and the shadow kernel walks that list.
 size_t rvb_group_records_temp_bytes(uint64_t n);
 hipError_t rvb_group_records(void * temp, size_t temp_bytes, const uint32_t * keys, uint32_t * keys_scratch, uint32_t * order,
@@ -80,18 +80,18 @@ hipError_t rvb_group_records(void * temp, size_t temp_bytes, const uint32_t * ke
 hipError_t rvb_group_records16(void * temp, size_t temp_bytes, const uint16_t * keys, uint16_t * keys_scratch, uint32_t * order,
                                uint64_t n, uint32_t first_record, int begin_bit, int end_bit, hipStream_t s);
 
-// ---- streaming kernels (stream_kernels.hip) ---------------------------------------------------
+// ---- the stages behind the trace: attenuate_kernels.hip (materialised attenuation, time range, predelay), histogram_kernels.hip
+// (fast mode), exact_kernels.hip (exact mode, flatten), rocprim_sort.hip (the sort); their shared device code: attenuation.h ----
+#define RVB_HRTF_ROWS (360 * 180 + 1)   // rows per ear of the device's HRTF table: one per (azimuth, elevation) degree, then the zero row behind quirk Q5
 struct AttenuationModel {
     int hrtf = 0;                       // 0: speakers, 1: hrtf
     uint32_t nchannels = 0;             // speakers: <= RVB_MAX_SPEAKERS; hrtf: 2
     float mic[3] = {0, 0, 0};
-    float speaker_dir[8][3] = {};       // normalised on device exactly as kernel.cpp:511 does
-    float speaker_coeff[8] = {};
-    // more than 8 speakers (wide_kernels.hip): the table in device memory, one 16-byte entry per channel — the direction normalised
-    // on the host with normalize3 exactly as make_model does for the eight above, then the coefficient.  speaker_dir / speaker_coeff
-    // then hold the first eight only (the kernels that take them never run for a wide layout).
+    rvb_speaker speakers[8] = {};       // as the caller gave them; make_model passes their device form (speaker_device_form, attenuation.h)
+    // more than 8 speakers (ordered_sum_wide_kernel): the table in device memory, one 16-byte entry per channel — the same device form,
+    // made by rvb_make_speaker_table.  speakers[] then holds the first eight only (the kernels that take them never run for a wide layout).
     const float4 * speaker_table = nullptr;
-    const float * hrtf_table = nullptr; // device [2][360*180+1][8]
+    const float * hrtf_table = nullptr; // device [2][RVB_HRTF_ROWS][8]
     float facing[3] = {0, 0, 0}, up[3] = {0, 0, 0};
 };
 
@@ -111,10 +111,10 @@ void rvb_launch_histogram_transpose(const float * acc, float * hist, uint32_t nc
 void rvb_launch_bin_keys(const AttenuationModel & m, uint32_t channel, const rvb_impulse * in, uint64_t n, uint64_t index_base,
                          float predelay, float sample_rate, uint32_t sentinel, uint32_t * keys, uint32_t * values, hipStream_t s);
 void rvb_launch_ordered_sum(const AttenuationModel & m, uint32_t first_channel, uint32_t nchannels, const rvb_impulse * diffuse,
-                            uint64_t ndiffuse, const rvb_impulse * images, uint64_t nimages,
+                            uint64_t ndiffuse, const rvb_impulse * images,
                             const uint32_t * sorted_values, const uint32_t * starts, const uint32_t * ends, uint64_t n,
                             uint64_t nbins, float * hist, hipStream_t s, uint64_t bin_begin = 0, uint64_t bin_end = ~0ull);   // bins [bin_begin, bin_end) only
-// The same fold for more than 8 speaker channels (wide_kernels.hip): ALL m.nchannels channels of bins [bin_begin, bin_end) in one
+// The same fold for more than 8 speaker channels (ordered_sum_wide_kernel): ALL m.nchannels channels of bins [bin_begin, bin_end) in one
 // launch, the speaker table read from m.speaker_table, every record gathered from HBM once.
 void rvb_make_speaker_table(const rvb_speaker * speakers, uint64_t nspeakers, float4 * table);      // host: the entries of speaker_table
 void rvb_launch_ordered_sum_wide(const AttenuationModel & m, const rvb_impulse * diffuse, uint64_t ndiffuse, const rvb_impulse * images,
@@ -136,13 +136,13 @@ void rvb_launch_flat_keys(const rvb_attenuated_impulse * in, uint64_t n, float s
 void rvb_launch_flat_ordered_sum(const rvb_attenuated_impulse * in, const uint32_t * sorted_keys, const uint32_t * sorted_values,
                                  const uint32_t * starts, uint64_t n, uint64_t nbins, float * out, hipStream_t s);
 void rvb_launch_fix_predelay(rvb_attenuated_impulse * a, uint64_t n, float seconds, hipStream_t s);
-// stable sort of (key, value) pairs by key (device radix sort); temp storage managed by the caller
 // csrc/radix_sort.hip: stable LSD radix sort whose kernels fit beside resident path waves (single-wave workgroups, <= 32 VGPRs)
 size_t rvb_radix_sort_temp_bytes(uint64_t n);
 hipError_t rvb_radix_sort_pairs(void * temp, size_t temp_bytes, const uint32_t * keys, const uint32_t * values, uint32_t value_base,
                                 uint32_t * keys_a, uint32_t * values_a, uint32_t * keys_b, uint32_t * values_b, uint64_t n,
                                 int begin_bit, int end_bit, bool want_keys, const uint32_t ** keys_sorted, const uint32_t ** values_sorted,
                                 hipStream_t s);
+// stable sort of (key, value) pairs by key (rocPRIM's device radix sort, rocprim_sort.hip); temp storage managed by the caller
 size_t rvb_sort_temp_bytes(uint64_t n);
 void rvb_sort_pairs(void * temp, size_t temp_bytes, const uint32_t * keys_in, uint32_t * keys_out,
                     const uint32_t * values_in, uint32_t * values_out, uint64_t n, int key_bits, hipStream_t s);

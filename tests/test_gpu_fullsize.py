@@ -547,7 +547,7 @@ def test_trace_group_one_launch_for_three_contexts_equals_three_traces(ctx):
 def test_c5_hrtf_rows_by_binary32_atan2_and_the_two_ear_list_equal_the_always_exact_evaluation(ctx):
     """The HRTF table row of an impulse needs only the INTEGER parts of two angles in degrees; the kernels take them from the binary32
     atan2f and fall back to the correctly rounded (binary64) evaluation when an angle lies within 2e-3 degrees of an integer
-    (stream_kernels.hip, angle_deg).  At BASELINE config C5's full size — every impulse of 100 000 rays x 128 bounces, two pairs —
+    (attenuation.h, angle_deg).  At BASELINE config C5's full size — every impulse of 100 000 rays x 128 bounces, two pairs —
     the materialised `hrtf` kernel of both ears and the exact-mode [2][8][nbins] histogram (one combined two-ear list, one sort, one
     fold) must give the bytes of the always-exact evaluation with one sorted list per ear (RVB_HRTF_EXACT_ROWS=1,
     RVB_HRTF_SPLIT_EARS=1: the round-2 path, which the oracle-chain tests above pin)."""

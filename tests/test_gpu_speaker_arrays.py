@@ -1,5 +1,5 @@
 """Speaker arrays of more than eight channels (up to capi.MAX_SPEAKERS = 64) through the fused impulse-response path: one key pass,
-one sort and one fold for all channels (csrc/wide_kernels.hip) against the CPU oracle's per-channel chain
+one sort and one fold for all channels (ordered_sum_wide_kernel, csrc/exact_kernels.hip) against the CPU oracle's per-channel chain
 attenuate -> findPredelay / fixPredelay -> flattenImpulses, against the eight-channel path on slices of the same layout, and through the
 step-wise entry points (exact_prepare / exact_fold, two contexts folding one after the other, the export to pinned memory).
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Developer tool: duration of the binning stage at workload C2 for speaker arrays of 8, 16, 24, 32 and 64 channels, both modes, two arms
 alternated in one process on ONE trace (HIP events around the stage, rvb_last_timings):
-    wide      one ir_configure_speakers(C) + ir_accumulate_tensor                       (above 8 channels: csrc/wide_kernels.hip)
+    wide      one ir_configure_speakers(C) + ir_accumulate_tensor                       (above 8 channels: ordered_sum_wide_kernel)
     by hand   ceil(C / 8) x (ir_configure_speakers of eight + ir_accumulate_tensor into that slice of the histogram): what a caller
               had to do while the fused path stopped at eight channels — the eight-channel kernels only
 Every shape is warmed first; min / median / max over the repeats per cell.
