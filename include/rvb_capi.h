@@ -99,7 +99,7 @@ int rvb_set_directions(rvb_ctx * ctx, const rvb_float3 * directions, uint64_t nr
 int rvb_set_directions_device(rvb_ctx * ctx, const void * d_directions, uint64_t nrays);        /* device, borrowed */
 /* A hint, never a change of results: how many traces of this size the caller keeps in flight on the device at a time (several
  * contexts whose streams run side by side; default 1).  The path kernel spends two lanes per ray instead of four when the rays in
- * flight fill the chip without the extra waves (csrc/trace_kernels.hip, rvb_path_lanes_for).  No reference counterpart: the
+ * flight fill the chip without the extra waves (csrc/trace_kernels.hip — the path stage —, rvb_path_lanes_for).  No reference counterpart: the
  * reference runs one 4096-ray group at a time (rayverb.cpp:586-591). */
 int rvb_set_concurrent_traces(rvb_ctx * ctx, uint32_t traces);
 /* Measurement / test hook, never a change of results: the path kernel of this context's traces with `lanes` lanes per ray — 4 (path_kernel),

@@ -22,10 +22,10 @@ __device__ __forceinline__ float4 attenuate_chunk_speaker(const ModelDev & m, ui
         const float len = length3(d);
         const float own = q == 0 ? d.x : (q == 1 ? d.y : d.z);
         const float n_own = len == 0.0f ? own : own / len;         // normalize3: a zero vector stays zero
-        const v3 n = mk3(qdpp_f<QUAD_BCAST(0)>(n_own), qdpp_f<QUAD_BCAST(1)>(n_own), qdpp_f<QUAD_BCAST(2)>(n_own));
+        const v3 n = mk3(dpp_f<QP_BCAST(0)>(n_own), dpp_f<QP_BCAST(1)>(n_own), dpp_f<QP_BCAST(2)>(n_own));
         const float len2 = length3(n);                             // kernel.cpp:511 normalises the unit vector again
         const float u_own = len2 == 0.0f ? n_own : n_own / len2;
-        const v3 u = mk3(qdpp_f<QUAD_BCAST(0)>(u_own), qdpp_f<QUAD_BCAST(1)>(u_own), qdpp_f<QUAD_BCAST(2)>(u_own));
+        const v3 u = mk3(dpp_f<QP_BCAST(0)>(u_own), dpp_f<QP_BCAST(1)>(u_own), dpp_f<QP_BCAST(2)>(u_own));
         const float g = (1 - m.coeff[ch]) + m.coeff[ch] * dot3(u, m.sdir[ch]);
         if (q < 2) o = make_float4(v.x * g, v.y * g, v.z * g, v.w * g);
         else if (q == 2) o.x = r.time;

@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "kernels.h"
+#include "quad.h"
 #include "rvb_math.h"
 
 namespace {
@@ -122,19 +123,6 @@ __device__ __forceinline__ int64_t hrtf_row(const ModelDev & m, v3 pos)
     return row_of(az, el);
 }
 
-// DPP moves inside a quad (lanes 4k..4k+3): quad_perm broadcast of lane K, pair swaps
-template <int CTRL> __device__ __forceinline__ float qdpp_f(float v)
-{
-    return __uint_as_float((uint32_t) __builtin_amdgcn_mov_dpp((int) __float_as_uint(v), CTRL, 0xF, 0xF, true));
-}
-template <int CTRL> __device__ __forceinline__ uint32_t qdpp_u(uint32_t v)
-{
-    return (uint32_t) __builtin_amdgcn_mov_dpp((int) v, CTRL, 0xF, 0xF, true);
-}
-#define QUAD_BCAST(k) ((k) * 0x55)
-#define QUAD_SWAP1 0xB1
-#define QUAD_SWAP2 0x4E
-
 // The same row for two neighbouring lanes that share one impulse (a quad of attenuate_kernel, the two lanes of a bin in
 // ordered_sum_hrtf_kernel): azimuth and elevation are both atan2(y, x) of different arguments, so the even lane evaluates the
 // azimuth and the odd lane the elevation with ONE call, then they swap by DPP.  Same operations on the same operands as hrtf_row.
@@ -145,7 +133,7 @@ __device__ __forceinline__ int64_t hrtf_row_quad(const ModelDev & m, v3 pos, uin
     const float y = odd ? t.y : t.x;
     const float x = odd ? sqrtf(t.x * t.x + t.z * t.z) : t.z;
     const float deg = angle_deg(y, x, odd ? 0.0f : 180.0f, m.exact_rows);
-    const float other = qdpp_f<QUAD_SWAP1>(deg);               // quad_perm [1,0,3,2]: the pair lane's angle
+    const float other = dpp_f<QP_SWAP1>(deg);               // quad_perm [1,0,3,2]: the pair lane's angle
     return row_of(odd ? other : deg, odd ? deg : other);
 }
 
@@ -181,11 +169,11 @@ struct QuadRecord { v3 pos; float time; uint32_t nonzero; };
 __device__ __forceinline__ QuadRecord quad_record(uint32_t q, const float4 v)
 {
     QuadRecord r;
-    r.pos = mk3(qdpp_f<QUAD_BCAST(2)>(v.x), qdpp_f<QUAD_BCAST(2)>(v.y), qdpp_f<QUAD_BCAST(2)>(v.z));
-    r.time = qdpp_f<QUAD_BCAST(3)>(v.x);
+    r.pos = mk3(dpp_f<QP_BCAST(2)>(v.x), dpp_f<QP_BCAST(2)>(v.y), dpp_f<QP_BCAST(2)>(v.z));
+    r.time = dpp_f<QP_BCAST(3)>(v.x);
     r.nonzero = (q < 2 && (v.x != 0.0f || v.y != 0.0f || v.z != 0.0f || v.w != 0.0f)) ? 1u : 0u;
-    r.nonzero |= qdpp_u<QUAD_SWAP1>(r.nonzero);
-    r.nonzero |= qdpp_u<QUAD_SWAP2>(r.nonzero);
+    r.nonzero |= dpp_u<QP_SWAP1>(r.nonzero);
+    r.nonzero |= dpp_u<QP_SWAP2>(r.nonzero);
     return r;
 }
 

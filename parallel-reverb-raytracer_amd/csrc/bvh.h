@@ -5,13 +5,13 @@
 // reference's own Möller–Trumbore arithmetic (rvb_math.h mt_intersect) and the winner is chosen
 // by the reference's rule (smallest distance > EPSILON, ties to the lowest triangle index,
 // kernel.cpp:180-188), so a query returns what the brute-force scan returns.  Boxes are padded
-// and the cull test carries slack (see kPad / cull_slack in trace_kernels.hip) because the
+// and the cull test carries slack (see BuiltScene::pad and the cull slack of slab() in traversal.h) because the
 // float result of the triangle test can land slightly outside the true triangle / true distance.
 //
 // HBM layout (all arrays read-only during a trace, resident in L2 / Infinity Cache):
 //   nodes   : BvhNode[],    64 B, 4-wide, breadth-first (top levels contiguous); one 16-byte
 //             record per child — box as six binary16 values rounded OUTWARD (lo down, hi up), so the
-//             four lanes that cooperate on one ray (trace_kernels.hip) read one contiguous 64-byte
+//             four lanes that cooperate on one ray (traversal.h) read one contiguous 64-byte
 //             half line per node visit with a single 16-byte load each.  Boxes only prune, so their
 //             precision does not touch results; halving node bytes halves the L1 (TCP) traffic.
 //   tris    : BvhTri[],     48 B, in leaf order: v0, e0, e1 (edges precomputed), original index
@@ -36,7 +36,7 @@
 struct BvhChild {                   // 16 B = one 16-byte load
     uint16_t lox, hix, loy, hiy, loz, hiz;   // binary16 bit patterns, the two planes of an axis in one 32-bit word (a conditional
                                     // swap of its halves puts the plane the ray meets first in the low half: slab_select in
-                                    // trace_kernels.hip).  An EMPTY slot holds lo = +inf, hi = -inf.
+                                    // traversal.h).  An EMPTY slot holds lo = +inf, hi = -inf.
     uint32_t ref;                   // EMPTY | LEAF|(count-1)<<28|first | node index << RVB_BVH_NODE_SHIFT
 };
 struct BvhNode { BvhChild c[4]; };  // 64 B

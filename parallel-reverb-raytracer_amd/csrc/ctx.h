@@ -5,7 +5,7 @@
 //   sort.hip     the sorts the other stages call, "sorted list and bin boundaries"
 //   ir.hip       materialised attenuate / flatten, the fused impulse-response stage
 // No compute happens in them and nothing falls back to the CPU: every entry point that produces results launches the HIP kernels
-// of trace_kernels.hip / attenuate_kernels.hip / histogram_kernels.hip / exact_kernels.hip (and the sorts of rocprim_sort.hip / radix_sort.hip).
+// of trace_kernels.hip / image_kernels.hip / shadow_kernels.hip / attenuate_kernels.hip / histogram_kernels.hip / exact_kernels.hip (and the sorts of rocprim_sort.hip / radix_sort.hip).
 #pragma once
 
 #include "../../include/rvb_capi.h"

@@ -56,7 +56,8 @@ struct TraceArgs {
     float air[8];
 };
 
-// Phase A: one lane per ray, the sequential closest-hit / reflect chain (kernel.cpp:359-375,
+// ---- the trace: trace_kernels.hip (path stage), image_kernels.hip, shadow_kernels.hip; their shared device code: traversal.h ----
+// Phase A (trace_kernels.hip): one lane per ray, the sequential closest-hit / reflect chain (kernel.cpp:359-375,
 // :459-461, :478, :492-501).  Leaves a work record per bounce in impulses[].
 void rvb_launch_path(const TraceArgs & a, hipStream_t s);
 // How many surfaces the quad kernels stage in LDS for this scene (all of them, or 0 when they would cost occupancy).
@@ -67,9 +68,9 @@ uint32_t rvb_path_lanes_for(uint64_t nrays, uint32_t concurrent);
 #define RVB_MAX_GROUP 4
 void rvb_launch_path_group(const TraceArgs * traces, uint32_t count, hipStream_t s);
 uint32_t rvb_shadow_lanes();        // lanes per record in the shadow kernel: 2 (shadow_pair_kernel) unless RVB_SHADOW_LANES=4
-// Phase C: image-source validation (kernel.cpp:379-457) + slot 0: a plan kernel (one lane per ray) and a check kernel (four lanes per listed pair).
+// Phase C (image_kernels.hip): image-source validation (kernel.cpp:379-457) + slot 0: a plan kernel (one lane per ray) and a check kernel (four lanes per listed pair).
 void rvb_launch_images(const TraceArgs & a, hipStream_t s);
-// Phase B: one lane per (ray, bounce): diffuse shadow ray to the microphone and the final
+// Phase B (shadow_kernels.hip): one lane per (ray, bounce): diffuse shadow ray to the microphone and the final
 // Impulse (kernel.cpp:463-490).  Overwrites the work records.
 void rvb_launch_shadow(const TraceArgs & a, hipStream_t s);
 // Grouping of the work records by the leaf position of the triangle they start from (rocprim_sort.hip):

@@ -107,7 +107,7 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
         RVB_HIP(fail, ctx, ctx->group_temp.ensure(group_bytes));
         // slots of escaped rays get key 0xFFFFFFFF from path_kernel: they land in the last bucket and the
         // shadow kernel skips them by their valid flag
-        // 16-bit keys in 64-byte runs (trace_kernels.hip, flush_key_run) whenever a ray's row divides into whole runs and rocPRIM sorts;
+        // 16-bit keys in 64-byte runs (the path stage, trace_kernels.hip: flush_key_run) whenever a ray's row divides into whole runs and rocPRIM sorts;
         // 32-bit keys, one store per record, otherwise (and for RVB_SORT=own)
         if (nreflections % 32 == 0 && !own_sort_enabled()) {
             a.sort_keys16 = ctx->sort_keys.as<uint16_t>();
@@ -203,7 +203,7 @@ int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
     return RVB_OK;
 }
 
-// the name a path launch is timed under: the kernel that ran (csrc/trace_kernels.hip, rvb_path_lanes_for)
+// the name a path launch is timed under: the kernel that ran (the path stage, csrc/trace_kernels.hip: rvb_path_lanes_for)
 const char * path_kernel_name(uint32_t lanes) { return lanes == 1 ? "path_lane_kernel" : (lanes == 2 ? "path_pair_kernel" : "path_kernel"); }
 
 int trace_common(rvb_ctx * ctx, const float * mics, const float * sources, uint64_t npairs, uint64_t nreflections,

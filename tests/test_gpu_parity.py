@@ -110,7 +110,10 @@ def test_trace_matches_oracle_on_seeded_scenes(ctx, oracle, name, make, nrays, n
 
 def test_quad_shadow_kernel_gives_the_same_bytes(ctx):
     """The shadow kernel runs two lanes per record; the four-lane kernel it replaced stays in the library for measurements
-    (RVB_SHADOW_LANES=4, read once per process).  A child process traces a seeded scene with it: same bytes."""
+    (RVB_SHADOW_LANES=4, read once per process).  A child process traces a seeded scene with it: same bytes.  A second launch covers
+    what a single pair never runs — the several-pairs branch of the shadow kernels (each record's microphone and time range by its
+    tag) and the 16-bit key runs: two pairs (the second: microphone and source swapped), 352 directions, 64 reflections, which in
+    this process are, pair by pair, the bytes of tracing that pair alone."""
     import os
     import subprocess
     import sys
@@ -120,22 +123,35 @@ def test_quad_shadow_kernel_gives_the_same_bytes(ctx):
     ctx.set_scene(scene)
     ctx.raytrace(info["mic"], info["source"], dirs, 40, AIR_COEFFICIENTS)
     mine = zlib.crc32(ctx.get_raw_diffuse().tobytes())
+    mics, sources = [info["mic"], info["source"]], [info["source"], info["mic"]]
+    ctx.set_directions(scenes.sphere_directions(352, seed=23))
+    ctx.trace_pairs(mics, sources, 64, AIR_COEFFICIENTS)
+    both = ctx.get_raw_diffuse()
+    for p, slice_ in enumerate(both.reshape(2, -1)):
+        ctx.trace(mics[p], sources[p], 64, AIR_COEFFICIENTS)
+        assert np.array_equal(slice_, ctx.get_raw_diffuse()), "pair %d of the two-pair launch" % p
+    mine_pairs = zlib.crc32(both.tobytes())
     code = ("import sys, zlib; sys.path.insert(0, %r); import rvb_import; rvb_import.load();"
             "from parallel_reverb_raytracer_amd import capi, scenes;"
             "from parallel_reverb_raytracer_amd.dtypes import AIR_COEFFICIENTS;"
             "scene, info = scenes.cathedral(3000); c = capi.Context(0); c.set_scene(scene);"
             "c.raytrace(info['mic'], info['source'], scenes.sphere_directions(700, seed=23), 40, AIR_COEFFICIENTS);"
-            "print('CRC', zlib.crc32(c.get_raw_diffuse().tobytes()), dict(c.last_timings()).keys())") % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, RVB_SHADOW_LANES="4"), capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-    line = [l for l in out.stdout.splitlines() if l.startswith("CRC")][-1]
-    assert "shadow_kernel" in line and "shadow_pair_kernel" not in line
-    assert int(line.split()[1]) == mine
+            "print('CRC', zlib.crc32(c.get_raw_diffuse().tobytes()), dict(c.last_timings()).keys());"
+            "c.set_directions(scenes.sphere_directions(352, seed=23));"
+            "c.trace_pairs([info['mic'], info['source']], [info['source'], info['mic']], 64, AIR_COEFFICIENTS);"
+            "print('PAIRS', zlib.crc32(c.get_raw_diffuse().tobytes()), dict(c.last_timings()).keys())") % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def child(lanes, kernel):
+        out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, RVB_SHADOW_LANES=lanes), capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        for word, want in (("CRC", mine), ("PAIRS", mine_pairs)):
+            line = [l for l in out.stdout.splitlines() if l.startswith(word)][-1]
+            assert "'%s'" % kernel in line and "shadow_pair_kernel" not in line, line
+            assert int(line.split()[1]) == want, word
+
+    child("4", "shadow_kernel")
     # ... and the one-lane-per-record form of round 4 (RVB_SHADOW_LANES=1: measured, not the default)
-    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, RVB_SHADOW_LANES="1"), capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-    line = [l for l in out.stdout.splitlines() if l.startswith("CRC")][-1]
-    assert "shadow_lane_kernel" in line and int(line.split()[1]) == mine
+    child("1", "shadow_lane_kernel")
 
 
 def test_own_radix_sort_gives_the_same_bytes(ctx, oracle):

@@ -3,7 +3,7 @@
 
     tools/isa_mix.py [node_steps leaf_steps done_steps]      (wave-level steps per bounce, default: tools/travsim.cpp on workload C2)
 
-Compiles csrc/trace_kernels.hip with -DRVB_ISA_MARKS=1 through the Makefile's `asm` target (comment lines at the borders of the
+Compiles csrc/trace_kernels.hip (the path stage) with -DRVB_ISA_MARKS=1 through the Makefile's `asm` target (comment lines at the borders of the
 schedule / node / leaf / shading blocks of traverse_pairs_cycle, the first still marked "vote"; the marked build is never shipped: the markers are volatile asm and pin the block order), classifies every
 instruction of path_pair_kernel between the markers and weights the three step kinds with the wave-level step counts of one bounce.
 Answers what the PMC class counters cannot: what the "other" VALU instructions (neither f32 add / mul / fma nor integer) ARE."""

@@ -1,5 +1,5 @@
 // travsim.cpp — developer tool (CPU only, not part of the product or the tests): replays the quad
-// traversal of csrc/trace_kernels.hip on the host for a dumped scene and counts ray-level and
+// traversal of csrc/traversal.h (path stage: csrc/trace_kernels.hip) on the host for a dumped scene and counts ray-level and
 // wave-level steps under alternative traversal policies, so that a policy can be judged before a
 // GPU run is spent on it.  Uses the product's own BVH builder and triangle arithmetic.
 //
