@@ -123,6 +123,12 @@ public:
     RaytracerResults getRawImages(bool removeDirect);       // de-duplicated image-source contributions
     RaytracerResults getAllRaw(bool removeDirect);          // diffuse, then images
 
+    // Directional source (no reference counterpart; rvb_set_source_pattern in rvb_capi.h states the contract): the source of the
+    // raytrace() calls that follow faces `direction` and radiates with polar-pattern shape[b] in band b (0 omni, 0.5 cardioid,
+    // 1 figure-of-eight).  clearSourcePattern() returns to the reference's omnidirectional source.
+    void setSourcePattern(const cl_float3 & direction, const std::array<float, 8> & shape);
+    void clearSourcePattern();
+
     ~Raytracer();
 
 private:

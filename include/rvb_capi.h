@@ -130,6 +130,35 @@ int rvb_trace_pairs(rvb_ctx * ctx, const float * mics, const float * sources, ui
  * counterpart (the reference traces one 4096-ray group at a time, rayverb.cpp:586-591). */
 int rvb_trace_group(rvb_ctx ** ctxs, uint64_t count, const float * mics, const float * sources, uint64_t nreflections,
                     const float air_coefficient[8], const uint64_t * ray_offsets);
+/* ---- directional sources: a per-band polar pattern at the SOURCE end (csrc/source_kernels.hip) ------------------------------------
+ * The twin of rvb_speaker at the other end of the path; no reference counterpart (the reference's source radiates equally in every
+ * direction and band).  `direction` is the way the source faces (any non-zero length; direction[3] is ignored), shape[b] the shape of
+ * band b as for a speaker: 0 omni, 0.5 cardioid, 1 figure-of-eight.
+ *
+ * CONTRACT.  For an impulse with departure vector v the gain of band b is
+ *     g_b = (1 - shape_b) + shape_b * dot3(normalize3(normalize3(v)), normalize3(direction))
+ * — the expression of kernel `attenuate` (kernel.cpp:505-513, speaker_gain in csrc/attenuation.h), double normalisation included, one
+ * IEEE binary32 operation per operator in the order written; normalize3(direction) is taken once on the host with the device's operations.
+ *   - diffuse impulses:               v = the ray's own direction (the entry of rvb_set_directions the record's ray was traced with);
+ *   - image-source impulses, direct:  v = mic - position, component by component in binary32.  The trace stores
+ *                                     position = mic + (source - mic_reflection), so mic - position is the direction in which the image
+ *                                     ray leaves the real source, up to the rounding of that one addition; taking v from the record
+ *                                     alone makes the gain a pure function of (record, microphone, ray direction).
+ * The stored impulse becomes volume_b = volume_b * g_b: ONE multiply per band after everything the trace computes without a pattern,
+ * applied to every diffuse Impulse the shadow pass wrote, to every image-source candidate and to the direct slot, each exactly once.
+ * Nothing else changes: rvb_get_diffuse, rvb_get_direct, rvb_get_image_candidates, the materialised attenuators, RVB_IR_FAST and
+ * RVB_IR_EXACT, the wide speaker fold and the HRTF model all see the scaled records.  An impulse whose eight scaled volumes are all
+ * zero (a null of the pattern, or underflow) is a zero-volume impulse from then on (quirk Q2): the diffuse time range of the trace —
+ * what rvb_ir_time_range returns for the speaker model, per pair after rvb_trace_pairs — is that of the SCALED records.
+ *
+ * npatterns == 0 (or patterns == NULL): off — the default; no extra launch, every byte and every kernel as without this call.
+ * npatterns == 1: that pattern for every pair of the traces that follow (rvb_trace, rvb_trace_pairs, rvb_trace_group: every context
+ * has its own).  npatterns == n: pattern p for pair p of rvb_trace_pairs, which fails with RVB_ERR_INVALID unless n is 1 or its npairs;
+ * rvb_trace and rvb_trace_group take n == 1 only.  The patterns are copied.  RVB_ERR_INVALID for a non-finite value or a zero-length
+ * direction.  Cost: one streaming pass over the records behind the shadow kernel ("source_pattern_kernel" in rvb_last_timings). */
+typedef struct { float direction[4]; float shape[8]; } rvb_source_pattern;               /* 48 B */
+int rvb_set_source_pattern(rvb_ctx * ctx, const rvb_source_pattern * patterns, uint64_t npatterns);
+
 /* Chooses the pair that rvb_get_direct and the rvb_ir_* calls below work on (pair 0 after a trace). */
 int rvb_ir_select_pair(rvb_ctx * ctx, uint64_t pair);
 
@@ -302,6 +331,9 @@ int rvb_multi_used_rccl(const rvb_multi * m);            /* 1 if the last RVB_IR
 int rvb_multi_set_scene(rvb_multi * m, const rvb_triangle * triangles, uint64_t ntriangles, const rvb_float3 * vertices, uint64_t nvertices,
                         const rvb_surface * surfaces, uint64_t nsurfaces);
 int rvb_multi_set_directions(rvb_multi * m, const rvb_float3 * directions, uint64_t nrays);
+/* rvb_set_source_pattern(ctx, pattern, 1) on every device's context (NULL: off).  Every device scales its own ray shard with its own
+ * slice of the directions, so the results stay the bytes one context gives. */
+int rvb_multi_set_source_pattern(rvb_multi * m, const rvb_source_pattern * pattern);
 /* Raytracer::raytrace on all devices at once (blocking, like the reference's). */
 int rvb_multi_trace(rvb_multi * m, const float mic[3], const float source[3], uint64_t nreflections, const float air_coefficient[8]);
 /* getRawDiffuse / getRawImages over all shards: ray-major [nrays * nreflections]; merged image sources in std::map key order. */
@@ -357,6 +389,17 @@ int rvb_pipeline_configure_hrtf(rvb_pipeline * p, const float * table /* [2][360
                                 const float air_coefficient[8]);
 int rvb_pipeline_submit(rvb_pipeline * p, const float mic[3], const float source[3]);
 int rvb_pipeline_submit_oriented(rvb_pipeline * p, const float mic[3], const float source[3], const float facing[3], const float up[3]);
+/* Directional sources (rvb_set_source_pattern above) for the jobs that follow; no jobs may be pending, like _configure_*.
+ *   rvb_pipeline_set_source_pattern   the shape per band and the default facing of the source (shape == NULL: off, direction ignored).
+ *                                     From the first call on, the pipeline sets (or clears) the pattern of its contexts with every
+ *                                     trace; a pipeline that never got the call leaves its contexts' patterns alone.
+ *   rvb_pipeline_submit_directed      rvb_pipeline_submit_oriented for ONE job whose source faces `source_direction` (NULL: the default
+ *                                     facing; facing / up may be NULL as in _submit).  RVB_ERR_STATE for a direction while the pattern
+ *                                     is off.  With pairs_per_launch > 1 a unit's launch gets its jobs' patterns in the per-pair form.
+ * RVB_ERR_INVALID for a non-finite value or a zero-length direction. */
+int rvb_pipeline_set_source_pattern(rvb_pipeline * p, const float shape[8], const float direction[3]);
+int rvb_pipeline_submit_directed(rvb_pipeline * p, const float mic[3], const float source[3], const float facing[3], const float up[3],
+                                 const float source_direction[3]);
 uint64_t rvb_pipeline_pending(const rvb_pipeline * p);
 int rvb_pipeline_next(rvb_pipeline * p, rvb_pipeline_result * out);
 

@@ -38,6 +38,7 @@ SYMBOLS = [
     "rvb_device_index", "rvb_pipeline_create", "rvb_pipeline_destroy", "rvb_pipeline_last_error", "rvb_pipeline_configure_speakers",
     "rvb_pipeline_configure_hrtf", "rvb_pipeline_submit", "rvb_pipeline_submit_oriented", "rvb_pipeline_pending", "rvb_pipeline_next",
     "rvb_pipeline_create_lanes",
+    "rvb_set_source_pattern", "rvb_multi_set_source_pattern", "rvb_pipeline_set_source_pattern", "rvb_pipeline_submit_directed",
 ]
 
 PIPELINE_MAX_PAIRS = 8      # RVB_PIPELINE_MAX_PAIRS
@@ -107,6 +108,31 @@ def make_speakers(directions, coefficients):
     sp["direction"][:, :3] = np.asarray(directions, np.float32).reshape(-1, 3)
     sp["coefficient"] = np.asarray(coefficients, np.float32)
     return sp
+
+
+class SourcePattern(ctypes.Structure):
+    """rvb_source_pattern of include/rvb_capi.h: the way the source faces, and a polar-pattern shape per band."""
+    _fields_ = [("direction", ctypes.c_float * 4), ("shape", ctypes.c_float * 8)]
+
+
+def _shape8(shape):
+    s = np.asarray(shape, dtype=np.float32).reshape(-1)
+    if s.shape[0] == 1:
+        s = np.repeat(s, 8)
+    assert s.shape[0] == 8, "shape: a scalar or eight values"
+    return s
+
+
+def make_source_patterns(directions, shapes):
+    """An array of SourcePattern: directions [n][3]; shapes a scalar, eight values (for all patterns) or [n][8]."""
+    d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+    sh = np.asarray(shapes, dtype=np.float32)
+    per = sh.reshape(d.shape[0], 8) if sh.size == 8 * d.shape[0] and sh.ndim == 2 else np.tile(_shape8(sh), (d.shape[0], 1))
+    out = (SourcePattern * d.shape[0])()
+    for i in range(d.shape[0]):
+        out[i].direction[:3] = [float(x) for x in d[i]]
+        out[i].shape[:] = [float(x) for x in per[i]]
+    return out
 
 
 def merge_images(candidates, direct, remove_direct):
@@ -207,6 +233,16 @@ class Context:
     def set_path_lanes(self, lanes):
         """Test / measurement hook: lanes per ray of this context's path kernel (4, 2, 1; 0 = chosen per launch).  Same bytes either way."""
         self._check(self.lib.rvb_set_path_lanes(self.handle, ctypes.c_uint32(int(lanes))))
+
+    def set_source_pattern(self, direction, shape=None):
+        """Directional source for the traces that follow (rvb_set_source_pattern): the source faces `direction` and radiates with
+        `shape` — a scalar or eight values, one per band: 0 omni, 0.5 cardioid, 1 figure-of-eight.  direction None (or shape None)
+        switches it off.  `direction` [n][3] with n > 1 is the per-pair form of trace_pairs (shape: scalar, eight values or [n][8])."""
+        if direction is None or shape is None:
+            self._check(self.lib.rvb_set_source_pattern(self.handle, None, _u64(0)))
+            return
+        pats = make_source_patterns(direction, shape)
+        self._check(self.lib.rvb_set_source_pattern(self.handle, pats, _u64(len(pats))))
 
     def trace(self, mic, source, nreflections, air, ray_offset=0):
         self._check(self.lib.rvb_trace(self.handle, _f3(mic), _f3(source), _u64(nreflections), _f8(air), _u64(ray_offset)))
@@ -475,6 +511,14 @@ class MultiContext:
         self._check(self.lib.rvb_multi_trace(self.handle, _f3(mic), _f3(source), _u64(nreflections), _f8(air)))
         self.nrays, self.nreflections = d.shape[0], int(nreflections)
 
+    def set_source_pattern(self, direction, shape=None):
+        """Context.set_source_pattern on every device's context (rvb_multi_set_source_pattern); None switches it off."""
+        if direction is None or shape is None:
+            self._check(self.lib.rvb_multi_set_source_pattern(self.handle, None))
+            return
+        pats = make_source_patterns([direction], shape)
+        self._check(self.lib.rvb_multi_set_source_pattern(self.handle, pats))
+
     def shard(self, index):
         first, count = _u64(0), _u64(0)
         self._check(self.lib.rvb_multi_context(self.handle, ctypes.c_int(index), None, ctypes.byref(first), ctypes.byref(count)))
@@ -598,8 +642,19 @@ class Pipeline:
                                                          ctypes.c_int(int(trim_predelay)), ctypes.c_float(sample_rate), ctypes.c_int(mode),
                                                          _u64(nreflections), _f8(air)))
 
-    def submit(self, mic, source, facing=None, up=None):
-        if facing is None:
+    def set_source_pattern(self, direction, shape=None):
+        """Directional sources for the jobs that follow (rvb_pipeline_set_source_pattern; no jobs may be pending): `shape` a scalar or
+        eight values, `direction` the default facing of the source; None switches it off."""
+        if direction is None or shape is None:
+            self._check(self.lib.rvb_pipeline_set_source_pattern(self.handle, None, None))
+            return
+        self._check(self.lib.rvb_pipeline_set_source_pattern(self.handle, _f8(_shape8(shape)), _f3(direction)))
+
+    def submit(self, mic, source, facing=None, up=None, source_direction=None):
+        if source_direction is not None:
+            self._check(self.lib.rvb_pipeline_submit_directed(self.handle, _f3(mic), _f3(source), _f3(facing) if facing is not None else None,
+                                                              _f3(up) if up is not None else None, _f3(source_direction)))
+        elif facing is None:
             self._check(self.lib.rvb_pipeline_submit(self.handle, _f3(mic), _f3(source)))
         else:
             self._check(self.lib.rvb_pipeline_submit_oriented(self.handle, _f3(mic), _f3(source), _f3(facing), _f3(up)))

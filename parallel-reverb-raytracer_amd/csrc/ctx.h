@@ -91,6 +91,13 @@ struct rvb_ctx {
     Event pair_stage_free;
     std::vector<rvb_impulse> pair_direct_host;
     std::vector<uint32_t> pair_range_host;
+    // directional sources (rvb_set_source_pattern): the patterns in their device form — empty: off —, uploaded in stream order by the
+    // first trace after they changed (through a pinned staging block of their own, as the per-pair geometry is)
+    std::vector<SourcePatternDev> source_patterns;
+    bool source_dirty = false;
+    DevBuf source_dev;
+    PinnedBuf source_stage;
+    Event source_stage_free;
     DevBuf image_items;                          // work list of the image-source check kernel
     DevBuf impulses, early, candidates, small, stamps, sort_keys, sort_scratch, sort_order, group_temp;       // small: one SmallBlock
     // host mirror of `small`, fetched once per trace together with the first few image-source candidates (usually all of them).

@@ -73,6 +73,14 @@ void rvb_launch_images(const TraceArgs & a, hipStream_t s);
 // Phase B (shadow_kernels.hip): one lane per (ray, bounce): diffuse shadow ray to the microphone and the final
 // Impulse (kernel.cpp:463-490).  Overwrites the work records.
 void rvb_launch_shadow(const TraceArgs & a, hipStream_t s);
+// Directional sources (source_kernels.hip): volume_b *= (1 - shape_b) + shape_b * dot3(normalize3(normalize3(v)), direction) on the final
+// records of a trace — the diffuse impulses (v = the ray's direction), the image-source candidates and the direct slot(s) (v = mic -
+// position) — and the time range of the scaled diffuse records into a.time_range, which the caller has reset (0xFFFFFFFF / 0 per pair).
+// patterns: device [npatterns] in their device form, npatterns 1 (every pair) or a.npairs.  Behind rvb_launch_shadow, on a stream that
+// has waited for rvb_launch_images.
+struct SourcePatternDev { float direction[4]; float shape[8]; };        // rvb_source_pattern with the direction normalised (w = 0)
+SourcePatternDev rvb_source_pattern_device_form(const rvb_source_pattern & p);                      // host
+void rvb_launch_source_pattern(const TraceArgs & a, const SourcePatternDev * patterns, uint32_t npatterns, hipStream_t s);
 // Grouping of the work records by the leaf position of the triangle they start from (rocprim_sort.hip):
 // order[] lists the records bucket by bucket and the shadow kernel walks that list.
 size_t rvb_group_records_temp_bytes(uint64_t n);

@@ -247,6 +247,17 @@ int rvb_multi_set_directions(rvb_multi * m, const rvb_float3 * directions, uint6
     return for_each_shard(m, [&](Shard & s) { return rvb_set_directions(s.ctx, directions + s.first, s.count); });
 }
 
+int rvb_multi_set_source_pattern(rvb_multi * m, const rvb_source_pattern * pattern)
+{
+    if (!m) return RVB_ERR_INVALID;
+    // every device scales its own shard: the records' rays are the shard's own direction slice
+    for (Shard & s : m->shards) {
+        const int rc = rvb_set_source_pattern(s.ctx, pattern, pattern ? 1 : 0);
+        if (rc != RVB_OK) return mfail(m, rc, "device " + std::to_string(s.device) + ": " + rvb_last_error(s.ctx));
+    }
+    return RVB_OK;
+}
+
 int rvb_multi_trace(rvb_multi * m, const float mic[3], const float source[3], uint64_t nreflections, const float air_coefficient[8])
 {
     if (!m) return RVB_ERR_INVALID;

@@ -22,6 +22,7 @@
 #include "hip_owned.h"
 
 #include <algorithm>
+#include <cmath>
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
@@ -38,6 +39,7 @@ struct Job {
     uint64_t id = 0;                          // the lane's submission number (the pipeline's for rvb_pipeline_create)
     uint64_t pair = 0, launch_pairs = 1;      // pairs > 1: this job's pair in its rvb_trace_pairs launch, and that launch's pair count
     float mic[3] = {0, 0, 0}, source[3] = {0, 0, 0}, facing[3] = {0, 0, 0}, up[3] = {0, 0, 0};
+    float source_direction[3] = {0, 0, 0};    // the way this job's source faces (Config::source_on)
     bool begun = false, staged = false;
     uint64_t nbins = 0, nimages = 0;
     float predelay = 0.0f, max_time = 0.0f;
@@ -62,6 +64,9 @@ struct Config {
     float sample_rate = 44100.0f;
     uint64_t nreflections = 0;
     float air[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // directional sources (rvb_pipeline_set_source_pattern): from its first call on the pipeline sets or clears its contexts' patterns
+    bool source_managed = false, source_on = false;
+    float source_shape[8] = {0, 0, 0, 0, 0, 0, 0, 0}, source_direction[3] = {0, 0, 1};
 };
 
 struct Lane {
@@ -132,6 +137,22 @@ Job & job_at(Lane * l, uint64_t id) { return l->jobs[(size_t) (id - l->returned)
 // job i runs on context (i / pairs) % contexts: units go round-robin over the lane's contexts
 Slot & slot_of(Lane * l, uint64_t id) { return l->slots[(size_t) ((id / l->pairs) % l->slots.size())]; }
 
+// the source pattern(s) of the trace that follows on `ctx`: jobs [first, first + count) of ONE launch (the per-pair form for count > 1)
+int set_source_patterns(Lane * l, rvb_ctx * ctx, uint64_t first, uint64_t count)
+{
+    const Config & c = *l->cfg;
+    if (!c.source_managed) return RVB_OK;
+    rvb_source_pattern pats[RVB_PIPELINE_MAX_PAIRS];
+    for (uint64_t k = 0; k < count && c.source_on; ++k) {
+        const Job & j = job_at(l, first + k);
+        for (int i = 0; i < 3; ++i) pats[k].direction[i] = j.source_direction[i];
+        pats[k].direction[3] = 0.0f;
+        std::memcpy(pats[k].shape, c.source_shape, sizeof(c.source_shape));
+    }
+    const int rc = c.source_on ? rvb_set_source_pattern(ctx, pats, count) : rvb_set_source_pattern(ctx, nullptr, 0);
+    return rc != RVB_OK ? cfail(l, rc, ctx, "rvb_pipeline: source pattern") : (int) RVB_OK;
+}
+
 // the traces of jobs [first, last): one launch for the group where the contexts allow it (rvb_trace_group decides); pairs > 1: one unit
 // (or the part of it that is submitted) in ONE rvb_trace_pairs launch on the unit's context
 int begin_jobs(Lane * l, uint64_t first, uint64_t last)
@@ -146,7 +167,9 @@ int begin_jobs(Lane * l, uint64_t first, uint64_t last)
             std::memcpy(mics + 3 * k, j.mic, sizeof(j.mic));
             std::memcpy(sources + 3 * k, j.source, sizeof(j.source));
         }
-        const int rc = rvb_trace_pairs(ctx, mics, sources, count, c.nreflections, c.air, 0);
+        int rc = set_source_patterns(l, ctx, first, count);
+        if (rc != RVB_OK) return rc;
+        rc = rvb_trace_pairs(ctx, mics, sources, count, c.nreflections, c.air, 0);
         if (rc != RVB_OK) return cfail(l, rc, ctx, "rvb_pipeline: trace");
         for (uint64_t k = 0; k < count; ++k) {
             Job & j = job_at(l, first + k);
@@ -163,6 +186,8 @@ int begin_jobs(Lane * l, uint64_t first, uint64_t last)
         ctxs[k] = l->slots[(size_t) ((first + k) % n)].ctx;
         std::memcpy(mics + 3 * k, j.mic, sizeof(j.mic));
         std::memcpy(sources + 3 * k, j.source, sizeof(j.source));
+        const int rs = set_source_patterns(l, ctxs[k], first + k, 1);
+        if (rs != RVB_OK) return rs;
     }
     int rc;
     if (count > 1) rc = rvb_trace_group(ctxs, count, mics, sources, c.nreflections, c.air, nullptr);
@@ -642,11 +667,49 @@ int rvb_pipeline_configure_hrtf(rvb_pipeline * p, const float * table, const flo
     return RVB_OK;
 }
 
+static bool usable_direction(const float d[3])
+{
+    // what rvb_set_source_pattern accepts: finite, and a length binary32 can normalise
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(d[i])) return false;
+    const float len = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    return len > 0.0f && std::isfinite(len);
+}
+
+int rvb_pipeline_set_source_pattern(rvb_pipeline * p, const float shape[8], const float direction[3])
+{
+    if (!p) return RVB_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);        // (the lane threads read the configuration while jobs are pending: none are)
+    if (p->threaded ? p->submitted != p->returned : p->lanes[0]->submitted != p->lanes[0]->returned)
+        return pfail(p, RVB_ERR_STATE, "rvb_pipeline_set_source_pattern: jobs are pending");
+    Config & c = p->cfg;
+    if (shape) {
+        if (!direction) return pfail(p, RVB_ERR_INVALID, "rvb_pipeline_set_source_pattern: a shape needs a direction");
+        for (int b = 0; b < 8; ++b)
+            if (!std::isfinite(shape[b])) return pfail(p, RVB_ERR_INVALID, "rvb_pipeline_set_source_pattern: a shape is not finite");
+        if (!usable_direction(direction)) return pfail(p, RVB_ERR_INVALID, "rvb_pipeline_set_source_pattern: the direction is not finite or has zero length");
+        std::memcpy(c.source_shape, shape, sizeof(c.source_shape));
+        std::memcpy(c.source_direction, direction, sizeof(c.source_direction));
+    }
+    c.source_on = shape != nullptr;
+    c.source_managed = true;
+    return RVB_OK;
+}
+
 int rvb_pipeline_submit_oriented(rvb_pipeline * p, const float mic[3], const float source[3], const float facing[3], const float up[3])
+{
+    return rvb_pipeline_submit_directed(p, mic, source, facing, up, nullptr);
+}
+
+int rvb_pipeline_submit_directed(rvb_pipeline * p, const float mic[3], const float source[3], const float facing[3], const float up[3],
+                                 const float source_direction[3])
 {
     if (!p) return RVB_ERR_INVALID;
     if (!p->cfg.configured) return pfail(p, RVB_ERR_STATE, "rvb_pipeline_submit: rvb_pipeline_configure_* first");
     if (!mic || !source) return pfail(p, RVB_ERR_INVALID, "rvb_pipeline_submit: null argument");
+    if (source_direction && !p->cfg.source_on) return pfail(p, RVB_ERR_STATE, "rvb_pipeline_submit_directed: rvb_pipeline_set_source_pattern first");
+    if (source_direction && !usable_direction(source_direction))
+        return pfail(p, RVB_ERR_INVALID, "rvb_pipeline_submit_directed: the source direction is not finite or has zero length");
     if (rvb_pipeline_pending(p) >= p->limit)
         return pfail(p, RVB_ERR_CAPACITY, p->threaded ? "rvb_pipeline_submit: take results first (2 x contexts x pairs per launch jobs are pending)"
                                                       : "rvb_pipeline_submit: take results first (4 x contexts jobs are pending)");
@@ -655,6 +718,7 @@ int rvb_pipeline_submit_oriented(rvb_pipeline * p, const float mic[3], const flo
     std::memcpy(j.source, source, sizeof(j.source));
     std::memcpy(j.facing, facing ? facing : p->cfg.facing, sizeof(j.facing));
     std::memcpy(j.up, up ? up : p->cfg.up, sizeof(j.up));
+    std::memcpy(j.source_direction, source_direction ? source_direction : p->cfg.source_direction, sizeof(j.source_direction));
     if (!p->threaded) return inline_rc(p, lane_submit(p->lanes[0].get(), j));
     // unit u (pairs per launch consecutive jobs) goes to lane u % lanes; the lane's thread takes it from there
     std::lock_guard<std::mutex> lk(p->mu);

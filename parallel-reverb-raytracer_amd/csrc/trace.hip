@@ -24,6 +24,9 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     if (!ctx->directions && ctx->nrays) return fail(ctx, RVB_ERR_STATE, "rvb_trace: no directions");
     if (nreflections >= (1ull << 31) || ctx->nrays * npairs * 9 >= (1ull << 32))
         return fail(ctx, RVB_ERR_CAPACITY, "rvb_trace: too many reflections or rays for one context");
+    if (ctx->source_patterns.size() > 1 && ctx->source_patterns.size() != npairs)
+        return fail(ctx, RVB_ERR_INVALID, "rvb_trace: " + std::to_string(ctx->source_patterns.size()) + " source patterns for " + std::to_string(npairs) +
+                                          " pair(s): one for all pairs, or one per pair (rvb_set_source_pattern)");
     const float * mic = mics, * source = sources;
     RVB_BIND(ctx);
     ctx->traced = false;                              // (until trace_finish: a failure below must not leave the last trace's results half reset)
@@ -126,6 +129,23 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     for (int i = 0; i < 3; ++i) { a.mic[i] = mic[i]; a.source[i] = source[i]; ctx->mic[i] = mic[i]; }
     for (int i = 0; i < 8; ++i) a.air[i] = air_coefficient[i];
 
+    if (ctx->source_dirty && !ctx->source_patterns.empty()) {
+        // the patterns go up in stream order, through pinned memory (no host synchronisation unless a block has to grow; the staging
+        // block is reused only after the previous copy has left it)
+        const size_t bytes = ctx->source_patterns.size() * sizeof(SourcePatternDev);
+        if (bytes > ctx->source_stage.cap || bytes > ctx->source_dev.cap) {
+            if (ctx->source_dev.p) RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));       // a pass or a copy may still use the old blocks
+            RVB_HIP(fail, ctx, ctx->source_stage.ensure(bytes));
+            RVB_HIP(fail, ctx, ctx->source_dev.ensure(bytes));
+        }
+        if (!ctx->source_stage_free) RVB_HIP(fail, ctx, hipEventCreateWithFlags(&ctx->source_stage_free.h, hipEventDisableTiming));
+        else RVB_HIP(fail, ctx, hipEventSynchronize(ctx->source_stage_free));
+        std::memcpy(ctx->source_stage.p, ctx->source_patterns.data(), bytes);
+        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->source_dev.p, ctx->source_stage.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+        RVB_HIP(fail, ctx, hipEventRecord(ctx->source_stage_free, ctx->stream));
+        ctx->source_dirty = false;
+    }
+
     // diagnostic builds (RVB_STAMPS): [0..15] path_kernel, [16..31] shadow_kernel
     RVB_HIP(fail, ctx, ctx->stamps.ensure(32 * sizeof(unsigned long long)));
     // (zeroed per trace only where a diagnostic build may write them: one tiny fill kernel less on the stream of every shipped trace)
@@ -191,6 +211,23 @@ int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
     rvb_launch_shadow(a, ctx->stream);
     ctx->end_timing();
     RVB_HIP(fail, ctx, hipGetLastError());
+    if (!ctx->source_patterns.empty()) {
+        // directional sources: the final records scaled once — this stream has waited for the image kernels, so the candidates are
+        // final too — and the diffuse time range taken again, over the scaled records: it replaces the shadow kernel's
+        if (npairs > 1) {
+            // (the initial ranges are still in the launch's staging block: trace_prepare's next use of it waits for pair_stage_free)
+            const uint32_t * init = reinterpret_cast<const uint32_t *>(ctx->pair_stage.as<float>() + 8 * npairs);
+            RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_range.p, init, 2 * npairs * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            RVB_HIP(fail, ctx, hipEventRecord(ctx->pair_stage_free, ctx->stream));
+        } else {
+            RVB_HIP(fail, ctx, hipMemsetAsync(a.time_range, 0xFF, 4, ctx->stream));
+            RVB_HIP(fail, ctx, hipMemsetAsync(a.time_range + 1, 0, 4, ctx->stream));
+        }
+        ctx->begin_timing("source_pattern_kernel");
+        rvb_launch_source_pattern(a, ctx->source_dev.as<SourcePatternDev>(), (uint32_t) ctx->source_patterns.size(), ctx->stream);
+        ctx->end_timing();
+        RVB_HIP(fail, ctx, hipGetLastError());
+    }
     ctx->nreflections = nreflections;
     ctx->traced = true;
     ctx->small_valid = false;
@@ -318,6 +355,31 @@ int rvb_trace_pairs(rvb_ctx * ctx, const float * mics, const float * sources, ui
     if (!ctx) return RVB_ERR_INVALID;
     if (!mics || !sources || !air_coefficient || npairs == 0) return fail(ctx, RVB_ERR_INVALID, "rvb_trace_pairs: null argument or no pairs");
     return trace_common(ctx, mics, sources, npairs, nreflections, air_coefficient, ray_offset);
+}
+
+int rvb_set_source_pattern(rvb_ctx * ctx, const rvb_source_pattern * patterns, uint64_t npatterns)
+{
+    if (!ctx) return RVB_ERR_INVALID;
+    if (!patterns) npatterns = 0;
+    std::vector<SourcePatternDev> form;
+    for (uint64_t p = 0; p < npatterns; ++p) {
+        bool finite = true;
+        for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(patterns[p].direction[i]);
+        for (int b = 0; b < 8; ++b) finite = finite && std::isfinite(patterns[p].shape[b]);
+        if (!finite) return fail(ctx, RVB_ERR_INVALID, "rvb_set_source_pattern: pattern " + std::to_string(p) + " holds a value that is not finite");
+        form.push_back(rvb_source_pattern_device_form(patterns[p]));
+        const float * d = form.back().direction;
+        // (a zero vector stays zero under normalize3; a length that overflows or underflows in binary32 does not give a unit vector either)
+        const float len2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+        if (!(len2 > 0.5f && len2 < 2.0f))
+            return fail(ctx, RVB_ERR_INVALID, "rvb_set_source_pattern: pattern " + std::to_string(p) + " has a direction of zero length (or one binary32 cannot normalise)");
+    }
+    // (the same patterns again — a pipeline sets them per job —: what is on the device stays)
+    if (form.size() == ctx->source_patterns.size() && (form.empty() || !std::memcmp(form.data(), ctx->source_patterns.data(), form.size() * sizeof(SourcePatternDev))))
+        return RVB_OK;
+    ctx->source_patterns.swap(form);
+    ctx->source_dirty = true;
+    return RVB_OK;
 }
 
 int rvb_ir_select_pair(rvb_ctx * ctx, uint64_t pair)

@@ -485,6 +485,26 @@ void Raytracer::raytrace(const cl_float3 & micpos, const cl_float3 & source, con
     check(rvb_synchronize(context()), "rvb_synchronize");     // the reference's raytrace() is blocking
 }
 
+void Raytracer::setSourcePattern(const cl_float3 & direction, const std::array<float, 8> & shape)
+{
+    rvb_source_pattern p;
+    for (int i = 0; i < 4; ++i) p.direction[i] = direction.s[i];
+    for (int b = 0; b < 8; ++b) p.shape[b] = shape[(size_t) b];
+    if (multi_) {
+        const int rc = rvb_multi_set_source_pattern(multi_.get(), &p);
+        if (rc != RVB_OK)
+            throw cl::Error(rc, (std::string("rvb_multi_set_source_pattern: ") + rvb_multi_last_error(multi_.get())).c_str());
+        return;
+    }
+    check(rvb_set_source_pattern(context(), &p, 1), "rvb_set_source_pattern");
+}
+
+void Raytracer::clearSourcePattern()
+{
+    if (multi_) (void) rvb_multi_set_source_pattern(multi_.get(), nullptr);
+    else check(rvb_set_source_pattern(context(), nullptr, 0), "rvb_set_source_pattern");
+}
+
 // diffuse impulses into out[0 .. nrays * nreflections), and the note that this buffer has a device copy
 void Raytracer::fetchDiffuse(std::vector<Impulse> & out)
 {
