@@ -94,7 +94,8 @@ __device__ __forceinline__ v3 to_listener(const ModelDev & m, v3 d)
 //   <= 57.3 * 1.5e-6 (atan2f: 6 ulp of pi at most, OpenCL / ocml accuracy) + 2 * 1.6e-5 < 1.2e-4 degrees,
 // so an angle that is farther than kAngleMargin = 2e-3 degrees from every integer truncates to the same integer either way
 // (about 0.4 % of the angles are nearer and take the binary64 path; NaN compares false and takes it too).
-// tests/test_gpu_parity.py holds whole traces' rows against the always-exact evaluation (RVB_HRTF_EXACT_ROWS=1).
+// tests/test_gpu_fullsize.py holds whole traces' rows against the always-exact evaluation (RVB_HRTF_EXACT_ROWS=1);
+// tests/test_gpu_attenuation_edges.py holds all three evaluations against the oracle on angles constructed round every integer boundary.
 #define RVB_DEG_PER_RAD 57.295779513082320877f
 __device__ __forceinline__ float angle_deg(float y, float x, float offset, bool always_exact)
 {
