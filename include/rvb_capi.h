@@ -159,6 +159,53 @@ int rvb_trace_group(rvb_ctx ** ctxs, uint64_t count, const float * mics, const f
 typedef struct { float direction[4]; float shape[8]; } rvb_source_pattern;               /* 48 B */
 int rvb_set_source_pattern(rvb_ctx * ctx, const rvb_source_pattern * patterns, uint64_t npatterns);
 
+/* ---- re-shading a finished trace: new surfaces and a new air coefficient without retracing (csrc/reshade_kernels.hip) -------------
+ * Everything a trace spends its time on — the closest-hit / reflect chain, the shadow rays, the image-source validation, every
+ * position, distance and arrival time — depends on geometry, microphone, source and directions only.  Surfaces and air enter in three
+ * places of the reference (kernel.cpp:461, :480-485, :260).  A caller that sweeps materials in a fixed room (reference chain
+ * cmd/main.cpp:241-298 once per material set) traces ONCE with keeping on and then calls rvb_reshade per material set: one streaming
+ * pass over the records instead of rvb_set_scene + rvb_trace.  No reference counterpart for the calls themselves.
+ *
+ * rvb_keep_paths(ctx, 1): from now on the traces of this context (rvb_trace, rvb_trace_pairs, rvb_trace_group) keep what rvb_reshade
+ * needs: per (ray, bounce) a 16-byte side record {newDist, DIFF, surface, spare} written by one more streaming kernel between the path
+ * and the shadow stage ("path_keep_kernel" in rvb_last_timings), and one float per image-source candidate and direct slot (INIT_DIST,
+ * which cannot be recovered from an impulse's time or position).  Keeping never changes what a trace returns.  Memory: 16 bytes per
+ * (ray, bounce) — 205 MB beside the 819 MB of records at 100 k rays x 128 —, allocated by the first trace made with keeping on.
+ * rvb_keep_paths(ctx, 0), the default: no extra launch, no extra allocation, every byte and every kernel as without this call; the side
+ * buffers of an earlier keep are freed (after waiting for the context's stream) and rvb_reshade fails until the next kept trace.
+ *
+ * rvb_reshade(ctx, surfaces, nsurfaces, air_coefficient), after a trace made with keeping on: the context is left in the state that
+ * rvb_trace / rvb_trace_pairs would have left with the same microphones, sources, directions, nreflections and ray_offset on a scene
+ * whose surface table is `surfaces` and with `air_coefficient`:
+ *   - every byte of the diffuse records (volume, position, time, padding), of the direct slot(s) and of the image-source candidates,
+ *     and the per-pair diffuse time range that rvb_ir_time_range reports for the speaker model, equal that trace's;
+ *     rvb_executed_bounces is unchanged;
+ *   - surfaces == NULL: the scene's own table (only the air changes); otherwise nsurfaces must equal the scene's (RVB_ERR_INVALID).
+ *     Values are taken as rvb_set_scene takes them (the triangles' surface indices were validated there; coefficients are not inspected);
+ *   - the scene stays as it is (it may be shared, rvb_share_scene): the next rvb_trace uses the scene's own surfaces.  The table is copied
+ *     into a buffer of the context; the caller's array is free on return;
+ *   - repeatable in any order: every call starts from the kept numbers, never from the volumes the records hold.  Re-shading with A,
+ *     then B, then the scene's own surfaces and the trace's own air returns the original trace bit for bit;
+ *   - with a source pattern set (rvb_set_source_pattern) the re-shaded records are scaled and the time range taken again, as a trace does;
+ *   - like a trace it voids the IR configuration and a prepared exact list (rvb_ir_configure_* again; rvb_ir_select_pair is back at 0);
+ *   - asynchronous on the context's stream; timed as "reshade_kernel" and "reshade_images_kernel" in rvb_last_timings.
+ * ARITHMETIC, one IEEE binary32 operation per operator in the order written, with the trace's own functions: for ray r, bounce k
+ *     vol_b(k) = -vol_b(k-1) * specular[surface(k)][b], vol_b(-1) = 1                                    (kernel.cpp:461)
+ *     dist     = visible ? newDist(k) + length3(mic - position(k)) : 0                                  (kernel.cpp:471)
+ *     volume_b = visible ? ((vol_b(k) * (air_attenuation(dist, air_b) * 1.0f)) * diffuse[surface(k)][b]) * DIFF(k) : 0
+ * where `visible` is what the shadow stage found (the record's time is non-zero exactly then); an image-source candidate in slot s gets
+ * vol_b(s-2) * (air_attenuation(INIT_DIST, air_b) * 1.0f) with the chain over the ray's first s - 1 triangles, the direct slot
+ * 1 * (air_attenuation(INIT_DIST, air_b) * 1.0f) (kernel.cpp:260).
+ * RVB_ERR_STATE: nothing traced, the last trace was made without keeping, or rvb_set_scene / rvb_share_scene / rvb_set_directions* came
+ * since.  RVB_ERR_HIP with the runtime's text when a buffer cannot be allocated (rvb_trace for the side buffers).  A failed call
+ * leaves the results as they were.  Not offered by rvb_multi_* and rvb_pipeline_*: a sweep is a loop on one context.
+ * MEASURED on one MI355X at 100 k rays x 128 in the 75 k-triangle cathedral (profiles/reshade_n1.txt, tools/reshade_bench.py; medians):
+ *     rvb_trace, keeping off 4.49 ms (the commit before this feature: 4.65 ms, its repetitions spread over 0.20 ms); keeping on 4.80 ms,
+ *     path_keep_kernel 0.335 ms (3.6 x its floor of 48 bytes per record at 6.6 TB/s: it fetches whole 64-byte records);
+ *     rvb_reshade 0.63 ms — reshade_kernel 0.58 ms beside shadow_pair_kernel's 1.24 ms — against 47.6 ms for rvb_set_scene + rvb_trace. */
+int rvb_keep_paths(rvb_ctx * ctx, int keep);
+int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces, const float air_coefficient[8]);
+
 /* Chooses the pair that rvb_get_direct and the rvb_ir_* calls below work on (pair 0 after a trace). */
 int rvb_ir_select_pair(rvb_ctx * ctx, uint64_t pair);
 

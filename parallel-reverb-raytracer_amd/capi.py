@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .dtypes import ATTENUATED, IMPULSE, SPEAKER, aligned_zeros
+from .dtypes import ATTENUATED, IMPULSE, SPEAKER, SURFACE, aligned_zeros
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RVB_LIB", os.path.join(_HERE, "librvb_hip.so"))   # RVB_LIB: A/B builds of the same ABI
@@ -39,6 +39,7 @@ SYMBOLS = [
     "rvb_pipeline_configure_hrtf", "rvb_pipeline_submit", "rvb_pipeline_submit_oriented", "rvb_pipeline_pending", "rvb_pipeline_next",
     "rvb_pipeline_create_lanes",
     "rvb_set_source_pattern", "rvb_multi_set_source_pattern", "rvb_pipeline_set_source_pattern", "rvb_pipeline_submit_directed",
+    "rvb_keep_paths", "rvb_reshade",
 ]
 
 PIPELINE_MAX_PAIRS = 8      # RVB_PIPELINE_MAX_PAIRS
@@ -133,6 +134,14 @@ def make_source_patterns(directions, shapes):
         out[i].direction[:3] = [float(x) for x in d[i]]
         out[i].shape[:] = [float(x) for x in per[i]]
     return out
+
+
+def surface_table(surfaces):
+    """The (array, count) that rvb_reshade takes: a contiguous rvb_surface array, or (None, 0) for the scene's own table."""
+    if surfaces is None:
+        return None, 0
+    table = np.ascontiguousarray(surfaces, dtype=SURFACE).reshape(-1)
+    return table, int(table.shape[0])
 
 
 def merge_images(candidates, direct, remove_direct):
@@ -243,6 +252,16 @@ class Context:
             return
         pats = make_source_patterns(direction, shape)
         self._check(self.lib.rvb_set_source_pattern(self.handle, pats, _u64(len(pats))))
+
+    def keep_paths(self, on):
+        """The traces that follow keep what reshade needs (rvb_keep_paths): 16 bytes per (ray, bounce); False frees them again."""
+        self._check(self.lib.rvb_keep_paths(self.handle, ctypes.c_int(1 if on else 0)))
+
+    def reshade(self, surfaces, air):
+        """The results of the last trace (made with keep_paths(True)) as if the scene had the surface table `surfaces` — None: the
+        scene's own — and the trace the air coefficients `air` (rvb_reshade): no path stage, no shadow rays."""
+        table, count = surface_table(surfaces)
+        self._check(self.lib.rvb_reshade(self.handle, _ptr(table), _u64(count), _f8(air)))
 
     def trace(self, mic, source, nreflections, air, ray_offset=0):
         self._check(self.lib.rvb_trace(self.handle, _f3(mic), _f3(source), _u64(nreflections), _f8(air), _u64(ray_offset)))

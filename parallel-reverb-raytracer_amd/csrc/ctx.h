@@ -1,11 +1,11 @@
 // ctx.h — the context behind include/rvb_capi.h and what its translation units share:
 //   context.hip  life cycle, scene, directions, timings, diagnostics
-//   trace.hip    the trace in three steps, its results, rvb_merge_images
+//   trace.hip    the trace in three steps, its results, rvb_merge_images; re-shading a finished trace
 //   memory.hip   caller-owned device / pinned memory, staged host copies, the export stream
 //   sort.hip     the sorts the other stages call, "sorted list and bin boundaries"
 //   ir.hip       materialised attenuate / flatten, the fused impulse-response stage
 // No compute happens in them and nothing falls back to the CPU: every entry point that produces results launches the HIP kernels
-// of trace_kernels.hip / image_kernels.hip / shadow_kernels.hip / attenuate_kernels.hip / histogram_kernels.hip / exact_kernels.hip (and the sorts of rocprim_sort.hip / radix_sort.hip).
+// of trace_kernels.hip / image_kernels.hip / shadow_kernels.hip / reshade_kernels.hip / attenuate_kernels.hip / histogram_kernels.hip / exact_kernels.hip (and the sorts of rocprim_sort.hip / radix_sort.hip).
 #pragma once
 
 #include "../../include/rvb_capi.h"
@@ -99,6 +99,18 @@ struct rvb_ctx {
     PinnedBuf source_stage;
     Event source_stage_free;
     DevBuf image_items;                          // work list of the image-source check kernel
+    // re-shading (rvb_keep_paths / rvb_reshade, csrc/reshade_kernels.hip).  While keeping is on a trace leaves, beside its results, a
+    // 16-byte side record per (ray, bounce) and the INIT_DIST of every image impulse, and `kept_args` remembers its kernel arguments:
+    // microphones, sources, air, ray offset and every buffer of the launch.  The buffers exist only while keeping is on.
+    bool keep_paths = false;
+    bool kept_valid = false;                     // the last trace was made with keeping on (and `traced` says nothing has voided it since)
+    TraceArgs kept_args = {};
+    DevBuf kept_paths, kept_image_dist;
+    // the surface table of the last rvb_reshade: the scene (which may be shared) keeps its own; uploaded in stream order through a
+    // pinned staging block, as the source patterns are
+    DevBuf reshade_surfaces;
+    PinnedBuf reshade_stage;
+    Event reshade_stage_free;
     DevBuf impulses, early, candidates, small, stamps, sort_keys, sort_scratch, sort_order, group_temp;       // small: one SmallBlock
     // host mirror of `small`, fetched once per trace together with the first few image-source candidates (usually all of them).
     // One PINNED block: a device-to-host copy into pageable memory is staged by the runtime and blocks the host per call (three

@@ -8,8 +8,9 @@
 
 namespace {
 
-// reference kernel.cpp:243-265 (add_image) for a known-valid slot
-__device__ __forceinline__ void make_image(const TraceArgs & a, v3 mic, v3 mic_reflection, v3 source,
+// reference kernel.cpp:243-265 (add_image) for a known-valid slot; returns INIT_DIST, the length of the image path (what a re-shade
+// keeps beside the impulse: TraceArgs::image_dist)
+__device__ __forceinline__ float make_image(const TraceArgs & a, v3 mic, v3 mic_reflection, v3 source,
                                            const float volume[8], rvb_impulse & out)
 {
     const v3 diff = source - mic_reflection;
@@ -21,6 +22,7 @@ __device__ __forceinline__ void make_image(const TraceArgs & a, v3 mic, v3 mic_r
     out.position[0] = pos.x; out.position[1] = pos.y; out.position[2] = pos.z; out.position[3] = 0.0f;
     out.time = seconds_per_meter() * dist;
     out.pad_[0] = out.pad_[1] = out.pad_[2] = 0.0f;
+    return dist;
 }
 
 __device__ __forceinline__ TriVerts load_corners(const SceneDev & sc, uint32_t tri)
@@ -191,11 +193,13 @@ __global__ __launch_bounds__(WAVE) void image_check_kernel(TraceArgs a)
             direct.pad_[0] = direct.pad_[1] = direct.pad_[2] = 0.0f;
             const bool visible = point_visible_quad(a.scene, source, mic, stack);
             if (c == 0) {
+                float dist = -1.0f;                 // (kept for a re-shade: negative = the direct path is hidden)
                 if (visible) {
                     float one[8] = {1, 1, 1, 1, 1, 1, 1, 1};
-                    make_image(a, mic, mic, source, one, direct);
+                    dist = make_image(a, mic, mic, source, one, direct);
                 }
                 a.direct[it.ray] = direct;
+                if (a.image_dist) a.image_dist[a.nrays * (RVB_NUM_IMAGE_SOURCE - 1) + it.ray] = dist;
             }
             continue;
         }
@@ -244,9 +248,10 @@ __global__ __launch_bounds__(WAVE) void image_check_kernel(TraceArgs a)
         cand.ray = a.ray_offset + it.ray;
         cand.slot = it.index + 1;
         cand.index = early[it.index] + 1;
-        make_image(a, mic, chain.mic_reflection, source, volume, cand.impulse);
+        const float dist = make_image(a, mic, chain.mic_reflection, source, volume, cand.impulse);
         const uint32_t at = atomicAdd(a.candidate_count, 1u);
         a.candidates[at] = cand;
+        if (a.image_dist) a.image_dist[at] = dist;
     }
 }
 

@@ -54,6 +54,8 @@ struct TraceArgs {
     float mic[3];
     float source[3];
     float air[8];
+    float * image_dist;                 // rvb_keep_paths only, else null: [nrays * 9 + npairs] INIT_DIST of candidates[i] at i, then of the direct path of every
+                                        // pair (negative: hidden) — what rvb_reshade cannot recover from an image impulse
 };
 
 // ---- the trace: trace_kernels.hip (path stage), image_kernels.hip, shadow_kernels.hip; their shared device code: traversal.h ----
@@ -81,6 +83,18 @@ void rvb_launch_shadow(const TraceArgs & a, hipStream_t s);
 struct SourcePatternDev { float direction[4]; float shape[8]; };        // rvb_source_pattern with the direction normalised (w = 0)
 SourcePatternDev rvb_source_pattern_device_form(const rvb_source_pattern & p);                      // host
 void rvb_launch_source_pattern(const TraceArgs & a, const SourcePatternDev * patterns, uint32_t npatterns, hipStream_t s);
+// Re-shading a finished trace (reshade_kernels.hip; rvb_keep_paths / rvb_reshade of include/rvb_capi.h).
+// path_keep_kernel, between the path and the shadow stage: what the shadow stage destroys of every work record, as a 16-byte side record
+// kept[nrays * nreflections] = {newDist, DIFF, surface (0xFFFFFFFF: the ray had escaped), 0}.  Only reads the records.
+void rvb_launch_path_keep(const TraceArgs & a, float4 * kept, hipStream_t s);
+// How many surfaces the re-shade pass stages in LDS (all of them, or 0: read through L2).
+uint32_t rvb_reshade_lds_surfaces(uint64_t nsurfaces);
+// reshade_kernel: the final volumes of every diffuse record again — the specular chain along the ray from 1, then the shadow stage's
+// product — with a.scene.surfaces, a.air and a.lds_surfaces those of the RE-SHADE, everything else the finished trace's TraceArgs; and
+// the time range into a.time_range, which the caller has reset.  reshade_images_kernel: the candidates [0, *candidate_count) and the
+// direct slot(s), from a.early, a.image_dist and the same table.
+void rvb_launch_reshade(const TraceArgs & a, const float4 * kept, hipStream_t s);
+void rvb_launch_reshade_images(const TraceArgs & a, hipStream_t s);
 // Grouping of the work records by the leaf position of the triangle they start from (rocprim_sort.hip):
 // order[] lists the records bucket by bucket and the shadow kernel walks that list.
 size_t rvb_group_records_temp_bytes(uint64_t n);

@@ -10,48 +10,6 @@
 
 namespace {
 
-// Arrival-time range of the non-zero diffuse impulses, the inputs of findPredelay / MAX_SAMPLE (rayverb.h:49-74, rayverb.cpp:54-57), in
-// a.time_range as float bits (non-negative floats order like their bit patterns).  An atomic is skipped when a plain read says it cannot
-// move the result (stale reads are harmless).
-// Several pairs per launch: one range per pair, updated record by record.
-__device__ __forceinline__ void time_range_of_pair(const TraceArgs & a, const uint32_t pair, const float t)
-{
-    const volatile uint32_t * seen = a.time_range + 2u * pair;
-    if (t != 0.0f && __float_as_uint(t) < seen[0]) atomicMin(a.time_range + 2u * pair, __float_as_uint(t));
-    if (__float_as_uint(t) > seen[1]) atomicMax(a.time_range + 2u * pair + 1u, __float_as_uint(t));
-}
-// One pair: every lane keeps its own range, the wave folds them at the kernel's end.
-__device__ __forceinline__ void time_range_of_wave(const TraceArgs & a, float tmin, float tmax_seen)
-{
-    for (int off = 32; off > 0; off >>= 1) {
-        tmin = fminf(tmin, __shfl_xor(tmin, off));
-        tmax_seen = fmaxf(tmax_seen, __shfl_xor(tmax_seen, off));
-    }
-    if (threadIdx.x == 0 && a.npairs <= 1) {
-        const volatile uint32_t * seen = a.time_range;
-        if (tmin != __builtin_inff() && __float_as_uint(tmin) < seen[0]) atomicMin(a.time_range + 0, __float_as_uint(tmin));
-        if (__float_as_uint(tmax_seen) > seen[1]) atomicMax(a.time_range + 1, __float_as_uint(tmax_seen));
-    }
-}
-
-// kernel.cpp:480-485 for one band: newVol * attenuation * diffuse * DIFF, left to right.  (One band at a time: a float4 form changes all three kernels.)
-__device__ __forceinline__ float band_product(const float vol, const float att, const float dc, const float diff) { return ((vol * att) * dc) * diff; }
-
-// inputs of findPredelay / MAX_SAMPLE (rayverb.h:49-74, rayverb.cpp:54-57): an impulse takes part iff any band is non-zero
-// (kernel.cpp:524).  Several pairs: the record's `writer` lane updates its pair's range; one pair: the lane's running range.
-__device__ __forceinline__ void note_time(const TraceArgs & a, const bool nonzero, const bool writer, const uint32_t pair, const float t,
-                                          float & tmin, float & tmax_seen)
-{
-    if (!nonzero)
-        return;
-    if (a.npairs > 1) {
-        if (writer) time_range_of_pair(a, pair, t);
-    } else {
-        if (t != 0.0f) tmin = fminf(tmin, t);
-        tmax_seen = fmaxf(tmax_seen, t);
-    }
-}
-
 // The shadow rays as Jobs: a quad walks the work records g, g + stride, ...; next() loads a record
 // (the quad reads its 64 bytes as one line, lane c = chunk c) and aims at the microphone
 // (kernel.cpp:463-469), done() finishes the Impulse in place (kernel.cpp:471-490).

@@ -17,6 +17,58 @@ struct TracePlan {
     int key_bits = 1;
 };
 
+// The patterns of rvb_set_source_pattern, where they have changed since the last upload.
+int upload_source_patterns(rvb_ctx * ctx)
+{
+    if (ctx->source_dirty && !ctx->source_patterns.empty()) {
+        // the patterns go up in stream order, through pinned memory (no host synchronisation unless a block has to grow; the staging
+        // block is reused only after the previous copy has left it)
+        const size_t bytes = ctx->source_patterns.size() * sizeof(SourcePatternDev);
+        if (bytes > ctx->source_stage.cap || bytes > ctx->source_dev.cap) {
+            if (ctx->source_dev.p) RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));       // a pass or a copy may still use the old blocks
+            RVB_HIP(fail, ctx, ctx->source_stage.ensure(bytes));
+            RVB_HIP(fail, ctx, ctx->source_dev.ensure(bytes));
+        }
+        if (!ctx->source_stage_free) RVB_HIP(fail, ctx, hipEventCreateWithFlags(&ctx->source_stage_free.h, hipEventDisableTiming));
+        else RVB_HIP(fail, ctx, hipEventSynchronize(ctx->source_stage_free));
+        std::memcpy(ctx->source_stage.p, ctx->source_patterns.data(), bytes);
+        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->source_dev.p, ctx->source_stage.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+        RVB_HIP(fail, ctx, hipEventRecord(ctx->source_stage_free, ctx->stream));
+        ctx->source_dirty = false;
+    }
+    return RVB_OK;
+}
+
+// The diffuse time range(s) of a launch back at "nothing seen": 0xFFFFFFFF / 0, per pair.
+int reset_time_ranges(rvb_ctx * ctx, const TraceArgs & a)
+{
+    if (a.npairs > 1) {
+        // (the initial ranges are still in the launch's staging block: trace_prepare's next use of it waits for pair_stage_free)
+        const uint32_t * init = reinterpret_cast<const uint32_t *>(ctx->pair_stage.as<float>() + 8 * (size_t) a.npairs);
+        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_range.p, init, 2 * (size_t) a.npairs * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        RVB_HIP(fail, ctx, hipEventRecord(ctx->pair_stage_free, ctx->stream));
+    } else {
+        RVB_HIP(fail, ctx, hipMemsetAsync(a.time_range, 0xFF, 4, ctx->stream));
+        RVB_HIP(fail, ctx, hipMemsetAsync(a.time_range + 1, 0, 4, ctx->stream));
+    }
+    return RVB_OK;
+}
+
+// Directional sources behind the kernel that wrote the final records (the shadow kernel of a trace, the re-shade kernels of rvb_reshade):
+// the records scaled once — this stream has waited for the image kernels, so the candidates are final too — and the diffuse time range
+// taken again, over the scaled records: it replaces that kernel's.
+int apply_source_patterns(rvb_ctx * ctx, const TraceArgs & a)
+{
+    if (ctx->source_patterns.empty()) return RVB_OK;
+    const int rc = reset_time_ranges(ctx, a);
+    if (rc != RVB_OK) return rc;
+    ctx->begin_timing("source_pattern_kernel");
+    rvb_launch_source_pattern(a, ctx->source_dev.as<SourcePatternDev>(), (uint32_t) ctx->source_patterns.size(), ctx->stream);
+    ctx->end_timing();
+    RVB_HIP(fail, ctx, hipGetLastError());
+    return RVB_OK;
+}
+
 int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint64_t npairs, uint64_t nreflections,
                   const float air_coefficient[8], uint64_t ray_offset, uint64_t rays_in_flight, TracePlan & plan)
 {
@@ -30,6 +82,7 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     const float * mic = mics, * source = sources;
     RVB_BIND(ctx);
     ctx->traced = false;                              // (until trace_finish: a failure below must not leave the last trace's results half reset)
+    ctx->kept_valid = false;
     const uint64_t nrays = ctx->nrays * npairs;       // rays of this launch
     const size_t imp_bytes = (size_t) nrays * nreflections * sizeof(rvb_impulse);
     const size_t early_bytes = (size_t) nrays * 9 * sizeof(uint32_t);
@@ -37,6 +90,10 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     RVB_HIP(fail, ctx, ctx->early.ensure(early_bytes));
     RVB_HIP(fail, ctx, ctx->candidates.ensure((size_t) nrays * 9 * sizeof(rvb_image_candidate)));
     RVB_HIP(fail, ctx, ctx->image_items.ensure(((size_t) nrays * 9 + npairs) * 3 * sizeof(uint32_t)));      // (ray, bounce) entries, then a state word each
+    if (ctx->keep_paths) {                            // rvb_keep_paths: what rvb_reshade needs beside the results
+        RVB_HIP(fail, ctx, ctx->kept_paths.ensure((size_t) nrays * nreflections * sizeof(float4)));
+        RVB_HIP(fail, ctx, ctx->kept_image_dist.ensure(((size_t) nrays * 9 + npairs) * sizeof(float)));
+    }
 
     // reference rayverb.cpp:600-616: outputs start zero-filled — path_kernel writes every slot of the
     // impulse array itself (work record or zeros), so no 819 MB fill is needed here
@@ -64,6 +121,7 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     a.pair_sources = nullptr;
     a.executed = &small->executed;
     a.time_range = small->trace_range;
+    a.image_dist = ctx->keep_paths ? ctx->kept_image_dist.as<float>() : nullptr;
     if (npairs > 1) {
         // several pairs per launch: geometry, direct path and time range per pair live in arrays of their own
         // staged through pinned memory and copied in stream order: no host synchronisation in front of the launch (the staging
@@ -129,22 +187,8 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     for (int i = 0; i < 3; ++i) { a.mic[i] = mic[i]; a.source[i] = source[i]; ctx->mic[i] = mic[i]; }
     for (int i = 0; i < 8; ++i) a.air[i] = air_coefficient[i];
 
-    if (ctx->source_dirty && !ctx->source_patterns.empty()) {
-        // the patterns go up in stream order, through pinned memory (no host synchronisation unless a block has to grow; the staging
-        // block is reused only after the previous copy has left it)
-        const size_t bytes = ctx->source_patterns.size() * sizeof(SourcePatternDev);
-        if (bytes > ctx->source_stage.cap || bytes > ctx->source_dev.cap) {
-            if (ctx->source_dev.p) RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));       // a pass or a copy may still use the old blocks
-            RVB_HIP(fail, ctx, ctx->source_stage.ensure(bytes));
-            RVB_HIP(fail, ctx, ctx->source_dev.ensure(bytes));
-        }
-        if (!ctx->source_stage_free) RVB_HIP(fail, ctx, hipEventCreateWithFlags(&ctx->source_stage_free.h, hipEventDisableTiming));
-        else RVB_HIP(fail, ctx, hipEventSynchronize(ctx->source_stage_free));
-        std::memcpy(ctx->source_stage.p, ctx->source_patterns.data(), bytes);
-        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->source_dev.p, ctx->source_stage.p, bytes, hipMemcpyHostToDevice, ctx->stream));
-        RVB_HIP(fail, ctx, hipEventRecord(ctx->source_stage_free, ctx->stream));
-        ctx->source_dirty = false;
-    }
+    const int rc = upload_source_patterns(ctx);
+    if (rc != RVB_OK) return rc;
 
     // diagnostic builds (RVB_STAMPS): [0..15] path_kernel, [16..31] shadow_kernel
     RVB_HIP(fail, ctx, ctx->stamps.ensure(32 * sizeof(unsigned long long)));
@@ -181,6 +225,13 @@ int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
     ctx->end_timing(ctx->side_stream);
     RVB_HIP(fail, ctx, hipEventRecord(ctx->side_done, ctx->side_stream));
     a.scene.stamps = ctx->stamps.as<unsigned long long>() + 16;
+    if (ctx->keep_paths) {
+        // rvb_keep_paths: what the shadow kernel is about to overwrite, while the image kernels read the same records on the side stream
+        ctx->begin_timing("path_keep_kernel");
+        rvb_launch_path_keep(a, ctx->kept_paths.as<float4>(), ctx->stream);
+        ctx->end_timing();
+        RVB_HIP(fail, ctx, hipGetLastError());
+    }
     if (a.sort_keys || a.sort_keys16) {
         ctx->begin_timing("record_sort_kernels");
         a.sort_order = ctx->sort_order.as<uint32_t>();
@@ -211,23 +262,10 @@ int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
     rvb_launch_shadow(a, ctx->stream);
     ctx->end_timing();
     RVB_HIP(fail, ctx, hipGetLastError());
-    if (!ctx->source_patterns.empty()) {
-        // directional sources: the final records scaled once — this stream has waited for the image kernels, so the candidates are
-        // final too — and the diffuse time range taken again, over the scaled records: it replaces the shadow kernel's
-        if (npairs > 1) {
-            // (the initial ranges are still in the launch's staging block: trace_prepare's next use of it waits for pair_stage_free)
-            const uint32_t * init = reinterpret_cast<const uint32_t *>(ctx->pair_stage.as<float>() + 8 * npairs);
-            RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_range.p, init, 2 * npairs * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-            RVB_HIP(fail, ctx, hipEventRecord(ctx->pair_stage_free, ctx->stream));
-        } else {
-            RVB_HIP(fail, ctx, hipMemsetAsync(a.time_range, 0xFF, 4, ctx->stream));
-            RVB_HIP(fail, ctx, hipMemsetAsync(a.time_range + 1, 0, 4, ctx->stream));
-        }
-        ctx->begin_timing("source_pattern_kernel");
-        rvb_launch_source_pattern(a, ctx->source_dev.as<SourcePatternDev>(), (uint32_t) ctx->source_patterns.size(), ctx->stream);
-        ctx->end_timing();
-        RVB_HIP(fail, ctx, hipGetLastError());
-    }
+    int rc = apply_source_patterns(ctx, a);
+    if (rc != RVB_OK) return rc;
+    ctx->kept_valid = ctx->keep_paths;
+    if (ctx->kept_valid) ctx->kept_args = a;
     ctx->nreflections = nreflections;
     ctx->traced = true;
     ctx->small_valid = false;
@@ -379,6 +417,77 @@ int rvb_set_source_pattern(rvb_ctx * ctx, const rvb_source_pattern * patterns, u
         return RVB_OK;
     ctx->source_patterns.swap(form);
     ctx->source_dirty = true;
+    return RVB_OK;
+}
+
+int rvb_keep_paths(rvb_ctx * ctx, int keep)
+{
+    if (!ctx) return RVB_ERR_INVALID;
+    if (keep) {
+        ctx->keep_paths = true;                   // (the buffers come with the next trace, sized for it)
+        return RVB_OK;
+    }
+    ctx->keep_paths = false;
+    ctx->kept_valid = false;
+    if (ctx->kept_paths.p || ctx->kept_image_dist.p || ctx->reshade_surfaces.p) {
+        RVB_BIND(ctx);
+        RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));        // a keep pass or a re-shade may still use them
+        RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->side_stream));
+        DevBuf paths(std::move(ctx->kept_paths)), dist(std::move(ctx->kept_image_dist)), table(std::move(ctx->reshade_surfaces));      // freed here
+    }
+    return RVB_OK;
+}
+
+int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces, const float air_coefficient[8])
+{
+    if (!ctx) return RVB_ERR_INVALID;
+    if (!air_coefficient) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade: null air coefficient");
+    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_reshade: nothing traced (or the scene or the directions have changed since)");
+    if (!ctx->kept_valid) return fail(ctx, RVB_ERR_STATE, "rvb_reshade: the last trace was made without rvb_keep_paths(ctx, 1)");
+    if (surfaces && nsurfaces != ctx->nsurfaces)
+        return fail(ctx, RVB_ERR_INVALID, "rvb_reshade: " + std::to_string(nsurfaces) + " surfaces for a scene of " + std::to_string(ctx->nsurfaces));
+    if (ctx->source_patterns.size() > 1 && ctx->source_patterns.size() != ctx->npairs)
+        return fail(ctx, RVB_ERR_INVALID, "rvb_reshade: " + std::to_string(ctx->source_patterns.size()) + " source patterns for " + std::to_string(ctx->npairs) +
+                                          " pair(s): one for all pairs, or one per pair (rvb_set_source_pattern)");
+    RVB_BIND(ctx);
+    TraceArgs a = ctx->kept_args;                    // the trace's own arguments; surfaces and air are the call's
+    if (surfaces) {
+        const size_t bytes = (size_t) nsurfaces * sizeof(rvb_surface);
+        if (bytes > ctx->reshade_stage.cap || bytes > ctx->reshade_surfaces.cap) {
+            if (ctx->reshade_surfaces.p) RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));     // a pass or a copy may still use the old blocks
+            RVB_HIP(fail, ctx, ctx->reshade_stage.ensure(bytes));
+            RVB_HIP(fail, ctx, ctx->reshade_surfaces.ensure(bytes));
+        }
+        if (!ctx->reshade_stage_free) RVB_HIP(fail, ctx, hipEventCreateWithFlags(&ctx->reshade_stage_free.h, hipEventDisableTiming));
+        else RVB_HIP(fail, ctx, hipEventSynchronize(ctx->reshade_stage_free));
+        std::memcpy(ctx->reshade_stage.p, surfaces, bytes);
+        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->reshade_surfaces.p, ctx->reshade_stage.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+        RVB_HIP(fail, ctx, hipEventRecord(ctx->reshade_stage_free, ctx->stream));
+        a.scene.surfaces = ctx->reshade_surfaces.as<const rvb_surface>();
+    } else {
+        a.scene.surfaces = ctx->scene.surfaces;
+    }
+    a.scene.stamps = nullptr;
+    a.lds_surfaces = rvb_reshade_lds_surfaces(ctx->nsurfaces);
+    for (int i = 0; i < 8; ++i) a.air[i] = air_coefficient[i];
+    int rc = upload_source_patterns(ctx);
+    if (rc != RVB_OK) return rc;
+    ctx->reset_timings();
+    if ((rc = reset_time_ranges(ctx, a)) != RVB_OK) return rc;
+    // from here on the results are no longer the trace's: what the host has fetched of them is void
+    ctx->small_valid = false;
+    ctx->ir_configured = false;
+    ctx->exact.valid = false;
+    ctx->begin_timing("reshade_kernel");
+    rvb_launch_reshade(a, ctx->kept_paths.as<const float4>(), ctx->stream);
+    ctx->end_timing();
+    ctx->begin_timing("reshade_images_kernel");
+    rvb_launch_reshade_images(a, ctx->stream);
+    ctx->end_timing();
+    RVB_HIP(fail, ctx, hipGetLastError());
+    if ((rc = apply_source_patterns(ctx, a)) != RVB_OK) return rc;
+    ctx->ir_pair = 0;                             // as a trace leaves it
+    for (int i = 0; i < 3; ++i) ctx->mic[i] = ctx->pair_mics_host[i];
     return RVB_OK;
 }
 

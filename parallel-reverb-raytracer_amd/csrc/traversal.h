@@ -823,6 +823,50 @@ __device__ __forceinline__ float4 surface_row(const TraceArgs & a, const lds_flo
     return reinterpret_cast<const float4 *>(a.scene.surfaces + surface)[chunk];
 }
 
+// ---- the final product of a record and the time range of a launch: shared by the shadow stage (shadow_kernels.hip) and the re-shade
+// pass (reshade_kernels.hip), which repeats that stage's arithmetic without its traversal ----
+// Arrival-time range of the non-zero diffuse impulses, the inputs of findPredelay / MAX_SAMPLE (rayverb.h:49-74, rayverb.cpp:54-57), in
+// a.time_range as float bits (non-negative floats order like their bit patterns).  An atomic is skipped when a plain read says it cannot
+// move the result (stale reads are harmless).
+// Several pairs per launch: one range per pair, updated record by record.
+__device__ __forceinline__ void time_range_of_pair(const TraceArgs & a, const uint32_t pair, const float t)
+{
+    const volatile uint32_t * seen = a.time_range + 2u * pair;
+    if (t != 0.0f && __float_as_uint(t) < seen[0]) atomicMin(a.time_range + 2u * pair, __float_as_uint(t));
+    if (__float_as_uint(t) > seen[1]) atomicMax(a.time_range + 2u * pair + 1u, __float_as_uint(t));
+}
+// One pair: every lane keeps its own range, the wave folds them at the kernel's end.
+__device__ __forceinline__ void time_range_of_wave(const TraceArgs & a, float tmin, float tmax_seen)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        tmin = fminf(tmin, __shfl_xor(tmin, off));
+        tmax_seen = fmaxf(tmax_seen, __shfl_xor(tmax_seen, off));
+    }
+    if (threadIdx.x == 0 && a.npairs <= 1) {
+        const volatile uint32_t * seen = a.time_range;
+        if (tmin != __builtin_inff() && __float_as_uint(tmin) < seen[0]) atomicMin(a.time_range + 0, __float_as_uint(tmin));
+        if (__float_as_uint(tmax_seen) > seen[1]) atomicMax(a.time_range + 1, __float_as_uint(tmax_seen));
+    }
+}
+
+// kernel.cpp:480-485 for one band: newVol * attenuation * diffuse * DIFF, left to right.  (One band at a time: a float4 form changes all three kernels.)
+__device__ __forceinline__ float band_product(const float vol, const float att, const float dc, const float diff) { return ((vol * att) * dc) * diff; }
+
+// inputs of findPredelay / MAX_SAMPLE (rayverb.h:49-74, rayverb.cpp:54-57): an impulse takes part iff any band is non-zero
+// (kernel.cpp:524).  Several pairs: the record's `writer` lane updates its pair's range; one pair: the lane's running range.
+__device__ __forceinline__ void note_time(const TraceArgs & a, const bool nonzero, const bool writer, const uint32_t pair, const float t,
+                                          float & tmin, float & tmax_seen)
+{
+    if (!nonzero)
+        return;
+    if (a.npairs > 1) {
+        if (writer) time_range_of_pair(a, pair, t);
+    } else {
+        if (t != 0.0f) tmin = fminf(tmin, t);
+        tmax_seen = fmaxf(tmax_seen, t);
+    }
+}
+
 // The LDS of a trace workgroup (one wave): [stack_rows][rays] stack words — a ray's (or record's) column, entries `rays` words apart —,
 // then the surface table (64 bytes per staged surface, stage_surfaces), then — path kernels with 16-bit keys only — [rays][RVB_KEY_RUN]
 // grouping keys.  The kernels take their pointers from it and the launchers their byte counts, so the two cannot drift apart.
