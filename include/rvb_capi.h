@@ -206,6 +206,52 @@ int rvb_set_source_pattern(rvb_ctx * ctx, const rvb_source_pattern * patterns, u
 int rvb_keep_paths(rvb_ctx * ctx, int keep);
 int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces, const float air_coefficient[8]);
 
+/* ---- material gradients of a weighted impulse response from a kept trace (csrc/reshade_grad_kernels.hip) ---------------------------
+ * The other half of a material sweep: a fit of absorption coefficients (or of the air) to a measured decay needs a gradient, and by
+ * finite differences that is 16 x nsurfaces + 8 re-shades and binnings per step.  Everything the analytic gradient needs is in the
+ * context after a kept trace: the side records, the records' positions and times, the current table and air, the speaker model.
+ * No reference counterpart.
+ *
+ * THE QUANTITY.  H = what rvb_ir_accumulate(ctx, predelay, sample_rate, nbins, RVB_IR_FAST, zeroed) adds for the current records of the
+ * selected pair (rvb_ir_select_pair) under the configured speaker model: every live diffuse record i adds speaker_gain_c(i) * volume_b(i)
+ * to bin time_bin(time_i, predelay, sample_rate) of row (c, b); records whose bin is >= nbins are skipped.  With the weights w in the
+ * histogram's own layout [nchannels][8][nbins] (device memory), L = sum_{c,b,bin} w[c][b][bin] * H[c][b][bin], and the call returns
+ *     grad_surfaces[s].specular[b] = dL/dspecular[s][b],  grad_surfaces[s].diffuse[b] = dL/ddiffuse[s][b]   (host, the scene's nsurfaces)
+ *     grad_air[b] = dL/dair_b                                                                                (host; may be NULL)
+ * taken at the surface table, air and source pattern that the records reflect now: the scene's own table and the trace's air after a
+ * kept trace, those of the last rvb_reshade after one.  A least-squares fit passes its residual, w = 2 (H - H_target).
+ * H is taken as the polynomial in the coefficients that rvb_reshade's ARITHMETIC writes down (with d air_attenuation / d air =
+ * dist * ln((float) M_E) * air_attenuation): a record whose volume is 0 because a coefficient is 0 still has its derivative.
+ *   - the call never divides by a coefficient: per (ray, band), with P_k = vol_b(k), a_k = air_attenuation * DIFF * pattern gain *
+ *     sum_c w[c][b][bin_k] * gain_c(k) (0 for an invisible or skipped record),
+ *         dL/ddiffuse[s_k][b] += P_k a_k,   dL/dair_b += P_k a_k diffuse[s_k][b] dist_k ln((float) M_E),
+ *         dL/dspecular[s_j][b] += -P_{j-1} B_j,   B_j = a_j diffuse[s_j][b] + (-specular[s_{j+1}][b]) B_{j+1};
+ *   - with a source pattern set, band b's gain of the ray's own direction is a factor of every term of that ray;
+ *   - a surface that no live record of the pair touches gets exactly 0; slots behind an escape and invisible records add nothing;
+ *   - terms in binary32 with the trace's own functions; sums over records and rays in binary64, in a fixed order (a table per
+ *     workgroup, no atomics; the tables added in a fixed order), rounded to float once: the error does not grow with the ray count and
+ *     two calls return identical bytes.
+ * SCOPE of this version.  Diffuse records only: the IR configuration must be rvb_ir_configure_speakers with which == RVB_IR_DIFFUSE and
+ * 1 to 8 channels.  RVB_ERR_STATE, with a text that names the condition, for anything else (the HRTF model, RVB_IR_IMAGES or RVB_IR_ALL,
+ * more than 8 channels, no configuration — rvb_reshade voids it: configure again) and where rvb_reshade itself would return
+ * RVB_ERR_STATE (no kept trace; the scene or the directions changed since).  RVB_ERR_INVALID for a NULL ctx (before any device is
+ * touched), d_weights or grad_surfaces, nbins == 0, a predelay or sample rate that is not finite.  RVB_ERR_CAPACITY above 2048
+ * reflections (a ray's chain checkpoints live in LDS).  Image-source gradients are a follow-up (the merged list has lost its chains), as
+ * are the HRTF model and more than 8 channels; not offered by rvb_multi_* and rvb_pipeline_*, as rvb_reshade is not.
+ * CALLING.  Synchronous: waits for the context's stream and fills the host arrays.  Changes no byte of the records, of the direct slot,
+ * of the candidates or of the time range; the IR configuration stays.  Uses the accumulation image's scratch for the transposed weights
+ * (rvb_ir_accumulate may be called again afterwards as before).  rvb_last_timings: "reshade_grad_weights_kernel" (the weights into the
+ * accumulation image's layout [bin][channel][band]: a record gathers one run of 32 x nchannels bytes), "reshade_grad_kernel",
+ * "reshade_grad_reduce_kernel".  A failed call leaves everything as it was.  A scene of more than 64 surfaces is swept once per 64.
+ * MEASURED on one MI355X at 100 k rays x 128 in the 75 k-triangle cathedral, 7 surfaces, stereo speakers, 846 731 bins
+ * (profiles/reshade_grad_n1.txt, tools/reshade_grad_bench.py; medians of one run): rvb_reshade_grad 1.81 ms — reshade_grad_kernel 1.71 ms,
+ *     reshade_grad_weights_kernel 0.026 ms, reshade_grad_reduce_kernel 0.023 ms — beside rvb_reshade 0.63 ms and rvb_ir_accumulate
+ *     (RVB_IR_FAST) 0.61 ms: 1.46 forward evaluations, where finite differences take 16 x 7 + 8 = 120 of them (148 ms).  Neither the
+ *     side records nor the weights bound it (0.36 TB/s of record bytes); the rest is arithmetic, one binary64 exponential per record
+ *     and band and the fixed-order combine of the rays' terms (no counter run has been made). */
+int rvb_reshade_grad(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins, const void * d_weights, rvb_surface * grad_surfaces,
+                     float grad_air[8]);
+
 /* Chooses the pair that rvb_get_direct and the rvb_ir_* calls below work on (pair 0 after a trace). */
 int rvb_ir_select_pair(rvb_ctx * ctx, uint64_t pair);
 

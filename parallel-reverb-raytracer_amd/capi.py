@@ -39,7 +39,7 @@ SYMBOLS = [
     "rvb_pipeline_configure_hrtf", "rvb_pipeline_submit", "rvb_pipeline_submit_oriented", "rvb_pipeline_pending", "rvb_pipeline_next",
     "rvb_pipeline_create_lanes",
     "rvb_set_source_pattern", "rvb_multi_set_source_pattern", "rvb_pipeline_set_source_pattern", "rvb_pipeline_submit_directed",
-    "rvb_keep_paths", "rvb_reshade",
+    "rvb_keep_paths", "rvb_reshade", "rvb_reshade_grad",
 ]
 
 PIPELINE_MAX_PAIRS = 8      # RVB_PIPELINE_MAX_PAIRS
@@ -88,6 +88,8 @@ def load_library():
         lib.rvb_pipeline_destroy.argtypes = [_vp]
         lib.rvb_pipeline_pending.restype = _u64
         lib.rvb_pipeline_pending.argtypes = [_vp]
+        lib.rvb_reshade_grad.restype = ctypes.c_int
+        lib.rvb_reshade_grad.argtypes = [_vp, ctypes.c_float, ctypes.c_float, _u64, _vp, _vp, _vp]
         _lib = lib
     return _lib
 
@@ -174,6 +176,7 @@ class Context:
         self.nrays = 0
         self.nreflections = 0
         self.nchannels = 0
+        self.nsurfaces = 0
         self._keep = []
 
     def close(self):
@@ -197,10 +200,12 @@ class Context:
         triangles, vertices, surfaces = (np.ascontiguousarray(x) for x in (triangles, vertices, surfaces))
         self._check(self.lib.rvb_set_scene(self.handle, _ptr(triangles), _u64(triangles.shape[0]), _ptr(vertices),
                                            _u64(vertices.shape[0]), _ptr(surfaces), _u64(surfaces.shape[0])))
+        self.nsurfaces = int(surfaces.shape[0])
 
     def share_scene(self, other):
         """This context reads the scene `other` holds: the same device buffers, no second build or copy (rvb_share_scene)."""
         self._check(self.lib.rvb_share_scene(self.handle, other.handle))
+        self.nsurfaces = other.nsurfaces
 
     def scene_info(self):
         nodes, kept, depth = _u64(0), _u64(0), ctypes.c_uint32(0)
@@ -262,6 +267,17 @@ class Context:
         scene's own — and the trace the air coefficients `air` (rvb_reshade): no path stage, no shadow rays."""
         table, count = surface_table(surfaces)
         self._check(self.lib.rvb_reshade(self.handle, _ptr(table), _u64(count), _f8(air)))
+
+    def reshade_grad(self, predelay, sample_rate, nbins, device_weights_pointer):
+        """(grads, grad_air) of L = sum w * H (rvb_reshade_grad): H the histogram ir_accumulate(predelay, sample_rate, nbins, IR_FAST) adds
+        for the selected pair's diffuse records under the configured speakers, w a device array of floats [nchannels][8][nbins].  grads is a
+        SURFACE array of the scene's length holding dL/dspecular and dL/ddiffuse, grad_air a float32[8]; both at the table and air that the
+        records reflect now.  Synchronous."""
+        grads = np.zeros(self.nsurfaces, dtype=SURFACE)
+        grad_air = np.zeros(8, dtype=np.float32)
+        self._check(self.lib.rvb_reshade_grad(self.handle, ctypes.c_float(predelay), ctypes.c_float(sample_rate), _u64(nbins),
+                                              _vp(device_weights_pointer), _ptr(grads), _ptr(grad_air)))
+        return grads, grad_air
 
     def trace(self, mic, source, nreflections, air, ray_offset=0):
         self._check(self.lib.rvb_trace(self.handle, _f3(mic), _f3(source), _u64(nreflections), _f8(air), _u64(ray_offset)))

@@ -79,6 +79,17 @@ __device__ __forceinline__ float speaker_gain(const ModelDev & m, uint32_t ch, v
     return (1 - m.coeff[ch]) + m.coeff[ch] * dot3(normalize3(direction), m.sdir[ch]);
 }
 
+// speaker_gain in its two steps, for a kernel that takes the direction once per impulse and the gain once per channel
+// (reshade_grad_kernels.hip): same operations on the same operands
+__device__ __forceinline__ v3 arrival_direction(const ModelDev & m, v3 pos) { return normalize3(normalize3(pos - m.mic)); }
+__device__ __forceinline__ float speaker_gain_toward(const ModelDev & m, uint32_t ch, v3 direction)
+{
+    return (1 - m.coeff[ch]) + m.coeff[ch] * dot3(direction, m.sdir[ch]);
+}
+
+// rvb_source_pattern's gain of one band (source_kernels.hip): from the band's shape and d = dot3(normalize3(normalize3(v)), direction)
+__device__ __forceinline__ float band_gain(const float shape, const float d) { return (1 - shape) + shape * d; }
+
 // reference kernel.cpp:563-584: table row selected for an impulse at `pos` (same for both ears)
 // transform (kernel.cpp:538-549) with the precomputed basis: the three dot products that remain per impulse
 __device__ __forceinline__ v3 to_listener(const ModelDev & m, v3 d)

@@ -1,11 +1,11 @@
 // ctx.h — the context behind include/rvb_capi.h and what its translation units share:
 //   context.hip  life cycle, scene, directions, timings, diagnostics
-//   trace.hip    the trace in three steps, its results, rvb_merge_images; re-shading a finished trace
+//   trace.hip    the trace in three steps, its results, rvb_merge_images; re-shading a finished trace and its material gradients
 //   memory.hip   caller-owned device / pinned memory, staged host copies, the export stream
 //   sort.hip     the sorts the other stages call, "sorted list and bin boundaries"
 //   ir.hip       materialised attenuate / flatten, the fused impulse-response stage
 // No compute happens in them and nothing falls back to the CPU: every entry point that produces results launches the HIP kernels
-// of trace_kernels.hip / image_kernels.hip / shadow_kernels.hip / reshade_kernels.hip / attenuate_kernels.hip / histogram_kernels.hip / exact_kernels.hip (and the sorts of rocprim_sort.hip / radix_sort.hip).
+// of trace_kernels.hip / image_kernels.hip / shadow_kernels.hip / reshade_kernels.hip / reshade_grad_kernels.hip / attenuate_kernels.hip / histogram_kernels.hip / exact_kernels.hip (and the sorts of rocprim_sort.hip / radix_sort.hip).
 #pragma once
 
 #include "../../include/rvb_capi.h"
@@ -111,6 +111,12 @@ struct rvb_ctx {
     DevBuf reshade_surfaces;
     PinnedBuf reshade_stage;
     Event reshade_stage_free;
+    // what the records reflect right now — the kept trace's table, air and source patterns, or those of the last rvb_reshade —: where
+    // rvb_reshade_grad (csrc/reshade_grad_kernels.hip) takes its derivatives.  Its result and partial tables live in grad_scratch.
+    const rvb_surface * shaded_surfaces = nullptr;
+    float shaded_air[8] = {};
+    std::vector<SourcePatternDev> shaded_patterns;
+    DevBuf grad_scratch;
     DevBuf impulses, early, candidates, small, stamps, sort_keys, sort_scratch, sort_order, group_temp;       // small: one SmallBlock
     // host mirror of `small`, fetched once per trace together with the first few image-source candidates (usually all of them).
     // One PINNED block: a device-to-host copy into pageable memory is staged by the runtime and blocks the host per call (three

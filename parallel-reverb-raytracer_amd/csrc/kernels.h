@@ -95,6 +95,30 @@ uint32_t rvb_reshade_lds_surfaces(uint64_t nsurfaces);
 // direct slot(s), from a.early, a.image_dist and the same table.
 void rvb_launch_reshade(const TraceArgs & a, const float4 * kept, hipStream_t s);
 void rvb_launch_reshade_images(const TraceArgs & a, hipStream_t s);
+// Material gradients of a weighted histogram from the kept trace (reshade_grad_kernels.hip; rvb_reshade_grad of include/rvb_capi.h).
+// The launch works on ONE pair's rays, [first_ray, first_ray + nrays) of the kept launch, with the speaker model `model` (<= 8 channels)
+// and the weights already in the accumulation image's layout [bin][channel][band] (rvb_launch_reshade_grad_weights makes it from the
+// histogram's layout [channel][8][nbins]).  Every workgroup keeps a binary64 table of nsurfaces * 16 + 8 sums — a surface's row in
+// rvb_surface's order, then the eight air derivatives — and leaves it in partials[block]; the reduce kernel adds the `blocks` tables in a
+// fixed order and rounds once: out[nsurfaces * 16 + 8] floats.  Bit-identical from run to run.
+struct AttenuationModel;
+struct ReshadeGradArgs {
+    const float * weights;              // device [nbins][nchannels][8]
+    uint64_t nbins;
+    float predelay, sample_rate;
+    uint64_t first_ray;                 // of the pair within the kept launch
+    uint32_t nrays;                     // rays of the pair
+    float mic[3];                       // the pair's microphone in the trace
+    bool has_pattern;                   // a source pattern scales the pair's records
+    SourcePatternDev pattern;
+    uint64_t nsurfaces;
+};
+#define RVB_RESHADE_GRAD_MAX_REFLECTIONS 2048     // a ray's chain checkpoints (one per tile of bounces and lane) live in LDS
+uint32_t rvb_reshade_grad_blocks(uint64_t nrays, uint64_t nsurfaces);      // workgroups (= partial tables) of the launch
+void rvb_launch_reshade_grad_weights(const float * weights, float * transposed, uint32_t nchannels, uint64_t nbins, hipStream_t s);
+void rvb_launch_reshade_grad(const TraceArgs & a, const float4 * kept, const AttenuationModel & model, const ReshadeGradArgs & g,
+                             double * partials, uint32_t blocks, hipStream_t s);
+void rvb_launch_reshade_grad_reduce(const double * partials, uint32_t blocks, uint64_t nsurfaces, float * out, hipStream_t s);
 // Grouping of the work records by the leaf position of the triangle they start from (rocprim_sort.hip):
 // order[] lists the records bucket by bucket and the shadow kernel walks that list.
 size_t rvb_group_records_temp_bytes(uint64_t n);

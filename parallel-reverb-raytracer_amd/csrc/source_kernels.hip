@@ -14,8 +14,7 @@
 
 namespace {
 
-// g_b of the contract, from the band's shape and d = dot3(normalize3(normalize3(v)), direction)
-__device__ __forceinline__ float band_gain(const float shape, const float d) { return (1 - shape) + shape * d; }
+// (g_b of the contract: band_gain of attenuation.h)
 
 // kernel.cpp:511 / :528 on the departure vector `v`: normalize3(normalize3(v)) with lane k of the quad dividing component k, as
 // attenuate_chunk_speaker does (one correctly rounded division per normalisation and wave instead of three; same operations on the

@@ -69,6 +69,14 @@ int apply_source_patterns(rvb_ctx * ctx, const TraceArgs & a)
     return RVB_OK;
 }
 
+// rvb_reshade_grad differentiates at the table, air and source patterns that the records reflect: those of the launch that wrote them last.
+void note_shading(rvb_ctx * ctx, const TraceArgs & a)
+{
+    ctx->shaded_surfaces = a.scene.surfaces;
+    for (int i = 0; i < 8; ++i) ctx->shaded_air[i] = a.air[i];
+    ctx->shaded_patterns = ctx->source_patterns;
+}
+
 int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint64_t npairs, uint64_t nreflections,
                   const float air_coefficient[8], uint64_t ray_offset, uint64_t rays_in_flight, TracePlan & plan)
 {
@@ -265,7 +273,10 @@ int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
     int rc = apply_source_patterns(ctx, a);
     if (rc != RVB_OK) return rc;
     ctx->kept_valid = ctx->keep_paths;
-    if (ctx->kept_valid) ctx->kept_args = a;
+    if (ctx->kept_valid) {
+        ctx->kept_args = a;
+        note_shading(ctx, a);
+    }
     ctx->nreflections = nreflections;
     ctx->traced = true;
     ctx->small_valid = false;
@@ -486,8 +497,72 @@ int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces,
     ctx->end_timing();
     RVB_HIP(fail, ctx, hipGetLastError());
     if ((rc = apply_source_patterns(ctx, a)) != RVB_OK) return rc;
+    note_shading(ctx, a);
     ctx->ir_pair = 0;                             // as a trace leaves it
     for (int i = 0; i < 3; ++i) ctx->mic[i] = ctx->pair_mics_host[i];
+    return RVB_OK;
+}
+
+int rvb_reshade_grad(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins, const void * d_weights, rvb_surface * grad_surfaces,
+                     float grad_air[8])
+{
+    if (!ctx) return RVB_ERR_INVALID;
+    if (!d_weights || !grad_surfaces) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: null weights or null output");
+    if (nbins == 0 || nbins >= (1ull << 32)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: no bins (or more than 32-bit bin numbers reach)");
+    if (!std::isfinite(predelay) || !std::isfinite(sample_rate)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: predelay or sample rate is not finite");
+    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: nothing traced (or the scene or the directions have changed since)");
+    if (!ctx->kept_valid) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: the last trace was made without rvb_keep_paths(ctx, 1)");
+    if (!ctx->ir_configured) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: no IR configuration (rvb_ir_configure_speakers after the trace or re-shade)");
+    if (ctx->model.hrtf) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: the HRTF model is configured; this version takes the speaker model only");
+    if (ctx->which != RVB_IR_DIFFUSE) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: configured with image sources; this version takes which == RVB_IR_DIFFUSE only");
+    if (ctx->model.nchannels > 8)
+        return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: " + std::to_string(ctx->model.nchannels) + " speaker channels configured; this version takes 1 to 8");
+    if (ctx->nreflections > RVB_RESHADE_GRAD_MAX_REFLECTIONS)
+        return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad: more than " RVB_STR(RVB_RESHADE_GRAD_MAX_REFLECTIONS) " reflections");
+    if (ctx->nsurfaces >= (1ull << 27)) return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad: too many surfaces");
+    RVB_BIND(ctx);
+    TraceArgs a = ctx->kept_args;                    // the trace's own arguments, with the surfaces and air that the records reflect now
+    a.scene.surfaces = ctx->shaded_surfaces;
+    a.scene.stamps = nullptr;
+    a.lds_surfaces = rvb_reshade_lds_surfaces(ctx->nsurfaces);
+    for (int i = 0; i < 8; ++i) a.air[i] = ctx->shaded_air[i];
+    const uint32_t nchannels = ctx->model.nchannels;
+    const uint64_t entries = ctx->nsurfaces * 16 + 8;
+    const uint32_t blocks = rvb_reshade_grad_blocks(ctx->nrays, ctx->nsurfaces);
+    // the weights in the accumulation image's layout go where that image goes; the result (floats), then the partial tables (doubles)
+    const size_t out_bytes = (entries * sizeof(float) + 15) & ~(size_t) 15;
+    RVB_HIP(fail, ctx, ctx->acc.ensure((size_t) nbins * nchannels * 8 * sizeof(float)));
+    RVB_HIP(fail, ctx, ctx->grad_scratch.ensure(out_bytes + (size_t) blocks * entries * sizeof(double)));
+    float * d_out = ctx->grad_scratch.as<float>();
+    double * partials = reinterpret_cast<double *>(ctx->grad_scratch.as<char>() + out_bytes);
+    ReshadeGradArgs g;
+    g.weights = ctx->acc.as<float>();
+    g.nbins = nbins;
+    g.predelay = predelay;
+    g.sample_rate = sample_rate;
+    g.first_ray = ctx->ir_pair * ctx->nrays;
+    g.nrays = (uint32_t) ctx->nrays;
+    for (int i = 0; i < 3; ++i) g.mic[i] = ctx->pair_mics_host[3 * ctx->ir_pair + i];
+    g.has_pattern = !ctx->shaded_patterns.empty();
+    g.pattern = g.has_pattern ? ctx->shaded_patterns[ctx->shaded_patterns.size() > 1 ? ctx->ir_pair : 0] : SourcePatternDev{};
+    g.nsurfaces = ctx->nsurfaces;
+    ctx->reset_timings();
+    ctx->begin_timing("reshade_grad_weights_kernel");
+    rvb_launch_reshade_grad_weights(reinterpret_cast<const float *>(d_weights), ctx->acc.as<float>(), nchannels, nbins, ctx->stream);
+    ctx->end_timing();
+    ctx->begin_timing("reshade_grad_kernel");
+    rvb_launch_reshade_grad(a, ctx->kept_paths.as<const float4>(), ctx->model, g, partials, blocks, ctx->stream);
+    ctx->end_timing();
+    ctx->begin_timing("reshade_grad_reduce_kernel");
+    rvb_launch_reshade_grad_reduce(partials, blocks, ctx->nsurfaces, d_out, ctx->stream);
+    ctx->end_timing();
+    RVB_HIP(fail, ctx, hipGetLastError());
+    RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<float> host(entries);
+    const int rc = rvb_copy_to_host(ctx, host.data(), d_out, entries * sizeof(float));
+    if (rc != RVB_OK) return rc;
+    std::memcpy(grad_surfaces, host.data(), (size_t) ctx->nsurfaces * sizeof(rvb_surface));
+    if (grad_air) std::memcpy(grad_air, host.data() + ctx->nsurfaces * 16, 8 * sizeof(float));
     return RVB_OK;
 }
 
