@@ -252,6 +252,71 @@ int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces,
 int rvb_reshade_grad(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins, const void * d_weights, rvb_surface * grad_surfaces,
                      float grad_air[8]);
 
+/* ---- decay curves: Schroeder integral, reverberation times, the loss against a measured decay and its adjoint (csrc/decay_kernels.hip) ---
+ * What a fit of materials to a measured decay needs between rvb_ir_accumulate, which leaves the histogram H on the device, and
+ * rvb_reshade_grad, which takes w = dL/dH: the energy decay curve of every row, a loss L against a target decay, and w.  Nothing leaves
+ * the device but a few numbers per row.  No reference counterpart (the reference has no decay analysis).
+ *
+ * All three calls work on the caller's own device arrays of nrows rows of nbins floats, row r at element r * nbins; a histogram
+ * [nchannels][8][nbins] is nrows = 8 * nchannels.  They use the context for its device, stream, scratch and timings only: no scene, trace
+ * or IR configuration is needed, none of them voids an IR configuration or a prepared exact list or touches a record, and their scratch
+ * is a block of its own in the context, grown on demand (never the sort buffers).
+ * THE ORDER of every sum is fixed by the bin numbers alone.  A row is cut into tiles of RVB_DECAY_TILE bins; every call is a launch that
+ * leaves one binary64 value per tile, a launch in which one wave per row combines the row's tiles one after the other, and a launch that
+ * scans every tile again on top of its carry.  No atomics, no hand-off between workgroups inside a launch, no dependence on dispatch
+ * order: this fixed order makes two calls return identical bytes.  Sums and logarithms are binary64; a result is rounded to float once.
+ *
+ * rvb_decay_curve   E[r][k] = sum_{j >= k} H[r][j]^2, the Schroeder integral: the squares (exact in binary64) and the sums in binary64,
+ *                   per tile, then the tiles of a row from the last to the first, then every tile from its last bin to its first on top
+ *                   of its carry.  |E - exact| <= one float ulp; E is exactly 0 where every later bin of H is 0.  Values are not
+ *                   inspected.  d_curve is [nrows][nbins] float and must not overlap d_histogram (RVB_ERR_INVALID).  Asynchronous on the
+ *                   context's stream.
+ * rvb_decay_times   seconds[r] = the reverberation time of row r of a curve E, extrapolated to 60 dB from the range db_begin .. db_end
+ *                   (-5, -35: T30; -5, -25: T20; 0, -10: the early decay time).  In binary64: level[k] = 10 log10(E[k] / E[0]); k0 is the
+ *                   first k with level <= db_begin, k1 the first k with level < db_end, both found by comparing E[k] with
+ *                   E[0] * 10^(db / 10), not through a logarithm per bin (a bin with E = 0 is below every level; E does not increase,
+ *                   so [k0, k1) is one run).  The least-squares line of level over x = k - k0, x centred on the window, has
+ *                   slope = sum (x - mean x) level / sum (x - mean x)^2 in dB per bin, the first sum over the bins in the fixed order,
+ *                   the second in closed form; seconds = -60 / (slope * sample_rate).  The result is a quiet NaN — the "not available"
+ *                   value — for a row with E[0] == 0, with fewer than 2 bins in the window, or whose curve never falls below db_end
+ *                   inside nbins.  Synchronous.  RVB_ERR_INVALID unless db_end < db_begin <= 0 with both finite, and sample_rate finite
+ *                   and > 0.
+ * rvb_decay_loss    the loss against a target decay T (linear energy, [nrows][nbins] float) under a mask m ([nrows][nbins] float,
+ *                   m >= 0: the caller zeroes what lies outside its evaluation range), with E the output of rvb_decay_curve for H or the
+ *                   caller's own curve.  Bin k of row r counts when m > 0, E > 0 and T > 0; with RVB_DECAY_NORMALISED in `flags` a row
+ *                   counts only when E[r][0] > 0 and T[r][0] > 0, and both curves are taken relative to their first bin:
+ *                       d[k] = ln E[k] - ln T[k] - (normalised ? ln E[0] - ln T[0] : 0)
+ *                       loss_rows[r] = sum_k m[k] d[k]^2                       (host; dB^2: scale by (10 / ln 10)^2)
+ *                       g[k] = 2 m[k] d[k] / E[k], with the flag g[0] -= (sum_k 2 m[k] d[k]) / E[0]
+ *                       w[r][j] = 2 H[r][j] * sum_{k <= j} g[k] = dL/dH[r][j]   (d_weights, device, H's layout)
+ *                   — exactly the weights rvb_reshade_grad takes for L = sum_r loss_rows[r].  Everything in binary64 in the fixed order;
+ *                   w is rounded to float once, is exactly 0 where H is 0 and in rows that do not count (their loss is 0), and no entry
+ *                   is left unwritten.  d_weights == NULL: the loss only.  d_weights must not overlap any of the four inputs
+ *                   (RVB_ERR_INVALID).  Synchronous.
+ * ALL THREE: RVB_ERR_INVALID for a NULL ctx (before any device is touched), a NULL required pointer, nrows == 0 or nbins == 0;
+ * RVB_ERR_CAPACITY for nrows > 4096 (and for 2^32 bins or more).  A failed call writes nothing.  rvb_last_timings names the kernels
+ * of the last decay call: "decay_curve_sums_kernel", "decay_curve_carry_kernel", "decay_curve_scan_kernel"; "decay_times_find_kernel",
+ * "decay_times_window_kernel", "decay_times_sums_kernel", "decay_times_fit_kernel"; "decay_loss_sums_kernel", "decay_loss_carry_kernel",
+ * "decay_loss_scan_kernel" (the last only with d_weights).
+ * MEASURED on one MI355X (profiles/decay_n1.txt, tools/decay_bench.py; medians of one run, calls by the host clock to the synchronisation,
+ * kernels by HIP events), at workload C2's stereo histogram, 16 x 846 741, and at 512 x 846 741 (64 channels):
+ *     rvb_decay_curve           0.085 ms / 0.93 ms — its three kernels 0.051 ms / 0.88 ms against a floor of 0.025 ms / 0.79 ms (H read
+ *                               twice, E written once, 6.6 TB/s): at C2 launch overhead is most of the call, at 512 rows the kernels
+ *                               run at 0.9 of the floor.  The float64 flip-cumsum-flip of the squares in torch on the same GPU, in the
+ *                               same run: 2.14 ms / 8.9 ms (25 x / 9.6 x the call); the pinned download of the histogram, which a host-side
+ *                               computation needs first: 0.96 ms / 30.4 ms;
+ *     rvb_decay_times (T30)     0.127 ms / 1.45 ms (decay_times_sums_kernel, a binary64 logarithm per bin of the window: 0.045 / 1.05 ms);
+ *     rvb_decay_loss            0.211 ms / 4.64 ms with weights, 0.120 ms / 2.37 ms without — kernels 0.167 ms / 4.58 ms against a floor of
+ *                               0.066 ms / 2.10 ms (E, T, m read twice, H once, w written once): the two binary64 logarithms per
+ *                               counting bin, taken in both passes, bound it, not the bytes (no counter run has been made). */
+#define RVB_DECAY_TILE 4096      /* bins per workgroup tile of the decay kernels (tests choose their edge shapes from it) */
+enum { RVB_DECAY_NORMALISED = 1 };
+int rvb_decay_curve(rvb_ctx * ctx, const void * d_histogram, uint64_t nrows, uint64_t nbins, void * d_curve);
+int rvb_decay_times(rvb_ctx * ctx, const void * d_curve, uint64_t nrows, uint64_t nbins, float sample_rate,
+                    float db_begin, float db_end, float * seconds /* host [nrows] */);
+int rvb_decay_loss(rvb_ctx * ctx, const void * d_histogram, const void * d_curve, const void * d_target, const void * d_mask,
+                   uint64_t nrows, uint64_t nbins, unsigned flags, double * loss_rows /* host [nrows] */, void * d_weights);
+
 /* Chooses the pair that rvb_get_direct and the rvb_ir_* calls below work on (pair 0 after a trace). */
 int rvb_ir_select_pair(rvb_ctx * ctx, uint64_t pair);
 

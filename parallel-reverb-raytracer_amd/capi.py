@@ -40,10 +40,13 @@ SYMBOLS = [
     "rvb_pipeline_create_lanes",
     "rvb_set_source_pattern", "rvb_multi_set_source_pattern", "rvb_pipeline_set_source_pattern", "rvb_pipeline_submit_directed",
     "rvb_keep_paths", "rvb_reshade", "rvb_reshade_grad",
+    "rvb_decay_curve", "rvb_decay_times", "rvb_decay_loss",
 ]
 
 PIPELINE_MAX_PAIRS = 8      # RVB_PIPELINE_MAX_PAIRS
 MAX_SPEAKERS = 64           # RVB_MAX_SPEAKERS
+DECAY_TILE = 4096           # RVB_DECAY_TILE
+DECAY_NORMALISED = 1        # RVB_DECAY_NORMALISED
 
 _vp = ctypes.c_void_p
 _u64 = ctypes.c_uint64
@@ -90,6 +93,12 @@ def load_library():
         lib.rvb_pipeline_pending.argtypes = [_vp]
         lib.rvb_reshade_grad.restype = ctypes.c_int
         lib.rvb_reshade_grad.argtypes = [_vp, ctypes.c_float, ctypes.c_float, _u64, _vp, _vp, _vp]
+        lib.rvb_decay_curve.restype = ctypes.c_int
+        lib.rvb_decay_curve.argtypes = [_vp, _vp, _u64, _u64, _vp]
+        lib.rvb_decay_times.restype = ctypes.c_int
+        lib.rvb_decay_times.argtypes = [_vp, _vp, _u64, _u64, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp]
+        lib.rvb_decay_loss.restype = ctypes.c_int
+        lib.rvb_decay_loss.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, _u64, ctypes.c_uint, _vp, _vp]
         _lib = lib
     return _lib
 
@@ -492,6 +501,67 @@ class Context:
 
     def synchronize_exports(self):
         self._check(self.lib.rvb_synchronize_exports(self.handle))
+
+    # ---- decay curves (rvb_decay_*): device arrays of nrows rows of nbins floats, the caller's own ------------------
+    def decay_curve(self, device_histogram_pointer, nrows, nbins, device_curve_pointer):
+        """E[r][k] = sum_{j >= k} H[r][j]^2 (rvb_decay_curve): binary64 sums in a fixed order, rounded to float once.  Asynchronous on the
+        context's stream."""
+        self._check(self.lib.rvb_decay_curve(self.handle, _vp(device_histogram_pointer), _u64(nrows), _u64(nbins), _vp(device_curve_pointer)))
+
+    def decay_times(self, device_curve_pointer, nrows, nbins, sample_rate, db_begin=-5.0, db_end=-35.0):
+        """Reverberation time in seconds of every row of a curve (rvb_decay_times), extrapolated to 60 dB from the least-squares line of the
+        level between db_begin and db_end (-5, -35: T30; 0, -10: EDT); NaN where it is not available.  float32 [nrows].  Synchronous."""
+        seconds = np.zeros(int(nrows), dtype=np.float32)
+        self._check(self.lib.rvb_decay_times(self.handle, _vp(device_curve_pointer), _u64(nrows), _u64(nbins), ctypes.c_float(sample_rate),
+                                             ctypes.c_float(db_begin), ctypes.c_float(db_end), _ptr(seconds)))
+        return seconds
+
+    def decay_loss(self, device_histogram_pointer, device_curve_pointer, device_target_pointer, device_mask_pointer, nrows, nbins,
+                   flags=DECAY_NORMALISED, device_weights_pointer=None):
+        """loss_rows float64 [nrows] = sum_k m d^2 with d the difference of the log curves (rvb_decay_loss; flags: DECAY_NORMALISED or 0); with
+        device_weights_pointer the adjoint w = dL/dH goes there in H's layout: what reshade_grad takes.  Synchronous."""
+        loss_rows = np.zeros(int(nrows), dtype=np.float64)
+        self._check(self.lib.rvb_decay_loss(self.handle, _vp(device_histogram_pointer), _vp(device_curve_pointer), _vp(device_target_pointer),
+                                            _vp(device_mask_pointer), _u64(nrows), _u64(nbins), ctypes.c_uint(int(flags)), _ptr(loss_rows),
+                                            _vp(device_weights_pointer) if device_weights_pointer else None))
+        return loss_rows
+
+    @staticmethod
+    def _decay_rows(tensor, *others):
+        """(nrows, nbins) of a float32 CUDA tensor [..., nbins] whose leading dimensions are the rows; the others have its shape."""
+        import torch
+        for t in (tensor,) + others:
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.shape == tensor.shape
+        assert tensor.dim() >= 1 and tensor.numel() > 0
+        return tensor.numel() // tensor.shape[-1], tensor.shape[-1]
+
+    def decay_curve_tensor(self, histogram, curve=None):
+        """decay_curve on torch CUDA tensors [..., nbins] (every leading index is a row): the context's stream waits for torch's current
+        stream through an event; returns the curve tensor (a new one unless given).  The caller synchronizes the context before torch
+        reads it, as after ir_accumulate_tensor."""
+        import torch
+        if curve is None:
+            curve = torch.empty_like(histogram)
+        nrows, nbins = self._decay_rows(histogram, curve)
+        self.ir_accumulate_wait_for_torch()
+        self.decay_curve(histogram.data_ptr(), nrows, nbins, curve.data_ptr())
+        return curve
+
+    def decay_times_tensor(self, curve, sample_rate, db_begin=-5.0, db_end=-35.0):
+        """decay_times on a torch CUDA tensor [..., nbins]: float32 of the leading shape."""
+        nrows, nbins = self._decay_rows(curve)
+        self.ir_accumulate_wait_for_torch()
+        return self.decay_times(curve.data_ptr(), nrows, nbins, sample_rate, db_begin, db_end).reshape(tuple(curve.shape[:-1]))
+
+    def decay_loss_tensor(self, histogram, curve, target, mask, flags=DECAY_NORMALISED, weights=None):
+        """decay_loss on torch CUDA tensors of one shape [..., nbins]: float64 losses of the leading shape; `weights` (a tensor of the same
+        shape, or None) receives dL/dH and is complete when the call returns."""
+        others = (curve, target, mask) + ((weights,) if weights is not None else ())
+        nrows, nbins = self._decay_rows(histogram, *others)
+        self.ir_accumulate_wait_for_torch()
+        loss = self.decay_loss(histogram.data_ptr(), curve.data_ptr(), target.data_ptr(), mask.data_ptr(), nrows, nbins, flags,
+                               weights.data_ptr() if weights is not None else None)
+        return loss.reshape(tuple(histogram.shape[:-1]))
 
     def ir_download(self, trim_predelay, sample_rate, mode=IR_FAST):
         """attenuate -> fixPredelay -> flattenImpulses (reference cmd/main.cpp:280-298) -> [nch][8][nbins]."""

@@ -4,8 +4,9 @@
 //   memory.hip   caller-owned device / pinned memory, staged host copies, the export stream
 //   sort.hip     the sorts the other stages call, "sorted list and bin boundaries"
 //   ir.hip       materialised attenuate / flatten, the fused impulse-response stage
+//   decay.hip    decay curves, reverberation times and the decay loss on the caller's device arrays
 // No compute happens in them and nothing falls back to the CPU: every entry point that produces results launches the HIP kernels
-// of trace_kernels.hip / image_kernels.hip / shadow_kernels.hip / reshade_kernels.hip / reshade_grad_kernels.hip / attenuate_kernels.hip / histogram_kernels.hip / exact_kernels.hip (and the sorts of rocprim_sort.hip / radix_sort.hip).
+// of trace_kernels.hip / image_kernels.hip / shadow_kernels.hip / reshade_kernels.hip / reshade_grad_kernels.hip / attenuate_kernels.hip / histogram_kernels.hip / exact_kernels.hip / decay_kernels.hip (and the sorts of rocprim_sort.hip / radix_sort.hip).
 #pragma once
 
 #include "../../include/rvb_capi.h"
@@ -117,6 +118,9 @@ struct rvb_ctx {
     float shaded_air[8] = {};
     std::vector<SourcePatternDev> shaded_patterns;
     DevBuf grad_scratch;
+    // rvb_decay_* (csrc/decay.hip): per-tile sums and carries, per-row windows and results; nothing else lives here, so the decay calls
+    // leave the sort buffers, the IR configuration and a prepared exact list alone
+    DevBuf decay_scratch;
     DevBuf impulses, early, candidates, small, stamps, sort_keys, sort_scratch, sort_order, group_temp;       // small: one SmallBlock
     // host mirror of `small`, fetched once per trace together with the first few image-source candidates (usually all of them).
     // One PINNED block: a device-to-host copy into pageable memory is staged by the runtime and blocks the host per call (three

@@ -119,6 +119,25 @@ void rvb_launch_reshade_grad_weights(const float * weights, float * transposed, 
 void rvb_launch_reshade_grad(const TraceArgs & a, const float4 * kept, const AttenuationModel & model, const ReshadeGradArgs & g,
                              double * partials, uint32_t blocks, hipStream_t s);
 void rvb_launch_reshade_grad_reduce(const double * partials, uint32_t blocks, uint64_t nsurfaces, float * out, hipStream_t s);
+// Decay curves (decay_kernels.hip; rvb_decay_curve / rvb_decay_times / rvb_decay_loss of include/rvb_capi.h) on nrows rows of nbins floats.
+// Every phase is a launch of its own — a value per tile of RVB_DECAY_TILE bins, one wave per row over the row's tiles, the tile again on
+// top of its carry —; `tiles` is [nrows][rvb_decay_tiles(nbins)] doubles (three such planes for the loss: m d^2, 2 m d, g), `first`
+// [2][nrows][tiles] bin numbers, `window` [nrows] {k0, k1}.
+inline uint32_t rvb_decay_tiles(uint64_t nbins) { return (uint32_t) ((nbins + RVB_DECAY_TILE - 1) / RVB_DECAY_TILE); }
+void rvb_launch_decay_curve_sums(const float * hist, uint64_t nrows, uint64_t nbins, double * tiles, hipStream_t s);
+void rvb_launch_decay_curve_carry(uint64_t nrows, uint64_t nbins, double * tiles, hipStream_t s);
+void rvb_launch_decay_curve_scan(const float * hist, uint64_t nrows, uint64_t nbins, const double * tiles, float * curve, hipStream_t s);
+// ratio_* = 10^(db / 10): the window is found by comparing E with E[0] * ratio
+void rvb_launch_decay_times_find(const float * curve, uint64_t nrows, uint64_t nbins, double ratio_begin, double ratio_end, uint32_t * first, hipStream_t s);
+void rvb_launch_decay_times_window(const uint32_t * first, uint64_t nrows, uint64_t nbins, uint2 * window, hipStream_t s);
+void rvb_launch_decay_times_sums(const float * curve, uint64_t nrows, uint64_t nbins, const uint2 * window, double * tiles, hipStream_t s);
+void rvb_launch_decay_times_fit(const float * curve, uint64_t nrows, uint64_t nbins, const uint2 * window, const double * tiles, double sample_rate,
+                                float * seconds, hipStream_t s);
+void rvb_launch_decay_loss_sums(const float * curve, const float * target, const float * mask, uint64_t nrows, uint64_t nbins, bool normalised,
+                                double * tiles, hipStream_t s);
+void rvb_launch_decay_loss_carry(const float * curve, uint64_t nrows, uint64_t nbins, bool normalised, double * tiles, double * loss_rows, hipStream_t s);
+void rvb_launch_decay_loss_scan(const float * hist, const float * curve, const float * target, const float * mask, uint64_t nrows, uint64_t nbins,
+                                bool normalised, const double * tiles, float * weights, hipStream_t s);
 // Grouping of the work records by the leaf position of the triangle they start from (rocprim_sort.hip):
 // order[] lists the records bucket by bucket and the shadow kernel walks that list.
 size_t rvb_group_records_temp_bytes(uint64_t n);

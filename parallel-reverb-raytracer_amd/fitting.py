@@ -1,0 +1,113 @@
+"""Fitting materials to a measured decay: the loop a user of rvb_reshade / rvb_reshade_grad would otherwise write (include/rvb_capi.h).
+
+One evaluation never leaves the device but for a few floats per row:
+
+    reshade(table, air)                          the kept trace's records under the candidate materials
+    ir_configure_speakers(..., IR_DIFFUSE)       (a re-shade voids the IR configuration)
+    ir_accumulate(IR_EXACT) into a zeroed H      the exact mode adds in a fixed order: L is repeatable bit for bit
+    decay_curve(H) -> E                          Schroeder integral
+    decay_loss(H, E, target, mask) -> L, w       w = dL/dH in H's layout
+    reshade_grad(w) -> dL/dtable, dL/dair        chain rule through the binning
+
+SCOPE: that of rvb_reshade_grad — a context that holds a trace made with keep_paths(True), the diffuse records only (IR_DIFFUSE), the
+speaker model with at most 8 channels; no image sources, no HRTF.  The target and the mask are float32 CUDA tensors [nchannels][8][nbins]
+(numpy arrays are uploaded): the target a decay curve in linear energy, the mask >= 0 and zero outside the evaluation range."""
+import numpy as np
+
+from . import capi
+from .dtypes import SURFACE, aligned_copy
+
+
+def coefficients(table):
+    """The float32 view [nsurfaces][16] of a SURFACE table: a surface's eight specular, then its eight diffuse coefficients."""
+    assert table.dtype == SURFACE and table.flags["C_CONTIGUOUS"]
+    return table.view(np.float32).reshape(table.shape[0], 16)
+
+
+def _on_device(x, shape):
+    import torch
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).cuda()
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == tuple(shape), "target / mask: float32 [nchannels][8][nbins]"
+    return x
+
+
+def _evaluate(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, want_grad):
+    import torch
+    ctx.reshade(table, air)
+    ctx.ir_configure_speakers(mic, speakers[0], speakers[1], capi.IR_DIFFUSE, None)
+    shape = (ctx.nchannels, 8, int(nbins))
+    nrows = ctx.nchannels * 8
+    target, mask = _on_device(target, shape), _on_device(mask, shape)
+    hist = torch.zeros(shape, dtype=torch.float32, device="cuda")
+    curve = torch.empty_like(hist)
+    weights = torch.empty_like(hist) if want_grad else None
+    ctx.ir_accumulate_tensor(predelay, sample_rate, nbins, capi.IR_EXACT, hist)      # (waits for torch's stream: the zero fill, the uploads)
+    ctx.decay_curve(hist.data_ptr(), nrows, nbins, curve.data_ptr())
+    loss_rows = ctx.decay_loss(hist.data_ptr(), curve.data_ptr(), target.data_ptr(), mask.data_ptr(), nrows, nbins,
+                               capi.DECAY_NORMALISED if normalised else 0, weights.data_ptr() if want_grad else None)
+    loss = float(loss_rows.sum())
+    if not want_grad:
+        return loss, None, None, None
+    times = ctx.decay_times(curve.data_ptr(), nrows, nbins, sample_rate).reshape(ctx.nchannels, 8)
+    grads, grad_air = ctx.reshade_grad(predelay, sample_rate, nbins, weights.data_ptr())
+    return loss, grads, grad_air, times
+
+
+def decay_loss_and_grad(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised=True):
+    """(loss, grad_surfaces, grad_air, times) of the kept trace in `ctx` under the surface table `table` and the air coefficients `air`:
+    loss = sum over the rows of sum_k mask (ln E - ln target - the difference at bin 0 if normalised)^2 (rvb_decay_loss), its gradient as a
+    SURFACE array and a float32[8] (rvb_reshade_grad), and the T30 of every row of the current curve, float32 [nchannels][8], NaN where
+    the curve does not reach -35 dB.  speakers = (directions, coefficients).  Leaves the context re-shaded with `table`."""
+    return _evaluate(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, True)
+
+
+def decay_loss(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised=True):
+    """The loss of decay_loss_and_grad alone (no weights, no gradient): what a line search evaluates."""
+    return _evaluate(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, False)[0]
+
+
+ARMIJO_C = 1e-4
+MAX_HALVINGS = 30
+
+
+def fit_decay(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, free, steps, lower=0.01, upper=0.99,
+              normalised=True):
+    """Projected gradient descent on the coefficients of `table` that the boolean array `free` ([nsurfaces][16], the layout of
+    `coefficients`) marks; every other entry keeps its bits.  A step from theta with gradient g tries theta(t) = clip(theta - t g, lower,
+    upper) and halves t until the Armijo condition L(theta(t)) <= L(theta) - c g.(theta - theta(t)) holds, c = 1e-4 (without clipping
+    that is L - c t |g|^2); a step that never satisfies it within 30 halvings ends the fit.  Only steps that satisfy it are taken.  The
+    first t moves the steepest coefficient by 0.25; later steps start from twice the last accepted t.
+
+    Returns (table, record): the fitted table (a copy) and one dict per accepted step — loss_before, loss, step (the accepted t),
+    halvings, descent (g.(theta - theta(t))).  The air is held fixed.  Scope: see the module text."""
+    table = aligned_copy(np.ascontiguousarray(table, dtype=SURFACE))
+    free = np.asarray(free, dtype=bool).reshape(table.shape[0], 16)
+    args = (air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised)
+    record = []
+    t = None
+    for _ in range(int(steps)):
+        loss, grads, _, _ = _evaluate(ctx, table, *args, True)
+        theta = coefficients(table)
+        g = np.where(free, coefficients(np.ascontiguousarray(grads)), np.float32(0.0)).astype(np.float64)
+        steepest = np.abs(g).max()
+        if not steepest > 0 or not np.isfinite(steepest):
+            break
+        t = 0.25 / steepest if t is None else 2.0 * t
+        accepted = None
+        for halvings in range(MAX_HALVINGS + 1):
+            trial = aligned_copy(table)
+            moved = np.clip(theta.astype(np.float64) - t * g, lower, upper).astype(np.float32)
+            coefficients(trial)[free] = moved[free]
+            descent = float((g * (theta.astype(np.float64) - coefficients(trial).astype(np.float64))).sum())
+            trial_loss = decay_loss(ctx, trial, *args[:-1], normalised=normalised)
+            if descent > 0 and trial_loss <= loss - ARMIJO_C * descent:
+                accepted = (trial, trial_loss, descent, halvings)
+                break
+            t *= 0.5
+        if accepted is None:
+            break
+        table = accepted[0]
+        record.append({"loss_before": loss, "loss": accepted[1], "step": t, "halvings": accepted[3], "descent": accepted[2]})
+    ctx.reshade(table, air)
+    return table, record
