@@ -173,6 +173,8 @@ int rvb_set_source_pattern(rvb_ctx * ctx, const rvb_source_pattern * patterns, u
  * (ray, bounce) — 205 MB beside the 819 MB of records at 100 k rays x 128 —, allocated by the first trace made with keeping on.
  * rvb_keep_paths(ctx, 0), the default: no extra launch, no extra allocation, every byte and every kernel as without this call; the side
  * buffers of an earlier keep are freed (after waiting for the context's stream) and rvb_reshade fails until the next kept trace.
+ * `keep` is a set of bits: RVB_KEEP_MATERIALS (1) is the above, exactly; with RVB_KEEP_LISTENER (2) set a trace keeps everything that 1
+ * keeps and in addition what rvb_relisten (below) needs: see there.
  *
  * rvb_reshade(ctx, surfaces, nsurfaces, air_coefficient), after a trace made with keeping on: the context is left in the state that
  * rvb_trace / rvb_trace_pairs would have left with the same microphones, sources, directions, nreflections and ray_offset on a scene
@@ -203,8 +205,46 @@ int rvb_set_source_pattern(rvb_ctx * ctx, const rvb_source_pattern * patterns, u
  *     rvb_trace, keeping off 4.49 ms (the commit before this feature: 4.65 ms, its repetitions spread over 0.20 ms); keeping on 4.80 ms,
  *     path_keep_kernel 0.335 ms (3.6 x its floor of 48 bytes per record at 6.6 TB/s: it fetches whole 64-byte records);
  *     rvb_reshade 0.63 ms — reshade_kernel 0.58 ms beside shadow_pair_kernel's 1.24 ms — against 47.6 ms for rvb_set_scene + rvb_trace. */
+enum { RVB_KEEP_MATERIALS = 1, RVB_KEEP_LISTENER = 2 };
 int rvb_keep_paths(rvb_ctx * ctx, int keep);
 int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces, const float air_coefficient[8]);
+
+/* ---- a new microphone on a kept trace without the path stage (csrc/relisten_kernels.hip) ------------------------------------------
+ * The closest-hit / reflect chain of the reference (kernel.cpp:359-375, :459-461, :478, :492-501) never reads the microphone: hit
+ * points, newDist, DIFF, triangles and the specular volume chain depend on scene, source and directions only.  The microphone enters in
+ * the shadow ray of every record (:463-490), the image-source validation (:379-457) and the direct path (:335-357).  A caller that maps
+ * one source over a grid of listeners traces ONCE with RVB_KEEP_LISTENER and then calls rvb_relisten per listener: one streaming pass
+ * that puts the path stage's work records back, then the shadow and image stages of a trace as they are.  No reference counterpart.
+ *
+ * rvb_keep_paths(ctx, RVB_KEEP_MATERIALS | RVB_KEEP_LISTENER): the traces that follow keep, beside the side records of rvb_reshade, the
+ * two words of a work record that nothing else recovers — the own-plane threshold of the shadow ray and the triangle —, written by the
+ * same "path_keep_kernel".  Memory: 8 bytes per (ray, bounce) beside the 16 kept for re-shading — 102 MB at 100 k rays x 128 —, allocated
+ * by the first such trace.  The grouping order of the records (4 bytes per (ray, bounce), which every trace allocates and fills) stays
+ * where the trace left it: only a trace's grouping writes it, and the next trace voids the kept state.  Where the trace grouped nothing
+ * (RVB_SHADOW_SORT=0, or 2^32 or more records) the shadow rays of a relisten run in natural order, as that trace's did.
+ *
+ * rvb_relisten(ctx, mics, npairs) — mics: [npairs][3]; npairs must equal that of the kept trace (1 after rvb_trace / rvb_trace_group):
+ * the context is left in the state that rvb_trace / rvb_trace_pairs would have left with the new microphone(s), the same sources,
+ * directions, nreflections and ray_offset, and the surface table, air and source patterns that the records reflect now (the scene's own
+ * after a kept trace, those of the last rvb_reshade after one):
+ *   - every byte of the diffuse records (padding too), of the direct slot(s) and of the image-source candidates as
+ *     rvb_get_image_candidates returns them, and the per-pair diffuse time range equal that trace's; rvb_executed_bounces is unchanged;
+ *   - like a trace it voids the IR configuration and a prepared exact list (rvb_ir_configure_* again; rvb_ir_select_pair is back at 0);
+ *   - the kept trace stays valid and is now that of the new microphone(s), the kept image distances included: later rvb_reshade,
+ *     rvb_reshade_grad and rvb_relisten calls work from there.  Repeatable in any order: A, B, C, then A again returns the original
+ *     trace bit for bit;
+ *   - asynchronous on the context's stream; rvb_last_timings: "relisten_records_kernel", "image_kernel", the shadow kernel's name and,
+ *     with a source pattern, "source_pattern_kernel" — no path kernel and no record grouping.
+ * RVB_ERR_INVALID (before any device is touched) for a NULL ctx or mics, a coordinate that is not finite, npairs other than the kept
+ * trace's.  RVB_ERR_STATE, with a text that names the condition: nothing traced, the last trace made without RVB_KEEP_LISTENER, or
+ * rvb_set_scene / rvb_share_scene / rvb_set_directions* since.  A failed call leaves the results as they were.
+ * SCOPE.  One context; not offered by rvb_multi_* and rvb_pipeline_*, as rvb_reshade is not: a listener grid is a loop on one context.
+ * MEASURED on one MI355X at 100 k rays x 128 in the 75 k-triangle cathedral (profiles/relisten_n1.txt, tools/relisten_bench.py; medians):
+ *     rvb_trace, keeping off 4.50 ms (the commit before this feature: 4.48 ms, its repetitions spread over 0.11 ms); RVB_KEEP_MATERIALS
+ *     4.79 ms, with RVB_KEEP_LISTENER 4.76 ms (path_keep_kernel 0.335 -> 0.343 ms: the 8 more bytes are not measurable in the trace);
+ *     rvb_relisten 1.83 ms — relisten_records_kernel 0.46 ms, image_kernel 0.10 ms, shadow_pair_kernel 1.20 ms — against 4.49 ms for
+ *     rvb_trace with the new microphone: 2.45 x.  With the kept grouping order ignored (natural order) 2.33 ms, the shadow kernel 1.70 ms. */
+int rvb_relisten(rvb_ctx * ctx, const float * mics, uint64_t npairs);
 
 /* ---- material gradients of a weighted impulse response from a kept trace (csrc/reshade_grad_kernels.hip) ---------------------------
  * The other half of a material sweep: a fit of absorption coefficients (or of the air) to a measured decay needs a gradient, and by

@@ -39,7 +39,7 @@ SYMBOLS = [
     "rvb_pipeline_configure_hrtf", "rvb_pipeline_submit", "rvb_pipeline_submit_oriented", "rvb_pipeline_pending", "rvb_pipeline_next",
     "rvb_pipeline_create_lanes",
     "rvb_set_source_pattern", "rvb_multi_set_source_pattern", "rvb_pipeline_set_source_pattern", "rvb_pipeline_submit_directed",
-    "rvb_keep_paths", "rvb_reshade", "rvb_reshade_grad",
+    "rvb_keep_paths", "rvb_reshade", "rvb_reshade_grad", "rvb_relisten",
     "rvb_decay_curve", "rvb_decay_times", "rvb_decay_loss",
 ]
 
@@ -47,6 +47,7 @@ PIPELINE_MAX_PAIRS = 8      # RVB_PIPELINE_MAX_PAIRS
 MAX_SPEAKERS = 64           # RVB_MAX_SPEAKERS
 DECAY_TILE = 4096           # RVB_DECAY_TILE
 DECAY_NORMALISED = 1        # RVB_DECAY_NORMALISED
+KEEP_MATERIALS, KEEP_LISTENER = 1, 2     # RVB_KEEP_MATERIALS, RVB_KEEP_LISTENER
 
 _vp = ctypes.c_void_p
 _u64 = ctypes.c_uint64
@@ -267,9 +268,17 @@ class Context:
         pats = make_source_patterns(direction, shape)
         self._check(self.lib.rvb_set_source_pattern(self.handle, pats, _u64(len(pats))))
 
-    def keep_paths(self, on):
-        """The traces that follow keep what reshade needs (rvb_keep_paths): 16 bytes per (ray, bounce); False frees them again."""
-        self._check(self.lib.rvb_keep_paths(self.handle, ctypes.c_int(1 if on else 0)))
+    def keep_paths(self, on, listener=False):
+        """The traces that follow keep what reshade needs (rvb_keep_paths): 16 bytes per (ray, bounce); False frees them again.
+        listener=True: and what relisten needs (RVB_KEEP_LISTENER), 8 bytes more."""
+        keep = (KEEP_MATERIALS | (KEEP_LISTENER if listener else 0)) if on else 0
+        self._check(self.lib.rvb_keep_paths(self.handle, ctypes.c_int(keep)))
+
+    def relisten(self, mics):
+        """The results of the last trace (made with keep_paths(True, listener=True)) as if it had been made with the microphone(s) `mics`
+        — one (x, y, z), or [npairs][3] after trace_pairs — (rvb_relisten): no path stage, no record grouping."""
+        m = np.ascontiguousarray(np.asarray(mics, dtype=np.float32).reshape(-1, 3))
+        self._check(self.lib.rvb_relisten(self.handle, _ptr(m), _u64(m.shape[0])))
 
     def reshade(self, surfaces, air):
         """The results of the last trace (made with keep_paths(True)) as if the scene had the surface table `surfaces` — None: the

@@ -6,7 +6,7 @@
 //   ir.hip       materialised attenuate / flatten, the fused impulse-response stage
 //   decay.hip    decay curves, reverberation times and the decay loss on the caller's device arrays
 // No compute happens in them and nothing falls back to the CPU: every entry point that produces results launches the HIP kernels
-// of trace_kernels.hip / image_kernels.hip / shadow_kernels.hip / reshade_kernels.hip / reshade_grad_kernels.hip / attenuate_kernels.hip / histogram_kernels.hip / exact_kernels.hip / decay_kernels.hip (and the sorts of rocprim_sort.hip / radix_sort.hip).
+// of trace_kernels.hip / image_kernels.hip / shadow_kernels.hip / reshade_kernels.hip / reshade_grad_kernels.hip / relisten_kernels.hip / attenuate_kernels.hip / histogram_kernels.hip / exact_kernels.hip / decay_kernels.hip (and the sorts of rocprim_sort.hip / radix_sort.hip).
 #pragma once
 
 #include "../../include/rvb_capi.h"
@@ -107,6 +107,13 @@ struct rvb_ctx {
     bool kept_valid = false;                     // the last trace was made with keeping on (and `traced` says nothing has voided it since)
     TraceArgs kept_args = {};
     DevBuf kept_paths, kept_image_dist;
+    // a new microphone (RVB_KEEP_LISTENER / rvb_relisten, csrc/relisten_kernels.hip): beside the above an 8-byte listener record per
+    // (ray, bounce), {own-plane threshold, triangle}.  The grouping order of the records is kept where the trace left it: `sort_order` is
+    // written by the record grouping of a trace and by nothing else (the binning stages sort in keys_a / keys_b / vals_a / vals_b), and
+    // the next trace voids the kept state before it regroups; kept_args.sort_order points there (null: the trace grouped nothing).
+    bool keep_listener = false;
+    bool kept_listener_valid = false;            // the last trace was made with RVB_KEEP_LISTENER
+    DevBuf kept_listen;
     // the surface table of the last rvb_reshade: the scene (which may be shared) keeps its own; uploaded in stream order through a
     // pinned staging block, as the source patterns are
     DevBuf reshade_surfaces;

@@ -86,7 +86,8 @@ void rvb_launch_source_pattern(const TraceArgs & a, const SourcePatternDev * pat
 // Re-shading a finished trace (reshade_kernels.hip; rvb_keep_paths / rvb_reshade of include/rvb_capi.h).
 // path_keep_kernel, between the path and the shadow stage: what the shadow stage destroys of every work record, as a 16-byte side record
 // kept[nrays * nreflections] = {newDist, DIFF, surface (0xFFFFFFFF: the ray had escaped), 0}.  Only reads the records.
-void rvb_launch_path_keep(const TraceArgs & a, float4 * kept, hipStream_t s);
+// listen != null (RVB_KEEP_LISTENER): also listen[nrays * nreflections] = {own-plane threshold, triangle} ({0, 0} where the ray had escaped).
+void rvb_launch_path_keep(const TraceArgs & a, float4 * kept, uint2 * listen, hipStream_t s);
 // How many surfaces the re-shade pass stages in LDS (all of them, or 0: read through L2).
 uint32_t rvb_reshade_lds_surfaces(uint64_t nsurfaces);
 // reshade_kernel: the final volumes of every diffuse record again — the specular chain along the ray from 1, then the shadow stage's
@@ -95,6 +96,12 @@ uint32_t rvb_reshade_lds_surfaces(uint64_t nsurfaces);
 // direct slot(s), from a.early, a.image_dist and the same table.
 void rvb_launch_reshade(const TraceArgs & a, const float4 * kept, hipStream_t s);
 void rvb_launch_reshade_images(const TraceArgs & a, hipStream_t s);
+// A new microphone on a finished trace (relisten_kernels.hip; RVB_KEEP_LISTENER / rvb_relisten of include/rvb_capi.h).
+// relisten_records_kernel: every slot of a.impulses as the work record the path stage left (trace_kernels.hip, "Work record") — the chain
+// volumes under a.scene.surfaces (a.lds_surfaces as rvb_reshade_lds_surfaces gives it), the position the record holds, DIFF and newDist of
+// `kept`, threshold and triangle of `listen`, the ray's pair tag; 64 zero bytes behind an escape.  rvb_launch_images, rvb_launch_shadow and
+// rvb_launch_source_pattern then run as behind a path kernel.
+void rvb_launch_relisten_records(const TraceArgs & a, const float4 * kept, const uint2 * listen, hipStream_t s);
 // Material gradients of a weighted histogram from the kept trace (reshade_grad_kernels.hip; rvb_reshade_grad of include/rvb_capi.h).
 // The launch works on ONE pair's rays, [first_ray, first_ray + nrays) of the kept launch, with the speaker model `model` (<= 8 channels)
 // and the weights already in the accumulation image's layout [bin][channel][band] (rvb_launch_reshade_grad_weights makes it from the

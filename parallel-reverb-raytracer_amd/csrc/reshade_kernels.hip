@@ -19,20 +19,27 @@ namespace {
 
 // ---- path_keep_kernel: one lane per record ------------------------------------------------------------------------------------------
 // reads chunk 3 (newDist, threshold, triangle, tag) and the last word of chunk 2 (DIFF) of the work record, 20 consecutive bytes
+// LISTEN (RVB_KEEP_LISTENER): the two words of chunk 3 that nothing else recovers — the own-plane threshold, fmaf(skip_b, t, skip_a) with
+// the segment length t, and the triangle — as an 8-byte record of their own for relisten_records_kernel (relisten_kernels.hip)
+typedef uint32_t nt_uint2 __attribute__((ext_vector_type(2)));
+template <bool LISTEN>
 __global__ __launch_bounds__(256) void path_keep_kernel(const float4 * __restrict__ records, const uint64_t nrecords, const TriShade * __restrict__ shade,
-                                                        float4 * __restrict__ kept)
+                                                        float4 * __restrict__ kept, uint2 * __restrict__ listen)
 {
     const uint64_t g = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= nrecords)
         return;
     const float4 tail = load_stream(records + 4 * g + 3);
     float4 o = make_float4(0.0f, 0.0f, __uint_as_float(NONE), 0.0f);        // tag 0: the ray had already escaped
+    nt_uint2 l = {0u, 0u};
     if (__float_as_uint(tail.w) != 0u) {
         const float diff = __builtin_nontemporal_load(reinterpret_cast<const float *>(records + 4 * g + 2) + 3);
         const uint32_t surface = shade[__float_as_uint(tail.z)].surface;
         o = make_float4(tail.x, diff, __uint_as_float(surface), 0.0f);
+        l = nt_uint2{__float_as_uint(tail.y), __float_as_uint(tail.z)};
     }
     store_stream(kept + g, o);
+    if (LISTEN) __builtin_nontemporal_store(l, reinterpret_cast<nt_uint2 *>(listen + g));
 }
 
 // ---- reshade_kernel -------------------------------------------------------------------------------------------------------------------
@@ -161,12 +168,12 @@ __global__ __launch_bounds__(256) void reshade_images_kernel(TraceArgs a)
 
 }  // namespace
 
-void rvb_launch_path_keep(const TraceArgs & a, float4 * kept, hipStream_t s)
+void rvb_launch_path_keep(const TraceArgs & a, float4 * kept, uint2 * listen, hipStream_t s)
 {
     const uint64_t nrecords = a.nrays * (uint64_t) a.nreflections;
     if (nrecords == 0) return;
-    hipLaunchKernelGGL(path_keep_kernel, dim3(stream_blocks(nrecords, 256)), dim3(256), 0, s, reinterpret_cast<const float4 *>(a.impulses), nrecords,
-                       a.scene.shade, kept);
+    hipLaunchKernelGGL(listen ? path_keep_kernel<true> : path_keep_kernel<false>, dim3(stream_blocks(nrecords, 256)), dim3(256), 0, s,
+                       reinterpret_cast<const float4 *>(a.impulses), nrecords, a.scene.shade, kept, listen);
 }
 
 // the whole table when it is small enough to leave the tiles' LDS most of a CU (64 surfaces: 4 KiB beside 12.4 KiB of tiles)

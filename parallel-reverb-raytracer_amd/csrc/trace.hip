@@ -1,5 +1,6 @@
 // trace.hip — the trace of include/rvb_capi.h: buffers, fills and kernel arguments; the path kernel; everything after it; then what a
-// trace leaves for the host (diffuse impulses, direct path, image-source candidates) and the image-source merge.
+// trace leaves for the host (diffuse impulses, direct path, image-source candidates) and the image-source merge.  Behind a kept trace:
+// re-shading (rvb_reshade), its material gradients (rvb_reshade_grad) and a new microphone (rvb_relisten), which replays the trace's tail.
 #include "ctx.h"
 
 #include <algorithm>
@@ -57,16 +58,43 @@ int reset_time_ranges(rvb_ctx * ctx, const TraceArgs & a)
 // Directional sources behind the kernel that wrote the final records (the shadow kernel of a trace, the re-shade kernels of rvb_reshade):
 // the records scaled once — this stream has waited for the image kernels, so the candidates are final too — and the diffuse time range
 // taken again, over the scaled records: it replaces that kernel's.
-int apply_source_patterns(rvb_ctx * ctx, const TraceArgs & a)
+// (`patterns`: those on the device — the context's after upload_source_patterns; rvb_relisten passes the ones the records reflect)
+int apply_source_patterns(rvb_ctx * ctx, const TraceArgs & a, const std::vector<SourcePatternDev> & patterns)
 {
-    if (ctx->source_patterns.empty()) return RVB_OK;
+    if (patterns.empty()) return RVB_OK;
     const int rc = reset_time_ranges(ctx, a);
     if (rc != RVB_OK) return rc;
     ctx->begin_timing("source_pattern_kernel");
-    rvb_launch_source_pattern(a, ctx->source_dev.as<SourcePatternDev>(), (uint32_t) ctx->source_patterns.size(), ctx->stream);
+    rvb_launch_source_pattern(a, ctx->source_dev.as<SourcePatternDev>(), (uint32_t) patterns.size(), ctx->stream);
     ctx->end_timing();
     RVB_HIP(fail, ctx, hipGetLastError());
     return RVB_OK;
+}
+
+// The tail of a trace behind the kernel that left the work records (a path kernel; relisten_records_kernel of rvb_relisten), in two steps.
+// image_kernel depends on that kernel only: it (latency-bound) runs on the side stream beside whatever the caller enqueues between the
+// two steps; shadow_kernel, which rewrites the records image_kernel reads, waits for it.
+int launch_images_beside(rvb_ctx * ctx, TraceArgs & a)
+{
+    RVB_HIP(fail, ctx, hipEventRecord(ctx->path_done, ctx->stream));
+    RVB_HIP(fail, ctx, hipStreamWaitEvent(ctx->side_stream, ctx->path_done, 0));
+    ctx->begin_timing("image_kernel", ctx->side_stream);
+    a.scene.stamps = nullptr;
+    rvb_launch_images(a, ctx->side_stream);
+    ctx->end_timing(ctx->side_stream);
+    RVB_HIP(fail, ctx, hipEventRecord(ctx->side_done, ctx->side_stream));
+    a.scene.stamps = ctx->stamps.as<unsigned long long>() + 16;
+    return RVB_OK;
+}
+
+int launch_shadow_behind_images(rvb_ctx * ctx, const TraceArgs & a, const std::vector<SourcePatternDev> & patterns)
+{
+    RVB_HIP(fail, ctx, hipStreamWaitEvent(ctx->stream, ctx->side_done, 0));
+    ctx->begin_timing(rvb_shadow_lanes() == 2 ? "shadow_pair_kernel" : (rvb_shadow_lanes() == 1 ? "shadow_lane_kernel" : "shadow_kernel"));
+    rvb_launch_shadow(a, ctx->stream);
+    ctx->end_timing();
+    RVB_HIP(fail, ctx, hipGetLastError());
+    return apply_source_patterns(ctx, a, patterns);
 }
 
 // rvb_reshade_grad differentiates at the table, air and source patterns that the records reflect: those of the launch that wrote them last.
@@ -91,6 +119,7 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     RVB_BIND(ctx);
     ctx->traced = false;                              // (until trace_finish: a failure below must not leave the last trace's results half reset)
     ctx->kept_valid = false;
+    ctx->kept_listener_valid = false;
     const uint64_t nrays = ctx->nrays * npairs;       // rays of this launch
     const size_t imp_bytes = (size_t) nrays * nreflections * sizeof(rvb_impulse);
     const size_t early_bytes = (size_t) nrays * 9 * sizeof(uint32_t);
@@ -101,6 +130,8 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     if (ctx->keep_paths) {                            // rvb_keep_paths: what rvb_reshade needs beside the results
         RVB_HIP(fail, ctx, ctx->kept_paths.ensure((size_t) nrays * nreflections * sizeof(float4)));
         RVB_HIP(fail, ctx, ctx->kept_image_dist.ensure(((size_t) nrays * 9 + npairs) * sizeof(float)));
+        if (ctx->keep_listener)                       // RVB_KEEP_LISTENER: and what rvb_relisten needs beside those
+            RVB_HIP(fail, ctx, ctx->kept_listen.ensure((size_t) nrays * nreflections * sizeof(uint2)));
     }
 
     // reference rayverb.cpp:600-616: outputs start zero-filled — path_kernel writes every slot of the
@@ -225,18 +256,12 @@ int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
     // image_kernel and the record grouping both depend on path_kernel only: the first (latency-bound) runs on the
     // side stream beside the second (bandwidth-bound); shadow_kernel, which rewrites the records image_kernel
     // reads, waits for both.
-    RVB_HIP(fail, ctx, hipEventRecord(ctx->path_done, ctx->stream));
-    RVB_HIP(fail, ctx, hipStreamWaitEvent(ctx->side_stream, ctx->path_done, 0));
-    ctx->begin_timing("image_kernel", ctx->side_stream);
-    a.scene.stamps = nullptr;
-    rvb_launch_images(a, ctx->side_stream);
-    ctx->end_timing(ctx->side_stream);
-    RVB_HIP(fail, ctx, hipEventRecord(ctx->side_done, ctx->side_stream));
-    a.scene.stamps = ctx->stamps.as<unsigned long long>() + 16;
+    int rc = launch_images_beside(ctx, a);
+    if (rc != RVB_OK) return rc;
     if (ctx->keep_paths) {
         // rvb_keep_paths: what the shadow kernel is about to overwrite, while the image kernels read the same records on the side stream
         ctx->begin_timing("path_keep_kernel");
-        rvb_launch_path_keep(a, ctx->kept_paths.as<float4>(), ctx->stream);
+        rvb_launch_path_keep(a, ctx->kept_paths.as<float4>(), ctx->keep_listener ? ctx->kept_listen.as<uint2>() : nullptr, ctx->stream);
         ctx->end_timing();
         RVB_HIP(fail, ctx, hipGetLastError());
     }
@@ -265,14 +290,9 @@ int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
         }
         ctx->end_timing();
     }
-    RVB_HIP(fail, ctx, hipStreamWaitEvent(ctx->stream, ctx->side_done, 0));
-    ctx->begin_timing(rvb_shadow_lanes() == 2 ? "shadow_pair_kernel" : (rvb_shadow_lanes() == 1 ? "shadow_lane_kernel" : "shadow_kernel"));
-    rvb_launch_shadow(a, ctx->stream);
-    ctx->end_timing();
-    RVB_HIP(fail, ctx, hipGetLastError());
-    int rc = apply_source_patterns(ctx, a);
-    if (rc != RVB_OK) return rc;
+    if ((rc = launch_shadow_behind_images(ctx, a, ctx->source_patterns)) != RVB_OK) return rc;
     ctx->kept_valid = ctx->keep_paths;
+    ctx->kept_listener_valid = ctx->keep_paths && ctx->keep_listener;
     if (ctx->kept_valid) {
         ctx->kept_args = a;
         note_shading(ctx, a);
@@ -436,16 +456,78 @@ int rvb_keep_paths(rvb_ctx * ctx, int keep)
     if (!ctx) return RVB_ERR_INVALID;
     if (keep) {
         ctx->keep_paths = true;                   // (the buffers come with the next trace, sized for it)
+        ctx->keep_listener = (keep & RVB_KEEP_LISTENER) != 0;
         return RVB_OK;
     }
     ctx->keep_paths = false;
+    ctx->keep_listener = false;
     ctx->kept_valid = false;
-    if (ctx->kept_paths.p || ctx->kept_image_dist.p || ctx->reshade_surfaces.p) {
+    ctx->kept_listener_valid = false;
+    if (ctx->kept_paths.p || ctx->kept_image_dist.p || ctx->reshade_surfaces.p || ctx->kept_listen.p) {
         RVB_BIND(ctx);
         RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));        // a keep pass or a re-shade may still use them
         RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->side_stream));
         DevBuf paths(std::move(ctx->kept_paths)), dist(std::move(ctx->kept_image_dist)), table(std::move(ctx->reshade_surfaces));      // freed here
+        DevBuf listen(std::move(ctx->kept_listen));
     }
+    return RVB_OK;
+}
+
+int rvb_relisten(rvb_ctx * ctx, const float * mics, uint64_t npairs)
+{
+    if (!ctx) return RVB_ERR_INVALID;
+    if (!mics) return fail(ctx, RVB_ERR_INVALID, "rvb_relisten: null microphones");
+    for (uint64_t i = 0; i < 3 * npairs; ++i)
+        if (!std::isfinite(mics[i])) return fail(ctx, RVB_ERR_INVALID, "rvb_relisten: microphone " + std::to_string(i / 3) + " holds a coordinate that is not finite");
+    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_relisten: nothing traced (or the scene or the directions have changed since)");
+    if (!ctx->kept_listener_valid)
+        return fail(ctx, RVB_ERR_STATE, "rvb_relisten: the last trace was made without rvb_keep_paths(ctx, RVB_KEEP_MATERIALS | RVB_KEEP_LISTENER)");
+    if (npairs != ctx->npairs)
+        return fail(ctx, RVB_ERR_INVALID, "rvb_relisten: " + std::to_string(npairs) + " microphone(s) for a kept trace of " + std::to_string(ctx->npairs) + " pair(s)");
+    RVB_BIND(ctx);
+    // the trace's own arguments; the table, the air and the source patterns are those the records reflect now (the scene's own after the
+    // kept trace, those of the last rvb_reshade after one: the patterns on the device are these, a pattern set since is not uploaded yet)
+    TraceArgs a = ctx->kept_args;
+    a.scene.surfaces = ctx->shaded_surfaces;
+    for (int i = 0; i < 8; ++i) a.air[i] = ctx->shaded_air[i];
+    for (int i = 0; i < 3; ++i) a.mic[i] = mics[i];
+    // measurements only (tools/relisten_bench.py): the shadow kernel walks the records in natural order instead of the trace's grouping
+    static const bool natural_order = getenv("RVB_RELISTEN_ORDER") && getenv("RVB_RELISTEN_ORDER")[0] == '0';
+    if (natural_order) a.sort_order = nullptr;
+    SmallBlock * small = ctx->small_dev();
+    ctx->reset_timings();
+    // from here on the results are no longer the trace's: what the host has fetched of them is void
+    ctx->small_valid = false;
+    ctx->ir_configured = false;
+    ctx->exact.valid = false;
+    // what the tail appends to or folds into, back where a trace starts; `executed` stays
+    RVB_HIP(fail, ctx, hipMemsetAsync(&small->candidate_count, 0, sizeof(uint32_t), ctx->stream));
+    RVB_HIP(fail, ctx, hipMemsetAsync(&small->image_item_count, 0, sizeof(SmallBlock) - offsetof(SmallBlock, image_item_count), ctx->stream));      // ... and the direct slot
+    if (npairs > 1) {
+        // the microphones through the launch's staging block (the sources and the initial ranges of the kept trace are still in it:
+        // trace_prepare is its only other writer), copied in stream order: a kernel of the previous call may still read pair_geom
+        RVB_HIP(fail, ctx, hipEventSynchronize(ctx->pair_stage_free));
+        float * geom = ctx->pair_stage.as<float>();
+        for (uint64_t p = 0; p < npairs; ++p)
+            for (int i = 0; i < 3; ++i) geom[4 * p + i] = mics[3 * p + i];
+        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_geom.p, geom, 4 * npairs * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        RVB_HIP(fail, ctx, hipMemsetAsync(ctx->pair_direct.p, 0, npairs * sizeof(rvb_impulse), ctx->stream));
+    }
+    int rc = reset_time_ranges(ctx, a);
+    if (rc != RVB_OK) return rc;
+    TraceArgs restore = a;
+    restore.scene.stamps = nullptr;
+    restore.lds_surfaces = rvb_reshade_lds_surfaces(ctx->nsurfaces);
+    ctx->begin_timing("relisten_records_kernel");
+    rvb_launch_relisten_records(restore, ctx->kept_paths.as<const float4>(), ctx->kept_listen.as<const uint2>(), ctx->stream);
+    ctx->end_timing();
+    RVB_HIP(fail, ctx, hipGetLastError());
+    if ((rc = launch_images_beside(ctx, a)) != RVB_OK) return rc;
+    if ((rc = launch_shadow_behind_images(ctx, a, ctx->shaded_patterns)) != RVB_OK) return rc;
+    // the kept trace is now that of the new microphone(s): later rvb_reshade, rvb_reshade_grad and rvb_relisten start from here
+    for (int i = 0; i < 3; ++i) { ctx->kept_args.mic[i] = mics[i]; ctx->mic[i] = mics[i]; }
+    ctx->pair_mics_host.assign(mics, mics + 3 * npairs);
+    ctx->ir_pair = 0;                             // as a trace leaves it
     return RVB_OK;
 }
 
@@ -496,7 +578,7 @@ int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces,
     rvb_launch_reshade_images(a, ctx->stream);
     ctx->end_timing();
     RVB_HIP(fail, ctx, hipGetLastError());
-    if ((rc = apply_source_patterns(ctx, a)) != RVB_OK) return rc;
+    if ((rc = apply_source_patterns(ctx, a, ctx->source_patterns)) != RVB_OK) return rc;
     note_shading(ctx, a);
     ctx->ir_pair = 0;                             // as a trace leaves it
     for (int i = 0; i < 3; ++i) ctx->mic[i] = ctx->pair_mics_host[i];

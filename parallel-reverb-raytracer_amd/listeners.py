@@ -1,0 +1,36 @@
+"""Decay times over a grid of listeners: the loop a user of rvb_relisten would otherwise write (include/rvb_capi.h).
+
+One source, many microphones: the context holds ONE trace made with keep_paths(True, listener=True); per listener
+
+    relisten(mic)                                the kept trace's records with the new microphone: no path stage
+    ir_configure_speakers(..., IR_DIFFUSE)       (a relisten voids the IR configuration)
+    ir_accumulate(mode) into a zeroed H          the exact mode adds in a fixed order: the times are repeatable bit for bit
+    decay_curve(H) -> E                          Schroeder integral
+    decay_times(E)                               T30 (db_begin, db_end = -5, -35), EDT (0, -10), ...
+
+and nothing leaves the device but eight floats per channel.  SCOPE: that of rvb_relisten — a single-pair trace on one context —, the
+diffuse records only (IR_DIFFUSE), the speaker model; the histogram starts at time 0 (no predelay), so that every listener's bins mean
+the same times."""
+import numpy as np
+
+from . import capi
+
+
+def decay_map(ctx, mics, speakers, sample_rate, nbins, db_begin=-5.0, db_end=-35.0, mode=capi.IR_EXACT):
+    """float32 [nlisteners][nchannels][8]: the reverberation time in seconds of every (channel, band) row at every microphone of `mics`
+    ([nlisteners][3]), NaN where the curve does not reach db_end within nbins bins.  speakers = (directions, coefficients).  Leaves the
+    context relistened at the last microphone."""
+    import torch
+    mics = np.asarray(mics, dtype=np.float32).reshape(-1, 3)
+    nchannels = len(speakers[1])
+    out = np.zeros((mics.shape[0], nchannels, 8), dtype=np.float32)
+    hist = torch.empty((nchannels, 8, int(nbins)), dtype=torch.float32, device="cuda")
+    curve = torch.empty_like(hist)
+    for i, mic in enumerate(mics):
+        ctx.relisten(mic)
+        ctx.ir_configure_speakers(mic, speakers[0], speakers[1], capi.IR_DIFFUSE, None)
+        hist.zero_()
+        ctx.ir_accumulate_tensor(0.0, sample_rate, nbins, mode, hist)       # (waits for torch's stream: the zero fill)
+        ctx.decay_curve(hist.data_ptr(), nchannels * 8, nbins, curve.data_ptr())
+        out[i] = ctx.decay_times(curve.data_ptr(), nchannels * 8, nbins, sample_rate, db_begin, db_end).reshape(nchannels, 8)     # synchronous
+    return out
