@@ -158,7 +158,7 @@ int rvb_set_scene(rvb_ctx * ctx, const rvb_triangle * triangles, uint64_t ntrian
     ctx->scene.cull_abs = built.pad;
     ctx->scene.cull_rel = 1e-4f;
     ctx->nnodes = built.nodes.size();
-    ctx->kept = built.tris.size();
+    ctx->kept_triangles = built.tris.size();
     ctx->depth = built.depth;
     ctx->stack_need = built.stack_need;
     ctx->nsurfaces = nsurfaces;
@@ -177,7 +177,7 @@ int rvb_share_scene(rvb_ctx * ctx, rvb_ctx * from)
     ctx->store = from->store;
     ctx->scene = from->scene;
     ctx->nnodes = from->nnodes;
-    ctx->kept = from->kept;
+    ctx->kept_triangles = from->kept_triangles;
     ctx->depth = from->depth;
     ctx->stack_need = from->stack_need;
     ctx->nsurfaces = from->nsurfaces;
@@ -191,7 +191,7 @@ int rvb_scene_info(rvb_ctx * ctx, uint64_t * nodes, uint64_t * kept_triangles, u
     if (!ctx) return RVB_ERR_INVALID;
     if (!ctx->have_scene) return fail(ctx, RVB_ERR_STATE, "rvb_scene_info: no scene");
     if (nodes) *nodes = ctx->nnodes;
-    if (kept_triangles) *kept_triangles = ctx->kept;
+    if (kept_triangles) *kept_triangles = ctx->kept_triangles;
     if (depth) *depth = ctx->depth;
     return RVB_OK;
 }

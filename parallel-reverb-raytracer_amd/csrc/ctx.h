@@ -1,6 +1,7 @@
 // ctx.h — the context behind include/rvb_capi.h and what its translation units share:
 //   context.hip  life cycle, scene, directions, timings, diagnostics
-//   trace.hip    the trace in three steps, its results, rvb_merge_images; re-shading a finished trace and its material gradients
+//   trace.hip    the trace in three steps, source patterns, its results, rvb_merge_images
+//   kept.hip     behind a kept trace: re-shading, its material gradients, a new microphone
 //   memory.hip   caller-owned device / pinned memory, staged host copies, the export stream
 //   sort.hip     the sorts the other stages call, "sorted list and bin boundaries"
 //   ir.hip       materialised attenuate / flatten, the fused impulse-response stage
@@ -17,6 +18,7 @@
 #include <cstddef>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #pragma GCC visibility push(hidden)
@@ -50,6 +52,61 @@ const size_t kFirstCandidates = 32;
 
 struct Timing { std::string name; hipEvent_t start, stop; };       // (events of the context's pool)
 
+// A kept trace (rvb_keep_paths; kept.hip works from it).  While keeping is on a trace leaves, beside its results, a 16-byte side record
+// per (ray, bounce) and the INIT_DIST of every image impulse (csrc/reshade_kernels.hip), and `args` remembers its kernel arguments:
+// microphones, sources, air, ray offset and every buffer of the launch.  With RVB_KEEP_LISTENER it leaves an 8-byte listener record per
+// (ray, bounce) too, {own-plane threshold, triangle} (csrc/relisten_kernels.hip).  The buffers exist only while keeping is on.
+// The kept state is valid while rvb_ctx::traced holds and nothing has voided it: a trace voids it first (void_all) and takes it last (take).
+// The grouping order of the records is kept where the trace left it: `sort_order` is written by the record grouping of a trace and by
+// nothing else (the binning stages sort in keys_a / keys_b / vals_a / vals_b), and the next trace voids the kept state before it
+// regroups; args.sort_order points there (null: the trace grouped nothing).
+struct KeptTrace {
+    bool keep_paths = false, keep_listener = false;      // asked for: the buffers come with the next trace, sized for it
+    bool valid = false;                                  // the last trace was made with keeping on
+    bool listener_valid = false;                         // ... and with RVB_KEEP_LISTENER
+    TraceArgs args = {};
+    // everything on the device that keeping owns.  `surfaces` is the table of the last rvb_reshade: the scene (which may be shared)
+    // keeps its own; uploaded in stream order through surfaces_stage, as the source patterns are.  `grad_scratch`: the result and the
+    // partial tables of rvb_reshade_grad (csrc/reshade_grad_kernels.hip).
+    struct Buffers {
+        DevBuf paths, image_dist, listen, surfaces, grad_scratch;
+        bool any() const { return paths.p || image_dist.p || listen.p || surfaces.p || grad_scratch.p; }
+    } dev;
+    static_assert(sizeof(Buffers) == 5 * sizeof(DevBuf), "any() names every buffer");
+    StagedBlock surfaces_stage;
+    // what the records reflect right now — the kept trace's table, air and source patterns, or those of the last rvb_reshade —: where
+    // rvb_reshade_grad takes its derivatives and what rvb_relisten shades with
+    const rvb_surface * shaded_surfaces = nullptr;
+    float shaded_air[8] = {};
+    std::vector<SourcePatternDev> shaded_patterns;
+
+    void void_all() { valid = false; listener_valid = false; }
+    // `a` with `patterns` wrote the records last: a trace's shadow kernel, the re-shade kernels
+    void note_shading(const TraceArgs & a, const std::vector<SourcePatternDev> & patterns)
+    {
+        shaded_surfaces = a.scene.surfaces;
+        for (int i = 0; i < 8; ++i) shaded_air[i] = a.air[i];
+        shaded_patterns = patterns;
+    }
+    // a trace with the arguments `a` is complete
+    void take(const TraceArgs & a, const std::vector<SourcePatternDev> & patterns)
+    {
+        valid = keep_paths;
+        listener_valid = keep_paths && keep_listener;
+        if (valid) { args = a; note_shading(a, patterns); }
+    }
+    // the kept trace's own arguments under the table and the air that the records reflect now
+    TraceArgs shaded_args() const
+    {
+        TraceArgs a = args;
+        a.scene.surfaces = shaded_surfaces;
+        for (int i = 0; i < 8; ++i) a.air[i] = shaded_air[i];
+        return a;
+    }
+    // frees the device buffers (the caller has synchronised the streams whose work may still use them)
+    void release() { Buffers freed(std::move(dev)); }
+};
+
 struct rvb_ctx {
     int device = 0;
     // (declared first: destroyed last, after everything that work on them may use)
@@ -68,7 +125,7 @@ struct rvb_ctx {
     bool have_scene = false;
     std::shared_ptr<SceneStore> store;          // (its own after rvb_set_scene, another context's after rvb_share_scene)
     SceneDev scene;
-    uint64_t nnodes = 0, kept = 0;
+    uint64_t nnodes = 0, kept_triangles = 0;
     uint32_t depth = 0;
     uint32_t stack_need = RVB_BVH_STACK;
     uint64_t nsurfaces = 0;
@@ -88,8 +145,7 @@ struct rvb_ctx {
     uint64_t npairs = 1, traced_rays = 0, ir_pair = 0;
     std::vector<float> pair_mics_host;          // [npairs][3]
     DevBuf pair_geom, pair_direct, pair_range;   // device: mics+sources [2*npairs] float4, direct [npairs] Impulse, ranges [npairs][2]
-    PinnedBuf pair_stage;                        // pinned staging of the per-pair geometry of a launch
-    Event pair_stage_free;
+    StagedBlock pair_stage;                      // staging of the per-pair geometry and initial time ranges of a launch
     std::vector<rvb_impulse> pair_direct_host;
     std::vector<uint32_t> pair_range_host;
     // directional sources (rvb_set_source_pattern): the patterns in their device form — empty: off —, uploaded in stream order by the
@@ -97,34 +153,9 @@ struct rvb_ctx {
     std::vector<SourcePatternDev> source_patterns;
     bool source_dirty = false;
     DevBuf source_dev;
-    PinnedBuf source_stage;
-    Event source_stage_free;
+    StagedBlock source_stage;
     DevBuf image_items;                          // work list of the image-source check kernel
-    // re-shading (rvb_keep_paths / rvb_reshade, csrc/reshade_kernels.hip).  While keeping is on a trace leaves, beside its results, a
-    // 16-byte side record per (ray, bounce) and the INIT_DIST of every image impulse, and `kept_args` remembers its kernel arguments:
-    // microphones, sources, air, ray offset and every buffer of the launch.  The buffers exist only while keeping is on.
-    bool keep_paths = false;
-    bool kept_valid = false;                     // the last trace was made with keeping on (and `traced` says nothing has voided it since)
-    TraceArgs kept_args = {};
-    DevBuf kept_paths, kept_image_dist;
-    // a new microphone (RVB_KEEP_LISTENER / rvb_relisten, csrc/relisten_kernels.hip): beside the above an 8-byte listener record per
-    // (ray, bounce), {own-plane threshold, triangle}.  The grouping order of the records is kept where the trace left it: `sort_order` is
-    // written by the record grouping of a trace and by nothing else (the binning stages sort in keys_a / keys_b / vals_a / vals_b), and
-    // the next trace voids the kept state before it regroups; kept_args.sort_order points there (null: the trace grouped nothing).
-    bool keep_listener = false;
-    bool kept_listener_valid = false;            // the last trace was made with RVB_KEEP_LISTENER
-    DevBuf kept_listen;
-    // the surface table of the last rvb_reshade: the scene (which may be shared) keeps its own; uploaded in stream order through a
-    // pinned staging block, as the source patterns are
-    DevBuf reshade_surfaces;
-    PinnedBuf reshade_stage;
-    Event reshade_stage_free;
-    // what the records reflect right now — the kept trace's table, air and source patterns, or those of the last rvb_reshade —: where
-    // rvb_reshade_grad (csrc/reshade_grad_kernels.hip) takes its derivatives.  Its result and partial tables live in grad_scratch.
-    const rvb_surface * shaded_surfaces = nullptr;
-    float shaded_air[8] = {};
-    std::vector<SourcePatternDev> shaded_patterns;
-    DevBuf grad_scratch;
+    KeptTrace kept;                              // rvb_keep_paths: what rvb_reshade, rvb_reshade_grad and rvb_relisten work from
     // rvb_decay_* (csrc/decay.hip): per-tile sums and carries, per-row windows and results; nothing else lives here, so the decay calls
     // leave the sort buffers, the IR configuration and a prepared exact list alone
     DevBuf decay_scratch;
@@ -199,6 +230,11 @@ struct rvb_ctx {
     }
     void end_timing(hipStream_t on = nullptr) { if (timing_open) (void) hipEventRecord(timings.back().stop, on ? on : stream.h); timing_open = false; }
     void reset_timings() { timings.clear(); events_used = 0; }
+    // From here on the results are no longer the last trace's (a trace has finished, rvb_reshade or rvb_relisten is about to rewrite
+    // them): what the host has fetched of them and what the IR stage has prepared from them is void.
+    void void_fetched_results() { small_valid = false; ir_configured = false; exact.valid = false; }
+    // the pair the IR stage works on, as a trace leaves it: the first, with its microphone
+    void select_first_pair() { ir_pair = 0; for (int i = 0; i < 3; ++i) mic[i] = pair_mics_host[i]; }
 };
 
 // ctx == NULL: the text of a failed rvb_create, per thread (rvb_last_error(NULL))
@@ -227,6 +263,12 @@ inline int key_bits_for(uint64_t nbins)
 
 // trace.hip: one synchronising 128-byte read per trace serves candidate count, direct path, time range, bounce count
 int fetch_small(rvb_ctx * ctx);
+// trace.hip: the steps of a trace that kept.hip replays (described where they are defined)
+int upload_source_patterns(rvb_ctx * ctx);
+int reset_time_ranges(rvb_ctx * ctx, const TraceArgs & a);
+int apply_source_patterns(rvb_ctx * ctx, const TraceArgs & a, const std::vector<SourcePatternDev> & patterns);
+int launch_images_beside(rvb_ctx * ctx, TraceArgs & a);
+int launch_shadow_behind_images(rvb_ctx * ctx, const TraceArgs & a, const std::vector<SourcePatternDev> & patterns);
 
 // sort.hip
 bool own_sort_enabled();

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <cstring>
 #include <string>
 
 #define RVB_STR_(x) #x
@@ -59,5 +60,36 @@ struct OwnedHandle {
 };
 using Stream = OwnedHandle<hipStream_t, hipStreamDestroy>;
 using Event = OwnedHandle<hipEvent_t, hipEventDestroy>;
+
+// A pinned staging block and the event behind the last copy that read it: host data goes up in stream order, with no host
+// synchronisation unless a block has to grow, and the block is written again only after that copy has left it.
+//   acquire(bytes, stream); fill host<T>(); hipMemcpyAsync from it, once or several times; record(stream)
+struct StagedBlock {
+    PinnedBuf block;
+    Event free;
+    // Room for `bytes` — in `dev` too, where one device buffer is filled from the block and grows with it —, then the block is the
+    // caller's to write.  `stream` is synchronised before a block in use is replaced: a pass or a copy may still use the old one.
+    hipError_t acquire(size_t bytes, hipStream_t stream, DevBuf * dev = nullptr)
+    {
+        hipError_t e = hipSuccess;
+        if ((bytes > block.cap && block.p) || (dev && bytes > dev->cap && dev->p)) e = hipStreamSynchronize(stream);
+        if (e == hipSuccess) e = block.ensure(bytes);
+        if (e == hipSuccess && dev) e = dev->ensure(bytes);
+        if (e != hipSuccess) return e;
+        return free ? hipEventSynchronize(free) : hipEventCreateWithFlags(&free.h, hipEventDisableTiming);
+    }
+    template <class T> T * host() const { return block.as<T>(); }
+    // behind the last copy out of the block on `stream`
+    hipError_t record(hipStream_t stream) { return hipEventRecord(free, stream); }
+    // the whole sequence for one device buffer
+    hipError_t upload(DevBuf & dev, const void * src, size_t bytes, hipStream_t stream)
+    {
+        hipError_t e = acquire(bytes, stream, &dev);
+        if (e != hipSuccess) return e;
+        std::memcpy(block.p, src, bytes);
+        e = hipMemcpyAsync(dev.p, block.p, bytes, hipMemcpyHostToDevice, stream);
+        return e == hipSuccess ? record(stream) : e;
+    }
+};
 
 #pragma GCC visibility pop

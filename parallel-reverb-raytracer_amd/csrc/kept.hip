@@ -1,0 +1,187 @@
+// kept.hip — behind a kept trace (rvb_keep_paths, KeptTrace in ctx.h): re-shading (rvb_reshade), its material gradients
+// (rvb_reshade_grad) and a new microphone (rvb_relisten), which replays the trace's tail with the steps trace.hip shares.
+#include "ctx.h"
+
+#include <cstdlib>
+#include <cstring>
+
+// `a` for a pass over the kept records (reshade_kernels.hip, reshade_grad_kernels.hip, relisten_kernels.hip): no stamps, and the share
+// of the surface table that those kernels stage in LDS
+static TraceArgs for_record_pass(const rvb_ctx * ctx, TraceArgs a)
+{
+    a.scene.stamps = nullptr;
+    a.lds_surfaces = rvb_reshade_lds_surfaces(ctx->nsurfaces);
+    return a;
+}
+
+extern "C" {
+
+int rvb_keep_paths(rvb_ctx * ctx, int keep)
+{
+    if (!ctx) return RVB_ERR_INVALID;
+    KeptTrace & kept = ctx->kept;
+    kept.keep_paths = keep != 0;                  // (the buffers come with the next trace, sized for it)
+    kept.keep_listener = (keep & RVB_KEEP_LISTENER) != 0;
+    if (keep) return RVB_OK;
+    kept.void_all();
+    if (kept.dev.any()) {
+        RVB_BIND(ctx);
+        RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));        // a keep pass or a re-shade may still use them
+        RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->side_stream));
+        kept.release();
+    }
+    return RVB_OK;
+}
+
+int rvb_relisten(rvb_ctx * ctx, const float * mics, uint64_t npairs)
+{
+    if (!ctx) return RVB_ERR_INVALID;
+    if (!mics) return fail(ctx, RVB_ERR_INVALID, "rvb_relisten: null microphones");
+    for (uint64_t i = 0; i < 3 * npairs; ++i)
+        if (!std::isfinite(mics[i])) return fail(ctx, RVB_ERR_INVALID, "rvb_relisten: microphone " + std::to_string(i / 3) + " holds a coordinate that is not finite");
+    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_relisten: nothing traced (or the scene or the directions have changed since)");
+    if (!ctx->kept.listener_valid)
+        return fail(ctx, RVB_ERR_STATE, "rvb_relisten: the last trace was made without rvb_keep_paths(ctx, RVB_KEEP_MATERIALS | RVB_KEEP_LISTENER)");
+    if (npairs != ctx->npairs)
+        return fail(ctx, RVB_ERR_INVALID, "rvb_relisten: " + std::to_string(npairs) + " microphone(s) for a kept trace of " + std::to_string(ctx->npairs) + " pair(s)");
+    RVB_BIND(ctx);
+    KeptTrace & kept = ctx->kept;
+    // the table, the air and the source patterns are those the records reflect now (the scene's own after the kept trace, those of the
+    // last rvb_reshade after one: the patterns on the device are these, a pattern set since is not uploaded yet)
+    TraceArgs a = kept.shaded_args();
+    for (int i = 0; i < 3; ++i) a.mic[i] = mics[i];
+    // measurements only (tools/relisten_bench.py): the shadow kernel walks the records in natural order instead of the trace's grouping
+    static const bool natural_order = getenv("RVB_RELISTEN_ORDER") && getenv("RVB_RELISTEN_ORDER")[0] == '0';
+    if (natural_order) a.sort_order = nullptr;
+    SmallBlock * small = ctx->small_dev();
+    ctx->reset_timings();
+    ctx->void_fetched_results();
+    // what the tail appends to or folds into, back where a trace starts; `executed` stays
+    RVB_HIP(fail, ctx, hipMemsetAsync(&small->candidate_count, 0, sizeof(uint32_t), ctx->stream));
+    RVB_HIP(fail, ctx, hipMemsetAsync(&small->image_item_count, 0, sizeof(SmallBlock) - offsetof(SmallBlock, image_item_count), ctx->stream));      // ... and the direct slot
+    if (npairs > 1) {
+        // the microphones through the launch's staging block (the sources and the initial ranges of the kept trace are still in it:
+        // trace_prepare is its only other writer, and it sized the block for this many pairs, so nothing grows here), copied in stream
+        // order: a kernel of the previous call may still read pair_geom.  reset_time_ranges, next, records the event.
+        RVB_HIP(fail, ctx, ctx->pair_stage.acquire(4 * npairs * sizeof(float), ctx->stream));
+        float * geom = ctx->pair_stage.host<float>();
+        for (uint64_t p = 0; p < npairs; ++p)
+            for (int i = 0; i < 3; ++i) geom[4 * p + i] = mics[3 * p + i];
+        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_geom.p, geom, 4 * npairs * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        RVB_HIP(fail, ctx, hipMemsetAsync(ctx->pair_direct.p, 0, npairs * sizeof(rvb_impulse), ctx->stream));
+    }
+    int rc = reset_time_ranges(ctx, a);
+    if (rc != RVB_OK) return rc;
+    ctx->begin_timing("relisten_records_kernel");
+    rvb_launch_relisten_records(for_record_pass(ctx, a), kept.dev.paths.as<const float4>(), kept.dev.listen.as<const uint2>(), ctx->stream);
+    ctx->end_timing();
+    RVB_HIP(fail, ctx, hipGetLastError());
+    if ((rc = launch_images_beside(ctx, a)) != RVB_OK) return rc;
+    if ((rc = launch_shadow_behind_images(ctx, a, kept.shaded_patterns)) != RVB_OK) return rc;
+    // the kept trace is now that of the new microphone(s): later rvb_reshade, rvb_reshade_grad and rvb_relisten start from here
+    for (int i = 0; i < 3; ++i) kept.args.mic[i] = mics[i];
+    ctx->pair_mics_host.assign(mics, mics + 3 * npairs);
+    ctx->select_first_pair();
+    return RVB_OK;
+}
+
+int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces, const float air_coefficient[8])
+{
+    if (!ctx) return RVB_ERR_INVALID;
+    if (!air_coefficient) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade: null air coefficient");
+    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_reshade: nothing traced (or the scene or the directions have changed since)");
+    if (!ctx->kept.valid) return fail(ctx, RVB_ERR_STATE, "rvb_reshade: the last trace was made without rvb_keep_paths(ctx, 1)");
+    if (surfaces && nsurfaces != ctx->nsurfaces)
+        return fail(ctx, RVB_ERR_INVALID, "rvb_reshade: " + std::to_string(nsurfaces) + " surfaces for a scene of " + std::to_string(ctx->nsurfaces));
+    if (ctx->source_patterns.size() > 1 && ctx->source_patterns.size() != ctx->npairs)
+        return fail(ctx, RVB_ERR_INVALID, "rvb_reshade: " + std::to_string(ctx->source_patterns.size()) + " source patterns for " + std::to_string(ctx->npairs) +
+                                          " pair(s): one for all pairs, or one per pair (rvb_set_source_pattern)");
+    RVB_BIND(ctx);
+    KeptTrace & kept = ctx->kept;
+    TraceArgs a = for_record_pass(ctx, kept.args);   // the trace's own arguments; surfaces and air are the call's
+    if (surfaces) {
+        RVB_HIP(fail, ctx, kept.surfaces_stage.upload(kept.dev.surfaces, surfaces, (size_t) nsurfaces * sizeof(rvb_surface), ctx->stream));
+        a.scene.surfaces = kept.dev.surfaces.as<const rvb_surface>();
+    } else {
+        a.scene.surfaces = ctx->scene.surfaces;
+    }
+    for (int i = 0; i < 8; ++i) a.air[i] = air_coefficient[i];
+    int rc = upload_source_patterns(ctx);
+    if (rc != RVB_OK) return rc;
+    ctx->reset_timings();
+    if ((rc = reset_time_ranges(ctx, a)) != RVB_OK) return rc;
+    ctx->void_fetched_results();
+    ctx->begin_timing("reshade_kernel");
+    rvb_launch_reshade(a, kept.dev.paths.as<const float4>(), ctx->stream);
+    ctx->end_timing();
+    ctx->begin_timing("reshade_images_kernel");
+    rvb_launch_reshade_images(a, ctx->stream);
+    ctx->end_timing();
+    RVB_HIP(fail, ctx, hipGetLastError());
+    if ((rc = apply_source_patterns(ctx, a, ctx->source_patterns)) != RVB_OK) return rc;
+    kept.note_shading(a, ctx->source_patterns);
+    ctx->select_first_pair();
+    return RVB_OK;
+}
+
+int rvb_reshade_grad(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins, const void * d_weights, rvb_surface * grad_surfaces,
+                     float grad_air[8])
+{
+    if (!ctx) return RVB_ERR_INVALID;
+    if (!d_weights || !grad_surfaces) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: null weights or null output");
+    if (nbins == 0 || nbins >= (1ull << 32)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: no bins (or more than 32-bit bin numbers reach)");
+    if (!std::isfinite(predelay) || !std::isfinite(sample_rate)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: predelay or sample rate is not finite");
+    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: nothing traced (or the scene or the directions have changed since)");
+    if (!ctx->kept.valid) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: the last trace was made without rvb_keep_paths(ctx, 1)");
+    if (!ctx->ir_configured) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: no IR configuration (rvb_ir_configure_speakers after the trace or re-shade)");
+    if (ctx->model.hrtf) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: the HRTF model is configured; this version takes the speaker model only");
+    if (ctx->which != RVB_IR_DIFFUSE) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: configured with image sources; this version takes which == RVB_IR_DIFFUSE only");
+    if (ctx->model.nchannels > 8)
+        return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: " + std::to_string(ctx->model.nchannels) + " speaker channels configured; this version takes 1 to 8");
+    if (ctx->nreflections > RVB_RESHADE_GRAD_MAX_REFLECTIONS)
+        return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad: more than " RVB_STR(RVB_RESHADE_GRAD_MAX_REFLECTIONS) " reflections");
+    if (ctx->nsurfaces >= (1ull << 27)) return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad: too many surfaces");
+    RVB_BIND(ctx);
+    KeptTrace & kept = ctx->kept;
+    const TraceArgs a = for_record_pass(ctx, kept.shaded_args());
+    const uint32_t nchannels = ctx->model.nchannels;
+    const uint64_t entries = ctx->nsurfaces * 16 + 8;
+    const uint32_t blocks = rvb_reshade_grad_blocks(ctx->nrays, ctx->nsurfaces);
+    // the weights in the accumulation image's layout go where that image goes; the result (floats), then the partial tables (doubles)
+    const size_t out_bytes = (entries * sizeof(float) + 15) & ~(size_t) 15;
+    RVB_HIP(fail, ctx, ctx->acc.ensure((size_t) nbins * nchannels * 8 * sizeof(float)));
+    RVB_HIP(fail, ctx, kept.dev.grad_scratch.ensure(out_bytes + (size_t) blocks * entries * sizeof(double)));
+    float * d_out = kept.dev.grad_scratch.as<float>();
+    double * partials = reinterpret_cast<double *>(kept.dev.grad_scratch.as<char>() + out_bytes);
+    ReshadeGradArgs g;
+    g.weights = ctx->acc.as<float>();
+    g.nbins = nbins;
+    g.predelay = predelay;
+    g.sample_rate = sample_rate;
+    g.first_ray = ctx->ir_pair * ctx->nrays;
+    g.nrays = (uint32_t) ctx->nrays;
+    for (int i = 0; i < 3; ++i) g.mic[i] = ctx->pair_mics_host[3 * ctx->ir_pair + i];
+    g.has_pattern = !kept.shaded_patterns.empty();
+    g.pattern = g.has_pattern ? kept.shaded_patterns[kept.shaded_patterns.size() > 1 ? ctx->ir_pair : 0] : SourcePatternDev{};
+    g.nsurfaces = ctx->nsurfaces;
+    ctx->reset_timings();
+    ctx->begin_timing("reshade_grad_weights_kernel");
+    rvb_launch_reshade_grad_weights(reinterpret_cast<const float *>(d_weights), ctx->acc.as<float>(), nchannels, nbins, ctx->stream);
+    ctx->end_timing();
+    ctx->begin_timing("reshade_grad_kernel");
+    rvb_launch_reshade_grad(a, kept.dev.paths.as<const float4>(), ctx->model, g, partials, blocks, ctx->stream);
+    ctx->end_timing();
+    ctx->begin_timing("reshade_grad_reduce_kernel");
+    rvb_launch_reshade_grad_reduce(partials, blocks, ctx->nsurfaces, d_out, ctx->stream);
+    ctx->end_timing();
+    RVB_HIP(fail, ctx, hipGetLastError());
+    RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<float> host(entries);
+    const int rc = rvb_copy_to_host(ctx, host.data(), d_out, entries * sizeof(float));
+    if (rc != RVB_OK) return rc;
+    std::memcpy(grad_surfaces, host.data(), (size_t) ctx->nsurfaces * sizeof(rvb_surface));
+    if (grad_air) std::memcpy(grad_air, host.data() + ctx->nsurfaces * 16, 8 * sizeof(float));
+    return RVB_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// kernels.h — launch interface between the C-ABI (trace.hip, sort.hip, ir.hip) and the HIP kernels.
+// kernels.h — launch interface between the C-ABI (trace.hip, kept.hip, sort.hip, ir.hip) and the HIP kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>

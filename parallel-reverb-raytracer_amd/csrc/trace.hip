@@ -1,6 +1,6 @@
 // trace.hip — the trace of include/rvb_capi.h: buffers, fills and kernel arguments; the path kernel; everything after it; then what a
-// trace leaves for the host (diffuse impulses, direct path, image-source candidates) and the image-source merge.  Behind a kept trace:
-// re-shading (rvb_reshade), its material gradients (rvb_reshade_grad) and a new microphone (rvb_relisten), which replays the trace's tail.
+// trace leaves for the host (diffuse impulses, direct path, image-source candidates) and the image-source merge.  The steps that a kept
+// trace replays (kept.hip) come first: they are declared in ctx.h.
 #include "ctx.h"
 
 #include <algorithm>
@@ -8,33 +8,12 @@
 #include <cstring>
 #include <map>
 
-namespace {
-
-// A trace in three steps — buffers, fills and kernel arguments; the path kernel; everything after it — so that rvb_trace_group can put
-// the path kernels of several contexts into ONE launch.
-struct TracePlan {
-    TraceArgs a;
-    uint64_t npairs = 1, nrays = 0, nreflections = 0;
-    int key_bits = 1;
-};
-
-// The patterns of rvb_set_source_pattern, where they have changed since the last upload.
+// The patterns of rvb_set_source_pattern, where they have changed since the last upload: up in stream order, through a staging block
+// of their own.
 int upload_source_patterns(rvb_ctx * ctx)
 {
     if (ctx->source_dirty && !ctx->source_patterns.empty()) {
-        // the patterns go up in stream order, through pinned memory (no host synchronisation unless a block has to grow; the staging
-        // block is reused only after the previous copy has left it)
-        const size_t bytes = ctx->source_patterns.size() * sizeof(SourcePatternDev);
-        if (bytes > ctx->source_stage.cap || bytes > ctx->source_dev.cap) {
-            if (ctx->source_dev.p) RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));       // a pass or a copy may still use the old blocks
-            RVB_HIP(fail, ctx, ctx->source_stage.ensure(bytes));
-            RVB_HIP(fail, ctx, ctx->source_dev.ensure(bytes));
-        }
-        if (!ctx->source_stage_free) RVB_HIP(fail, ctx, hipEventCreateWithFlags(&ctx->source_stage_free.h, hipEventDisableTiming));
-        else RVB_HIP(fail, ctx, hipEventSynchronize(ctx->source_stage_free));
-        std::memcpy(ctx->source_stage.p, ctx->source_patterns.data(), bytes);
-        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->source_dev.p, ctx->source_stage.p, bytes, hipMemcpyHostToDevice, ctx->stream));
-        RVB_HIP(fail, ctx, hipEventRecord(ctx->source_stage_free, ctx->stream));
+        RVB_HIP(fail, ctx, ctx->source_stage.upload(ctx->source_dev, ctx->source_patterns.data(), ctx->source_patterns.size() * sizeof(SourcePatternDev), ctx->stream));
         ctx->source_dirty = false;
     }
     return RVB_OK;
@@ -44,10 +23,10 @@ int upload_source_patterns(rvb_ctx * ctx)
 int reset_time_ranges(rvb_ctx * ctx, const TraceArgs & a)
 {
     if (a.npairs > 1) {
-        // (the initial ranges are still in the launch's staging block: trace_prepare's next use of it waits for pair_stage_free)
-        const uint32_t * init = reinterpret_cast<const uint32_t *>(ctx->pair_stage.as<float>() + 8 * (size_t) a.npairs);
+        // (the initial ranges are still in the launch's staging block: trace_prepare's next use of it waits for the event recorded here)
+        const uint32_t * init = reinterpret_cast<const uint32_t *>(ctx->pair_stage.host<float>() + 8 * (size_t) a.npairs);
         RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_range.p, init, 2 * (size_t) a.npairs * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        RVB_HIP(fail, ctx, hipEventRecord(ctx->pair_stage_free, ctx->stream));
+        RVB_HIP(fail, ctx, ctx->pair_stage.record(ctx->stream));
     } else {
         RVB_HIP(fail, ctx, hipMemsetAsync(a.time_range, 0xFF, 4, ctx->stream));
         RVB_HIP(fail, ctx, hipMemsetAsync(a.time_range + 1, 0, 4, ctx->stream));
@@ -97,13 +76,15 @@ int launch_shadow_behind_images(rvb_ctx * ctx, const TraceArgs & a, const std::v
     return apply_source_patterns(ctx, a, patterns);
 }
 
-// rvb_reshade_grad differentiates at the table, air and source patterns that the records reflect: those of the launch that wrote them last.
-void note_shading(rvb_ctx * ctx, const TraceArgs & a)
-{
-    ctx->shaded_surfaces = a.scene.surfaces;
-    for (int i = 0; i < 8; ++i) ctx->shaded_air[i] = a.air[i];
-    ctx->shaded_patterns = ctx->source_patterns;
-}
+namespace {
+
+// A trace in three steps — buffers, fills and kernel arguments; the path kernel; everything after it — so that rvb_trace_group can put
+// the path kernels of several contexts into ONE launch.
+struct TracePlan {
+    TraceArgs a;
+    uint64_t npairs = 1, nrays = 0, nreflections = 0;
+    int key_bits = 1;
+};
 
 int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint64_t npairs, uint64_t nreflections,
                   const float air_coefficient[8], uint64_t ray_offset, uint64_t rays_in_flight, TracePlan & plan)
@@ -118,8 +99,7 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     const float * mic = mics, * source = sources;
     RVB_BIND(ctx);
     ctx->traced = false;                              // (until trace_finish: a failure below must not leave the last trace's results half reset)
-    ctx->kept_valid = false;
-    ctx->kept_listener_valid = false;
+    ctx->kept.void_all();
     const uint64_t nrays = ctx->nrays * npairs;       // rays of this launch
     const size_t imp_bytes = (size_t) nrays * nreflections * sizeof(rvb_impulse);
     const size_t early_bytes = (size_t) nrays * 9 * sizeof(uint32_t);
@@ -127,11 +107,12 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     RVB_HIP(fail, ctx, ctx->early.ensure(early_bytes));
     RVB_HIP(fail, ctx, ctx->candidates.ensure((size_t) nrays * 9 * sizeof(rvb_image_candidate)));
     RVB_HIP(fail, ctx, ctx->image_items.ensure(((size_t) nrays * 9 + npairs) * 3 * sizeof(uint32_t)));      // (ray, bounce) entries, then a state word each
-    if (ctx->keep_paths) {                            // rvb_keep_paths: what rvb_reshade needs beside the results
-        RVB_HIP(fail, ctx, ctx->kept_paths.ensure((size_t) nrays * nreflections * sizeof(float4)));
-        RVB_HIP(fail, ctx, ctx->kept_image_dist.ensure(((size_t) nrays * 9 + npairs) * sizeof(float)));
-        if (ctx->keep_listener)                       // RVB_KEEP_LISTENER: and what rvb_relisten needs beside those
-            RVB_HIP(fail, ctx, ctx->kept_listen.ensure((size_t) nrays * nreflections * sizeof(uint2)));
+    KeptTrace & kept = ctx->kept;
+    if (kept.keep_paths) {                            // rvb_keep_paths: what rvb_reshade needs beside the results
+        RVB_HIP(fail, ctx, kept.dev.paths.ensure((size_t) nrays * nreflections * sizeof(float4)));
+        RVB_HIP(fail, ctx, kept.dev.image_dist.ensure(((size_t) nrays * 9 + npairs) * sizeof(float)));
+        if (kept.keep_listener)                       // RVB_KEEP_LISTENER: and what rvb_relisten needs beside those
+            RVB_HIP(fail, ctx, kept.dev.listen.ensure((size_t) nrays * nreflections * sizeof(uint2)));
     }
 
     // reference rayverb.cpp:600-616: outputs start zero-filled — path_kernel writes every slot of the
@@ -160,20 +141,15 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     a.pair_sources = nullptr;
     a.executed = &small->executed;
     a.time_range = small->trace_range;
-    a.image_dist = ctx->keep_paths ? ctx->kept_image_dist.as<float>() : nullptr;
+    a.image_dist = kept.keep_paths ? kept.dev.image_dist.as<float>() : nullptr;
     if (npairs > 1) {
         // several pairs per launch: geometry, direct path and time range per pair live in arrays of their own
         // staged through pinned memory and copied in stream order: no host synchronisation in front of the launch (the staging
         // block is reused only after the copies of the previous launch have left it)
         const size_t geom_floats = 8 * npairs, init_words = 2 * npairs;
         const size_t stage_bytes = geom_floats * sizeof(float) + init_words * sizeof(uint32_t);
-        if (stage_bytes > ctx->pair_stage.cap) {
-            if (ctx->pair_stage.p) RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));      // the copies of the previous launch may still read it
-            RVB_HIP(fail, ctx, ctx->pair_stage.ensure(stage_bytes));
-        }
-        if (!ctx->pair_stage_free) RVB_HIP(fail, ctx, hipEventCreateWithFlags(&ctx->pair_stage_free.h, hipEventDisableTiming));
-        else RVB_HIP(fail, ctx, hipEventSynchronize(ctx->pair_stage_free));
-        float * geom = ctx->pair_stage.as<float>();
+        RVB_HIP(fail, ctx, ctx->pair_stage.acquire(stage_bytes, ctx->stream));
+        float * geom = ctx->pair_stage.host<float>();
         uint32_t * init = reinterpret_cast<uint32_t *>(geom + geom_floats);
         std::memset(geom, 0, geom_floats * sizeof(float));
         for (uint64_t p = 0; p < npairs; ++p)
@@ -184,7 +160,7 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
         RVB_HIP(fail, ctx, ctx->pair_range.ensure(npairs * 2 * sizeof(uint32_t)));
         RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_geom.p, geom, geom_floats * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
         RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_range.p, init, init_words * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        RVB_HIP(fail, ctx, hipEventRecord(ctx->pair_stage_free, ctx->stream));
+        RVB_HIP(fail, ctx, ctx->pair_stage.record(ctx->stream));
         a.pair_mics = ctx->pair_geom.as<float4>();
         a.pair_sources = ctx->pair_geom.as<float4>() + npairs;
         a.direct = ctx->pair_direct.as<rvb_impulse>();
@@ -258,10 +234,10 @@ int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
     // reads, waits for both.
     int rc = launch_images_beside(ctx, a);
     if (rc != RVB_OK) return rc;
-    if (ctx->keep_paths) {
+    if (ctx->kept.keep_paths) {
         // rvb_keep_paths: what the shadow kernel is about to overwrite, while the image kernels read the same records on the side stream
         ctx->begin_timing("path_keep_kernel");
-        rvb_launch_path_keep(a, ctx->kept_paths.as<float4>(), ctx->keep_listener ? ctx->kept_listen.as<uint2>() : nullptr, ctx->stream);
+        rvb_launch_path_keep(a, ctx->kept.dev.paths.as<float4>(), ctx->kept.keep_listener ? ctx->kept.dev.listen.as<uint2>() : nullptr, ctx->stream);
         ctx->end_timing();
         RVB_HIP(fail, ctx, hipGetLastError());
     }
@@ -291,21 +267,14 @@ int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
         ctx->end_timing();
     }
     if ((rc = launch_shadow_behind_images(ctx, a, ctx->source_patterns)) != RVB_OK) return rc;
-    ctx->kept_valid = ctx->keep_paths;
-    ctx->kept_listener_valid = ctx->keep_paths && ctx->keep_listener;
-    if (ctx->kept_valid) {
-        ctx->kept_args = a;
-        note_shading(ctx, a);
-    }
+    ctx->kept.take(a, ctx->source_patterns);
     ctx->nreflections = nreflections;
     ctx->traced = true;
-    ctx->small_valid = false;
-    ctx->ir_configured = false;
-    ctx->exact.valid = false;
+    ctx->void_fetched_results();
     ctx->npairs = npairs;
     ctx->traced_rays = nrays;
-    ctx->ir_pair = 0;
     ctx->pair_mics_host.assign(mics, mics + 3 * npairs);
+    ctx->select_first_pair();
     return RVB_OK;
 }
 
@@ -448,203 +417,6 @@ int rvb_set_source_pattern(rvb_ctx * ctx, const rvb_source_pattern * patterns, u
         return RVB_OK;
     ctx->source_patterns.swap(form);
     ctx->source_dirty = true;
-    return RVB_OK;
-}
-
-int rvb_keep_paths(rvb_ctx * ctx, int keep)
-{
-    if (!ctx) return RVB_ERR_INVALID;
-    if (keep) {
-        ctx->keep_paths = true;                   // (the buffers come with the next trace, sized for it)
-        ctx->keep_listener = (keep & RVB_KEEP_LISTENER) != 0;
-        return RVB_OK;
-    }
-    ctx->keep_paths = false;
-    ctx->keep_listener = false;
-    ctx->kept_valid = false;
-    ctx->kept_listener_valid = false;
-    if (ctx->kept_paths.p || ctx->kept_image_dist.p || ctx->reshade_surfaces.p || ctx->kept_listen.p) {
-        RVB_BIND(ctx);
-        RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));        // a keep pass or a re-shade may still use them
-        RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->side_stream));
-        DevBuf paths(std::move(ctx->kept_paths)), dist(std::move(ctx->kept_image_dist)), table(std::move(ctx->reshade_surfaces));      // freed here
-        DevBuf listen(std::move(ctx->kept_listen));
-    }
-    return RVB_OK;
-}
-
-int rvb_relisten(rvb_ctx * ctx, const float * mics, uint64_t npairs)
-{
-    if (!ctx) return RVB_ERR_INVALID;
-    if (!mics) return fail(ctx, RVB_ERR_INVALID, "rvb_relisten: null microphones");
-    for (uint64_t i = 0; i < 3 * npairs; ++i)
-        if (!std::isfinite(mics[i])) return fail(ctx, RVB_ERR_INVALID, "rvb_relisten: microphone " + std::to_string(i / 3) + " holds a coordinate that is not finite");
-    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_relisten: nothing traced (or the scene or the directions have changed since)");
-    if (!ctx->kept_listener_valid)
-        return fail(ctx, RVB_ERR_STATE, "rvb_relisten: the last trace was made without rvb_keep_paths(ctx, RVB_KEEP_MATERIALS | RVB_KEEP_LISTENER)");
-    if (npairs != ctx->npairs)
-        return fail(ctx, RVB_ERR_INVALID, "rvb_relisten: " + std::to_string(npairs) + " microphone(s) for a kept trace of " + std::to_string(ctx->npairs) + " pair(s)");
-    RVB_BIND(ctx);
-    // the trace's own arguments; the table, the air and the source patterns are those the records reflect now (the scene's own after the
-    // kept trace, those of the last rvb_reshade after one: the patterns on the device are these, a pattern set since is not uploaded yet)
-    TraceArgs a = ctx->kept_args;
-    a.scene.surfaces = ctx->shaded_surfaces;
-    for (int i = 0; i < 8; ++i) a.air[i] = ctx->shaded_air[i];
-    for (int i = 0; i < 3; ++i) a.mic[i] = mics[i];
-    // measurements only (tools/relisten_bench.py): the shadow kernel walks the records in natural order instead of the trace's grouping
-    static const bool natural_order = getenv("RVB_RELISTEN_ORDER") && getenv("RVB_RELISTEN_ORDER")[0] == '0';
-    if (natural_order) a.sort_order = nullptr;
-    SmallBlock * small = ctx->small_dev();
-    ctx->reset_timings();
-    // from here on the results are no longer the trace's: what the host has fetched of them is void
-    ctx->small_valid = false;
-    ctx->ir_configured = false;
-    ctx->exact.valid = false;
-    // what the tail appends to or folds into, back where a trace starts; `executed` stays
-    RVB_HIP(fail, ctx, hipMemsetAsync(&small->candidate_count, 0, sizeof(uint32_t), ctx->stream));
-    RVB_HIP(fail, ctx, hipMemsetAsync(&small->image_item_count, 0, sizeof(SmallBlock) - offsetof(SmallBlock, image_item_count), ctx->stream));      // ... and the direct slot
-    if (npairs > 1) {
-        // the microphones through the launch's staging block (the sources and the initial ranges of the kept trace are still in it:
-        // trace_prepare is its only other writer), copied in stream order: a kernel of the previous call may still read pair_geom
-        RVB_HIP(fail, ctx, hipEventSynchronize(ctx->pair_stage_free));
-        float * geom = ctx->pair_stage.as<float>();
-        for (uint64_t p = 0; p < npairs; ++p)
-            for (int i = 0; i < 3; ++i) geom[4 * p + i] = mics[3 * p + i];
-        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_geom.p, geom, 4 * npairs * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        RVB_HIP(fail, ctx, hipMemsetAsync(ctx->pair_direct.p, 0, npairs * sizeof(rvb_impulse), ctx->stream));
-    }
-    int rc = reset_time_ranges(ctx, a);
-    if (rc != RVB_OK) return rc;
-    TraceArgs restore = a;
-    restore.scene.stamps = nullptr;
-    restore.lds_surfaces = rvb_reshade_lds_surfaces(ctx->nsurfaces);
-    ctx->begin_timing("relisten_records_kernel");
-    rvb_launch_relisten_records(restore, ctx->kept_paths.as<const float4>(), ctx->kept_listen.as<const uint2>(), ctx->stream);
-    ctx->end_timing();
-    RVB_HIP(fail, ctx, hipGetLastError());
-    if ((rc = launch_images_beside(ctx, a)) != RVB_OK) return rc;
-    if ((rc = launch_shadow_behind_images(ctx, a, ctx->shaded_patterns)) != RVB_OK) return rc;
-    // the kept trace is now that of the new microphone(s): later rvb_reshade, rvb_reshade_grad and rvb_relisten start from here
-    for (int i = 0; i < 3; ++i) { ctx->kept_args.mic[i] = mics[i]; ctx->mic[i] = mics[i]; }
-    ctx->pair_mics_host.assign(mics, mics + 3 * npairs);
-    ctx->ir_pair = 0;                             // as a trace leaves it
-    return RVB_OK;
-}
-
-int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces, const float air_coefficient[8])
-{
-    if (!ctx) return RVB_ERR_INVALID;
-    if (!air_coefficient) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade: null air coefficient");
-    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_reshade: nothing traced (or the scene or the directions have changed since)");
-    if (!ctx->kept_valid) return fail(ctx, RVB_ERR_STATE, "rvb_reshade: the last trace was made without rvb_keep_paths(ctx, 1)");
-    if (surfaces && nsurfaces != ctx->nsurfaces)
-        return fail(ctx, RVB_ERR_INVALID, "rvb_reshade: " + std::to_string(nsurfaces) + " surfaces for a scene of " + std::to_string(ctx->nsurfaces));
-    if (ctx->source_patterns.size() > 1 && ctx->source_patterns.size() != ctx->npairs)
-        return fail(ctx, RVB_ERR_INVALID, "rvb_reshade: " + std::to_string(ctx->source_patterns.size()) + " source patterns for " + std::to_string(ctx->npairs) +
-                                          " pair(s): one for all pairs, or one per pair (rvb_set_source_pattern)");
-    RVB_BIND(ctx);
-    TraceArgs a = ctx->kept_args;                    // the trace's own arguments; surfaces and air are the call's
-    if (surfaces) {
-        const size_t bytes = (size_t) nsurfaces * sizeof(rvb_surface);
-        if (bytes > ctx->reshade_stage.cap || bytes > ctx->reshade_surfaces.cap) {
-            if (ctx->reshade_surfaces.p) RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));     // a pass or a copy may still use the old blocks
-            RVB_HIP(fail, ctx, ctx->reshade_stage.ensure(bytes));
-            RVB_HIP(fail, ctx, ctx->reshade_surfaces.ensure(bytes));
-        }
-        if (!ctx->reshade_stage_free) RVB_HIP(fail, ctx, hipEventCreateWithFlags(&ctx->reshade_stage_free.h, hipEventDisableTiming));
-        else RVB_HIP(fail, ctx, hipEventSynchronize(ctx->reshade_stage_free));
-        std::memcpy(ctx->reshade_stage.p, surfaces, bytes);
-        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->reshade_surfaces.p, ctx->reshade_stage.p, bytes, hipMemcpyHostToDevice, ctx->stream));
-        RVB_HIP(fail, ctx, hipEventRecord(ctx->reshade_stage_free, ctx->stream));
-        a.scene.surfaces = ctx->reshade_surfaces.as<const rvb_surface>();
-    } else {
-        a.scene.surfaces = ctx->scene.surfaces;
-    }
-    a.scene.stamps = nullptr;
-    a.lds_surfaces = rvb_reshade_lds_surfaces(ctx->nsurfaces);
-    for (int i = 0; i < 8; ++i) a.air[i] = air_coefficient[i];
-    int rc = upload_source_patterns(ctx);
-    if (rc != RVB_OK) return rc;
-    ctx->reset_timings();
-    if ((rc = reset_time_ranges(ctx, a)) != RVB_OK) return rc;
-    // from here on the results are no longer the trace's: what the host has fetched of them is void
-    ctx->small_valid = false;
-    ctx->ir_configured = false;
-    ctx->exact.valid = false;
-    ctx->begin_timing("reshade_kernel");
-    rvb_launch_reshade(a, ctx->kept_paths.as<const float4>(), ctx->stream);
-    ctx->end_timing();
-    ctx->begin_timing("reshade_images_kernel");
-    rvb_launch_reshade_images(a, ctx->stream);
-    ctx->end_timing();
-    RVB_HIP(fail, ctx, hipGetLastError());
-    if ((rc = apply_source_patterns(ctx, a, ctx->source_patterns)) != RVB_OK) return rc;
-    note_shading(ctx, a);
-    ctx->ir_pair = 0;                             // as a trace leaves it
-    for (int i = 0; i < 3; ++i) ctx->mic[i] = ctx->pair_mics_host[i];
-    return RVB_OK;
-}
-
-int rvb_reshade_grad(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins, const void * d_weights, rvb_surface * grad_surfaces,
-                     float grad_air[8])
-{
-    if (!ctx) return RVB_ERR_INVALID;
-    if (!d_weights || !grad_surfaces) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: null weights or null output");
-    if (nbins == 0 || nbins >= (1ull << 32)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: no bins (or more than 32-bit bin numbers reach)");
-    if (!std::isfinite(predelay) || !std::isfinite(sample_rate)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: predelay or sample rate is not finite");
-    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: nothing traced (or the scene or the directions have changed since)");
-    if (!ctx->kept_valid) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: the last trace was made without rvb_keep_paths(ctx, 1)");
-    if (!ctx->ir_configured) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: no IR configuration (rvb_ir_configure_speakers after the trace or re-shade)");
-    if (ctx->model.hrtf) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: the HRTF model is configured; this version takes the speaker model only");
-    if (ctx->which != RVB_IR_DIFFUSE) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: configured with image sources; this version takes which == RVB_IR_DIFFUSE only");
-    if (ctx->model.nchannels > 8)
-        return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: " + std::to_string(ctx->model.nchannels) + " speaker channels configured; this version takes 1 to 8");
-    if (ctx->nreflections > RVB_RESHADE_GRAD_MAX_REFLECTIONS)
-        return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad: more than " RVB_STR(RVB_RESHADE_GRAD_MAX_REFLECTIONS) " reflections");
-    if (ctx->nsurfaces >= (1ull << 27)) return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad: too many surfaces");
-    RVB_BIND(ctx);
-    TraceArgs a = ctx->kept_args;                    // the trace's own arguments, with the surfaces and air that the records reflect now
-    a.scene.surfaces = ctx->shaded_surfaces;
-    a.scene.stamps = nullptr;
-    a.lds_surfaces = rvb_reshade_lds_surfaces(ctx->nsurfaces);
-    for (int i = 0; i < 8; ++i) a.air[i] = ctx->shaded_air[i];
-    const uint32_t nchannels = ctx->model.nchannels;
-    const uint64_t entries = ctx->nsurfaces * 16 + 8;
-    const uint32_t blocks = rvb_reshade_grad_blocks(ctx->nrays, ctx->nsurfaces);
-    // the weights in the accumulation image's layout go where that image goes; the result (floats), then the partial tables (doubles)
-    const size_t out_bytes = (entries * sizeof(float) + 15) & ~(size_t) 15;
-    RVB_HIP(fail, ctx, ctx->acc.ensure((size_t) nbins * nchannels * 8 * sizeof(float)));
-    RVB_HIP(fail, ctx, ctx->grad_scratch.ensure(out_bytes + (size_t) blocks * entries * sizeof(double)));
-    float * d_out = ctx->grad_scratch.as<float>();
-    double * partials = reinterpret_cast<double *>(ctx->grad_scratch.as<char>() + out_bytes);
-    ReshadeGradArgs g;
-    g.weights = ctx->acc.as<float>();
-    g.nbins = nbins;
-    g.predelay = predelay;
-    g.sample_rate = sample_rate;
-    g.first_ray = ctx->ir_pair * ctx->nrays;
-    g.nrays = (uint32_t) ctx->nrays;
-    for (int i = 0; i < 3; ++i) g.mic[i] = ctx->pair_mics_host[3 * ctx->ir_pair + i];
-    g.has_pattern = !ctx->shaded_patterns.empty();
-    g.pattern = g.has_pattern ? ctx->shaded_patterns[ctx->shaded_patterns.size() > 1 ? ctx->ir_pair : 0] : SourcePatternDev{};
-    g.nsurfaces = ctx->nsurfaces;
-    ctx->reset_timings();
-    ctx->begin_timing("reshade_grad_weights_kernel");
-    rvb_launch_reshade_grad_weights(reinterpret_cast<const float *>(d_weights), ctx->acc.as<float>(), nchannels, nbins, ctx->stream);
-    ctx->end_timing();
-    ctx->begin_timing("reshade_grad_kernel");
-    rvb_launch_reshade_grad(a, ctx->kept_paths.as<const float4>(), ctx->model, g, partials, blocks, ctx->stream);
-    ctx->end_timing();
-    ctx->begin_timing("reshade_grad_reduce_kernel");
-    rvb_launch_reshade_grad_reduce(partials, blocks, ctx->nsurfaces, d_out, ctx->stream);
-    ctx->end_timing();
-    RVB_HIP(fail, ctx, hipGetLastError());
-    RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<float> host(entries);
-    const int rc = rvb_copy_to_host(ctx, host.data(), d_out, entries * sizeof(float));
-    if (rc != RVB_OK) return rc;
-    std::memcpy(grad_surfaces, host.data(), (size_t) ctx->nsurfaces * sizeof(rvb_surface));
-    if (grad_air) std::memcpy(grad_air, host.data() + ctx->nsurfaces * 16, 8 * sizeof(float));
     return RVB_OK;
 }
 

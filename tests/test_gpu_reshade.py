@@ -206,6 +206,93 @@ def test_every_pair_of_trace_pairs_is_reshaded(ctx, oracle, cathedral):
         ctx.npairs = 1
 
 
+def staged_upload_cases(oracle, cathedral):
+    """The oracle's side of test_staged_uploads_in_sequence: 2 pairs x 130 rays x 24, per step the (diffuse, images) each pair must
+    show, the source pattern's gain applied.  Asserts the ground on the oracle's data: no step may pass on an unchanged state."""
+    scene, nrays, nrefl = cathedral["scene"], 130, 24
+    dirs = scenes.sphere_directions(nrays, seed=23)
+    mics = np.array([cathedral["mic"], (-10.28, 3.85, -2.24)], np.float32)
+    sources = np.array([cathedral["source"], (-12.0, 2.5, 3.0)], np.float32)
+    other_mics = mics[::-1].copy()
+    facings = np.array([FACING, (-1.0, 0.0, 0.0)], np.float32)
+    b2 = set_b(scene[2], 1, 3, 6)
+    assert (b2["specular"] != cathedral["B"]["specular"]).any() and (b2["diffuse"] != cathedral["B"]["diffuse"]).any()
+
+    def want(table, air, pair_mics, pair_facings, tag):
+        out = []
+        for p in range(2):
+            case = oracle_case(oracle, scene, table, tuple(pair_mics[p]), tuple(sources[p]), dirs, nrefl, air, key=("staged", tag, p))
+            diffuse, images, g_diffuse, _ = expected_records(oracle, case, pair_facings[p], SHAPES)
+            assert (g_diffuse < 0).any() and (g_diffuse > 0).any()
+            out.append({"mic": tuple(pair_mics[p]), "diffuse": diffuse, "images": images})
+        return out
+
+    for p in range(2):            # assert_ground's preconditions on the unscaled cases, per pair
+        args = (tuple(mics[p]), tuple(sources[p]), dirs, nrefl)
+        assert_ground(oracle_case(oracle, scene, scene[2], *args, AIR_COEFFICIENTS, key=("staged", "A", p)),
+                      oracle_case(oracle, scene, cathedral["B"], *args, AIR_B, key=("staged", "B", p)))
+    steps = {"traced": want(scene[2], AIR_COEFFICIENTS, mics, [FACING, FACING], "A"),
+             "B": want(cathedral["B"], AIR_B, mics, facings, "B"),
+             "B2": want(b2, AIR_COEFFICIENTS, mics, facings, "B2"),
+             "relistened": want(cathedral["B"], AIR_B, other_mics, facings, "B at the other microphones")}
+    for p in range(2):            # every state differs from the one the context is in before it, and B2 from both its neighbours
+        for x, y in (("traced", "B"), ("B", "B2"), ("B2", "traced"), ("B", "relistened")):
+            one, two = steps[x][p], steps[y][p]
+            assert not same_records(one["diffuse"], two["diffuse"]) and not same_records(one["images"], two["images"]), (x, y, p)
+        assert oracle_range(steps["traced"][p]["diffuse"]) != oracle_range(steps["B"][p]["diffuse"]), p
+        assert oracle_range(steps["B"][p]["diffuse"]) != oracle_range(steps["relistened"][p]["diffuse"]), p
+        assert (steps["relistened"][p]["images"]["volume"][0] != 0).any(), "the direct path is hidden from the other microphone"
+    return {"dirs": dirs, "nrefl": nrefl, "mics": mics, "sources": sources, "other_mics": other_mics, "facings": facings, "B2": b2, "steps": steps}
+
+
+def test_staged_uploads_in_sequence(oracle, cathedral):
+    """The uploads that go through a pinned staging block (source patterns, the re-shade surface table, the per-pair geometry), back
+    to back on one context: blocks that grow while in use, a second upload that has to wait for the block, the pair staging written
+    again by rvb_relisten, and the kept buffers released and made again.  Every state is the oracle's, bit for bit, pair by pair."""
+    from parallel_reverb_raytracer_amd import capi
+    w = staged_upload_cases(oracle, cathedral)
+    steps, nrefl = w["steps"], w["nrefl"]
+
+    def assert_pairs(c, want):
+        diffuse, cand = c.get_raw_diffuse().reshape(2, -1), c.get_image_candidates()
+        for p in range(2):
+            assert same_records(diffuse[p], want[p]["diffuse"]), p
+            assert not diffuse[p]["pad"].any() and not diffuse[p]["position"][:, 3].any()
+            c.select_pair(p)
+            direct = c.get_direct()
+            assert same_records(direct, want[p]["images"][:1]), p
+            images = capi.merge_images(c.get_pair_candidates(p, cand), direct, False)
+            assert images.shape == want[p]["images"].shape and same_records(images, want[p]["images"]), p
+            assert time_range(c, want[p]["mic"]) == oracle_range(want[p]["diffuse"]), p
+        return diffuse.tobytes(), cand.tobytes()
+
+    c = capi.Context(0)
+    try:
+        c.set_scene(cathedral["scene"])
+        c.keep_paths(True, listener=True)
+        c.set_directions(w["dirs"])
+        c.set_source_pattern(FACING, SHAPES)                             # 1. one pattern for both pairs
+        c.trace_pairs(w["mics"], w["sources"], nrefl, AIR_COEFFICIENTS)
+        assert_pairs(c, steps["traced"])
+        c.set_source_pattern(w["facings"], SHAPES)                       # 2. one per pair: the pattern blocks grow while in use;
+        c.reshade(cathedral["B"], AIR_B)                                 #    the first surface upload
+        first = assert_pairs(c, steps["B"])
+        c.reshade(w["B2"], AIR_COEFFICIENTS)                             # 3. no host read in between: the second upload waits for the block
+        c.reshade(cathedral["B"], AIR_B)
+        assert assert_pairs(c, steps["B"]) == first
+        c.relisten(w["other_mics"])                                      # 4. the pair staging again
+        assert_pairs(c, steps["relistened"])
+        c.keep_paths(False)                                              # 5. released and made again: the bytes of step 2
+        c.keep_paths(True, listener=True)
+        c.trace_pairs(w["mics"], w["sources"], nrefl, AIR_COEFFICIENTS)
+        c.reshade(cathedral["B"], AIR_B)
+        assert assert_pairs(c, steps["B"]) == first
+        c.reshade(w["B2"], AIR_COEFFICIENTS)                             # the intermediate state of step 3, on its own
+        assert assert_pairs(c, steps["B2"]) != first
+    finally:
+        c.close()
+
+
 def test_a_source_pattern_is_applied_to_the_reshaded_records(ctx, oracle, cathedral):
     a, b = cathedral_cases(oracle, cathedral, 509, 24)
     diffuse, images, g_diffuse, _ = expected_records(oracle, b, FACING, SHAPES)
