@@ -7,7 +7,7 @@
 //   ir.hip       materialised attenuate / flatten, the fused impulse-response stage
 //   decay.hip    decay curves, reverberation times and the decay loss on the caller's device arrays
 // No compute happens in them and nothing falls back to the CPU: every entry point that produces results launches the HIP kernels
-// of trace_kernels.hip / image_kernels.hip / shadow_kernels.hip / reshade_kernels.hip / reshade_grad_kernels.hip / relisten_kernels.hip / attenuate_kernels.hip / histogram_kernels.hip / exact_kernels.hip / decay_kernels.hip (and the sorts of rocprim_sort.hip / radix_sort.hip).
+// of trace_kernels.hip / image_kernels.hip / shadow_kernels.hip / reshade_kernels.hip / reshade_grad_kernels.hip / relisten_kernels.hip (the three over kept_tiles.h) / attenuate_kernels.hip / histogram_kernels.hip / exact_kernels.hip / decay_kernels.hip (and the sorts of rocprim_sort.hip / radix_sort.hip).
 #pragma once
 
 #include "../../include/rvb_capi.h"
@@ -53,7 +53,7 @@ const size_t kFirstCandidates = 32;
 struct Timing { std::string name; hipEvent_t start, stop; };       // (events of the context's pool)
 
 // A kept trace (rvb_keep_paths; kept.hip works from it).  While keeping is on a trace leaves, beside its results, a 16-byte side record
-// per (ray, bounce) and the INIT_DIST of every image impulse (csrc/reshade_kernels.hip), and `args` remembers its kernel arguments:
+// per (ray, bounce) (SideRecord of csrc/kept_tiles.h) and the INIT_DIST of every image impulse (csrc/reshade_kernels.hip), and `args` remembers its kernel arguments:
 // microphones, sources, air, ray offset and every buffer of the launch.  With RVB_KEEP_LISTENER it leaves an 8-byte listener record per
 // (ray, bounce) too, {own-plane threshold, triangle} (csrc/relisten_kernels.hip).  The buffers exist only while keeping is on.
 // The kept state is valid while rvb_ctx::traced holds and nothing has voided it: a trace voids it first (void_all) and takes it last (take).

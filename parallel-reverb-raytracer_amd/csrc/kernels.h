@@ -85,21 +85,22 @@ SourcePatternDev rvb_source_pattern_device_form(const rvb_source_pattern & p);  
 void rvb_launch_source_pattern(const TraceArgs & a, const SourcePatternDev * patterns, uint32_t npatterns, hipStream_t s);
 // Re-shading a finished trace (reshade_kernels.hip; rvb_keep_paths / rvb_reshade of include/rvb_capi.h).
 // path_keep_kernel, between the path and the shadow stage: what the shadow stage destroys of every work record, as a 16-byte side record
-// kept[nrays * nreflections] = {newDist, DIFF, surface (0xFFFFFFFF: the ray had escaped), 0}.  Only reads the records.
-// listen != null (RVB_KEEP_LISTENER): also listen[nrays * nreflections] = {own-plane threshold, triangle} ({0, 0} where the ray had escaped).
+// kept[nrays * nreflections] (SideRecord of kept_tiles.h: newDist, DIFF, the surface or "the ray had escaped").  Only reads the records.
+// listen != null (RVB_KEEP_LISTENER): also listen[nrays * nreflections], own-plane threshold and triangle (ListenRecord of kept_tiles.h).
 void rvb_launch_path_keep(const TraceArgs & a, float4 * kept, uint2 * listen, hipStream_t s);
 // How many surfaces the re-shade pass stages in LDS (all of them, or 0: read through L2).
 uint32_t rvb_reshade_lds_surfaces(uint64_t nsurfaces);
 // reshade_kernel: the final volumes of every diffuse record again — the specular chain along the ray from 1, then the shadow stage's
 // product — with a.scene.surfaces, a.air and a.lds_surfaces those of the RE-SHADE, everything else the finished trace's TraceArgs; and
 // the time range into a.time_range, which the caller has reset.  reshade_images_kernel: the candidates [0, *candidate_count) and the
-// direct slot(s), from a.early, a.image_dist and the same table.
+// direct slot(s), from a.early, a.image_dist and the same table.  (The wave's tiles in LDS: KeptTileLds of kept_tiles.h, from which the
+// launchers of reshade_kernel and relisten_records_kernel take their workgroups and byte counts.)
 void rvb_launch_reshade(const TraceArgs & a, const float4 * kept, hipStream_t s);
 void rvb_launch_reshade_images(const TraceArgs & a, hipStream_t s);
 // A new microphone on a finished trace (relisten_kernels.hip; RVB_KEEP_LISTENER / rvb_relisten of include/rvb_capi.h).
 // relisten_records_kernel: every slot of a.impulses as the work record the path stage left (trace_kernels.hip, "Work record") — the chain
 // volumes under a.scene.surfaces (a.lds_surfaces as rvb_reshade_lds_surfaces gives it), the position the record holds, DIFF and newDist of
-// `kept`, threshold and triangle of `listen`, the ray's pair tag; 64 zero bytes behind an escape.  rvb_launch_images, rvb_launch_shadow and
+// `kept` (SideRecord), threshold and triangle of `listen` (ListenRecord), the ray's pair tag; 64 zero bytes behind an escape.  rvb_launch_images, rvb_launch_shadow and
 // rvb_launch_source_pattern then run as behind a path kernel.
 void rvb_launch_relisten_records(const TraceArgs & a, const float4 * kept, const uint2 * listen, hipStream_t s);
 // Material gradients of a weighted histogram from the kept trace (reshade_grad_kernels.hip; rvb_reshade_grad of include/rvb_capi.h).

@@ -10,7 +10,8 @@
 // and no division by a coefficient anywhere: a coefficient that is 0 gets its derivative like any other.
 //   reshade_grad_weights_kernel   the weights from the histogram's layout [channel][8][nbins] into the accumulation image's
 //                                 [bin][channel][band]: a record then gathers ONE run of 32 * nchannels bytes.
-//   reshade_grad_kernel           reshade_kernel's shape: a wave takes GRAD_RAYS rays, lane (ray, band) owns a chain.  A first sweep over
+//   reshade_grad_kernel           reshade_kernel's shape: a wave takes eight rays, lane (ray, band) owns a chain (the staged records' rows, the
+//                                 side record, the chain step and the two-lane read of a record: kept_tiles.h).  A first sweep over
 //                                 the side records' surfaces leaves P at every tile start in LDS; then the tiles in REVERSE: the tile's
 //                                 records two lanes per record (distance, bin, arrival direction — what does not depend on the band) into
 //                                 LDS, the lane's weight gathers of the tile, its chain forward over the tile (P, a_k, the diffuse and air
@@ -19,16 +20,16 @@
 //                                 of them, which alone updates the wave's table in LDS — no atomics, one fixed order.
 //   reshade_grad_reduce_kernel    the workgroups' tables added in a fixed order, rounded to binary32 once.
 // A table in LDS holds GRAD_WINDOW surfaces; a scene with more is swept once per window of surfaces.
-#include "traversal.h"
+#include "kept_tiles.h"
 #include "attenuation.h"
 
 #include <algorithm>
 
 namespace {
 
-#define GRAD_RAYS 8u                 // rays per wave: one lane per (ray, band)
 #define GRAD_TILE 16u                // bounces per tile
-#define GRAD_ROW (GRAD_TILE + 1u)    // a ray's row of staged records, padded by one: the eight rays' reads of one bounce fall into different banks
+typedef KeptRows<GRAD_TILE> GradRows;    // eight rays per wave, a ray's row of staged records padded by one
+#define GRAD_BIN_WORD 3u             // a staged record is the side record with dist for newDist and, in this word, the bin (NONE: adds nothing)
 #define GRAD_GATHER 8u               // weight gathers of a lane in flight together
 #define GRAD_WINDOW 64u             // surfaces per table in LDS (8 KiB of binary64 sums)
 #define GRAD_MAX_BLOCKS 16384u       // (4096 left every wave three or four groups of rays at workload C2: 1.87 ms against 1.71 ms, profiles/reshade_grad_n1.txt)
@@ -44,16 +45,14 @@ struct GradDev {
     double * partials;
 };
 
-// LDS of a wave, in words: the table (window * 16 + 8 doubles), [RAYS][ROW] staged records twice (float4 each), [TILE][WAVE] floats twice
+// LDS of a wave, in words: the table (window * 16 + 8 doubles), a GradRows region of staged records twice (float4 each), [TILE][WAVE] floats twice
 // (a_k * diffuse and P_{k-1} of the forward sweep, for the backward one), [ntiles][WAVE] chain checkpoints, the surface table (stage_surfaces)
 __host__ __device__ __forceinline__ uint32_t grad_table_words(uint32_t window) { return (window * 16u + 8u) * 2u; }
-#define GRAD_STAGE_WORDS (GRAD_RAYS * GRAD_ROW * 4u)
+#define GRAD_STAGE_WORDS (GradRows::RECORDS * 4u)
 __host__ __device__ __forceinline__ uint32_t grad_surfaces_at(uint32_t window, uint32_t ntiles)
 {
     return grad_table_words(window) + 2u * GRAD_STAGE_WORDS + 2u * GRAD_TILE * WAVE + ntiles * WAVE;
 }
-
-__device__ __forceinline__ float pick(const float4 v, const uint32_t e) { return e == 0 ? v.x : (e == 1 ? v.y : (e == 2 ? v.z : v.w)); }
 
 // `v` of this lane's (ray, band) added to column `column` of its surface's row: the rays of the wave that hit the same surface are summed
 // in ray order, in binary64, and the first of them updates the table — every address of one update is written by one lane.  Called by the
@@ -64,7 +63,7 @@ __device__ __forceinline__ void add_by_surface(double * table, const GradDev & d
     double sum = 0.0;
     bool first = true;
 #pragma unroll
-    for (uint32_t o = 0; o < GRAD_RAYS; ++o) {
+    for (uint32_t o = 0; o < GradRows::RAYS; ++o) {
         const uint32_t so = __shfl(surface, (int) (o * 8u + band));
         const float vo = __shfl(v, (int) (o * 8u + band));
         if (so == surface) {
@@ -83,9 +82,9 @@ __global__ __launch_bounds__(WAVE) void reshade_grad_kernel(TraceArgs a, GradDev
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     double * table = reinterpret_cast<double *>(lds);
     uint32_t * side_words = lds + grad_table_words(d.window);
-    float4 * side = reinterpret_cast<float4 *>(side_words);                  // {dist, DIFF, surface, bin (NONE: adds nothing)}
-    float4 * toward = side + GRAD_RAYS * GRAD_ROW;                           // the record's arrival direction at the microphone
-    float * us = reinterpret_cast<float *>(toward + GRAD_RAYS * GRAD_ROW);   // a_k * diffuse[s_k][b]
+    float4 * side = reinterpret_cast<float4 *>(side_words);                  // staged records (GRAD_BIN_WORD)
+    float4 * toward = side + GradRows::RECORDS;                              // the record's arrival direction at the microphone
+    float * us = reinterpret_cast<float *>(toward + GradRows::RECORDS);      // a_k * diffuse[s_k][b]
     float * prevs = us + GRAD_TILE * WAVE;                                   // P_{k-1}
     float * starts = prevs + GRAD_TILE * WAVE;                               // P at the start of every tile
     const lds_float4_ptr surf_lds = stage_surfaces(a, lds + grad_surfaces_at(d.window, d.ntiles));
@@ -97,7 +96,7 @@ __global__ __launch_bounds__(WAVE) void reshade_grad_kernel(TraceArgs a, GradDev
     for (uint32_t i = lane; i < d.window * 16u + 8u; i += WAVE) table[i] = 0.0;
     double air_sum = 0.0;
     for (uint32_t grp = blockIdx.x; grp < d.ngroups; grp += gridDim.x) {
-        const uint32_t ray0 = grp * GRAD_RAYS;                               // within the pair
+        const uint32_t ray0 = grp * GradRows::RAYS;                             // within the pair
         // the source pattern's gain of this lane's band: constant along the ray (source_pattern_kernel, v = the ray's own direction)
         float pattern_gain = 1.0f;
         if (g.has_pattern) {
@@ -113,21 +112,21 @@ __global__ __launch_bounds__(WAVE) void reshade_grad_kernel(TraceArgs a, GradDev
                 starts[t * WAVE + lane] = vol;
                 if (t + 1u == d.ntiles) break;
                 __syncthreads();                                             // (the tile before has been read)
-                for (uint32_t i = lane; i < GRAD_RAYS * GRAD_TILE; i += WAVE) {
+                for (uint32_t i = lane; i < GradRows::RAYS * GRAD_TILE; i += WAVE) {
                     const uint32_t rr = i / GRAD_TILE, k = i % GRAD_TILE, bounce = t * GRAD_TILE + k;
                     uint32_t s = NONE;
                     if (ray0 + rr < g.nrays && bounce < a.nreflections)
-                        s = reinterpret_cast<const uint32_t *>(kept + (g.first_ray + ray0 + rr) * a.nreflections + bounce)[2];
-                    side_words[(rr * GRAD_ROW + k) * 4u + 2u] = s;
+                        s = SideRecord::surface_of(kept, (g.first_ray + ray0 + rr) * a.nreflections + bounce);
+                    side_words[GradRows::surface_word(rr, k)] = s;
                 }
                 __syncthreads();
                 for (uint32_t k = 0; k < GRAD_TILE && alive; ++k) {
-                    const uint32_t surface = side_words[(r * GRAD_ROW + k) * 4u + 2u];
+                    const uint32_t surface = side_words[GradRows::surface_word(r, k)];
                     if (surface == NONE) {                                   // escaped (or past the last ray): no record from here on
                         alive = false;
                         break;
                     }
-                    vol = -vol * pick(surface_row<SURF_LDS>(a, surf_lds, surface, band >> 2), band & 3u);
+                    vol = chain_step<SURF_LDS>(a, surf_lds, vol, surface, band);
                 }
             }
         }
@@ -136,25 +135,25 @@ __global__ __launch_bounds__(WAVE) void reshade_grad_kernel(TraceArgs a, GradDev
         for (uint32_t t = d.ntiles; t-- > 0;) {
             const uint32_t first = t * GRAD_TILE;
             __syncthreads();                                                 // (what the wave read of the stage before)
-            // (1) the tile's records, two lanes per record: lane 0 the position chunk, lane 1 the time chunk, as reshade_kernel reads them
-            for (uint32_t j = lane >> 1; j < GRAD_RAYS * GRAD_TILE; j += WAVE / 2) {
+            // (1) the tile's records, two lanes per record (FinishedRecord), as reshade_kernel reads them
+            for (uint32_t j = lane >> 1; j < GradRows::RAYS * GRAD_TILE; j += WAVE / 2) {
                 const uint32_t rr = j / GRAD_TILE, k = j % GRAD_TILE;
                 const bool inside = ray0 + rr < g.nrays && first + k < a.nreflections;
                 const uint64_t record = inside ? (g.first_ray + ray0 + rr) * a.nreflections + first + k : 0;
-                float4 sd = make_float4(0.0f, 0.0f, __uint_as_float(NONE), 0.0f), aux = make_float4(0, 0, 0, 0);
-                if (inside) {
-                    sd = load_stream(kept + record);
-                    aux = load_stream(reinterpret_cast<const float4 *>(a.impulses + record) + 2 + h);
-                }
-                const v3 p = mk3(dpp_f<QP_PAIR_LO>(aux.x), dpp_f<QP_PAIR_LO>(aux.y), dpp_f<QP_PAIR_LO>(aux.z));
-                const float time = dpp_f<QP_PAIR_HI>(aux.x);
-                const bool visible = __float_as_uint(sd.z) != NONE && time != 0.0f;
-                const float dist = sd.x + length3(mic - p);                  // kernel.cpp:471, as reshade_kernel
+                float4 sd = SideRecord::none();
+                if (inside) sd = load_stream(kept + record);
+                const FinishedRecord fin = FinishedRecord::read(reinterpret_cast<const float4 *>(a.impulses + record), inside, h);
+                const v3 p = fin.position();
+                const float time = fin.time();
+                const bool visible = fin.visible(sd);
+                const float dist = dist_to_mic(sd, p, mic);
                 const uint32_t bin = time_bin(time, g.predelay, g.sample_rate);
                 const bool adds = visible && bin < g.nbins;
                 const v3 dir = arrival_direction(d.m, p);
-                if (h == 0) side[rr * GRAD_ROW + k] = make_float4(dist, sd.y, sd.z, __uint_as_float(adds ? bin : NONE));
-                else toward[rr * GRAD_ROW + k] = make_float4(dir.x, dir.y, dir.z, 0.0f);
+                float4 staged = SideRecord::make(dist, SideRecord::diff(sd), SideRecord::surface(sd));
+                staged.w = __uint_as_float(adds ? bin : NONE);
+                if (h == 0) side[GradRows::at(rr, k)] = staged;
+                else toward[GradRows::at(rr, k)] = make_float4(dir.x, dir.y, dir.z, 0.0f);
             }
             __syncthreads();
             // (2) the weight gather, sum_c w[c][b][bin_k] * gain_c(k) of this lane's band for the tile's records: channel by channel with
@@ -168,8 +167,8 @@ __global__ __launch_bounds__(WAVE) void reshade_grad_kernel(TraceArgs a, GradDev
                 for (uint32_t c = 0; c < nch; ++c) {
 #pragma unroll
                     for (uint32_t k = 0; k < GRAD_GATHER; ++k) {
-                        const uint32_t bin = side_words[(r * GRAD_ROW + k0 + k) * 4u + 3u];
-                        const float4 t4 = toward[r * GRAD_ROW + k0 + k];
+                        const uint32_t bin = side_words[(GradRows::at(r, k0) + k) * 4u + GRAD_BIN_WORD];       // (k added last: a constant offset of the read)
+                        const float4 t4 = toward[GradRows::at(r, k0) + k];
                         const float w = g.weights[(uint64_t) (bin != NONE ? bin : 0u) * cb + c * 8u + band];
                         wsum[k] += w * speaker_gain_toward(d.m, c, mk3(t4.x, t4.y, t4.z));
                     }
@@ -180,29 +179,30 @@ __global__ __launch_bounds__(WAVE) void reshade_grad_kernel(TraceArgs a, GradDev
             // (3) forward along the ray, one band per lane
             float vol = starts[t * WAVE + lane];
             for (uint32_t k = 0; k < GRAD_TILE; ++k) {
-                const float4 sd = side[r * GRAD_ROW + k];
-                const uint32_t surface = __float_as_uint(sd.z), bin = __float_as_uint(sd.w);
+                const float4 sd = side[GradRows::at(r, k)];
+                const uint32_t surface = SideRecord::surface(sd), bin = __float_as_uint(sd.w);
+                const float dist = SideRecord::new_dist(sd), diff = SideRecord::diff(sd);
                 const float prev = vol;
                 float dc = 0.0f, ak = 0.0f;
                 if (surface != NONE) {
-                    vol = -vol * pick(surface_row<SURF_LDS>(a, surf_lds, surface, band >> 2), band & 3u);
-                    dc = pick(surface_row<SURF_LDS>(a, surf_lds, surface, 2u + (band >> 2)), band & 3u);
-                    if (bin != NONE) ak = ((air_attenuation(sd.x, air) * sd.y) * pattern_gain) * us[k * WAVE + lane];
+                    vol = chain_step<SURF_LDS>(a, surf_lds, vol, surface, band);
+                    dc = diffuse_band<SURF_LDS>(a, surf_lds, surface, band);
+                    if (bin != NONE) ak = ((air_attenuation(dist, air) * diff) * pattern_gain) * us[k * WAVE + lane];
                 }
                 const float u = ak * dc;
-                air_sum += (double) ((vol * u) * sd.x);
+                air_sum += (double) ((vol * u) * dist);
                 us[k * WAVE + lane] = u;
                 prevs[k * WAVE + lane] = prev;
                 add_by_surface(table, d, lane, surface, 8u + band, vol * ak);
             }
             // (4) backward
             for (uint32_t k = GRAD_TILE; k-- > 0;) {
-                const uint32_t surface = side_words[(r * GRAD_ROW + k) * 4u + 2u];
+                const uint32_t surface = side_words[GradRows::surface_word(r, k)];
                 float gs = 0.0f;
                 if (surface != NONE) {
                     const float b = us[k * WAVE + lane] + carry;
                     gs = -prevs[k * WAVE + lane] * b;
-                    carry = -pick(surface_row<SURF_LDS>(a, surf_lds, surface, band >> 2), band & 3u) * b;
+                    carry = -specular_band<SURF_LDS>(a, surf_lds, surface, band) * b;
                 } else {
                     carry = 0.0f;
                 }
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(WAVE) void reshade_grad_kernel(TraceArgs a, GradDev
     // the air derivative of a band: the wave's rays in ray order
     double air_total = 0.0;
 #pragma unroll
-    for (uint32_t o = 0; o < GRAD_RAYS; ++o) air_total += __shfl(air_sum, (int) (o * 8u + band));
+    for (uint32_t o = 0; o < GradRows::RAYS; ++o) air_total += __shfl(air_sum, (int) (o * 8u + band));
     const double ln_e = 0x1.fffffefb245eap-1;                                // ln((float) M_E), rvb_math.h air_attenuation
     if (r == 0) table[d.window * 16u + band] = air_total * ln_e;
     __syncthreads();
@@ -262,7 +262,7 @@ __global__ __launch_bounds__(256) void reshade_grad_reduce_kernel(const double *
 
 uint32_t rvb_reshade_grad_blocks(uint64_t nrays, uint64_t nsurfaces)
 {
-    const uint64_t groups = (nrays + GRAD_RAYS - 1) / GRAD_RAYS;
+    const uint64_t groups = GradRows::groups(nrays);
     const uint64_t fit = GRAD_PARTIAL_BYTES / ((nsurfaces * 16 + 8) * sizeof(double));
     return (uint32_t) std::max<uint64_t>(std::min<uint64_t>(groups, std::min<uint64_t>(std::max<uint64_t>(fit, 64), GRAD_MAX_BLOCKS)), 1);
 }
@@ -279,7 +279,7 @@ void rvb_launch_reshade_grad(const TraceArgs & a, const float4 * kept, const Att
     GradDev d;
     d.m = make_model(model);
     d.g = g;
-    d.ngroups = (g.nrays + GRAD_RAYS - 1) / GRAD_RAYS;
+    d.ngroups = (uint32_t) GradRows::groups(g.nrays);
     d.ntiles = std::max((a.nreflections + GRAD_TILE - 1) / GRAD_TILE, 1u);
     d.entries = (uint32_t) (g.nsurfaces * 16 + 8);
     d.partials = partials;

@@ -3,14 +3,14 @@
 // the three places of reference rayverb/kernel.cpp where surfaces and air enter: :461 (the specular chain), :480-485 (the diffuse
 // product) and :260 (add_image), with the functions the trace itself uses (traversal.h, rvb_math.h).
 //   path_keep_kernel        between the path and the shadow stage: the three numbers of a work record that the shadow stage destroys
-//                           (newDist, DIFF, the surface of the triangle) as a 16-byte side record.  A streaming pass.
-//   reshade_kernel          a wave takes RESHADE_RAYS rays.  Tile by tile of RESHADE_TILE bounces: the side records of the tile go to LDS;
-//                           lane (ray, band) runs the sequential chain vol = -vol * specular over the tile into LDS; then the wave streams
-//                           the tile's records two lanes per record, whole 16-byte chunks, each lane finishing the four bands of the
-//                           volume chunk it stores (as shadow_pair_kernel does), and folds the time range.
+//                           (newDist, DIFF, the surface of the triangle) as a 16-byte side record (SideRecord, kept_tiles.h).  A streaming pass.
+//   reshade_kernel          a wave takes eight rays, tile by tile of RESHADE_TILE bounces (the layout: KeptTileLds, kept_tiles.h): the side
+//                           records of the tile go to LDS; lane (ray, band) runs the sequential chain vol = -vol * specular over the tile
+//                           into LDS; then the wave streams the tile's records two lanes per record, whole 16-byte chunks, each lane
+//                           finishing the four bands of the volume chunk it stores (as shadow_pair_kernel does), and folds the time range.
 //   reshade_images_kernel   the image-source candidates and the direct slot(s), one lane each: the chain over the ray's first bounces
 //                           (TraceArgs::early), then make_image's product with the kept INIT_DIST.
-#include "traversal.h"
+#include "kept_tiles.h"
 #include "attenuation.h"
 
 #include <algorithm>
@@ -19,9 +19,8 @@ namespace {
 
 // ---- path_keep_kernel: one lane per record ------------------------------------------------------------------------------------------
 // reads chunk 3 (newDist, threshold, triangle, tag) and the last word of chunk 2 (DIFF) of the work record, 20 consecutive bytes
-// LISTEN (RVB_KEEP_LISTENER): the two words of chunk 3 that nothing else recovers — the own-plane threshold, fmaf(skip_b, t, skip_a) with
-// the segment length t, and the triangle — as an 8-byte record of their own for relisten_records_kernel (relisten_kernels.hip)
-typedef uint32_t nt_uint2 __attribute__((ext_vector_type(2)));
+// LISTEN (RVB_KEEP_LISTENER): the own-plane threshold, fmaf(skip_b, t, skip_a) with the segment length t, and the triangle as a
+// ListenRecord of their own for relisten_records_kernel (relisten_kernels.hip)
 template <bool LISTEN>
 __global__ __launch_bounds__(256) void path_keep_kernel(const float4 * __restrict__ records, const uint64_t nrecords, const TriShade * __restrict__ shade,
                                                         float4 * __restrict__ kept, uint2 * __restrict__ listen)
@@ -30,99 +29,70 @@ __global__ __launch_bounds__(256) void path_keep_kernel(const float4 * __restric
     if (g >= nrecords)
         return;
     const float4 tail = load_stream(records + 4 * g + 3);
-    float4 o = make_float4(0.0f, 0.0f, __uint_as_float(NONE), 0.0f);        // tag 0: the ray had already escaped
-    nt_uint2 l = {0u, 0u};
+    float4 o = SideRecord::none();                     // tag 0: the ray had already escaped
+    ListenRecord l = ListenRecord::make(0u, 0u);
     if (__float_as_uint(tail.w) != 0u) {
         const float diff = __builtin_nontemporal_load(reinterpret_cast<const float *>(records + 4 * g + 2) + 3);
         const uint32_t surface = shade[__float_as_uint(tail.z)].surface;
-        o = make_float4(tail.x, diff, __uint_as_float(surface), 0.0f);
-        l = nt_uint2{__float_as_uint(tail.y), __float_as_uint(tail.z)};
+        o = SideRecord::make(tail.x, diff, surface);
+        l = ListenRecord::make(__float_as_uint(tail.y), __float_as_uint(tail.z));
     }
     store_stream(kept + g, o);
-    if (LISTEN) __builtin_nontemporal_store(l, reinterpret_cast<nt_uint2 *>(listen + g));
+    if (LISTEN) l.store(listen, g);
 }
 
 // ---- reshade_kernel -------------------------------------------------------------------------------------------------------------------
-#define RESHADE_RAYS 8u              // rays per wave: one lane per (ray, band) in the chain phase
 #define RESHADE_TILE 32u             // bounces per tile
-// LDS of a wave, in words: [RAYS][TILE + 1] side records (a row padded by one record: the eight rays' reads of one bounce fall into
-// different banks), [RAYS][(TILE + 1) * 8] chain volumes (padded alike), then the surface table (stage_surfaces)
-#define RESHADE_SIDE_ROW ((RESHADE_TILE + 1u) * 4u)
-#define RESHADE_VOL_ROW ((RESHADE_TILE + 1u) * 8u)
-#define RESHADE_VOL_AT (RESHADE_RAYS * RESHADE_SIDE_ROW)
-#define RESHADE_SURFACES_AT (RESHADE_VOL_AT + RESHADE_RAYS * RESHADE_VOL_ROW)
 #define RESHADE_MAX_LDS_SURFACES 64u
+typedef KeptTileLds<RESHADE_TILE> ReshadeLds;
 
 template <bool SURF_LDS>
 __global__ __launch_bounds__(WAVE) void reshade_kernel(TraceArgs a, const float4 * __restrict__ kept)
 {
+    typedef ReshadeLds L;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    float4 * side = reinterpret_cast<float4 *>(lds);
-    float * chain = reinterpret_cast<float *>(lds + RESHADE_VOL_AT);
-    const lds_float4_ptr surf_lds = stage_surfaces(a, lds + RESHADE_SURFACES_AT);
+    float4 * side = L::side(lds);
+    float * chain = L::chain(lds);
+    const lds_float4_ptr surf_lds = stage_surfaces(a, L::surfaces(lds));
     const uint32_t lane = threadIdx.x, h = lane & 1u;
-    const uint64_t ray0 = (uint64_t) blockIdx.x * RESHADE_RAYS;
-    const uint32_t chain_ray = lane >> 3, band = lane & 7u;
+    const uint64_t ray0 = (uint64_t) blockIdx.x * L::RAYS;
     const float air0 = a.air[4 * h], air1 = a.air[4 * h + 1], air2 = a.air[4 * h + 2], air3 = a.air[4 * h + 3];
     v3 mic = ld3(a.mic);
     float vol = 1.0f;                                        // vol_b(-1) of this lane's (ray, band)
     bool alive = true;
     float tmin = __builtin_inff(), tmax_seen = 0.0f;
     for (uint32_t first = 0; first < a.nreflections; first += RESHADE_TILE) {
-        // (1) the tile's side records, 16 bytes per lane, a ray's run of bounces contiguous
-        for (uint32_t i = lane; i < RESHADE_RAYS * RESHADE_TILE; i += WAVE) {
-            const uint32_t r = i / RESHADE_TILE, k = i % RESHADE_TILE;
-            float4 s = make_float4(0.0f, 0.0f, __uint_as_float(NONE), 0.0f);
-            if (ray0 + r < a.nrays && first + k < a.nreflections)
-                s = load_stream(kept + (ray0 + r) * a.nreflections + first + k);
-            side[r * (RESHADE_TILE + 1u) + k] = s;
-        }
+        stage_side_records<RESHADE_TILE>(a, kept, ray0, first, side);                     // (1)
         __syncthreads();
-        // (2) kernel.cpp:461 along the ray, one band per lane: sequential, float products do not reassociate
-        for (uint32_t k = 0; k < RESHADE_TILE && alive; ++k) {
-            const uint32_t surface = lds[chain_ray * RESHADE_SIDE_ROW + 4u * k + 2u];
-            if (surface == NONE) {                           // escaped (or past the last bounce): no record from here on
-                alive = false;
-                break;
-            }
-            const float4 sp = surface_row<SURF_LDS>(a, surf_lds, surface, band >> 2);
-            const uint32_t e = band & 3u;
-            const float s = e == 0 ? sp.x : (e == 1 ? sp.y : (e == 2 ? sp.z : sp.w));
-            vol = -vol * s;
-            chain[chain_ray * RESHADE_VOL_ROW + 8u * k + band] = vol;
-        }
+        chain_over_tile<SURF_LDS, RESHADE_TILE>(a, surf_lds, lds, chain, vol, alive);     // (2) kernel.cpp:461 along the ray
         __syncthreads();
         // (3) kernel.cpp:471-490 for the tile's records, two lanes per record: lane h stores volume chunk h
-        for (uint32_t j = lane >> 1; j < RESHADE_RAYS * RESHADE_TILE; j += WAVE / 2) {
+        for (uint32_t j = lane >> 1; j < L::RAYS * RESHADE_TILE; j += WAVE / 2) {
             const uint32_t r = j / RESHADE_TILE, k = j % RESHADE_TILE;
             const uint64_t ray = ray0 + r;
             const bool inside = ray < a.nrays && first + k < a.nreflections;
             float4 * rec = reinterpret_cast<float4 *>(a.impulses + (inside ? ray * a.nreflections + first + k : 0));
-            // lane 0: the position chunk, lane 1: the time chunk (the final Impulse the shadow stage left; neither changes)
-            float4 aux = make_float4(0, 0, 0, 0);
-            if (inside) aux = load_stream(rec + h + 2);
-            const float4 sd = side[r * (RESHADE_TILE + 1u) + k];
-            const uint32_t surface = __float_as_uint(sd.z);
-            const v3 p = mk3(dpp_f<QP_PAIR_LO>(aux.x), dpp_f<QP_PAIR_LO>(aux.y), dpp_f<QP_PAIR_LO>(aux.z));
-            // the shadow stage wrote time = seconds_per_meter() * dist for a visible record and 0 otherwise
-            const bool visible = surface != NONE && dpp_f<QP_PAIR_HI>(aux.x) != 0.0f;
+            const FinishedRecord fin = FinishedRecord::read(rec, inside, h);          // (neither chunk changes)
+            const float4 sd = side[L::at(r, k)];
+            const v3 p = fin.position();
+            const bool visible = fin.visible(sd);
             uint32_t pair = 0;
             if (a.npairs > 1) {
                 pair = (uint32_t) ((inside ? ray : 0) / a.rays_per_pair);
                 const float4 m4 = a.pair_mics[pair];
                 mic = mk3(m4.x, m4.y, m4.z);
             }
-            const v3 b2p = mic - p;                       // kernel.cpp:282-286
-            const float mag = length3(b2p);
-            const float dist = visible ? sd.x + mag : 0.0f;             // kernel.cpp:471
+            const float reach = dist_to_mic(sd, p, mic);            // (for every record: inside the select it costs reshade_kernel<false> two VGPRs)
+            const float dist = visible ? reach : 0.0f;
+            const float diff = SideRecord::diff(sd);
             float4 o = make_float4(0, 0, 0, 0);
             if (visible) {
-                const float4 dc = surface_row<SURF_LDS>(a, surf_lds, surface, 2 + h);       // diffuse coefficients of this lane's four bands
-                const float4 v = *reinterpret_cast<const float4 *>(chain + r * RESHADE_VOL_ROW + 8u * k + 4u * h);
-                o.x = band_product(v.x, air_attenuation(dist, air0) * 1.0f, dc.x, sd.y);
-                o.y = band_product(v.y, air_attenuation(dist, air1) * 1.0f, dc.y, sd.y);
-                o.z = band_product(v.z, air_attenuation(dist, air2) * 1.0f, dc.z, sd.y);
-                o.w = band_product(v.w, air_attenuation(dist, air3) * 1.0f, dc.w, sd.y);
+                const float4 dc = surface_row<SURF_LDS>(a, surf_lds, SideRecord::surface(sd), 2 + h);       // diffuse coefficients of this lane's four bands
+                const float4 v = *reinterpret_cast<const float4 *>(chain + L::vol_at(r, k) + 4u * h);
+                o.x = band_product(v.x, air_attenuation(dist, air0) * 1.0f, dc.x, diff);
+                o.y = band_product(v.y, air_attenuation(dist, air1) * 1.0f, dc.y, diff);
+                o.z = band_product(v.z, air_attenuation(dist, air2) * 1.0f, dc.z, diff);
+                o.w = band_product(v.w, air_attenuation(dist, air3) * 1.0f, dc.w, diff);
             }
             // (slots of escaped rays get their zeros again: a source pattern may have left them as -0)
             if (inside) store_stream(rec + h, o);
@@ -182,9 +152,8 @@ uint32_t rvb_reshade_lds_surfaces(uint64_t nsurfaces) { return nsurfaces <= RESH
 void rvb_launch_reshade(const TraceArgs & a, const float4 * kept, hipStream_t s)
 {
     if (a.nrays * (uint64_t) a.nreflections == 0) return;
-    const uint64_t blocks = (a.nrays + RESHADE_RAYS - 1) / RESHADE_RAYS;
-    const size_t lds = ((size_t) RESHADE_SURFACES_AT + 16u * a.lds_surfaces) * sizeof(uint32_t);
-    hipLaunchKernelGGL(a.lds_surfaces ? reshade_kernel<true> : reshade_kernel<false>, dim3((unsigned) blocks), dim3(WAVE), lds, s, a, kept);
+    hipLaunchKernelGGL(a.lds_surfaces ? reshade_kernel<true> : reshade_kernel<false>, dim3((unsigned) ReshadeLds::groups(a.nrays)), dim3(WAVE),
+                       ReshadeLds::bytes(a.lds_surfaces), s, a, kept);
 }
 
 void rvb_launch_reshade_images(const TraceArgs & a, hipStream_t s)

@@ -108,10 +108,12 @@ def assert_state(ctx, case):
     assert time_range(ctx, case["mic"]) == oracle_range(case["diffuse"])
 
 
-@pytest.mark.parametrize("nrays,nrefl", [(509, 24), (5, 70), (130, 64)])
+@pytest.mark.parametrize("nrays,nrefl", [(509, 24), (5, 70), (130, 64), (8, 33), (17, 32), (8, 1)])
 def test_reshaded_records_equal_the_oracle_trace_of_the_other_surfaces(ctx, oracle, cathedral, nrays, nrefl):
     """509 x 24: a partial last workgroup and wave, several rays per wave, a ray shorter than a tile; 5 x 70: a ray longer than a wave
-    and longer than an LDS tile, fewer rays than a wave takes; 130 x 64: nrefl % 32 == 0 selects the 16-bit key runs of the trace."""
+    and longer than an LDS tile, fewer rays than a wave takes; 130 x 64: nrefl % 32 == 0 selects the 16-bit key runs of the trace.
+    The edges of a wave and of a tile: 8 x 33: exactly one wave's rays, a second tile that holds one bounce; 17 x 32: a last wave of one
+    ray, exactly one tile (and the 16-bit key runs); 8 x 1: a single bounce."""
     a, b = cathedral_cases(oracle, cathedral, nrays, nrefl)
     assert_ground(a, b, want_images=2 if nrays == 509 else 1)
     ctx.raytrace(a["mic"], a["source"], a["dirs"], nrefl, AIR_COEFFICIENTS)
@@ -123,6 +125,44 @@ def test_reshaded_records_equal_the_oracle_trace_of_the_other_surfaces(ctx, orac
     assert "reshade_kernel" in names and "reshade_images_kernel" in names and not any("path" in k or "shadow" in k for k in names)
     assert_state(ctx, b)
     assert ctx.executed_bounces() == executed
+
+
+PLACE = np.array([0, 63, 64, 65, 3, 69, 6])
+
+
+def spread_over_70(scene, *tables):
+    """The scene with its seven surfaces at PLACE in a table of 70 (triangles renumbered), and every table of `tables` spread the same
+    way: more surfaces than a table in LDS holds, so the kept-trace kernels read the table through L2."""
+    assert scene[2].shape[0] == PLACE.shape[0]
+    triangles = aligned_copy(scene[0])
+    triangles["surface"] = PLACE[scene[0]["surface"]]
+    wide = []
+    for table in (scene[2],) + tables:
+        w = aligned_copy(np.resize(table, 70))
+        w[PLACE] = table
+        wide.append(w)
+    return ((triangles, scene[1], wide[0]),) + tuple(wide[1:])
+
+
+def test_the_surface_table_read_through_l2(oracle, cathedral):
+    """130 x 24 with the seven surfaces spread over a table of 70: reshade_kernel reads the table from memory.  The records carry no
+    surface number, so the seven-surface oracle cases are the expectation, byte for byte."""
+    from parallel_reverb_raytracer_amd import capi
+    nrays, nrefl = 130, 24
+    a, b = cathedral_cases(oracle, cathedral, nrays, nrefl)
+    assert_ground(a, b)
+    wide_scene, wide_b = spread_over_70(cathedral["scene"], cathedral["B"])
+    c = capi.Context(0)
+    try:
+        c.set_scene(wide_scene)
+        c.keep_paths(True)
+        c.raytrace(a["mic"], a["source"], a["dirs"], nrefl, AIR_COEFFICIENTS)
+        assert_state(c, a)
+        c.reshade(wide_b, AIR_B)
+        assert [k for k, _ in c.last_timings()] == ["reshade_kernel", "reshade_images_kernel"]
+        assert_state(c, b)
+    finally:
+        c.close()
 
 
 def test_slots_behind_an_escape_stay_zero(oracle):

@@ -206,10 +206,12 @@ def traced(ctx, oracle, cathedral, nrays, nrefl, seed=23):
     return chain, dirs
 
 
-@pytest.mark.parametrize("nrays,nrefl", [(509, 24), (5, 70), (130, 64)])
+@pytest.mark.parametrize("nrays,nrefl", [(509, 24), (5, 70), (130, 64), (8, 33), (17, 32), (8, 1)])
 def test_gradient_equals_the_reference_after_a_trace_and_after_a_reshade(ctx, oracle, cathedral, nrays, nrefl):
     """509 x 24: a partial last wave, several rays per wave, a ray of two tiles with a partial one; 5 x 70: a ray longer than a wave,
-    fewer rays than a wave takes; 130 x 64: whole tiles, the 16-bit key runs of the trace."""
+    fewer rays than a wave takes; 130 x 64: whole tiles, the 16-bit key runs of the trace.  The edges of a wave and of a tile: 8 x 33:
+    exactly one wave's rays, a third tile that holds one bounce; 17 x 32: a last wave of one ray, exactly two tiles; 8 x 1: a single
+    bounce."""
     chain, _ = traced(ctx, oracle, cathedral, nrays, nrefl)
     mic = cathedral["mic"]
     compare(ctx, chain, cathedral["scene"][2], mic, nrefl, "cathedral %dx%d after the trace" % (nrays, nrefl))
