@@ -1,22 +1,33 @@
-"""Multi-GPU impulse-response generation: one process per GPU, `torch.distributed` (backend "nccl" =
-RCCL over xGMI on ROCm; "gloo" in the CPU tests).
+"""Multi-GPU impulse-response generation: one process per GPU, `torch.distributed` (backend "nccl" = RCCL over xGMI on ROCm; "gloo" in
+the CPU tests).
 
-The path shards by rays: the scene is replicated, rank r traces the contiguous ray
-range [r*n, (r+1)*n) of one seeded global ray set, and the only data-path collective is ONE
-all-reduce(sum) of the [channels][8][nbins] histograms.  ONE small control collective makes the shards
-agree on the binning: an all-gather of a few-KB block per rank holding the shard's diffuse time range
-— the inputs of findPredelay (reference rayverb.h:49-74) and MAX_SAMPLE (rayverb.cpp:57) — and its
-few valid image-source candidates.  Every rank merges the candidates itself with the reference's
-"lowest ray index wins" rule (rayverb.cpp:654-676), so all ranks know the global time range without a
-second exchange; rank 0 alone adds the merged image impulses to its histogram.
+The path shards by rays: the scene is replicated, rank r traces the contiguous ray range [r*n, (r+1)*n) of one seeded
+global ray set, and the only data-path collective is ONE all-reduce(sum) of the [channels][8][nbins] histograms.  ONE small control
+collective makes the shards agree on the binning: an all-gather of a few-KB block per rank holding the shard's diffuse time range — the
+inputs of findPredelay (reference rayverb.h:49-74) and MAX_SAMPLE (rayverb.cpp:57) — and its few valid image-source candidates.  Every
+rank merges the candidates itself with the reference's "lowest ray index wins" rule (rayverb.cpp:654-676), so all ranks know the global
+time range without a second exchange; rank 0 alone adds the merged image impulses to its histogram.
 
 `tracer` is a capi.Context (GPU) or any object with the same methods (the CPU tests drive this module
-with an oracle-backed stand-in).
+with an oracle-backed stand-in, tests/oracle_tracer.py).  The TRACER PROTOCOL, as capi.Context defines it:
+  tracing: trace, trace_group (static), trace_pairs, select_pair, set_concurrent_traces, `nrays`;
+  small results on the host: get_image_candidates, get_pair_candidates, get_direct;
+  binning: ir_configure_speakers, ir_configure_hrtf, ir_time_range, ir_bins, ir_accumulate_tensor,
+  ir_accumulate_export_tensor, ir_exact_prepare, ir_exact_fold_tensor;
+  order and the way to the host: synchronize, ir_accumulate_wait_for_torch, export_tensor_to_host, and
+  synchronize_exports for the caller who reads info["host"].
+This module's contract, per rank, is the ORDER of these calls and of the collectives
+(tests/test_distributed_call_order.py holds it against a recorded log).
 """
+import os
+import types
+
 import numpy as np
 
 from . import capi
 from .dtypes import IMPULSE
+
+_EMPTY = np.zeros(0, dtype=IMPULSE)
 
 
 def shard_range(total_rays, rank, world):
@@ -125,22 +136,142 @@ def begin_ir(tracer, mic, source, nreflections, air, ray_offset=0):
     tracer.trace(mic, source, nreflections, air, ray_offset=ray_offset)
 
 
+class _Ir:
+    """One rank's part in one impulse response: the plain record that the phases _plan -> _enqueue -> _finish hand on."""
+
+    def __init__(self, tracer, model, mic, which, mode, sample_rate, device, rank=0, world=1, chain_blocks=8, on_stage=None):
+        self.tracer, self.model, self.mic, self.mode, self.sample_rate, self.device = tracer, model, mic, mode, sample_rate, device
+        self.which, self.rank, self.world = which, rank, world       # (`which`: the caller's selection for the WHOLE impulse response)
+        self.chain_blocks, self.on_stage = chain_blocks, on_stage
+        self.reduce = None                               # fixed by _plan from here on: _reduce_none | _reduce_sum | _reduce_chain
+        self.bins_now = True                             # _enqueue bins what _plan configured (a chain folds in _finish; a rank may have nothing to add)
+        self.images = _EMPTY                             # merged image impulses that this rank adds (all-reduce: rank 0) or, in a chain, the last rank will
+        self.predelay, self.max_time, self.nbins = 0.0, 0.0, 0
+        self.hist, self.host, self.export_behind_reduce = None, None, False      # fixed by _enqueue (the last: _finish sends hist to host)
+
+    def stage(self, name):
+        if self.on_stage:
+            self.on_stage(name, self.tracer)
+
+
+def _plan(p, candidates, direct, remove_direct, trim_predelay, collectives=False, chain_exact=False):
+    """Phase 1, host work on the trace's small results: merges the image sources, fixes predelay and nbins, and decides ONCE which reduce
+    path applies and what this rank bins.  candidates() / direct() -> this trace's image-source candidates / direct impulse; a rank on
+    its own asks for them only when images are wanted.  Leaves the tracer configured for what _enqueue bins."""
+    tracer, model, want_images = p.tracer, p.model, bool(p.which & capi.IR_IMAGES)
+    if not collectives:                                      # no other rank: everything asked for, images from this trace's candidates
+        p.reduce = _reduce_none
+        p.images = capi.merge_images(candidates(), direct(), remove_direct) if want_images else _EMPTY
+        model.configure(tracer, p.mic, p.which, p.images)
+        lo, hi = tracer.ir_time_range()
+        p.stage("time_range")
+    else:
+        lo = hi = 0.0
+        if p.which & capi.IR_DIFFUSE:                        # this shard's diffuse impulses alone
+            model.configure(tracer, p.mic, capi.IR_DIFFUSE, _EMPTY)
+            lo, hi = tracer.ir_time_range()
+            p.stage("time_range")
+        everyones, ranges = exchange_shard_summaries(candidates(), lo, hi, p.world, p.device)
+        p.images = capi.merge_images(everyones, direct(), remove_direct) if want_images else _EMPTY
+        if p.images.shape[0]:                                # the merged images' own range, the same on every rank
+            model.configure(tracer, p.mic, capi.IR_IMAGES, p.images)
+            ranges.append(tracer.ir_time_range())
+        lo, hi = combine_time_ranges(ranges)
+        if chain_exact and p.mode == capi.IR_EXACT and p.world > 1:
+            p.reduce, p.bins_now = _reduce_chain, False      # (its last rank adds the merged images, after the folds)
+        else:
+            p.reduce = _reduce_sum                           # rank 0 adds the merged images to its own sum
+            mine = p.which if p.rank == 0 else p.which & capi.IR_DIFFUSE
+            p.bins_now = mine != 0
+            p.images = p.images if p.rank == 0 else _EMPTY
+            if p.bins_now:
+                model.configure(tracer, p.mic, mine, p.images)
+    p.predelay, p.max_time = (lo if trim_predelay else 0.0), hi
+    p.nbins = tracer.ir_bins(hi, p.predelay, p.sample_rate)
+
+
+def _enqueue(p, host_out=None):
+    """Phase 2: the zeroed histogram, the caller's host tensor, the binning (asynchronous on a GPU context: the tracer's stream waits for
+    torch's zero fill by an event).  Returns generate_ir's (hist, info).  HOW THE HISTOGRAM REACHES THE HOST is decided here and nowhere else:
+      - no reduction: FUSED with the binning, one call (rvb_ir_accumulate_export: in exact mode the bin ranges leave as they become final);
+      - a reduction: BEHIND THE COLLECTIVE, in _finish — the collective runs on torch's stream, so the tracer's stream first waits for it by
+        an event (ir_accumulate_wait_for_torch), then export_tensor_to_host on the tracer's export stream.
+    (A copy in stream order behind a separate binning call has no user: without a reduction a rank always bins, and the fused call does both.)"""
+    import torch
+    p.hist = torch.zeros((p.model.nchannels, 8, p.nbins), device=p.device, dtype=torch.float32)
+    info = {"nbins": p.nbins, "predelay": p.predelay, "images": int(p.images.shape[0]), "max_time": p.max_time}
+    if host_out is not None:
+        p.host = info["host"] = host_out(tuple(p.hist.shape))
+        p.export_behind_reduce = p.reduce is not _reduce_none
+    if p.host is not None and not p.export_behind_reduce:
+        p.tracer.ir_accumulate_export_tensor(p.predelay, p.sample_rate, p.nbins, p.mode, p.hist, p.host)
+    elif p.bins_now:
+        p.tracer.ir_accumulate_tensor(p.predelay, p.sample_rate, p.nbins, p.mode, p.hist)
+    return p.hist, info
+
+
+def _finish(p):
+    """Phase 3: waits for the binning, reduces over the ranks, sends the reduced histogram to the host."""
+    p.stage("accumulate")
+    p.reduce(p)
+    if p.export_behind_reduce:
+        p.tracer.ir_accumulate_wait_for_torch()
+        p.tracer.export_tensor_to_host(p.hist, p.host)
+
+
+def _reduce_none(p):
+    p.tracer.synchronize()
+
+
+def _reduce_sum(p):
+    """All-reduce of the ranks' own sums: the single-GPU histogram up to float re-association."""
+    import torch.distributed as dist
+    p.tracer.synchronize()
+    dist.all_reduce(p.hist, op=dist.ReduceOp.SUM)            # RCCL over xGMI: [channels][8][nbins] floats
+
+
+def _reduce_chain(p):
+    """One serial sum over all ranks, in ray order (generate_ir's docstring) — SYSTOLIC: the histogram travels in bin-range blocks, rank r
+    folds block k while rank r + 1 folds block k - 1; a rank keys and sorts its impulses (ir_exact_prepare) before the first block arrives."""
+    import torch.distributed as dist
+    tracer, hist, nbins, last = p.tracer, p.hist, p.nbins, p.world - 1
+    blocks = max(1, min(int(p.chain_blocks), (nbins + 15) // 16))
+    per = ((nbins + blocks - 1) // blocks + 15) & ~15
+    folds = bool(p.which & capi.IR_DIFFUSE)
+    if folds:
+        p.model.configure(tracer, p.mic, capi.IR_DIFFUSE, _EMPTY)
+        tracer.ir_exact_prepare(p.predelay, p.sample_rate, nbins)
+    for b0 in range(0, nbins, per):
+        b1 = min(nbins, b0 + per)
+        if p.rank > 0:
+            hist[:, :, b0:b1] = _recv_block(hist[:, :, b0:b1], p.rank - 1)
+        if folds:
+            tracer.ir_exact_fold_tensor(nbins, b0, b1, hist)
+            tracer.synchronize()
+        if p.rank < last:
+            _send_block(hist[:, :, b0:b1], p.rank + 1)
+    if p.rank == last and (p.which & capi.IR_IMAGES) and p.images.shape[0]:
+        p.model.configure(tracer, p.mic, capi.IR_IMAGES, p.images)
+        tracer.ir_accumulate_tensor(p.predelay, p.sample_rate, nbins, p.mode, hist)
+        tracer.synchronize()
+    dist.broadcast(hist, src=last)
+
+
 def generate_ir(tracer, mic, source, nreflections, air, speakers_dir=None, speakers_coeff=None, sample_rate=44100.0,
                 trim_predelay=True, mode=capi.IR_FAST, rank=0, world=1, ray_offset=0, device="cpu",
                 which=capi.IR_ALL, remove_direct=False, on_stage=None, begun=False, model=None, collectives=None, defer=False,
                 host_out=None, chain_exact=False, chain_blocks=8):
-    """One impulse response from the rays already set on `tracer`.  Returns (hist tensor
-    [nchannels][8][nbins] — identical on every rank —, info dict).
+    """One impulse response from the rays already set on `tracer`.  Returns (hist tensor [nchannels][8][nbins] — identical on every
+    rank —, info dict).  A short driver over three phases: _plan (host), _enqueue (binning), _finish (wait, reduce, export).
 
     world == 1: trace -> merge image sources -> time range -> bin.
-    world > 1: two collectives in all.  (1) exchange_shard_summaries: every rank learns every shard's
-    image-source candidates and diffuse time range, merges the candidates itself (deterministic, a few
-    dozen records) and so knows the global predelay / length without a further exchange; (2) the
-    all-reduce(sum) of the histograms.  Only rank 0 adds the merged image impulses to its histogram.
+    world > 1: two collectives in all.  (1) exchange_shard_summaries: every rank learns every shard's image-source candidates and
+    diffuse time range, merges the candidates itself (deterministic, a few dozen records) and so knows the global predelay / length
+    without a further exchange; (2) the all-reduce(sum) of the histograms.  Only rank 0 adds the merged image impulses to its histogram.
 
-    begun=True: begin_ir(tracer, ...) has already enqueued this IR's trace.  A caller with two contexts per GPU
-    calls begin_ir on the second before generate_ir(..., begun=True) on the first, so that one IR's trace (VALU-bound)
-    runs beside the other's record grouping, binning, host work and collectives (IrPipeline below).
+    begun=True: begin_ir(tracer, ...) has already enqueued this IR's trace.  A caller with two contexts per GPU calls begin_ir on the
+    second before generate_ir(..., begun=True) on the first, so that one IR's trace (VALU-bound) runs beside the other's record
+    grouping, binning, host work and collectives (IrPipeline below).
 
     chain_exact=True (several ranks, exact mode): instead of all-reducing the ranks' serial sums — which is the single-GPU histogram
     only up to float re-association — the ranks continue ONE serial sum in ray order: rank r receives the histogram from rank r-1,
@@ -158,252 +289,131 @@ def generate_ir(tracer, mic, source, nreflections, air, speakers_dir=None, speak
     defer=True: returns (hist, info, finish) as soon as the binning is ENQUEUED; finish() waits for it (and runs the all-reduce).
     A caller that finishes several IRs enqueues all their binning stages first, so that they run side by side instead of each
     waiting for the one before (IrPipeline: the stages of a group)."""
-    import torch
-    import torch.distributed as dist
-
-    empty = np.zeros(0, dtype=IMPULSE)
     if collectives is None:                              # True with world == 1 rehearses the multi-rank code path on one rank
         collectives = world > 1
     if model is None:                                    # the two-list form: speakers (what bench.py and the reference demo configs use)
         model = SpeakerModel(speakers_dir, speakers_coeff)
     if not begun:
         begin_ir(tracer, mic, source, nreflections, air, ray_offset)
+    p = _Ir(tracer, model, mic, which, mode, sample_rate, device, rank, world, chain_blocks, on_stage)
     candidates = tracer.get_image_candidates()           # small: valid image-source paths only
-    if on_stage:
-        on_stage("trace", tracer)
-    direct = tracer.get_direct()
-    want_images = bool(which & capi.IR_IMAGES)
-    if not collectives:
-        images = capi.merge_images(candidates, direct, remove_direct) if want_images else empty
-        model.configure(tracer, mic, which, images)
-        lo, hi = tracer.ir_time_range()
-        if on_stage:
-            on_stage("time_range", tracer)
-        contributes = True
-    else:
-        ranges = []
-        lo_d = hi_d = 0.0
-        if which & capi.IR_DIFFUSE:                      # this shard's diffuse impulses alone
-            model.configure(tracer, mic, capi.IR_DIFFUSE, empty)
-            lo_d, hi_d = tracer.ir_time_range()
-            if on_stage:
-                on_stage("time_range", tracer)
-        candidates, shard_ranges = exchange_shard_summaries(candidates, lo_d, hi_d, world, device)
-        ranges += shard_ranges
-        images = capi.merge_images(candidates, direct, remove_direct) if want_images else empty
-        if images.shape[0]:                              # the merged images' own range, the same on every rank
-            model.configure(tracer, mic, capi.IR_IMAGES, images)
-            ranges.append(tracer.ir_time_range())
-        lo, hi = combine_time_ranges(ranges)
-        chain = bool(chain_exact) and mode == capi.IR_EXACT and world > 1
-        adds_images = rank == (world - 1 if chain else 0)      # one rank adds the merged image impulses: the last of a chain, else rank 0
-        mine = which if adds_images else (which & capi.IR_DIFFUSE)
-        contributes = mine != 0
-        if contributes and not chain:
-            model.configure(tracer, mic, mine, images if adds_images else empty)
-        if not adds_images and not chain:
-            images = empty
-    predelay = lo if trim_predelay else 0.0
-    nbins = tracer.ir_bins(hi, predelay, sample_rate)
-    hist = torch.zeros((model.nchannels, 8, nbins), device=device, dtype=torch.float32)
-    chain = collectives and bool(chain_exact) and mode == capi.IR_EXACT and world > 1
-    info = {"nbins": nbins, "predelay": predelay, "images": int(images.shape[0]), "max_time": hi}
-    host = host_out(tuple(hist.shape)) if host_out is not None else None
-    # one call for the binning AND the histogram's way to the host where the tracer offers it (rvb_ir_accumulate_export: in exact
-    # mode the bin ranges leave as they become final); otherwise the binning, then the copy behind it in stream order
-    fused_export = host is not None and not collectives and contributes and hasattr(tracer, "ir_accumulate_export_tensor")
-    if contributes and not chain:                        # (the tracer's stream waits for torch's zero fill by an event)
-        if fused_export:
-            tracer.ir_accumulate_export_tensor(predelay, sample_rate, nbins, mode, hist, host)
-        else:
-            tracer.ir_accumulate_tensor(predelay, sample_rate, nbins, mode, hist)
-    if host is not None:
-        info["host"] = host
-        if not collectives and hasattr(tracer, "export_tensor_to_host") and not fused_export:
-            if not contributes:                          # (nothing was enqueued on the tracer's stream: order the copy behind torch's zero fill)
-                tracer.ir_accumulate_wait_for_torch()
-            tracer.export_tensor_to_host(hist, host)     # stream order: behind the binning
-
-    def finish():
-        if on_stage:
-            on_stage("accumulate", tracer)
-        if chain:
-            # one serial sum over all ranks, in ray order (see the docstring) — SYSTOLIC: the histogram travels in bin-range blocks, rank r
-            # folds block k while rank r + 1 folds block k - 1; a rank keys and sorts its impulses (ir_exact_prepare) before the first
-            # block arrives.  Tracers without the two-step form fold the whole histogram as one block.
-            two_step = hasattr(tracer, "ir_exact_prepare")
-            blocks = max(1, min(int(chain_blocks), (nbins + 15) // 16)) if two_step else 1
-            per = ((nbins + blocks - 1) // blocks + 15) & ~15
-            folds = bool(which & capi.IR_DIFFUSE)
-            if folds:
-                model.configure(tracer, mic, capi.IR_DIFFUSE, empty)
-                if two_step:
-                    tracer.ir_exact_prepare(predelay, sample_rate, nbins)
-            for b0 in range(0, nbins, per):
-                b1 = min(nbins, b0 + per)
-                if rank > 0:
-                    hist[:, :, b0:b1] = _recv_block(hist[:, :, b0:b1], rank - 1)
-                if folds:
-                    if two_step:
-                        tracer.ir_exact_fold_tensor(nbins, b0, b1, hist)
-                    else:
-                        tracer.ir_accumulate_tensor(predelay, sample_rate, nbins, mode, hist)
-                    tracer.synchronize()
-                if rank < world - 1:
-                    _send_block(hist[:, :, b0:b1], rank + 1)
-            if rank == world - 1 and (which & capi.IR_IMAGES) and images.shape[0]:
-                model.configure(tracer, mic, capi.IR_IMAGES, images)
-                tracer.ir_accumulate_tensor(predelay, sample_rate, nbins, mode, hist)
-                tracer.synchronize()
-            dist.broadcast(hist, src=world - 1)
-        else:
-            tracer.synchronize()
-            if collectives:
-                dist.all_reduce(hist, op=dist.ReduceOp.SUM)  # RCCL over xGMI: [channels][8][nbins] floats
-        if host is not None and (collectives or not hasattr(tracer, "export_tensor_to_host")):
-            if hist.is_cuda and hasattr(tracer, "export_tensor_to_host"):
-                tracer.ir_accumulate_wait_for_torch()    # the collective ran on torch's stream: the tracer's stream waits for it by an event
-                tracer.export_tensor_to_host(hist, host)
-            else:
-                host.copy_(hist)
-
+    p.stage("trace")
+    direct = tracer.get_direct()                         # (a host wait on a GPU context: here, whether or not images are wanted)
+    _plan(p, lambda: candidates, lambda: direct, remove_direct, trim_predelay, collectives, chain_exact)
+    hist, info = _enqueue(p, host_out)
     if defer:
-        return hist, info, finish
-    finish()
+        return hist, info, lambda: _finish(p)
+    _finish(p)
     return hist, info
 
 
 class IrPipeline:
-    """Impulse responses back to back with TWO contexts per GPU: the trace of IR i+1 is enqueued on the other context
-    before IR i is finished, so its VALU-bound path kernel runs beside IR i's bandwidth-, atomic- and host-bound stages
-    (record grouping, binning, candidate merge, collectives).  Single host thread, collectives in program order: safe
-    with any world size.  Measured on one MI355X at workload C2: 6.45 -> 5.6 ms per IR."""
+    """Impulse responses back to back with TWO contexts per GPU: the trace of IR i+1 is enqueued on the other context before IR i is
+    finished, so its VALU-bound path kernel runs beside IR i's bandwidth-, atomic- and host-bound stages (record grouping, binning,
+    candidate merge, collectives).  Single host thread, collectives in program order: safe with any world size.  Measured on one
+    MI355X at workload C2: 6.45 -> 5.6 ms per IR."""
 
     def __init__(self, tracers):
         assert len(tracers) >= 1
         self.tracers = list(tracers)
-        self.next_slot = 0
-        self.begun = [False] * len(self.tracers)
-        self.fuse_groups = __import__("os").environ.get("RVB_PIPELINE_FUSE", "1") != "0"       # one path-kernel launch per group
+        self.next_slot, self.begun = 0, [False] * len(self.tracers)
+        self.fuse_groups = os.environ.get("RVB_PIPELINE_FUSE", "1") != "0"       # one path-kernel launch per group
         # the traces of a group run side by side (run_jobs): tell the contexts, so that the path kernel is sized for the rays in flight
         for t in self.tracers:
-            if hasattr(t, "set_concurrent_traces"):
-                t.set_concurrent_traces(self.group_size(len(self.tracers)))
+            t.set_concurrent_traces(self.group_size(len(self.tracers)))
 
     @staticmethod
     def group_size(n):
         group = max(1, n // 2) if n > 1 else 1
-        return min(group, int(__import__("os").environ.get("RVB_PIPELINE_GROUP", group)))       # (an override may only shrink it)
+        return min(group, int(os.environ.get("RVB_PIPELINE_GROUP", group)))       # (an override may only shrink it)
 
     def run(self, count, trace_args, ir_kwargs, on_result=None):
         """`count` IRs with the same arguments (bench) — trace_args = (mic, source, nreflections, air), ir_kwargs as
         generate_ir takes them.  on_result(hist, info, tracer) is called per IR in order."""
         self.run_jobs([(trace_args, ir_kwargs)] * count, on_result)
 
+    def _begin(self, run, k):
+        trace_args, ir_kwargs = run.jobs[k]
+        begin_ir(self.tracers[run.slots[k]], *trace_args, ray_offset=ir_kwargs.get("ray_offset", 0))
+        self.begun[run.slots[k]] = True
+
+    def _begin_group(self, run, ks):
+        """The traces of a group in ONE path-kernel launch (Context.trace_group) when the jobs agree in reflection count and air
+        coefficients (and RVB_PIPELINE_FUSE allows it); one after the other otherwise."""
+        args = [run.jobs[k][0] for k in ks]
+        same = all(a[2] == args[0][2] and tuple(a[3]) == tuple(args[0][3]) for a in args)
+        if len(ks) > 1 and same and self.fuse_groups:
+            tracers = [self.tracers[run.slots[k]] for k in ks]
+            tracers[0].trace_group(tracers, [a[0] for a in args], [a[1] for a in args], args[0][2], args[0][3],
+                                   [run.jobs[k][1].get("ray_offset", 0) for k in ks])
+            for k in ks:
+                self.begun[run.slots[k]] = True
+        else:
+            for k in ks:
+                self._begin(run, k)
+
+    def _begin_upto(self, run, k):
+        """Begins the traces of jobs [run.begun_upto, k): group by group in the default schedule, else one by one."""
+        grouped = len(self.tracers) > 1 and run.ahead <= 0 and run.group > 1
+        while run.begun_upto < min(k, len(run.jobs)):        # (group boundaries: begun_upto is a multiple of group here)
+            ks = list(range(run.begun_upto, min(run.begun_upto + (run.group if grouped else 1), k, len(run.jobs))))
+            self._begin_group(run, ks)
+            run.begun_upto += len(ks)
+
+    def _enqueue(self, run, i):
+        """generate_ir of job i up to its enqueued binning: (hist, info, finish, tracer)."""
+        slot = run.slots[i]
+        trace_args, ir_kwargs = run.jobs[i]
+        began, self.begun[slot] = self.begun[slot], False
+        return generate_ir(self.tracers[slot], *trace_args, begun=began, defer=True, **ir_kwargs) + (self.tracers[slot],)
+
     def run_jobs(self, jobs, on_result=None):
         """One IR per job = (trace_args, ir_kwargs), e.g. the source / listener pairs of a hall (BASELINE config C5): every
-        context must hold the same scene and rays.  Results arrive in job order."""
+        context must hold the same scene and rays.  Results arrive in job order.
+
+        Default schedule: jobs are enqueued in GROUPS of `group` traces (their path kernels then run side by side: more waves per SIMD,
+        see DESIGN.md "rays per launch"), and group j+1 is enqueued before group j is finished: the traces of the group after next are
+        enqueued, then the binning stages of ALL IRs of this group (each needs its own trace's image-source candidates on the host
+        first), and only then the host waits for them — the stages of a group run side by side, beside the next group's path kernels.
+        group = len(tracers) // 2; two contexts: group 1 = the plain alternation.  RVB_PIPELINE_AHEAD=k (and a single context) instead
+        finishes the IRs one by one and keeps k traces enqueued ahead of the one being finished (k < len(tracers))."""
         n = len(self.tracers)
         if not jobs:
             return
-        first = self.next_slot
-
-        def begin(k):
-            slot = (first + k) % n
-            trace_args, ir_kwargs = jobs[k]
-            begin_ir(self.tracers[slot], *trace_args, ray_offset=ir_kwargs.get("ray_offset", 0))
-            self.begun[slot] = True
-
-        def begin_group(ks):
-            """The traces of a group in ONE path-kernel launch (Context.trace_group) when the contexts offer it and the jobs agree in
-            reflection count and air coefficients; one after the other otherwise."""
-            tracers = [self.tracers[(first + k) % n] for k in ks]
-            same = all(jobs[k][0][2] == jobs[ks[0]][0][2] and tuple(jobs[k][0][3]) == tuple(jobs[ks[0]][0][3]) for k in ks)
-            if len(ks) > 1 and same and all(hasattr(t, "trace_group") for t in tracers) and self.fuse_groups:
-                tracers[0].trace_group(tracers, [jobs[k][0][0] for k in ks], [jobs[k][0][1] for k in ks], jobs[ks[0]][0][2], jobs[ks[0]][0][3],
-                                       [jobs[k][1].get("ray_offset", 0) for k in ks])
-                for k in ks:
-                    self.begun[(first + k) % n] = True
-            else:
-                for k in ks:
-                    begin(k)
-
-        # Default schedule: jobs are enqueued in GROUPS of `group` traces (their path kernels then run side by side: more waves
-        # per SIMD, see DESIGN.md "rays per launch"), and group j+1 is enqueued before group j is finished.  group =
-        # len(tracers) // 2; two contexts: group 1 = the plain alternation.  RVB_PIPELINE_AHEAD=k instead keeps k traces
-        # enqueued ahead of the IR being finished (k < len(tracers)).
-        group = self.group_size(n)
-        ahead = min(n - 1, int(__import__("os").environ.get("RVB_PIPELINE_AHEAD", 0)))
-        begun_upto = [0]                                     # jobs [0, begun_upto) have been begun
-
-        def begin_upto(k):
-            while begun_upto[0] < min(k, len(jobs)):
-                if n > 1 and ahead <= 0 and group > 1:               # (group boundaries: begun_upto is a multiple of group here)
-                    ks = list(range(begun_upto[0], min(begun_upto[0] + group, k, len(jobs))))
-                    begin_group(ks)
-                    begun_upto[0] += len(ks)
-                else:
-                    begin(begun_upto[0])
-                    begun_upto[0] += 1
-
-        begin_upto(group if ahead <= 0 else 1 + ahead)
-        if n > 1 and ahead <= 0:
-            # group by group: the traces of the group after next are enqueued, then the binning stages of ALL IRs of this group
-            # (each needs its own trace's image-source candidates on the host first), and only then the host waits for them — the
-            # stages of a group run side by side, beside the next group's path kernels, instead of one after the other
-            in_flight = max(2, n // group)                   # groups whose traces are enqueued at a time (each context holds one IR)
-            for g0 in range(0, len(jobs), group):
-                begin_upto((g0 // group + in_flight) * group)
-                pending = []
-                for i in range(g0, min(g0 + group, len(jobs))):
-                    slot = (first + i) % n
-                    trace_args, ir_kwargs = jobs[i]
-                    began = self.begun[slot]
-                    self.begun[slot] = False
-                    hist, info, finish = generate_ir(self.tracers[slot], *trace_args, begun=began, defer=True, **ir_kwargs)
-                    pending.append((hist, info, finish, self.tracers[slot]))
-                for hist, info, finish, tracer in pending:
-                    finish()
-                    if on_result:
-                        on_result(hist, info, tracer)
-            self.next_slot = (first + len(jobs)) % n
-            return
-        for i, (trace_args, ir_kwargs) in enumerate(jobs):
-            slot = (first + i) % n
-            if n > 1:
-                begin_upto(i + 1 + ahead)
-            else:
-                begin_upto(i + 1)
-            began = self.begun[slot]
-            self.begun[slot] = False
-            hist, info = generate_ir(self.tracers[slot], *trace_args, begun=began, **ir_kwargs)
-            if on_result:
-                on_result(hist, info, self.tracers[slot])
-        self.next_slot = (first + len(jobs)) % n
+        run = types.SimpleNamespace(jobs=jobs, slots=[(self.next_slot + k) % n for k in range(len(jobs))], begun_upto=0,       # (jobs [0, begun_upto) are begun)
+                                    group=self.group_size(n), ahead=min(n - 1, int(os.environ.get("RVB_PIPELINE_AHEAD", 0))))
+        by_groups = n > 1 and run.ahead <= 0
+        step = run.group if by_groups else 1                 # IRs whose binning stages are enqueued before the host waits for the first
+        in_flight = max(2, n // run.group)                   # groups whose traces are enqueued at a time (each context holds one IR)
+        self._begin_upto(run, run.group if run.ahead <= 0 else 1 + run.ahead)
+        for g0 in range(0, len(jobs), step):
+            self._begin_upto(run, (g0 // step + in_flight) * step if by_groups else g0 + 1 + max(0, run.ahead))
+            pending = [self._enqueue(run, i) for i in range(g0, min(g0 + step, len(jobs)))]
+            for hist, info, finish, tracer in pending:
+                finish()
+                if on_result:
+                    on_result(hist, info, tracer)
+        self.next_slot = (self.next_slot + len(jobs)) % n
 
 
 def generate_pair_irs(tracers, pairs, nreflections, air, model_for_pair, sample_rate, rank=0, world=1, device="cpu",
                       trim_predelay=True, mode=capi.IR_FAST, which=capi.IR_ALL, remove_direct=False, pairs_per_launch=1):
-    """BASELINE config C5: many (source, listener) pairs in one scene.  The PAIRS shard over the ranks (contiguous blocks,
-    shard_range) and every rank traces its own pairs with all of its rays — no collective at all.
-    `pairs` = [(mic, source)], `model_for_pair(i)` -> SpeakerModel / HrtfModel of pair i; `tracers` = this rank's contexts
-    (same scene and rays on each).  Returns {pair index: (hist, info)} for this rank's pairs.
+    """BASELINE config C5: many (source, listener) pairs in one scene.  The PAIRS shard over the ranks (contiguous blocks, shard_range)
+    and every rank traces its own pairs with all of its rays — no collective at all.  `pairs` = [(mic, source)],
+    `model_for_pair(i)` -> SpeakerModel / HrtfModel of pair i; `tracers` = this rank's contexts (same scene and rays on each).
+    Returns {pair index: (hist, info)} for this rank's pairs.
 
     pairs_per_launch == 1: the pairs are jobs of the two-context pipeline, one trace each.
     pairs_per_launch > 1: that many pairs are traced in ONE launch (Context.trace_pairs: the path kernel runs with more waves per
     SIMD), the next launch is enqueued on the other context before this launch's pairs are binned."""
-    import torch
     first, count = shard_range(len(pairs), rank, world)
     out = {}
     if pairs_per_launch <= 1:
-        jobs = []
-        for i in range(first, first + count):
-            mic, source = pairs[i]
-            jobs.append(((mic, source, nreflections, air),
-                         dict(model=model_for_pair(i), sample_rate=sample_rate, trim_predelay=trim_predelay, mode=mode, device=device,
-                              which=which, remove_direct=remove_direct)))    # rank 0 / world 1 inside generate_ir: a pair is not sharded
-        order = list(range(first, first + count))
-        IrPipeline(tracers).run_jobs(jobs, lambda hist, info, _tracer: out.__setitem__(order[len(out)], (hist, info)))
+        kwargs = dict(sample_rate=sample_rate, trim_predelay=trim_predelay, mode=mode, device=device, which=which,
+                      remove_direct=remove_direct)                  # rank 0 / world 1 inside generate_ir: a pair is not sharded
+        jobs = [((*pairs[i], nreflections, air), dict(kwargs, model=model_for_pair(i))) for i in range(first, first + count)]
+        order = iter(range(first, first + count))
+        IrPipeline(tracers).run_jobs(jobs, lambda hist, info, _tracer: out.__setitem__(next(order), (hist, info)))
         return out
 
     batches = [list(range(b, min(first + count, b + pairs_per_launch))) for b in range(first, first + count, pairs_per_launch)]
@@ -414,28 +424,18 @@ def generate_pair_irs(tracers, pairs, nreflections, air, model_for_pair, sample_
 
     if batches:
         begin(0)
-    empty = np.zeros(0, dtype=IMPULSE)
     for j, batch in enumerate(batches):
         if j + 1 < len(batches) and n > 1:
             begin(j + 1)
         tracer = tracers[j % n]
         candidates = tracer.get_image_candidates()           # all pairs of the launch, global ray numbers
-        for k, i in enumerate(batch):
+        for k, i in enumerate(batch):                        # generate_ir's single-rank staging, pair by pair; ONE wait for the launch
             tracer.select_pair(k)
-            images = empty
-            if which & capi.IR_IMAGES:
-                images = capi.merge_images(tracer.get_pair_candidates(k, candidates), tracer.get_direct(), remove_direct)
-            model = model_for_pair(i)
-            model.configure(tracer, pairs[i][0], which, images)
-            lo, hi = tracer.ir_time_range()
-            predelay = lo if trim_predelay else 0.0
-            nbins = tracer.ir_bins(hi, predelay, sample_rate)
-            hist = torch.zeros((model.nchannels, 8, nbins), device=device, dtype=torch.float32)
-            tracer.ir_accumulate_tensor(predelay, sample_rate, nbins, mode, hist)
-            out[i] = (hist, {"nbins": nbins, "predelay": predelay, "images": int(images.shape[0]), "max_time": hi})
+            p = _Ir(tracer, model_for_pair(i), pairs[i][0], which, mode, sample_rate, device)
+            _plan(p, lambda: tracer.get_pair_candidates(k, candidates), tracer.get_direct, remove_direct, trim_predelay)
+            out[i] = _enqueue(p)
+        tracer.synchronize()
         if n == 1 and j + 1 < len(batches):
-            tracer.synchronize()                             # the next launch reuses this context's buffers
-            begin(j + 1)
-        else:
-            tracer.synchronize()
+            begin(j + 1)                                     # (only now: the next launch reuses this context's buffers)
     return out
+

@@ -11,21 +11,45 @@ class OracleTracer:
     def __init__(self, oracle, scene, directions):
         self.oracle, self.scene, self.directions = oracle, scene, directions
         self.nchannels = 0
+        self.nrays = int(directions.shape[0])
+
+    def set_concurrent_traces(self, traces):
+        pass                                                           # (a sizing hint for the path kernel)
 
     def trace(self, mic, source, nreflections, air, ray_offset=0):
-        self.mic = mic
-        self.diffuse, self.image, self.index = self.oracle.raytrace(self.scene, mic, source, self.directions, nreflections, air)
+        self._trace(((mic, source),), nreflections, air, ray_offset)
+
+    @staticmethod
+    def trace_group(tracers, mics, sources, nreflections, air, ray_offsets=None):
+        for k, t in enumerate(tracers):
+            t.trace(mics[k], sources[k], nreflections, air, ray_offsets[k] if ray_offsets is not None else 0)
+
+    def trace_pairs(self, mics, sources, nreflections, air, ray_offset=0):
+        """One oracle run per pair; select_pair(k) picks the pair the ir_* calls and get_direct work on (pair 0 to begin with)."""
+        self._trace(tuple(zip(mics, sources)), nreflections, air, ray_offset)
+
+    def _trace(self, pairs, nreflections, air, ray_offset):
+        self.pairs = [(mic, self.oracle.raytrace(self.scene, mic, source, self.directions, nreflections, air)) for mic, source in pairs]
         self.ray_offset = ray_offset
+        self.mic, (self.diffuse, self.image, self.index) = self.pairs[0]
+
+    def select_pair(self, pair):
+        self.mic, (self.diffuse, self.image, self.index) = self.pairs[pair]
 
     def get_image_candidates(self):
-        nrays = self.directions.shape[0]
-        idx = self.index.reshape(nrays, NUM_IMAGE_SOURCE)
-        rays, slots = np.nonzero(idx[:, 1:])
-        cand = np.zeros(rays.shape[0], dtype=capi.IMAGE_CANDIDATE)
-        cand["ray"], cand["slot"] = rays + self.ray_offset, slots + 1
-        cand["index"] = idx[rays, slots + 1]
-        cand["impulse"] = self.image.reshape(nrays, NUM_IMAGE_SOURCE)[rays, slots + 1]
-        return cand
+        """All pairs' candidates, ray numbers global: ray + pair * nrays (+ the trace's ray_offset)."""
+        parts = []
+        for pair, (_, (_, image, index)) in enumerate(self.pairs):
+            idx = index.reshape(self.nrays, NUM_IMAGE_SOURCE)
+            rays, slots = np.nonzero(idx[:, 1:])
+            cand = np.zeros(rays.shape[0], dtype=capi.IMAGE_CANDIDATE)
+            cand["ray"], cand["slot"] = rays + pair * self.nrays + self.ray_offset, slots + 1
+            cand["index"] = idx[rays, slots + 1]
+            cand["impulse"] = image.reshape(self.nrays, NUM_IMAGE_SOURCE)[rays, slots + 1]
+            parts.append(cand)
+        return np.concatenate(parts)
+
+    get_pair_candidates = capi.Context.get_pair_candidates             # (pure host code over get_image_candidates and nrays)
 
     def get_direct(self):
         return self.image[:1].copy()
@@ -72,6 +96,19 @@ class OracleTracer:
             vol = att["volume"]
             for i in range(att.shape[0]):
                 hist[:, bins[i]] += vol[i]
+
+    def ir_accumulate_wait_for_torch(self):
+        pass                                                           # (one host thread, no streams: everything is in program order)
+
+    def export_tensor_to_host(self, tensor, host):
+        host.copy_(tensor)
+
+    def ir_accumulate_export_tensor(self, predelay, sample_rate, nbins, mode, tensor, host, slices=0):
+        OracleTracer.ir_accumulate_tensor(self, predelay, sample_rate, nbins, mode, tensor)
+        host.copy_(tensor)
+
+    def synchronize_exports(self):
+        pass
 
     def ir_exact_prepare(self, predelay, sample_rate, nbins):
         """The per-impulse bins of every channel (what rvb_ir_exact_prepare sorts on the GPU)."""

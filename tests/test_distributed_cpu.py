@@ -1,5 +1,5 @@
 """world_size-2 `gloo` test of the N>1 path (distributed.generate_ir): ray-range shards, candidate
-all-gather + lowest-ray-wins merge, time-range all-reduce, histogram all-reduce(sum).  The per-rank
+all-gather (it carries the shards' time ranges too) + lowest-ray-wins merge, histogram all-reduce(sum).  The per-rank
 compute is the CPU oracle (tests/oracle_tracer.py), so this runs without a GPU."""
 import os
 import socket
@@ -257,3 +257,27 @@ def test_source_listener_pairs_shard_over_ranks_without_a_collective(tmp_path, o
         for i in two[r]["index"]:
             assert np.array_equal(two[r]["hist%d" % i], one["hist%d" % i])
     assert any(one["hist%d" % i].any() for i in range(5))
+
+
+def test_two_pairs_per_launch_give_what_one_pair_per_launch_gives(oracle):
+    """generate_pair_irs with two pairs per launch (trace_pairs, select_pair, each pair's own candidates) on two tracers: for every
+    pair exactly the histogram and nbins of the one-trace-per-pair form."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from oracle_tracer import OracleTracer
+    from parallel_reverb_raytracer_amd import capi, distributed, dtypes, scenes
+    scene, _ = scenes.concert_hall(900)
+    src, mic = scenes.source_mic_pairs(5, seed=2)
+    table = scenes.hrtf_synthetic_table()
+    tracers = [OracleTracer(oracle, scene, scenes.sphere_directions(40, seed=4)) for _ in range(2)]
+
+    def model(i):
+        facing = src[i] - mic[i]
+        return distributed.HrtfModel(table, facing / np.linalg.norm(facing), (0, 1, 0))
+
+    got = {per_launch: distributed.generate_pair_irs(tracers, [(mic[i], src[i]) for i in range(5)], 6, dtypes.AIR_COEFFICIENTS, model, 44100.0,
+                                                     mode=capi.IR_EXACT, pairs_per_launch=per_launch) for per_launch in (1, 2)}
+    assert sorted(got[1]) == sorted(got[2]) == [0, 1, 2, 3, 4]
+    for i in range(5):
+        assert got[2][i][1]["nbins"] == got[1][i][1]["nbins"]
+        assert np.array_equal(got[2][i][0].numpy(), got[1][i][0].numpy())
+    assert all(got[1][i][0].numpy().any() for i in range(5))
