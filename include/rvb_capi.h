@@ -159,6 +159,59 @@ int rvb_trace_group(rvb_ctx ** ctxs, uint64_t count, const float * mics, const f
 typedef struct { float direction[4]; float shape[8]; } rvb_source_pattern;               /* 48 B */
 int rvb_set_source_pattern(rvb_ctx * ctx, const rvb_source_pattern * patterns, uint64_t npatterns);
 
+/* ---- tabulated source directivity: a per-band gain table at the SOURCE end (csrc/source_kernels.hip) -------------------------------
+ * The twin of the HRTF table at the other end of the path, for a loudspeaker balloon: measured gain per octave band over azimuth and
+ * elevation.  No reference counterpart for the stage; the row selection is the reference's own.
+ *
+ * LAYOUT.  `table` has the layout of ONE ear of the HRTF table (rvb_ir_configure_hrtf): row a * 180 + e, a = 0 .. 359, e = 0 .. 179, eight
+ * band gains per row; [360*180*8] floats, copied.  On the device it is followed by one zero row, row 64800.
+ *
+ * CONTRACT.  For an impulse with departure vector v the selected row is
+ *     row_of(to_listener(basis(facing, up), normalize3(v)))
+ * — exactly the expression of the reference's kernel `hrtf` (kernel.cpp:538-584, hrtf_row in csrc/attenuation.h) with pos - mic replaced
+ * by v: x = normalize3(cross3(up, facing)), y = cross3(facing, x), z = facing; a = (long) (degrees(atan2(t.x, t.z)) + 180) % 360,
+ * e = 90 - (long) degrees(atan2(t.y, sqrt(t.x^2 + t.z^2))), the quirk by which e == 180 runs into the next azimuth row included, and with
+ * the margin scheme of angle_deg, so that the integer parts are those of the correctly rounded binary32 atan2.  facing and up are taken
+ * as given, as rvb_ir_configure_hrtf takes them (facing[3], up[3] ignored); the basis is computed once on the host with the device's
+ * operations.  The departure vector is that of a pattern:
+ *   - diffuse impulses:               v = the ray's own direction;
+ *   - image-source impulses, direct:  v = mic - position, component by component in binary32.
+ * The stored impulse becomes volume_b = volume_b * table[row][b]: ONE binary32 multiply per band, applied to every diffuse record, every
+ * image-source candidate and every direct slot exactly once.  An impulse whose eight scaled volumes are all zero is a zero-volume
+ * impulse from then on, and the per-pair diffuse time range is that of the SCALED records.  An index outside 0 .. 64800 reads the zero
+ * row: finite inputs cannot produce one, but no address outside the table is ever formed.
+ *
+ * norientations == 1: that orientation for every pair.  norientations == n: orientation p for pair p of rvb_trace_pairs; as with
+ * patterns the trace (or re-shade) fails with RVB_ERR_INVALID unless n is 1 or its npairs.  The table itself is one per context.
+ *
+ * ONE DIRECTIVITY SLOT.  A source has one directivity at a time: a call with a table turns any pattern off; table == NULL (orientations
+ * and count are then ignored) turns the table off; ANY call of rvb_set_source_pattern turns the table off, the one with npatterns == 0
+ * included, which still means "nothing at the source end".  With the table off there is no extra launch and no extra allocation: every
+ * byte and every kernel as without this call.
+ *
+ * RVB_ERR_INVALID, before any device is touched: a NULL ctx; a table with orientations NULL or count 0; a value in table, facing or up
+ * that is not finite; an orientation whose normalize3(cross3(up, facing)) is zero or not finite.
+ *
+ * UPLOAD.  Lazily, in stream order, by the next trace or re-shade, through a staging block as the patterns are.  A table set after a kept
+ * trace is therefore NOT what rvb_relisten uses: relisten uses what the records reflect now — pattern, table or nothing, as the kept
+ * trace or the last rvb_reshade left them — and reuses the per-ray gains, which do not depend on the microphone; rvb_reshade applies
+ * what is set now; rvb_reshade_grad takes a ray's gain as a factor of every term of that ray, where a pattern's gain enters.
+ * KERNELS.  The diffuse gain depends on (pair, ray) only, never on the bounce: "source_table_rays_kernel" selects one row per (pair, ray)
+ * and leaves its 32 bytes in a buffer of the context (32 bytes per (pair, ray)); "source_table_kernel" is the streaming pass over the
+ * records, shaped like "source_pattern_kernel", followed by the candidates and direct slots, one lane and one row selection each.
+ * SCOPE.  Contexts only, through rvb_trace, rvb_trace_pairs, rvb_trace_group, rvb_reshade, rvb_relisten and rvb_reshade_grad; not
+ * offered through rvb_multi_* and rvb_pipeline_* in this version.  One table per context; no interpolation between rows (the reference's
+ * table semantics are nearest-cell by truncation; resample on the host).
+ * MEASURED on one MI355X at 100 k rays x 128 in the 75 k-triangle cathedral (profiles/source_table_n1.txt, tools/source_table_bench.py;
+ * medians, all in one run):
+ *     rvb_trace with the directivity off 4.53 ms (the commit before this feature: 4.51 ms, its repetitions spread over 0.15 ms); with a
+ *     polar pattern 4.99 ms, source_pattern_kernel 0.465 ms; with a table 4.95 ms — source_table_rays_kernel 0.007 ms for the 100 k row
+ *     selections, source_table_kernel 0.417 ms (3.9 TB/s of 128 bytes per record; the pattern pass 3.5 TB/s): not slower than the polar
+ *     pass, the difference of 0.05 ms is inside that kernel's own spread. */
+typedef struct { float facing[4]; float up[4]; } rvb_source_orientation;     /* [3] ignored */
+int rvb_set_source_table(rvb_ctx * ctx, const float * table /* [360*180*8] */,
+                         const rvb_source_orientation * orientations, uint64_t norientations);
+
 /* ---- re-shading a finished trace: new surfaces and a new air coefficient without retracing (csrc/reshade_kernels.hip) -------------
  * Everything a trace spends its time on — the closest-hit / reflect chain, the shadow rays, the image-source validation, every
  * position, distance and arrival time — depends on geometry, microphone, source and directions only.  Surfaces and air enter in three

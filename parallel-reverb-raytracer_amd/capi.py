@@ -38,6 +38,7 @@ SYMBOLS = [
     "rvb_device_index", "rvb_pipeline_create", "rvb_pipeline_destroy", "rvb_pipeline_last_error", "rvb_pipeline_configure_speakers",
     "rvb_pipeline_configure_hrtf", "rvb_pipeline_submit", "rvb_pipeline_submit_oriented", "rvb_pipeline_pending", "rvb_pipeline_next",
     "rvb_pipeline_create_lanes",
+    "rvb_set_source_table",
     "rvb_set_source_pattern", "rvb_multi_set_source_pattern", "rvb_pipeline_set_source_pattern", "rvb_pipeline_submit_directed",
     "rvb_keep_paths", "rvb_reshade", "rvb_reshade_grad", "rvb_relisten",
     "rvb_decay_curve", "rvb_decay_times", "rvb_decay_loss",
@@ -145,6 +146,24 @@ def make_source_patterns(directions, shapes):
     for i in range(d.shape[0]):
         out[i].direction[:3] = [float(x) for x in d[i]]
         out[i].shape[:] = [float(x) for x in per[i]]
+    return out
+
+
+class SourceOrientation(ctypes.Structure):
+    """rvb_source_orientation of include/rvb_capi.h: the way the source faces and its up vector, as rvb_ir_configure_hrtf takes them."""
+    _fields_ = [("facing", ctypes.c_float * 4), ("up", ctypes.c_float * 4)]
+
+
+def make_source_orientations(facing, up):
+    """An array of SourceOrientation: facing and up [3] or [n][3] (one of them may be [3] for all n)."""
+    f = np.asarray(facing, dtype=np.float32).reshape(-1, 3)
+    u = np.asarray(up, dtype=np.float32).reshape(-1, 3)
+    n = max(f.shape[0], u.shape[0])
+    f, u = np.broadcast_to(f, (n, 3)), np.broadcast_to(u, (n, 3))
+    out = (SourceOrientation * n)()
+    for i in range(n):
+        out[i].facing[:3] = [float(x) for x in f[i]]
+        out[i].up[:3] = [float(x) for x in u[i]]
     return out
 
 
@@ -267,6 +286,18 @@ class Context:
             return
         pats = make_source_patterns(direction, shape)
         self._check(self.lib.rvb_set_source_pattern(self.handle, pats, _u64(len(pats))))
+
+    def set_source_table(self, table, facing=None, up=None):
+        """Tabulated source directivity for the traces and re-shades that follow (rvb_set_source_table): `table` [360][180][8] band gains
+        in the layout of one ear of the HRTF table (directivity.py builds one from a function or a balloon), the source facing `facing`
+        with `up` up; [n][3] is the per-pair form of trace_pairs.  It replaces a pattern; table None switches it off."""
+        if table is None:
+            self._check(self.lib.rvb_set_source_table(self.handle, None, None, _u64(0)))
+            return
+        t = np.ascontiguousarray(table, dtype=np.float32).reshape(-1)
+        assert t.shape[0] == 360 * 180 * 8
+        o = make_source_orientations(facing, up)
+        self._check(self.lib.rvb_set_source_table(self.handle, _ptr(t), o, _u64(len(o))))
 
     def keep_paths(self, on, listener=False):
         """The traces that follow keep what reshade needs (rvb_keep_paths): 16 bytes per (ray, bounce); False frees them again.

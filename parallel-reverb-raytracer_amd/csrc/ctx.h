@@ -50,6 +50,14 @@ static_assert(offsetof(SmallBlock, trace_range) == 32 && offsetof(SmallBlock, im
 static_assert(offsetof(SmallBlock, direct) == 64 && sizeof(SmallBlock) == 128, "small block layout");
 const size_t kFirstCandidates = 32;
 
+// What shades the records at the source end — a source has one directivity at a time —: nothing, the patterns of rvb_set_source_pattern
+// in their device form, or the table of rvb_set_source_table with this many orientations.
+struct SourceShading {
+    std::vector<SourcePatternDev> patterns;
+    uint32_t table_orientations = 0;
+    bool off() const { return patterns.empty() && table_orientations == 0; }
+};
+
 struct Timing { std::string name; hipEvent_t start, stop; };       // (events of the context's pool)
 
 // A kept trace (rvb_keep_paths; kept.hip works from it).  While keeping is on a trace leaves, beside its results, a 16-byte side record
@@ -74,26 +82,26 @@ struct KeptTrace {
     } dev;
     static_assert(sizeof(Buffers) == 5 * sizeof(DevBuf), "any() names every buffer");
     StagedBlock surfaces_stage;
-    // what the records reflect right now — the kept trace's table, air and source patterns, or those of the last rvb_reshade —: where
-    // rvb_reshade_grad takes its derivatives and what rvb_relisten shades with
+    // what the records reflect right now — the kept trace's table, air and source directivity (pattern, table or nothing), or those of
+    // the last rvb_reshade —: where rvb_reshade_grad takes its derivatives and what rvb_relisten shades with
     const rvb_surface * shaded_surfaces = nullptr;
     float shaded_air[8] = {};
-    std::vector<SourcePatternDev> shaded_patterns;
+    SourceShading shaded_source;
 
     void void_all() { valid = false; listener_valid = false; }
-    // `a` with `patterns` wrote the records last: a trace's shadow kernel, the re-shade kernels
-    void note_shading(const TraceArgs & a, const std::vector<SourcePatternDev> & patterns)
+    // `a` with `source` wrote the records last: a trace's shadow kernel, the re-shade kernels
+    void note_shading(const TraceArgs & a, const SourceShading & source)
     {
         shaded_surfaces = a.scene.surfaces;
         for (int i = 0; i < 8; ++i) shaded_air[i] = a.air[i];
-        shaded_patterns = patterns;
+        shaded_source = source;
     }
     // a trace with the arguments `a` is complete
-    void take(const TraceArgs & a, const std::vector<SourcePatternDev> & patterns)
+    void take(const TraceArgs & a, const SourceShading & source)
     {
         valid = keep_paths;
         listener_valid = keep_paths && keep_listener;
-        if (valid) { args = a; note_shading(a, patterns); }
+        if (valid) { args = a; note_shading(a, source); }
     }
     // the kept trace's own arguments under the table and the air that the records reflect now
     TraceArgs shaded_args() const
@@ -154,6 +162,25 @@ struct rvb_ctx {
     bool source_dirty = false;
     DevBuf source_dev;
     StagedBlock source_stage;
+    // the tabulated directivity (rvb_set_source_table) beside them: the host copy of the table — empty: off — and the bases of its
+    // orientations (rvb_source_table_basis), uploaded together in stream order by the first trace or re-shade after they changed; on the
+    // device [RVB_HRTF_ROWS][8] floats (the zero row last), then the bases.  `gains`: ray_gains of the last launch that applied the table.
+    struct SourceTable {
+        std::vector<float> table;               // [360 * 180][8]
+        std::vector<float> bases;               // [norientations][12]
+        bool dirty = false;
+        DevBuf dev, gains;
+        StagedBlock stage;
+        uint32_t norientations() const { return table.empty() ? 0u : (uint32_t) (bases.size() / 12); }
+    } source_table;
+    // what the traces and re-shades that follow apply
+    SourceShading source_shading() const
+    {
+        SourceShading s;
+        s.patterns = source_patterns;
+        s.table_orientations = source_table.norientations();
+        return s;
+    }
     DevBuf image_items;                          // work list of the image-source check kernel
     KeptTrace kept;                              // rvb_keep_paths: what rvb_reshade, rvb_reshade_grad and rvb_relisten work from
     // rvb_decay_* (csrc/decay.hip): per-tile sums and carries, per-row windows and results; nothing else lives here, so the decay calls
@@ -265,10 +292,11 @@ inline int key_bits_for(uint64_t nbins)
 int fetch_small(rvb_ctx * ctx);
 // trace.hip: the steps of a trace that kept.hip replays (described where they are defined)
 int upload_source_patterns(rvb_ctx * ctx);
+int check_source_counts(rvb_ctx * ctx, const char * who, uint64_t npairs);
 int reset_time_ranges(rvb_ctx * ctx, const TraceArgs & a);
-int apply_source_patterns(rvb_ctx * ctx, const TraceArgs & a, const std::vector<SourcePatternDev> & patterns);
+int apply_source_patterns(rvb_ctx * ctx, const TraceArgs & a, const SourceShading & source, bool gains_stand = false);
 int launch_images_beside(rvb_ctx * ctx, TraceArgs & a);
-int launch_shadow_behind_images(rvb_ctx * ctx, const TraceArgs & a, const std::vector<SourcePatternDev> & patterns);
+int launch_shadow_behind_images(rvb_ctx * ctx, const TraceArgs & a, const SourceShading & source, bool gains_stand = false);
 
 // sort.hip
 bool own_sort_enabled();

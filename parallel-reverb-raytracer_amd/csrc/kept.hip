@@ -46,8 +46,9 @@ int rvb_relisten(rvb_ctx * ctx, const float * mics, uint64_t npairs)
         return fail(ctx, RVB_ERR_INVALID, "rvb_relisten: " + std::to_string(npairs) + " microphone(s) for a kept trace of " + std::to_string(ctx->npairs) + " pair(s)");
     RVB_BIND(ctx);
     KeptTrace & kept = ctx->kept;
-    // the table, the air and the source patterns are those the records reflect now (the scene's own after the kept trace, those of the
-    // last rvb_reshade after one: the patterns on the device are these, a pattern set since is not uploaded yet)
+    // the table, the air and the source directivity are those the records reflect now (the scene's own after the kept trace, those of the
+    // last rvb_reshade after one: the patterns or the source table on the device are these, one set since is not uploaded yet; the
+    // source table's per-ray gains do not depend on the microphone and stand)
     TraceArgs a = kept.shaded_args();
     for (int i = 0; i < 3; ++i) a.mic[i] = mics[i];
     // measurements only (tools/relisten_bench.py): the shadow kernel walks the records in natural order instead of the trace's grouping
@@ -77,7 +78,7 @@ int rvb_relisten(rvb_ctx * ctx, const float * mics, uint64_t npairs)
     ctx->end_timing();
     RVB_HIP(fail, ctx, hipGetLastError());
     if ((rc = launch_images_beside(ctx, a)) != RVB_OK) return rc;
-    if ((rc = launch_shadow_behind_images(ctx, a, kept.shaded_patterns)) != RVB_OK) return rc;
+    if ((rc = launch_shadow_behind_images(ctx, a, kept.shaded_source, true)) != RVB_OK) return rc;
     // the kept trace is now that of the new microphone(s): later rvb_reshade, rvb_reshade_grad and rvb_relisten start from here
     for (int i = 0; i < 3; ++i) kept.args.mic[i] = mics[i];
     ctx->pair_mics_host.assign(mics, mics + 3 * npairs);
@@ -93,9 +94,7 @@ int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces,
     if (!ctx->kept.valid) return fail(ctx, RVB_ERR_STATE, "rvb_reshade: the last trace was made without rvb_keep_paths(ctx, 1)");
     if (surfaces && nsurfaces != ctx->nsurfaces)
         return fail(ctx, RVB_ERR_INVALID, "rvb_reshade: " + std::to_string(nsurfaces) + " surfaces for a scene of " + std::to_string(ctx->nsurfaces));
-    if (ctx->source_patterns.size() > 1 && ctx->source_patterns.size() != ctx->npairs)
-        return fail(ctx, RVB_ERR_INVALID, "rvb_reshade: " + std::to_string(ctx->source_patterns.size()) + " source patterns for " + std::to_string(ctx->npairs) +
-                                          " pair(s): one for all pairs, or one per pair (rvb_set_source_pattern)");
+    if (check_source_counts(ctx, "rvb_reshade", ctx->npairs) != RVB_OK) return RVB_ERR_INVALID;
     RVB_BIND(ctx);
     KeptTrace & kept = ctx->kept;
     TraceArgs a = for_record_pass(ctx, kept.args);   // the trace's own arguments; surfaces and air are the call's
@@ -118,8 +117,9 @@ int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces,
     rvb_launch_reshade_images(a, ctx->stream);
     ctx->end_timing();
     RVB_HIP(fail, ctx, hipGetLastError());
-    if ((rc = apply_source_patterns(ctx, a, ctx->source_patterns)) != RVB_OK) return rc;
-    kept.note_shading(a, ctx->source_patterns);
+    const SourceShading source = ctx->source_shading();
+    if ((rc = apply_source_patterns(ctx, a, source)) != RVB_OK) return rc;
+    kept.note_shading(a, source);
     ctx->select_first_pair();
     return RVB_OK;
 }
@@ -161,8 +161,11 @@ int rvb_reshade_grad(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t 
     g.first_ray = ctx->ir_pair * ctx->nrays;
     g.nrays = (uint32_t) ctx->nrays;
     for (int i = 0; i < 3; ++i) g.mic[i] = ctx->pair_mics_host[3 * ctx->ir_pair + i];
-    g.has_pattern = !kept.shaded_patterns.empty();
-    g.pattern = g.has_pattern ? kept.shaded_patterns[kept.shaded_patterns.size() > 1 ? ctx->ir_pair : 0] : SourcePatternDev{};
+    const std::vector<SourcePatternDev> & shaded_patterns = kept.shaded_source.patterns;
+    g.has_pattern = !shaded_patterns.empty();
+    g.pattern = g.has_pattern ? shaded_patterns[shaded_patterns.size() > 1 ? ctx->ir_pair : 0] : SourcePatternDev{};
+    // a table shaded the records: the pair's rows of the gains that launch left (source_table_rays_kernel)
+    g.ray_gains = kept.shaded_source.table_orientations ? ctx->source_table.gains.as<const float>() + ctx->ir_pair * ctx->nrays * 8 : nullptr;
     g.nsurfaces = ctx->nsurfaces;
     ctx->reset_timings();
     ctx->begin_timing("reshade_grad_weights_kernel");

@@ -83,6 +83,23 @@ void rvb_launch_shadow(const TraceArgs & a, hipStream_t s);
 struct SourcePatternDev { float direction[4]; float shape[8]; };        // rvb_source_pattern with the direction normalised (w = 0)
 SourcePatternDev rvb_source_pattern_device_form(const rvb_source_pattern & p);                      // host
 void rvb_launch_source_pattern(const TraceArgs & a, const SourcePatternDev * patterns, uint32_t npatterns, hipStream_t s);
+// The tabulated directivity (rvb_set_source_table of include/rvb_capi.h) at the same place: volume_b *= table[row(v)][b] with the row of
+// csrc/attenuation.h (hrtf_row with pos - mic replaced by v) in the source's basis.  rvb_launch_source_table_rays: one row selection per
+// (pair, ray) from a.directions into ray_gains[a.npairs][a.rays_per_pair][8] — it reads no record, so rvb_relisten reuses what it left.
+// rvb_launch_source_table: the streaming pass over the records with those gains and the time range into a.time_range (reset by the
+// caller), then the candidates and the direct slot(s), row by row from the table.
+#define RVB_HRTF_ROWS (360 * 180 + 1)   // rows per ear of the device's HRTF table: one per (azimuth, elevation) degree, then the zero row behind quirk Q5
+struct SourceTableDev {
+    const float * table;                // device [RVB_HRTF_ROWS][8]: the caller's rows, then the zero row
+    const float4 * bases;               // device [norientations][3]: bx, by, bz of rvb_source_table_basis
+    uint32_t basis_stride;              // float4s between the bases of two pairs: 0 (one orientation for every pair) or 3
+    float * ray_gains;                  // device [a.npairs][a.rays_per_pair][8]
+};
+// host: the basis of kernel.cpp:538-549 for (facing, up) as twelve floats (bx, by, bz; w = 0), with the device's operations; false where
+// normalize3(cross3(up, facing)) is zero or a value is not finite
+bool rvb_source_table_basis(const rvb_source_orientation & o, float basis[12]);
+void rvb_launch_source_table_rays(const TraceArgs & a, const SourceTableDev & t, hipStream_t s);
+void rvb_launch_source_table(const TraceArgs & a, const SourceTableDev & t, hipStream_t s);
 // Re-shading a finished trace (reshade_kernels.hip; rvb_keep_paths / rvb_reshade of include/rvb_capi.h).
 // path_keep_kernel, between the path and the shadow stage: what the shadow stage destroys of every work record, as a 16-byte side record
 // kept[nrays * nreflections] (SideRecord of kept_tiles.h: newDist, DIFF, the surface or "the ray had escaped").  Only reads the records.
@@ -119,6 +136,7 @@ struct ReshadeGradArgs {
     float mic[3];                       // the pair's microphone in the trace
     bool has_pattern;                   // a source pattern scales the pair's records
     SourcePatternDev pattern;
+    const float * ray_gains;            // device [nrays][8], the pair's rows of SourceTableDev::ray_gains: a source table scales the pair's records; null: none
     uint64_t nsurfaces;
 };
 #define RVB_RESHADE_GRAD_MAX_REFLECTIONS 2048     // a ray's chain checkpoints (one per tile of bounces and lane) live in LDS
@@ -156,7 +174,7 @@ hipError_t rvb_group_records16(void * temp, size_t temp_bytes, const uint16_t * 
 
 // ---- the stages behind the trace: attenuate_kernels.hip (materialised attenuation, time range, predelay), histogram_kernels.hip
 // (fast mode), exact_kernels.hip (exact mode, flatten), rocprim_sort.hip (the sort); their shared device code: attenuation.h ----
-#define RVB_HRTF_ROWS (360 * 180 + 1)   // rows per ear of the device's HRTF table: one per (azimuth, elevation) degree, then the zero row behind quirk Q5
+// (RVB_HRTF_ROWS, above: the rows of one ear of the device's HRTF table)
 struct AttenuationModel {
     int hrtf = 0;                       // 0: speakers, 1: hrtf
     uint32_t nchannels = 0;             // speakers: <= RVB_MAX_SPEAKERS; hrtf: 2

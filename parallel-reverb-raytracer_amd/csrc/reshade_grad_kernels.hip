@@ -98,8 +98,11 @@ __global__ __launch_bounds__(WAVE) void reshade_grad_kernel(TraceArgs a, GradDev
     for (uint32_t grp = blockIdx.x; grp < d.ngroups; grp += gridDim.x) {
         const uint32_t ray0 = grp * GradRows::RAYS;                             // within the pair
         // the source pattern's gain of this lane's band: constant along the ray (source_pattern_kernel, v = the ray's own direction)
+        // (or the source table's, from the gains that source_table_rays_kernel left for the ray)
         float pattern_gain = 1.0f;
-        if (g.has_pattern) {
+        if (g.ray_gains) {
+            pattern_gain = g.ray_gains[(size_t) (ray0 + r < g.nrays ? ray0 + r : g.nrays - 1u) * 8u + band];
+        } else if (g.has_pattern) {
             const float4 dv = a.directions[ray0 + r < g.nrays ? ray0 + r : g.nrays - 1u];
             const v3 u = normalize3(normalize3(mk3(dv.x, dv.y, dv.z)));
             pattern_gain = band_gain(g.pattern.shape[band], dot3(u, mk3(g.pattern.direction[0], g.pattern.direction[1], g.pattern.direction[2])));

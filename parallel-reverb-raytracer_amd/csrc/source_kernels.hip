@@ -10,6 +10,7 @@
 //                                  records at most, one lane each.
 #include "attenuation.h"
 
+#include <cmath>
 #include <cstring>
 
 namespace {
@@ -127,6 +128,122 @@ __global__ __launch_bounds__(256) void source_pattern_images_kernel(rvb_image_ca
     }
 }
 
+// ---- the tabulated directivity of include/rvb_capi.h (rvb_set_source_table): a gain row per departure direction -------------------
+//   source_table_rays_kernel       one row selection per (pair, ray), v = the ray's own direction: the diffuse gain never depends on
+//                                  the bounce, so the row's 32 bytes go to ray_gains[pair][ray][8] once and the streaming pass reads them
+//   source_table_kernel            source_pattern_kernel's sibling: volume_b *= ray_gains[pair][ray][b], the time range of the scaled records
+//   source_table_images_kernel     candidates and direct slot(s): v = mic - position, the row per record, gathered from the table
+
+// The table row for the departure vector `v`: hrtf_row of attenuation.h with pos - mic replaced by v — the listener's basis is the
+// source's (bx, by, bz of rvb_source_table_basis), the margin scheme of angle_deg and quirk Q5 of row_of included.  A row outside the table
+// (finite inputs give none) reads the zero row: no address outside the table is formed.
+__device__ __forceinline__ uint32_t departure_row(const float4 bx, const float4 by, const float4 bz, const v3 v)
+{
+    const v3 d = normalize3(v);
+    const v3 t = mk3(dot3(mk3(bx.x, bx.y, bx.z), d), dot3(mk3(by.x, by.y, by.z), d), dot3(mk3(bz.x, bz.y, bz.z), d));
+    const float az = angle_deg(t.x, t.z, 180.0f, false);
+    const float el = angle_deg(t.y, sqrtf(t.x * t.x + t.z * t.z), 0.0f, false);
+    const int64_t row = row_of(az, el);
+    return row >= 0 && row < RVB_HRTF_ROWS ? (uint32_t) row : (uint32_t) (RVB_HRTF_ROWS - 1);
+}
+
+// One lane per (pair, ray).
+__global__ __launch_bounds__(256) void source_table_rays_kernel(const float4 * __restrict__ directions, const float4 * __restrict__ table,
+                                                                const float4 * __restrict__ bases, const uint32_t basis_stride,
+                                                                const uint32_t rays_per_pair, const uint64_t nrays, float4 * __restrict__ ray_gains)
+{
+    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < nrays; i += (uint64_t) gridDim.x * blockDim.x) {
+        const uint64_t pair = i / rays_per_pair;
+        const float4 dv = directions[i - pair * rays_per_pair];
+        const float4 * basis = bases + pair * basis_stride;
+        const uint32_t row = departure_row(basis[0], basis[1], basis[2], mk3(dv.x, dv.y, dv.z));
+        ray_gains[2 * i + 0] = table[2 * (size_t) row + 0];
+        ray_gains[2 * i + 1] = table[2 * (size_t) row + 1];
+    }
+}
+
+// source_pattern_kernel with the gain read instead of computed: the same walk (whole 1 KiB runs of 16 records per wave, uniform trip
+// count), the same stores (whole 64-byte records leave the wave; lanes past the end store nothing), the same reduction of the time range.
+// A ray's gain row is read by its nreflections consecutive records: once from HBM, then from the caches.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void source_table_kernel(float4 * __restrict__ records, const uint64_t nrecords, const float4 * __restrict__ ray_gains,
+                                                           const uint32_t nreflections, const uint32_t rays_per_pair, const uint32_t npairs,
+                                                           uint32_t * range)
+{
+    const uint32_t q = threadIdx.x & 3u, lane = threadIdx.x & 63u;
+    const uint64_t nchunks = nrecords * 4;
+    const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
+    for (uint64_t w0 = (uint64_t) blockIdx.x * blockDim.x + (threadIdx.x & ~63u); w0 < nchunks; w0 += stride) {
+        const uint64_t c = w0 + lane;
+        const bool inside = c < nchunks;
+        const uint64_t rec = (inside ? c : nchunks - 1) >> 2;      // (lanes past the end: the last record's ray, a valid address)
+        const uint32_t ray = WIDE ? (uint32_t) (rec / nreflections) : (uint32_t) rec / nreflections;       // within the launch: [pair][ray]
+        const uint32_t pair = npairs > 1 ? ray / rays_per_pair : 0u;
+        float4 v = make_float4(0, 0, 0, 0);
+        if (inside) v = records[c];
+        float4 o = v;
+        if (q < 2) {
+            const float4 g = ray_gains[2 * (size_t) ray + q];
+            o = make_float4(v.x * g.x, v.y * g.y, v.z * g.z, v.w * g.w);
+        }
+        if (inside) records[c] = o;
+        // the time range of the records that still carry volume (kernel.cpp:524 any(volume != 0) on the scaled record)
+        const QuadRecord r = quad_record(q, o);
+        const bool live = inside && r.nonzero;
+        float tmin = live && r.time != 0.0f ? r.time : __builtin_inff();
+        float tmax = live ? r.time : 0.0f;
+        // one pair per wave run, or record by record where the run straddles two pairs: as in source_pattern_kernel
+        const uint64_t rec_first = w0 >> 2, rec_last = (w0 + 63 < nchunks ? w0 + 63 : nchunks - 1) >> 2;
+        const uint64_t per_pair = (uint64_t) rays_per_pair * nreflections;
+        const bool one_pair = npairs <= 1 || rec_first / per_pair == rec_last / per_pair;         // (wave-uniform)
+        if (one_pair) {
+            for (int off = 32; off > 0; off >>= 1) {
+                tmin = fminf(tmin, __shfl_xor(tmin, off));
+                tmax = fmaxf(tmax, __shfl_xor(tmax, off));
+            }
+            if (lane == 0) {
+                uint32_t * mine = range + 2u * pair;
+                const volatile uint32_t * seen = mine;
+                if (tmin != __builtin_inff() && __float_as_uint(tmin) < seen[0]) atomicMin(mine + 0, __float_as_uint(tmin));
+                if (__float_as_uint(tmax) > seen[1]) atomicMax(mine + 1, __float_as_uint(tmax));
+            }
+        } else if (live && q == 0) {
+            uint32_t * mine = range + 2u * pair;
+            if (tmin != __builtin_inff()) atomicMin(mine + 0, __float_as_uint(tmin));
+            atomicMax(mine + 1, __float_as_uint(tmax));
+        }
+    }
+}
+
+// The image-source candidates [0, *count) and the direct slot of every pair, one lane each: v = mic - position, component by component.
+__global__ __launch_bounds__(256) void source_table_images_kernel(rvb_image_candidate * __restrict__ candidates, const uint32_t * __restrict__ count,
+                                                                  rvb_impulse * __restrict__ direct, const uint32_t npairs, const uint32_t rays_per_pair,
+                                                                  const uint64_t ray_offset, const float4 * __restrict__ pair_mics, const v3 mic,
+                                                                  const float4 * __restrict__ table, const float4 * __restrict__ bases, const uint32_t basis_stride)
+{
+    const uint32_t ncand = *count, ndirect = npairs > 1 ? npairs : 1u;
+    const uint64_t total = (uint64_t) ncand + ndirect;
+    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t) gridDim.x * blockDim.x) {
+        rvb_impulse * imp;
+        uint32_t pair = 0;
+        if (i < ncand) {
+            imp = &candidates[i].impulse;
+            if (npairs > 1) pair = (uint32_t) ((candidates[i].ray - ray_offset) / rays_per_pair);
+        } else {
+            pair = (uint32_t) (i - ncand);
+            imp = direct + pair;
+        }
+        if (pair >= ndirect) pair = ndirect - 1u;                    // (a candidate's ray is always one of the launch's)
+        v3 m = mic;
+        if (npairs > 1) { const float4 pm = pair_mics[pair]; m = mk3(pm.x, pm.y, pm.z); }
+        const float4 * basis = bases + (size_t) pair * basis_stride;
+        const v3 v = m - mk3(imp->position[0], imp->position[1], imp->position[2]);
+        const float * g = reinterpret_cast<const float *>(table + 2 * (size_t) departure_row(basis[0], basis[1], basis[2], v));
+#pragma unroll
+        for (int b = 0; b < 8; ++b) imp->volume[b] = imp->volume[b] * g[b];
+    }
+}
+
 // Which stores the streaming pass uses.  Measured at workload C2 (profiles/source_pattern_n1.txt); RVB_SOURCE_STORE = volumes | record |
 // volumes_nt | record_nt chooses another form for measurements (read per launch; same bytes in memory either way).
 enum StoreForm { STORE_VOLUMES = 0, STORE_RECORD = 1, STORE_VOLUMES_NT = 2, STORE_RECORD_NT = 3 };
@@ -162,6 +279,43 @@ SourcePatternDev rvb_source_pattern_device_form(const rvb_source_pattern & p)
     d.direction[0] = n.x; d.direction[1] = n.y; d.direction[2] = n.z; d.direction[3] = 0.0f;
     for (int b = 0; b < 8; ++b) d.shape[b] = p.shape[b];
     return d;
+}
+
+bool rvb_source_table_basis(const rvb_source_orientation & o, float basis[12])
+{
+    const v3 facing = mk3(o.facing[0], o.facing[1], o.facing[2]), up = mk3(o.up[0], o.up[1], o.up[2]);
+    const v3 bx = normalize3(cross3(up, facing));                   // kernel.cpp:538-549 (transform3, make_model), with the device's operations
+    const v3 by = cross3(facing, bx);
+    const float rows[12] = {bx.x, bx.y, bx.z, 0.0f, by.x, by.y, by.z, 0.0f, facing.x, facing.y, facing.z, 0.0f};
+    for (int i = 0; i < 12; ++i) basis[i] = rows[i];
+    bool finite = true;
+    for (int i = 0; i < 12; ++i) finite = finite && std::isfinite(rows[i]);
+    return finite && (bx.x != 0.0f || bx.y != 0.0f || bx.z != 0.0f);
+}
+
+void rvb_launch_source_table_rays(const TraceArgs & a, const SourceTableDev & t, hipStream_t s)
+{
+    if (!a.nrays) return;
+    hipLaunchKernelGGL(source_table_rays_kernel, dim3(stream_blocks(a.nrays, 256)), dim3(256), 0, s, a.directions, reinterpret_cast<const float4 *>(t.table),
+                       t.bases, t.basis_stride, a.rays_per_pair, a.nrays, reinterpret_cast<float4 *>(t.ray_gains));
+}
+
+void rvb_launch_source_table(const TraceArgs & a, const SourceTableDev & t, hipStream_t s)
+{
+    const uint64_t nrecords = a.nrays * a.nreflections;
+    if (nrecords) {
+        const dim3 grid(stream_blocks(nrecords * 4, 256));
+        float4 * records = reinterpret_cast<float4 *>(a.impulses);
+        const float4 * gains = reinterpret_cast<const float4 *>(t.ray_gains);
+        if (nrecords > 0xFFFFFFFFull)
+            hipLaunchKernelGGL((source_table_kernel<true>), grid, dim3(256), 0, s, records, nrecords, gains, a.nreflections, a.rays_per_pair, a.npairs, a.time_range);
+        else
+            hipLaunchKernelGGL((source_table_kernel<false>), grid, dim3(256), 0, s, records, nrecords, gains, a.nreflections, a.rays_per_pair, a.npairs, a.time_range);
+    }
+    // (the candidates: as in rvb_launch_source_pattern)
+    const unsigned blocks = (unsigned) std::min<uint64_t>(std::max<uint64_t>((a.nrays * 9 + a.npairs + 255) / 256, 1), 64);
+    hipLaunchKernelGGL(source_table_images_kernel, dim3(blocks), dim3(256), 0, s, a.candidates, a.candidate_count, a.direct, a.npairs, a.rays_per_pair,
+                       a.ray_offset, a.pair_mics, mk3(a.mic[0], a.mic[1], a.mic[2]), reinterpret_cast<const float4 *>(t.table), t.bases, t.basis_stride);
 }
 
 void rvb_launch_source_pattern(const TraceArgs & a, const SourcePatternDev * patterns, uint32_t npatterns, hipStream_t s)

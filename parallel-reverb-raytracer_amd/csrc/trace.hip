@@ -16,6 +16,31 @@ int upload_source_patterns(rvb_ctx * ctx)
         RVB_HIP(fail, ctx, ctx->source_stage.upload(ctx->source_dev, ctx->source_patterns.data(), ctx->source_patterns.size() * sizeof(SourcePatternDev), ctx->stream));
         ctx->source_dirty = false;
     }
+    // ... and the table of rvb_set_source_table with the bases of its orientations behind it, in one block
+    rvb_ctx::SourceTable & t = ctx->source_table;
+    if (t.dirty && !t.table.empty()) {
+        const size_t table_floats = (size_t) RVB_HRTF_ROWS * 8, bytes = (table_floats + t.bases.size()) * sizeof(float);
+        RVB_HIP(fail, ctx, t.stage.acquire(bytes, ctx->stream, &t.dev));
+        float * host = t.stage.host<float>();
+        std::memcpy(host, t.table.data(), t.table.size() * sizeof(float));
+        std::memset(host + t.table.size(), 0, (table_floats - t.table.size()) * sizeof(float));           // the zero row
+        std::memcpy(host + table_floats, t.bases.data(), t.bases.size() * sizeof(float));
+        RVB_HIP(fail, ctx, hipMemcpyAsync(t.dev.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+        RVB_HIP(fail, ctx, t.stage.record(ctx->stream));
+        t.dirty = false;
+    }
+    return RVB_OK;
+}
+
+// "n orientations / patterns for npairs pairs": one for all pairs, or one per pair
+int check_source_counts(rvb_ctx * ctx, const char * who, uint64_t npairs)
+{
+    if (ctx->source_patterns.size() > 1 && ctx->source_patterns.size() != npairs)
+        return fail(ctx, RVB_ERR_INVALID, std::string(who) + ": " + std::to_string(ctx->source_patterns.size()) + " source patterns for " + std::to_string(npairs) +
+                                          " pair(s): one for all pairs, or one per pair (rvb_set_source_pattern)");
+    if (ctx->source_table.norientations() > 1 && ctx->source_table.norientations() != npairs)
+        return fail(ctx, RVB_ERR_INVALID, std::string(who) + ": " + std::to_string(ctx->source_table.norientations()) + " source orientations for " +
+                                          std::to_string(npairs) + " pair(s): one for all pairs, or one per pair (rvb_set_source_table)");
     return RVB_OK;
 }
 
@@ -37,15 +62,36 @@ int reset_time_ranges(rvb_ctx * ctx, const TraceArgs & a)
 // Directional sources behind the kernel that wrote the final records (the shadow kernel of a trace, the re-shade kernels of rvb_reshade):
 // the records scaled once — this stream has waited for the image kernels, so the candidates are final too — and the diffuse time range
 // taken again, over the scaled records: it replaces that kernel's.
-// (`patterns`: those on the device — the context's after upload_source_patterns; rvb_relisten passes the ones the records reflect)
-int apply_source_patterns(rvb_ctx * ctx, const TraceArgs & a, const std::vector<SourcePatternDev> & patterns)
+// `source` names which directivity, the patterns of rvb_set_source_pattern or the table of rvb_set_source_table: what is on the device —
+// the context's after upload_source_patterns; rvb_relisten passes what the records reflect.  The table's diffuse gains are taken once per (pair, ray)
+// in front of the streaming pass; gains_stand: those of the launch that shaded the records last are still there (rvb_relisten: they do
+// not depend on the microphone).
+int apply_source_patterns(rvb_ctx * ctx, const TraceArgs & a, const SourceShading & source, bool gains_stand)
 {
-    if (patterns.empty()) return RVB_OK;
+    if (source.off()) return RVB_OK;
+    rvb_ctx::SourceTable & t = ctx->source_table;
+    if (source.table_orientations && !gains_stand) RVB_HIP(fail, ctx, t.gains.ensure((size_t) a.nrays * 8 * sizeof(float)));
     const int rc = reset_time_ranges(ctx, a);
     if (rc != RVB_OK) return rc;
-    ctx->begin_timing("source_pattern_kernel");
-    rvb_launch_source_pattern(a, ctx->source_dev.as<SourcePatternDev>(), (uint32_t) patterns.size(), ctx->stream);
-    ctx->end_timing();
+    if (source.table_orientations) {
+        SourceTableDev d;
+        d.table = t.dev.as<const float>();
+        d.bases = reinterpret_cast<const float4 *>(d.table + (size_t) RVB_HRTF_ROWS * 8);
+        d.basis_stride = source.table_orientations > 1 ? 3u : 0u;
+        d.ray_gains = t.gains.as<float>();
+        if (!gains_stand) {
+            ctx->begin_timing("source_table_rays_kernel");
+            rvb_launch_source_table_rays(a, d, ctx->stream);
+            ctx->end_timing();
+        }
+        ctx->begin_timing("source_table_kernel");
+        rvb_launch_source_table(a, d, ctx->stream);
+        ctx->end_timing();
+    } else {
+        ctx->begin_timing("source_pattern_kernel");
+        rvb_launch_source_pattern(a, ctx->source_dev.as<SourcePatternDev>(), (uint32_t) source.patterns.size(), ctx->stream);
+        ctx->end_timing();
+    }
     RVB_HIP(fail, ctx, hipGetLastError());
     return RVB_OK;
 }
@@ -66,14 +112,14 @@ int launch_images_beside(rvb_ctx * ctx, TraceArgs & a)
     return RVB_OK;
 }
 
-int launch_shadow_behind_images(rvb_ctx * ctx, const TraceArgs & a, const std::vector<SourcePatternDev> & patterns)
+int launch_shadow_behind_images(rvb_ctx * ctx, const TraceArgs & a, const SourceShading & source, bool gains_stand)
 {
     RVB_HIP(fail, ctx, hipStreamWaitEvent(ctx->stream, ctx->side_done, 0));
     ctx->begin_timing(rvb_shadow_lanes() == 2 ? "shadow_pair_kernel" : (rvb_shadow_lanes() == 1 ? "shadow_lane_kernel" : "shadow_kernel"));
     rvb_launch_shadow(a, ctx->stream);
     ctx->end_timing();
     RVB_HIP(fail, ctx, hipGetLastError());
-    return apply_source_patterns(ctx, a, patterns);
+    return apply_source_patterns(ctx, a, source, gains_stand);
 }
 
 namespace {
@@ -93,9 +139,7 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     if (!ctx->directions && ctx->nrays) return fail(ctx, RVB_ERR_STATE, "rvb_trace: no directions");
     if (nreflections >= (1ull << 31) || ctx->nrays * npairs * 9 >= (1ull << 32))
         return fail(ctx, RVB_ERR_CAPACITY, "rvb_trace: too many reflections or rays for one context");
-    if (ctx->source_patterns.size() > 1 && ctx->source_patterns.size() != npairs)
-        return fail(ctx, RVB_ERR_INVALID, "rvb_trace: " + std::to_string(ctx->source_patterns.size()) + " source patterns for " + std::to_string(npairs) +
-                                          " pair(s): one for all pairs, or one per pair (rvb_set_source_pattern)");
+    if (check_source_counts(ctx, "rvb_trace", npairs) != RVB_OK) return RVB_ERR_INVALID;
     const float * mic = mics, * source = sources;
     RVB_BIND(ctx);
     ctx->traced = false;                              // (until trace_finish: a failure below must not leave the last trace's results half reset)
@@ -266,8 +310,9 @@ int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
         }
         ctx->end_timing();
     }
-    if ((rc = launch_shadow_behind_images(ctx, a, ctx->source_patterns)) != RVB_OK) return rc;
-    ctx->kept.take(a, ctx->source_patterns);
+    const SourceShading source = ctx->source_shading();
+    if ((rc = launch_shadow_behind_images(ctx, a, source)) != RVB_OK) return rc;
+    ctx->kept.take(a, source);
     ctx->nreflections = nreflections;
     ctx->traced = true;
     ctx->void_fetched_results();
@@ -412,11 +457,42 @@ int rvb_set_source_pattern(rvb_ctx * ctx, const rvb_source_pattern * patterns, u
         if (!(len2 > 0.5f && len2 < 2.0f))
             return fail(ctx, RVB_ERR_INVALID, "rvb_set_source_pattern: pattern " + std::to_string(p) + " has a direction of zero length (or one binary32 cannot normalise)");
     }
+    ctx->source_table.table.clear();            // one directivity at a time: any accepted call turns the table off (what is on the device stays)
+    ctx->source_table.bases.clear();
     // (the same patterns again — a pipeline sets them per job —: what is on the device stays)
     if (form.size() == ctx->source_patterns.size() && (form.empty() || !std::memcmp(form.data(), ctx->source_patterns.data(), form.size() * sizeof(SourcePatternDev))))
         return RVB_OK;
     ctx->source_patterns.swap(form);
     ctx->source_dirty = true;
+    return RVB_OK;
+}
+
+int rvb_set_source_table(rvb_ctx * ctx, const float * table, const rvb_source_orientation * orientations, uint64_t norientations)
+{
+    if (!ctx) return RVB_ERR_INVALID;
+    rvb_ctx::SourceTable & t = ctx->source_table;
+    if (!table) {                               // off: what is on the device stays (a kept trace may reflect it)
+        t.table.clear();
+        t.bases.clear();
+        return RVB_OK;
+    }
+    if (!orientations || norientations == 0) return fail(ctx, RVB_ERR_INVALID, "rvb_set_source_table: a table without orientations");
+    const size_t table_floats = (size_t) (RVB_HRTF_ROWS - 1) * 8;
+    for (size_t i = 0; i < table_floats; ++i)
+        if (!std::isfinite(table[i]))
+            return fail(ctx, RVB_ERR_INVALID, "rvb_set_source_table: row " + std::to_string(i / 8) + " of the table holds a value that is not finite");
+    std::vector<float> bases(12 * (size_t) norientations);
+    for (uint64_t p = 0; p < norientations; ++p) {
+        bool finite = true;
+        for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(orientations[p].facing[i]) && std::isfinite(orientations[p].up[i]);
+        if (!finite) return fail(ctx, RVB_ERR_INVALID, "rvb_set_source_table: orientation " + std::to_string(p) + " holds a value that is not finite");
+        if (!rvb_source_table_basis(orientations[p], bases.data() + 12 * p))
+            return fail(ctx, RVB_ERR_INVALID, "rvb_set_source_table: orientation " + std::to_string(p) + ": normalize3(cross3(up, facing)) is zero or not finite");
+    }
+    ctx->source_patterns.clear();               // one directivity at a time: the table turns any pattern off
+    t.table.assign(table, table + table_floats);
+    t.bases.swap(bases);
+    t.dirty = true;
     return RVB_OK;
 }
 
