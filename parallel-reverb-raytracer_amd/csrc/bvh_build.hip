@@ -544,6 +544,7 @@ std::string rvb_build_scene(const rvb_triangle * triangles, uint64_t ntriangles,
             for (int a = 0; a < 3; ++a) p.ukey[a] = p.c[a];
     }
     if (nprims == 0) {
+        out.leafpos.assign(ntriangles, 0xFFFFFFFFu);       // every triangle dropped
         BvhNode root;
         std::memset(&root, 0, sizeof(root));
         for (int c = 0; c < 4; ++c) {

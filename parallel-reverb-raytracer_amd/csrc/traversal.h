@@ -92,11 +92,15 @@ __device__ __forceinline__ float4 load_stream(const float4 * p)
 }
 
 // Inverse direction for the (conservative, padded) slab test only — never used by a triangle test,
-// so the 1-ulp hardware reciprocal is enough.
+// so the 1-ulp hardware reciprocal is enough.  Clamped to +-2^97: with coordinates up to 2^30 (rvb_build_scene's limit) the product
+// o * inv stays finite (2^127), and so does a binary16 plane times inv (< 2^113).  A larger clamp (1e30 until the constructed scenes
+// of tests/bvh_edges.py) made o * inv infinite above |o| = 3.4e8 for a ray with a zero direction component; the min / max form of the
+// slab test then rejected every box: fmaf(finite plane, inv, -inf) = -inf on one side, NaN on the saturated other.  With a power of
+// two the product is exact, so for such a component the sign of fmaf(plane, inv, -o * inv) is the sign of plane - o.
 __device__ __forceinline__ float clamp_inv(float d)
 {
     float inv = __builtin_amdgcn_rcpf(d);         // +-inf for d == 0
-    return fminf(fmaxf(inv, -1e30f), 1e30f);      // keeps 0 * inf out of the slab test
+    return fminf(fmaxf(inv, -0x1p97f), 0x1p97f);  // keeps 0 * inf out of the slab test
 }
 
 // byte offset of leaf-order triangle i < 2^24 (rvb_build_scene's limit): one full-rate 24-bit multiply

@@ -41,7 +41,7 @@ static std::vector<char> slurp(const char * path)
     return b;
 }
 static float half_to_float(uint16_t b) { _Float16 h; memcpy(&h, &b, 2); return (float) h; }
-static float clamp_inv(float d) { float inv = 1.0f / d; return inv > 1e30f ? 1e30f : (inv < -1e30f ? -1e30f : inv); }
+static float clamp_inv(float d) { float inv = 1.0f / d;   /* +-2^97, traversal.h */ return inv > 1.5845632502852868e29f ? 1.5845632502852868e29f : (inv < -1.5845632502852868e29f ? -1.5845632502852868e29f : inv); }
 
 // ---- a tree of any width derived from the product's 4-wide tree ---------------------------------------------------------------
 struct WChild { float lo[3], hi[3]; uint32_t ref; };      // ref: LEAF | ... as in bvh.h, or index of a WNode

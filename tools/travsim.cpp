@@ -58,8 +58,8 @@ struct Query {
 static float clamp_inv(float d)
 {
     float inv = 1.0f / d;
-    if (inv > 1e30f) inv = 1e30f;
-    if (inv < -1e30f) inv = -1e30f;
+    if (inv > 1.5845632502852868e29f) inv = 1.5845632502852868e29f;
+    if (inv < -1.5845632502852868e29f) inv = -1.5845632502852868e29f;
     return inv;
 }
 
