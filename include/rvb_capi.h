@@ -345,6 +345,58 @@ int rvb_relisten(rvb_ctx * ctx, const float * mics, uint64_t npairs);
 int rvb_reshade_grad(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins, const void * d_weights, rvb_surface * grad_surfaces,
                      float grad_air[8]);
 
+/* ---- sensitivity map: the material gradients per TRIANGLE (csrc/reshade_grad_map_kernels.hip) --------------------------------------
+ * rvb_reshade_grad says which coefficients matter; a room designer asks WHERE on the walls treatment changes this decay at this seat.
+ * That is the same derivative kept per triangle instead of summed per surface.  A trace kept with RVB_KEEP_LISTENER holds what it takes:
+ * the listener record beside the side record names the triangle of every (ray, bounce).  No reference counterpart.
+ *
+ * THE QUANTITY.  L is exactly the L of rvb_reshade_grad — the same H, the same weights layout [nchannels][8][nbins] (device memory), the
+ * same selected pair, the same table, air and source directivity that the records reflect now.  Triangle t is treated as if it owned a
+ * private copy of its surface's coefficients; with the terms of rvb_reshade_grad above,
+ *     d_map[t].specular[b] = sum over the records (ray, j) with triangle_j == t of -P_{j-1} B_j
+ *     d_map[t].diffuse[b]  = sum over the records (ray, k) with triangle_k == t of  P_k a_k
+ * so that in exact arithmetic the entries of the triangles of a surface add up to that surface's grad_surfaces.  d_map is device memory,
+ * [ntriangles] rvb_surface, t the caller's triangle index as passed to rvb_set_scene (ntriangles must be the scene's).  There is no
+ * air derivative here: rvb_reshade_grad has it.
+ *   - every term is the binary32 value rvb_reshade_grad forms, by the same device code (one kernel body, two places for a term); the
+ *     call never divides by a coefficient;
+ *   - the sums per triangle are binary64, rounded to float once.  The records of a triangle are taken in ascending (ray, bounce) order —
+ *     a stable sort by triangle of (triangle, record number) —, cut by position in the sorted list: tiles of RVB_GRAD_MAP_TILE entries,
+ *     16 segments per tile; a segment's records one after the other, a run's segments one after the other, its tiles one after the
+ *     other.  No atomics, nothing depends on the order of dispatch: two calls return identical bytes, and the bytes do not depend on
+ *     the surface numbers;
+ *   - EVERY entry is written: exactly 0.0 in all 16 slots for a triangle that no live record of the pair touches, for one that lies
+ *     behind an escape only and for one the BVH builder dropped.
+ * SCOPE and errors mirror rvb_reshade_grad, each with a text that names the condition.  RVB_ERR_INVALID, before any device is touched,
+ * for a NULL ctx, d_weights or d_map, nbins == 0, a predelay or sample rate that is not finite, ntriangles other than the scene's, d_map
+ * overlapping d_weights.  RVB_ERR_STATE for nothing traced, a last trace made without RVB_KEEP_LISTENER, the scene or the directions
+ * changed since, no IR configuration, the HRTF model, which != RVB_IR_DIFFUSE, more than 8 channels.  RVB_ERR_CAPACITY above 2048
+ * reflections and for nrays * nreflections >= 2^32 in the pair (record numbers are 32-bit sort values).  A failed call writes nothing
+ * and leaves everything as it was.  Image-source and direct-sound terms, the HRTF model and more than 8 channels are out of scope; not
+ * offered by rvb_multi_* and rvb_pipeline_*, like the rest of the family.
+ * CALLING.  Asynchronous on the context's stream, like rvb_decay_curve.  Changes no byte of the records, of the direct slot, of the
+ * candidates or of the time range; the IR configuration stays.  It works after rvb_reshade and after rvb_relisten (the listener records
+ * do not depend on the microphone).  It uses the sort buffers, so like rvb_ir_accumulate it voids a prepared exact list
+ * (rvb_ir_exact_fold then returns RVB_ERR_STATE), and the accumulation image's scratch for the transposed weights, as the gradient does.
+ * Its own scratch is one term row of 64 bytes per record of the pair (and 256 bytes per tile of the fold): 819 MB at 100 k x 128.  It
+ * lives with the kept buffers, is allocated by the first call and freed by rvb_keep_paths(ctx, 0).  No table per triangle is kept per
+ * workgroup: nothing but d_map grows with the triangle count.  rvb_last_timings: "reshade_grad_weights_kernel",
+ * "reshade_grad_map_terms_kernel" (reshade_grad_kernel's sweep; a record's 16 terms go to its row, stored as whole 64-byte rows),
+ * "reshade_grad_map_sort" (the stable sort and the run boundaries), "reshade_grad_map_fold_kernel", "reshade_grad_map_combine_kernel".
+ * MEASURED on one MI355X at 100 k rays x 128, stereo speakers (profiles/reshade_grad_map_n1.txt, tools/reshade_grad_map_bench.py; medians of
+ * one run, calls by the host clock to the synchronisation): in the 75 252-triangle cathedral rvb_reshade_grad_map 2.56 ms —
+ *     reshade_grad_map_terms_kernel 1.75 ms, reshade_grad_map_sort 0.42 ms, reshade_grad_map_fold_kernel 0.30 ms, the weights 0.03 ms, the
+ *     combine 0.01 ms — where rvb_reshade_grad on the scene relabelled with one surface per triangle takes 60.5 s (1 176 sweeps, each on
+ *     the 64 workgroups whose tables fit its scratch); in the 3 006-triangle one 2.44 ms (sort 0.30 ms) against 832 ms (47 sweeps).  The
+ *     terms pass bounds the call, and arithmetic bounds the terms pass as it bounds rvb_reshade_grad (1.62 ms): its 128 bytes per
+ *     record are 0.94 TB/s against a floor of 0.25 ms at 6.6 TB/s.  The fold gathers its 72 bytes per record at 3.1 TB/s (floor
+ *     0.14 ms), the sort stands at 0.42 ms over a floor of 0.09 ms for three passes of 17 key bits.  rvb_trace with keeping on and
+ *     rvb_reshade_grad stand 0.06 - 0.07 ms and 0.015 ms from the parent commit's, inside the spread of its repetitions (0.09 - 0.10 ms,
+ *     0.04 - 0.05 ms); the device code of the trace is the parent's line for line. */
+#define RVB_GRAD_MAP_TILE 1024    /* sorted entries per workgroup tile of the fold; tests choose their edge shapes from it */
+int rvb_reshade_grad_map(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins, const void * d_weights,
+                         void * d_map /* device, [ntriangles] rvb_surface */, uint64_t ntriangles);
+
 /* ---- decay curves: Schroeder integral, reverberation times, the loss against a measured decay and its adjoint (csrc/decay_kernels.hip) ---
  * What a fit of materials to a measured decay needs between rvb_ir_accumulate, which leaves the histogram H on the device, and
  * rvb_reshade_grad, which takes w = dL/dH: the energy decay curve of every row, a loss L against a target decay, and w.  Nothing leaves

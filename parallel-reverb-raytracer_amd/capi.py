@@ -40,7 +40,7 @@ SYMBOLS = [
     "rvb_pipeline_create_lanes",
     "rvb_set_source_table",
     "rvb_set_source_pattern", "rvb_multi_set_source_pattern", "rvb_pipeline_set_source_pattern", "rvb_pipeline_submit_directed",
-    "rvb_keep_paths", "rvb_reshade", "rvb_reshade_grad", "rvb_relisten",
+    "rvb_keep_paths", "rvb_reshade", "rvb_reshade_grad", "rvb_reshade_grad_map", "rvb_relisten",
     "rvb_decay_curve", "rvb_decay_times", "rvb_decay_loss",
 ]
 
@@ -48,6 +48,7 @@ PIPELINE_MAX_PAIRS = 8      # RVB_PIPELINE_MAX_PAIRS
 MAX_SPEAKERS = 64           # RVB_MAX_SPEAKERS
 DECAY_TILE = 4096           # RVB_DECAY_TILE
 DECAY_NORMALISED = 1        # RVB_DECAY_NORMALISED
+GRAD_MAP_TILE = 1024        # RVB_GRAD_MAP_TILE
 KEEP_MATERIALS, KEEP_LISTENER = 1, 2     # RVB_KEEP_MATERIALS, RVB_KEEP_LISTENER
 
 _vp = ctypes.c_void_p
@@ -95,6 +96,8 @@ def load_library():
         lib.rvb_pipeline_pending.argtypes = [_vp]
         lib.rvb_reshade_grad.restype = ctypes.c_int
         lib.rvb_reshade_grad.argtypes = [_vp, ctypes.c_float, ctypes.c_float, _u64, _vp, _vp, _vp]
+        lib.rvb_reshade_grad_map.restype = ctypes.c_int
+        lib.rvb_reshade_grad_map.argtypes = [_vp, ctypes.c_float, ctypes.c_float, _u64, _vp, _vp, _u64]
         lib.rvb_decay_curve.restype = ctypes.c_int
         lib.rvb_decay_curve.argtypes = [_vp, _vp, _u64, _u64, _vp]
         lib.rvb_decay_times.restype = ctypes.c_int
@@ -206,6 +209,7 @@ class Context:
         self.nreflections = 0
         self.nchannels = 0
         self.nsurfaces = 0
+        self.ntriangles = 0
         self._keep = []
 
     def close(self):
@@ -230,11 +234,13 @@ class Context:
         self._check(self.lib.rvb_set_scene(self.handle, _ptr(triangles), _u64(triangles.shape[0]), _ptr(vertices),
                                            _u64(vertices.shape[0]), _ptr(surfaces), _u64(surfaces.shape[0])))
         self.nsurfaces = int(surfaces.shape[0])
+        self.ntriangles = int(triangles.shape[0])
 
     def share_scene(self, other):
         """This context reads the scene `other` holds: the same device buffers, no second build or copy (rvb_share_scene)."""
         self._check(self.lib.rvb_share_scene(self.handle, other.handle))
         self.nsurfaces = other.nsurfaces
+        self.ntriangles = other.ntriangles
 
     def scene_info(self):
         nodes, kept, depth = _u64(0), _u64(0), ctypes.c_uint32(0)
@@ -327,6 +333,22 @@ class Context:
         self._check(self.lib.rvb_reshade_grad(self.handle, ctypes.c_float(predelay), ctypes.c_float(sample_rate), _u64(nbins),
                                               _vp(device_weights_pointer), _ptr(grads), _ptr(grad_air)))
         return grads, grad_air
+
+    def reshade_grad_map(self, predelay, sample_rate, nbins, device_weights_pointer, out=None):
+        """The gradient of reshade_grad per TRIANGLE (rvb_reshade_grad_map): a float32 CUDA tensor [ntriangles][16], row t the derivatives of
+        L with respect to a private copy of the coefficients of triangle t's surface — specular 0..7, then diffuse 8..15 —, t the index of
+        the triangle in the scene given to set_scene.  Needs a trace kept with keep_paths(True, listener=True).  The tensor is a new one
+        unless `out` is given; every entry is written.  The context's stream waits for torch's current stream first, and the call returns
+        when the map is complete."""
+        import torch
+        if out is None:
+            out = torch.empty((self.ntriangles, 16), dtype=torch.float32, device="cuda")
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (self.ntriangles, 16)
+        self.ir_accumulate_wait_for_torch()
+        self._check(self.lib.rvb_reshade_grad_map(self.handle, ctypes.c_float(predelay), ctypes.c_float(sample_rate), _u64(nbins),
+                                                  _vp(device_weights_pointer), _vp(out.data_ptr()), _u64(self.ntriangles)))
+        self.synchronize()
+        return out
 
     def trace(self, mic, source, nreflections, air, ray_offset=0):
         self._check(self.lib.rvb_trace(self.handle, _f3(mic), _f3(source), _u64(nreflections), _f8(air), _u64(ray_offset)))

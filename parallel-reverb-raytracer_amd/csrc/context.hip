@@ -162,6 +162,7 @@ int rvb_set_scene(rvb_ctx * ctx, const rvb_triangle * triangles, uint64_t ntrian
     ctx->depth = built.depth;
     ctx->stack_need = built.stack_need;
     ctx->nsurfaces = nsurfaces;
+    ctx->ntriangles = ntriangles;
     ctx->have_scene = true;
     return RVB_OK;
 }
@@ -181,6 +182,7 @@ int rvb_share_scene(rvb_ctx * ctx, rvb_ctx * from)
     ctx->depth = from->depth;
     ctx->stack_need = from->stack_need;
     ctx->nsurfaces = from->nsurfaces;
+    ctx->ntriangles = from->ntriangles;
     ctx->have_scene = true;
     ctx->traced = false;
     return RVB_OK;

@@ -1,13 +1,13 @@
 // ctx.h — the context behind include/rvb_capi.h and what its translation units share:
 //   context.hip  life cycle, scene, directions, timings, diagnostics
 //   trace.hip    the trace in three steps, source patterns, its results, rvb_merge_images
-//   kept.hip     behind a kept trace: re-shading, its material gradients, a new microphone
+//   kept.hip     behind a kept trace: re-shading, its material gradients per surface and per triangle, a new microphone
 //   memory.hip   caller-owned device / pinned memory, staged host copies, the export stream
 //   sort.hip     the sorts the other stages call, "sorted list and bin boundaries"
 //   ir.hip       materialised attenuate / flatten, the fused impulse-response stage
 //   decay.hip    decay curves, reverberation times and the decay loss on the caller's device arrays
 // No compute happens in them and nothing falls back to the CPU: every entry point that produces results launches the HIP kernels
-// of trace_kernels.hip / image_kernels.hip / shadow_kernels.hip / reshade_kernels.hip / reshade_grad_kernels.hip / relisten_kernels.hip (the three over kept_tiles.h) / attenuate_kernels.hip / histogram_kernels.hip / exact_kernels.hip / decay_kernels.hip (and the sorts of rocprim_sort.hip / radix_sort.hip).
+// of trace_kernels.hip / image_kernels.hip / shadow_kernels.hip / reshade_kernels.hip / reshade_grad_kernels.hip / relisten_kernels.hip (the three over kept_tiles.h) / reshade_grad_map_kernels.hip / attenuate_kernels.hip / histogram_kernels.hip / exact_kernels.hip / decay_kernels.hip (and the sorts of rocprim_sort.hip / radix_sort.hip).
 #pragma once
 
 #include "../../include/rvb_capi.h"
@@ -75,12 +75,13 @@ struct KeptTrace {
     TraceArgs args = {};
     // everything on the device that keeping owns.  `surfaces` is the table of the last rvb_reshade: the scene (which may be shared)
     // keeps its own; uploaded in stream order through surfaces_stage, as the source patterns are.  `grad_scratch`: the result and the
-    // partial tables of rvb_reshade_grad (csrc/reshade_grad_kernels.hip).
+    // partial tables of rvb_reshade_grad (csrc/reshade_grad_kernels.hip).  `map_scratch`: the term rows of rvb_reshade_grad_map, 64 bytes per
+    // record of a pair, and behind them the fold's partials (csrc/reshade_grad_map_kernels.hip); allocated by its first call.
     struct Buffers {
-        DevBuf paths, image_dist, listen, surfaces, grad_scratch;
-        bool any() const { return paths.p || image_dist.p || listen.p || surfaces.p || grad_scratch.p; }
+        DevBuf paths, image_dist, listen, surfaces, grad_scratch, map_scratch;
+        bool any() const { return paths.p || image_dist.p || listen.p || surfaces.p || grad_scratch.p || map_scratch.p; }
     } dev;
-    static_assert(sizeof(Buffers) == 5 * sizeof(DevBuf), "any() names every buffer");
+    static_assert(sizeof(Buffers) == 6 * sizeof(DevBuf), "any() names every buffer");
     StagedBlock surfaces_stage;
     // what the records reflect right now — the kept trace's table, air and source directivity (pattern, table or nothing), or those of
     // the last rvb_reshade —: where rvb_reshade_grad takes its derivatives and what rvb_relisten shades with
@@ -137,6 +138,7 @@ struct rvb_ctx {
     uint32_t depth = 0;
     uint32_t stack_need = RVB_BVH_STACK;
     uint64_t nsurfaces = 0;
+    uint64_t ntriangles = 0;                     // as passed to rvb_set_scene: the index space of a record's triangle
 
     // rays + trace results
     DevBuf directions_own;

@@ -1,5 +1,6 @@
-// kept.hip — behind a kept trace (rvb_keep_paths, KeptTrace in ctx.h): re-shading (rvb_reshade), its material gradients
-// (rvb_reshade_grad) and a new microphone (rvb_relisten), which replays the trace's tail with the steps trace.hip shares.
+// kept.hip — behind a kept trace (rvb_keep_paths, KeptTrace in ctx.h): re-shading (rvb_reshade), its material gradients per surface
+// (rvb_reshade_grad) and per triangle (rvb_reshade_grad_map), and a new microphone (rvb_relisten), which replays the trace's tail with
+// the steps trace.hip shares.
 #include "ctx.h"
 
 #include <cstdlib>
@@ -12,6 +13,28 @@ static TraceArgs for_record_pass(const rvb_ctx * ctx, TraceArgs a)
     a.scene.stamps = nullptr;
     a.lds_surfaces = rvb_reshade_lds_surfaces(ctx->nsurfaces);
     return a;
+}
+
+// what a gradient pass takes beside `a`: the selected pair's rays and microphone, the binning, the weights where the accumulation image
+// goes (rvb_launch_reshade_grad_weights puts them there), and the source directivity that the records reflect now
+static ReshadeGradArgs grad_args(const rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins)
+{
+    const KeptTrace & kept = ctx->kept;
+    ReshadeGradArgs g;
+    g.weights = ctx->acc.as<float>();
+    g.nbins = nbins;
+    g.predelay = predelay;
+    g.sample_rate = sample_rate;
+    g.first_ray = ctx->ir_pair * ctx->nrays;
+    g.nrays = (uint32_t) ctx->nrays;
+    for (int i = 0; i < 3; ++i) g.mic[i] = ctx->pair_mics_host[3 * ctx->ir_pair + i];
+    const std::vector<SourcePatternDev> & shaded_patterns = kept.shaded_source.patterns;
+    g.has_pattern = !shaded_patterns.empty();
+    g.pattern = g.has_pattern ? shaded_patterns[shaded_patterns.size() > 1 ? ctx->ir_pair : 0] : SourcePatternDev{};
+    // a table shaded the records: the pair's rows of the gains that launch left (source_table_rays_kernel)
+    g.ray_gains = kept.shaded_source.table_orientations ? ctx->source_table.gains.as<const float>() + ctx->ir_pair * ctx->nrays * 8 : nullptr;
+    g.nsurfaces = ctx->nsurfaces;
+    return g;
 }
 
 extern "C" {
@@ -153,20 +176,7 @@ int rvb_reshade_grad(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t 
     RVB_HIP(fail, ctx, kept.dev.grad_scratch.ensure(out_bytes + (size_t) blocks * entries * sizeof(double)));
     float * d_out = kept.dev.grad_scratch.as<float>();
     double * partials = reinterpret_cast<double *>(kept.dev.grad_scratch.as<char>() + out_bytes);
-    ReshadeGradArgs g;
-    g.weights = ctx->acc.as<float>();
-    g.nbins = nbins;
-    g.predelay = predelay;
-    g.sample_rate = sample_rate;
-    g.first_ray = ctx->ir_pair * ctx->nrays;
-    g.nrays = (uint32_t) ctx->nrays;
-    for (int i = 0; i < 3; ++i) g.mic[i] = ctx->pair_mics_host[3 * ctx->ir_pair + i];
-    const std::vector<SourcePatternDev> & shaded_patterns = kept.shaded_source.patterns;
-    g.has_pattern = !shaded_patterns.empty();
-    g.pattern = g.has_pattern ? shaded_patterns[shaded_patterns.size() > 1 ? ctx->ir_pair : 0] : SourcePatternDev{};
-    // a table shaded the records: the pair's rows of the gains that launch left (source_table_rays_kernel)
-    g.ray_gains = kept.shaded_source.table_orientations ? ctx->source_table.gains.as<const float>() + ctx->ir_pair * ctx->nrays * 8 : nullptr;
-    g.nsurfaces = ctx->nsurfaces;
+    const ReshadeGradArgs g = grad_args(ctx, predelay, sample_rate, nbins);
     ctx->reset_timings();
     ctx->begin_timing("reshade_grad_weights_kernel");
     rvb_launch_reshade_grad_weights(reinterpret_cast<const float *>(d_weights), ctx->acc.as<float>(), nchannels, nbins, ctx->stream);
@@ -184,6 +194,78 @@ int rvb_reshade_grad(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t 
     if (rc != RVB_OK) return rc;
     std::memcpy(grad_surfaces, host.data(), (size_t) ctx->nsurfaces * sizeof(rvb_surface));
     if (grad_air) std::memcpy(grad_air, host.data() + ctx->nsurfaces * 16, 8 * sizeof(float));
+    return RVB_OK;
+}
+
+int rvb_reshade_grad_map(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins, const void * d_weights, void * d_map, uint64_t ntriangles)
+{
+    if (!ctx) return RVB_ERR_INVALID;
+    if (!d_weights || !d_map) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_map: null weights or null map");
+    if (nbins == 0 || nbins >= (1ull << 32)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_map: no bins (or more than 32-bit bin numbers reach)");
+    if (!std::isfinite(predelay) || !std::isfinite(sample_rate)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_map: predelay or sample rate is not finite");
+    // (without a scene there is no count to hold against: nothing is traced then, the next refusal)
+    if (ctx->have_scene && ntriangles != ctx->ntriangles)
+        return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_map: a map of " + std::to_string(ntriangles) + " triangles for a scene of " + std::to_string(ctx->ntriangles));
+    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: nothing traced (or the scene or the directions have changed since)");
+    if (!ctx->kept.valid || !ctx->kept.listener_valid)
+        return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: the last trace was made without rvb_keep_paths(ctx, RVB_KEEP_MATERIALS | RVB_KEEP_LISTENER): "
+                                        "a record's triangle is in its listener record");
+    if (!ctx->ir_configured) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: no IR configuration (rvb_ir_configure_speakers after the trace or re-shade)");
+    if (ctx->model.hrtf) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: the HRTF model is configured; this version takes the speaker model only");
+    if (ctx->which != RVB_IR_DIFFUSE)
+        return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: configured with image sources; this version takes which == RVB_IR_DIFFUSE only");
+    const uint32_t nchannels = ctx->model.nchannels;
+    if (nchannels > 8) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: " + std::to_string(nchannels) + " speaker channels configured; this version takes 1 to 8");
+    {
+        const uintptr_t m0 = (uintptr_t) d_map, m1 = m0 + ntriangles * sizeof(rvb_surface);
+        const uintptr_t w0 = (uintptr_t) d_weights, w1 = w0 + (uintptr_t) nbins * nchannels * 8 * sizeof(float);
+        if (m0 < w1 && w0 < m1) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_map: the map overlaps the weights");
+    }
+    if (ctx->nreflections > RVB_RESHADE_GRAD_MAX_REFLECTIONS)
+        return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad_map: more than " RVB_STR(RVB_RESHADE_GRAD_MAX_REFLECTIONS) " reflections");
+    const uint64_t n = ctx->nrays * ctx->nreflections;              // records of the pair
+    if (n >= (1ull << 32))
+        return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad_map: nrays * nreflections reaches 2^32 (record numbers are 32-bit sort values)");
+    if (ntriangles >= (1ull << 27)) return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad_map: too many triangles (2^27 or more)");
+    RVB_BIND(ctx);
+    KeptTrace & kept = ctx->kept;
+    if (n == 0) {                                                   // no record: every entry is still written
+        RVB_HIP(fail, ctx, hipMemsetAsync(d_map, 0, ntriangles * sizeof(rvb_surface), ctx->stream));
+        return RVB_OK;
+    }
+    const TraceArgs a = for_record_pass(ctx, kept.shaded_args());
+    // the term rows, then the fold's partials; the (key, value) list in the sort buffers, which voids a prepared exact list and the keys
+    // that a size query of rvb_flatten left
+    const size_t term_bytes = (size_t) n * 16 * sizeof(float);
+    RVB_HIP(fail, ctx, ctx->acc.ensure((size_t) nbins * nchannels * 8 * sizeof(float)));
+    RVB_HIP(fail, ctx, kept.dev.map_scratch.ensure(term_bytes + (size_t) rvb_grad_map_tiles(n) * 2 * 16 * sizeof(double)));
+    int rc = ensure_sort_buffers(ctx, n);
+    if (rc != RVB_OK) return rc;
+    ctx->flat_host = nullptr;
+    float * terms = kept.dev.map_scratch.as<float>();
+    double * partials = reinterpret_cast<double *>(kept.dev.map_scratch.as<char>() + term_bytes);
+    const ReshadeGradArgs g = grad_args(ctx, predelay, sample_rate, nbins);
+    ctx->reset_timings();
+    ctx->begin_timing("reshade_grad_weights_kernel");
+    rvb_launch_reshade_grad_weights(reinterpret_cast<const float *>(d_weights), ctx->acc.as<float>(), nchannels, nbins, ctx->stream);
+    ctx->end_timing();
+    ctx->begin_timing("reshade_grad_map_terms_kernel");
+    rvb_launch_reshade_grad_map_terms(a, kept.dev.paths.as<const float4>(), kept.dev.listen.as<const uint2>(), ctx->model, g, (uint32_t) ntriangles, terms,
+                                      ctx->keys_a.as<uint32_t>(), ctx->vals_a.as<uint32_t>(), ctx->stream);
+    ctx->end_timing();
+    ctx->begin_timing("reshade_grad_map_sort");
+    rc = sort_and_bin(ctx, n, ntriangles + 1, key_bits_for(ntriangles), true);     // (values are the entry numbers: either sort)
+    ctx->end_timing();
+    if (rc != RVB_OK) return rc;
+    const uint32_t * starts = ctx->bin_starts.as<uint32_t>();
+    ctx->begin_timing("reshade_grad_map_fold_kernel");
+    rvb_launch_reshade_grad_map_fold(ctx->keys_b.as<uint32_t>(), ctx->vals_b.as<uint32_t>(), n, (uint32_t) ntriangles, terms, partials,
+                                     reinterpret_cast<float *>(d_map), ctx->stream);
+    ctx->end_timing();
+    ctx->begin_timing("reshade_grad_map_combine_kernel");
+    rvb_launch_reshade_grad_map_combine(starts, starts + ntriangles + 1, (uint32_t) ntriangles, partials, reinterpret_cast<float *>(d_map), ctx->stream);
+    ctx->end_timing();
+    RVB_HIP(fail, ctx, hipGetLastError());
     return RVB_OK;
 }
 

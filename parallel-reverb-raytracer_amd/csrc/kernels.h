@@ -145,6 +145,19 @@ void rvb_launch_reshade_grad_weights(const float * weights, float * transposed, 
 void rvb_launch_reshade_grad(const TraceArgs & a, const float4 * kept, const AttenuationModel & model, const ReshadeGradArgs & g,
                              double * partials, uint32_t blocks, hipStream_t s);
 void rvb_launch_reshade_grad_reduce(const double * partials, uint32_t blocks, uint64_t nsurfaces, float * out, hipStream_t s);
+// The same gradient per TRIANGLE (rvb_reshade_grad_map of include/rvb_capi.h).  The terms pass (reshade_grad_kernels.hip: reshade_grad_kernel
+// with another place for a term) leaves, by the record's number i within the pair, terms[i][16] — specular 0..7, diffuse 8..15; no row
+// for a slot without a record —, keys[i] = the record's triangle from `listen` (ntriangles for such a slot) and values[i] = i.  After a
+// stable sort by key the fold (reshade_grad_map_kernels.hip) adds the rows of every run in binary64 in entry order: tiles of
+// RVB_GRAD_MAP_TILE entries, `partials` [rvb_grad_map_tiles(n)][2][16] doubles for the runs that cross a tile edge, which the combine
+// adds in tile order; it also writes the zeros of a triangle without a run (starts / ends: rvb_launch_bin_starts).  Together they write
+// every entry of map[ntriangles][16] exactly once.
+inline uint64_t rvb_grad_map_tiles(uint64_t n) { return (n + RVB_GRAD_MAP_TILE - 1) / RVB_GRAD_MAP_TILE; }
+void rvb_launch_reshade_grad_map_terms(const TraceArgs & a, const float4 * kept, const uint2 * listen, const AttenuationModel & model, const ReshadeGradArgs & g,
+                                       uint32_t ntriangles, float * terms, uint32_t * keys, uint32_t * values, hipStream_t s);
+void rvb_launch_reshade_grad_map_fold(const uint32_t * sorted_keys, const uint32_t * sorted_values, uint64_t n, uint32_t ntriangles, const float * terms,
+                                      double * partials, float * map, hipStream_t s);
+void rvb_launch_reshade_grad_map_combine(const uint32_t * starts, const uint32_t * ends, uint32_t ntriangles, const double * partials, float * map, hipStream_t s);
 // Decay curves (decay_kernels.hip; rvb_decay_curve / rvb_decay_times / rvb_decay_loss of include/rvb_capi.h) on nrows rows of nbins floats.
 // Every phase is a launch of its own — a value per tile of RVB_DECAY_TILE bins, one wave per row over the row's tiles, the tile again on
 // top of its carry —; `tiles` is [nrows][rvb_decay_tiles(nbins)] doubles (three such planes for the loss: m d^2, 2 m d, g), `first`

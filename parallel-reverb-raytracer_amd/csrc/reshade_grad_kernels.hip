@@ -20,6 +20,11 @@
 //                                 of them, which alone updates the wave's table in LDS — no atomics, one fixed order.
 //   reshade_grad_reduce_kernel    the workgroups' tables added in a fixed order, rounded to binary32 once.
 // A table in LDS holds GRAD_WINDOW surfaces; a scene with more is swept once per window of surfaces.
+//   reshade_grad_kernel<.., true> the TERMS PASS of rvb_reshade_grad_map (reshade_grad_map_kernels.hip holds the fold behind it): the same
+//                                 body, but a term goes to its record's row of 16 floats instead of into the table — the eight diffuse
+//                                 terms P_k a_k behind the eight specular ones -P_{k-1} B_k —, staged per tile in LDS where the table
+//                                 stands otherwise and stored as whole 64-byte rows, a ray's run of a tile in one piece; beside it the
+//                                 record's sort key (its triangle, ntriangles for a slot without a record) and its number.
 #include "kept_tiles.h"
 #include "attenuation.h"
 
@@ -43,15 +48,24 @@ struct GradDev {
     uint32_t surface0, window;       // this sweep's surfaces [surface0, surface0 + window)
     uint32_t entries;                // binary64 sums per partial table: nsurfaces * 16 + 8
     double * partials;
+    // the terms pass (MAP): rows, keys and values by the record's number within the pair; listen by its number within the kept launch
+    float4 * terms;
+    uint32_t * keys, * values;
+    const uint2 * listen;
+    uint32_t ntriangles;
 };
 
 // LDS of a wave, in words: the table (window * 16 + 8 doubles), a GradRows region of staged records twice (float4 each), [TILE][WAVE] floats twice
 // (a_k * diffuse and P_{k-1} of the forward sweep, for the backward one), [ntiles][WAVE] chain checkpoints, the surface table (stage_surfaces)
-__host__ __device__ __forceinline__ uint32_t grad_table_words(uint32_t window) { return (window * 16u + 8u) * 2u; }
+// (the terms pass: in the table's place the tile's term rows, [RAYS][TILE] rows of 16 floats, a ray's rows padded by 8 words so that the
+// 64 lanes of a sweep's store fall into 64 banks)
+#define GRAD_TERM_RAY_WORDS (GRAD_TILE * 16u + 8u)
+#define GRAD_TERM_WORDS (GradRows::RAYS * GRAD_TERM_RAY_WORDS)
+__host__ __device__ __forceinline__ uint32_t grad_table_words(uint32_t window, bool map = false) { return map ? GRAD_TERM_WORDS : (window * 16u + 8u) * 2u; }
 #define GRAD_STAGE_WORDS (GradRows::RECORDS * 4u)
-__host__ __device__ __forceinline__ uint32_t grad_surfaces_at(uint32_t window, uint32_t ntiles)
+__host__ __device__ __forceinline__ uint32_t grad_surfaces_at(uint32_t window, uint32_t ntiles, bool map = false)
 {
-    return grad_table_words(window) + 2u * GRAD_STAGE_WORDS + 2u * GRAD_TILE * WAVE + ntiles * WAVE;
+    return grad_table_words(window, map) + 2u * GRAD_STAGE_WORDS + 2u * GRAD_TILE * WAVE + ntiles * WAVE;
 }
 
 // `v` of this lane's (ray, band) added to column `column` of its surface's row: the rays of the wave that hit the same surface are summed
@@ -76,24 +90,39 @@ __device__ __forceinline__ void add_by_surface(double * table, const GradDev & d
         table[local * 16u + column] += sum;
 }
 
-template <bool SURF_LDS>
+// Where a term goes: column `column` of surface `surface`'s row of the table (add_by_surface), or, MAP, of the row of record (r, k) of
+// the tile staged in LDS.  Called by the whole wave.
+template <bool MAP>
+__device__ __forceinline__ void put_term(double * table, float * rows, const GradDev & d, const uint32_t lane, const uint32_t k, const uint32_t surface,
+                                         const uint32_t column, const float v)
+{
+    if (MAP) {
+        if (surface != NONE) rows[(lane >> 3) * GRAD_TERM_RAY_WORDS + k * 16u + column] = v;
+    } else {
+        add_by_surface(table, d, lane, surface, column, v);
+    }
+}
+
+template <bool SURF_LDS, bool MAP>
 __global__ __launch_bounds__(WAVE) void reshade_grad_kernel(TraceArgs a, GradDev d, const float4 * __restrict__ kept)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     double * table = reinterpret_cast<double *>(lds);
-    uint32_t * side_words = lds + grad_table_words(d.window);
+    float * rows = reinterpret_cast<float *>(lds);                           // MAP: the tile's term rows instead
+    uint32_t * side_words = lds + grad_table_words(d.window, MAP);
     float4 * side = reinterpret_cast<float4 *>(side_words);                  // staged records (GRAD_BIN_WORD)
     float4 * toward = side + GradRows::RECORDS;                              // the record's arrival direction at the microphone
     float * us = reinterpret_cast<float *>(toward + GradRows::RECORDS);      // a_k * diffuse[s_k][b]
     float * prevs = us + GRAD_TILE * WAVE;                                   // P_{k-1}
     float * starts = prevs + GRAD_TILE * WAVE;                               // P at the start of every tile
-    const lds_float4_ptr surf_lds = stage_surfaces(a, lds + grad_surfaces_at(d.window, d.ntiles));
+    const lds_float4_ptr surf_lds = stage_surfaces(a, lds + grad_surfaces_at(d.window, d.ntiles, MAP));
     const ReshadeGradArgs & g = d.g;
     const uint32_t lane = threadIdx.x, h = lane & 1u, r = lane >> 3, band = lane & 7u;
     const uint32_t nch = d.m.nchannels, cb = nch * 8u;
     const float air = a.air[band];
     const v3 mic = mk3(g.mic[0], g.mic[1], g.mic[2]);
-    for (uint32_t i = lane; i < d.window * 16u + 8u; i += WAVE) table[i] = 0.0;
+    if (!MAP)
+        for (uint32_t i = lane; i < d.window * 16u + 8u; i += WAVE) table[i] = 0.0;
     double air_sum = 0.0;
     for (uint32_t grp = blockIdx.x; grp < d.ngroups; grp += gridDim.x) {
         const uint32_t ray0 = grp * GradRows::RAYS;                             // within the pair
@@ -157,6 +186,16 @@ __global__ __launch_bounds__(WAVE) void reshade_grad_kernel(TraceArgs a, GradDev
                 staged.w = __uint_as_float(adds ? bin : NONE);
                 if (h == 0) side[GradRows::at(rr, k)] = staged;
                 else toward[GradRows::at(rr, k)] = make_float4(dir.x, dir.y, dir.z, 0.0f);
+                if (MAP && inside) {                                         // the record's sort entry: lane 0 the key, lane 1 the value
+                    const uint64_t own = record - g.first_ray * a.nreflections;      // the record's number within the pair
+                    if (h == 0) {
+                        uint32_t key = d.ntriangles;
+                        if (SideRecord::surface(sd) != NONE) key = min(ListenRecord::load(d.listen, record).triangle(), d.ntriangles);
+                        d.keys[own] = key;
+                    } else {
+                        d.values[own] = (uint32_t) own;
+                    }
+                }
             }
             __syncthreads();
             // (2) the weight gather, sum_c w[c][b][bin_k] * gain_c(k) of this lane's band for the tile's records: channel by channel with
@@ -193,10 +232,10 @@ __global__ __launch_bounds__(WAVE) void reshade_grad_kernel(TraceArgs a, GradDev
                     if (bin != NONE) ak = ((air_attenuation(dist, air) * diff) * pattern_gain) * us[k * WAVE + lane];
                 }
                 const float u = ak * dc;
-                air_sum += (double) ((vol * u) * dist);
+                if (!MAP) air_sum += (double) ((vol * u) * dist);
                 us[k * WAVE + lane] = u;
                 prevs[k * WAVE + lane] = prev;
-                add_by_surface(table, d, lane, surface, 8u + band, vol * ak);
+                put_term<MAP>(table, rows, d, lane, k, surface, 8u + band, vol * ak);
             }
             // (4) backward
             for (uint32_t k = GRAD_TILE; k-- > 0;) {
@@ -209,10 +248,22 @@ __global__ __launch_bounds__(WAVE) void reshade_grad_kernel(TraceArgs a, GradDev
                 } else {
                     carry = 0.0f;
                 }
-                add_by_surface(table, d, lane, surface, band, gs);
+                put_term<MAP>(table, rows, d, lane, k, surface, band, gs);
+            }
+            if (MAP) {
+                // the tile's rows out: ray rr's run of the tile is contiguous in memory, four lanes per 64-byte row; no row for a slot
+                // without a record (nothing reads it)
+                __syncthreads();
+                const uint32_t k = lane >> 2, q = lane & 3u;
+                for (uint32_t rr = 0; rr < GradRows::RAYS; ++rr) {
+                    if (ray0 + rr >= g.nrays || first + k >= a.nreflections || side_words[GradRows::surface_word(rr, k)] == NONE) continue;
+                    const float4 v = *reinterpret_cast<const float4 *>(rows + rr * GRAD_TERM_RAY_WORDS + k * 16u + q * 4u);
+                    store_stream(d.terms + ((uint64_t) (ray0 + rr) * a.nreflections + first + k) * 4u + q, v);
+                }
             }
         }
     }
+    if (MAP) return;
     // the air derivative of a band: the wave's rays in ray order
     double air_total = 0.0;
 #pragma unroll
@@ -291,8 +342,27 @@ void rvb_launch_reshade_grad(const TraceArgs & a, const float4 * kept, const Att
         d.surface0 = (uint32_t) s0;
         d.window = (uint32_t) std::min<uint64_t>(GRAD_WINDOW, g.nsurfaces - std::min(s0, g.nsurfaces));
         const size_t lds = ((size_t) grad_surfaces_at(d.window, d.ntiles) + 16u * a.lds_surfaces) * sizeof(uint32_t);
-        hipLaunchKernelGGL(a.lds_surfaces ? reshade_grad_kernel<true> : reshade_grad_kernel<false>, dim3(blocks), dim3(WAVE), lds, s, a, d, kept);
+        hipLaunchKernelGGL((a.lds_surfaces ? reshade_grad_kernel<true, false> : reshade_grad_kernel<false, false>), dim3(blocks), dim3(WAVE), lds, s, a, d, kept);
     }
+}
+
+void rvb_launch_reshade_grad_map_terms(const TraceArgs & a, const float4 * kept, const uint2 * listen, const AttenuationModel & model, const ReshadeGradArgs & g,
+                                       uint32_t ntriangles, float * terms, uint32_t * keys, uint32_t * values, hipStream_t s)
+{
+    GradDev d = {};
+    d.m = make_model(model);
+    d.g = g;
+    d.ngroups = (uint32_t) GradRows::groups(g.nrays);
+    d.ntiles = std::max((a.nreflections + GRAD_TILE - 1) / GRAD_TILE, 1u);
+    d.terms = reinterpret_cast<float4 *>(terms);
+    d.keys = keys;
+    d.values = values;
+    d.listen = listen;
+    d.ntriangles = ntriangles;
+    if (d.ngroups == 0) return;
+    const uint32_t blocks = std::min(d.ngroups, GRAD_MAX_BLOCKS);
+    const size_t lds = ((size_t) grad_surfaces_at(0u, d.ntiles, true) + 16u * a.lds_surfaces) * sizeof(uint32_t);
+    hipLaunchKernelGGL((a.lds_surfaces ? reshade_grad_kernel<true, true> : reshade_grad_kernel<false, true>), dim3(blocks), dim3(WAVE), lds, s, a, d, kept);
 }
 
 void rvb_launch_reshade_grad_reduce(const double * partials, uint32_t blocks, uint64_t nsurfaces, float * out, hipStream_t s)

@@ -8,6 +8,7 @@ One evaluation never leaves the device but for a few floats per row:
     decay_curve(H) -> E                          Schroeder integral
     decay_loss(H, E, target, mask) -> L, w       w = dL/dH in H's layout
     reshade_grad(w) -> dL/dtable, dL/dair        chain rule through the binning
+    (reshade_grad_map(w) -> dL/dtable per TRIANGLE: decay_sensitivity_map, "where on the walls"; needs keep_paths(True, listener=True))
 
 SCOPE: that of rvb_reshade_grad — a context that holds a trace made with keep_paths(True), the diffuse records only (IR_DIFFUSE), the
 speaker model with at most 8 channels; no image sources, no HRTF.  The target and the mask are float32 CUDA tensors [nchannels][8][nbins]
@@ -32,7 +33,8 @@ def _on_device(x, shape):
     return x
 
 
-def _evaluate(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, want_grad):
+def _forward(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, want_weights):
+    """The evaluation up to the loss: (loss, curve, weights), the tensors [nchannels][8][nbins]; weights = dL/dH, or None."""
     import torch
     ctx.reshade(table, air)
     ctx.ir_configure_speakers(mic, speakers[0], speakers[1], capi.IR_DIFFUSE, None)
@@ -41,15 +43,19 @@ def _evaluate(ctx, table, air, mic, speakers, target, mask, sample_rate, predela
     target, mask = _on_device(target, shape), _on_device(mask, shape)
     hist = torch.zeros(shape, dtype=torch.float32, device="cuda")
     curve = torch.empty_like(hist)
-    weights = torch.empty_like(hist) if want_grad else None
+    weights = torch.empty_like(hist) if want_weights else None
     ctx.ir_accumulate_tensor(predelay, sample_rate, nbins, capi.IR_EXACT, hist)      # (waits for torch's stream: the zero fill, the uploads)
     ctx.decay_curve(hist.data_ptr(), nrows, nbins, curve.data_ptr())
     loss_rows = ctx.decay_loss(hist.data_ptr(), curve.data_ptr(), target.data_ptr(), mask.data_ptr(), nrows, nbins,
-                               capi.DECAY_NORMALISED if normalised else 0, weights.data_ptr() if want_grad else None)
-    loss = float(loss_rows.sum())
+                               capi.DECAY_NORMALISED if normalised else 0, weights.data_ptr() if want_weights else None)
+    return float(loss_rows.sum()), curve, weights
+
+
+def _evaluate(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, want_grad):
+    loss, curve, weights = _forward(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, want_grad)
     if not want_grad:
         return loss, None, None, None
-    times = ctx.decay_times(curve.data_ptr(), nrows, nbins, sample_rate).reshape(ctx.nchannels, 8)
+    times = ctx.decay_times(curve.data_ptr(), ctx.nchannels * 8, nbins, sample_rate).reshape(ctx.nchannels, 8)
     grads, grad_air = ctx.reshade_grad(predelay, sample_rate, nbins, weights.data_ptr())
     return loss, grads, grad_air, times
 
@@ -65,6 +71,23 @@ def decay_loss_and_grad(ctx, table, air, mic, speakers, target, mask, sample_rat
 def decay_loss(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised=True):
     """The loss of decay_loss_and_grad alone (no weights, no gradient): what a line search evaluates."""
     return _evaluate(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, False)[0]
+
+
+def decay_sensitivity_map(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised=True):
+    """(loss, map): the loss of decay_loss_and_grad, bit for bit, and its gradient per TRIANGLE (rvb_reshade_grad_map) as a SURFACE array
+    [ntriangles] — where on the walls a change of the coefficients changes this decay at this microphone; entry t belongs to triangle t of
+    the scene given to set_scene.  Needs a trace kept with keep_paths(True, listener=True).  Leaves the context re-shaded with `table`."""
+    loss, _, weights = _forward(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, True)
+    per_triangle = ctx.reshade_grad_map(predelay, sample_rate, nbins, weights.data_ptr())
+    return loss, np.ascontiguousarray(per_triangle.cpu().numpy()).view(SURFACE).reshape(-1)
+
+
+def surface_sums(map, triangles, nsurfaces):
+    """The binary64 sums [nsurfaces][16] of a sensitivity map's entries over the triangles of every surface (`triangles`: the scene's
+    triangle array): up to rounding the gradient per surface, coefficients(grad_surfaces) of decay_loss_and_grad."""
+    out = np.zeros((int(nsurfaces), 16), np.float64)
+    np.add.at(out, np.asarray(triangles["surface"], np.int64), coefficients(np.ascontiguousarray(map)).astype(np.float64))
+    return out
 
 
 ARMIJO_C = 1e-4
