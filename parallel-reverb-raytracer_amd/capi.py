@@ -207,6 +207,7 @@ class Context:
             raise RvbError(rc, self.lib.rvb_last_error(None).decode())
         self.nrays = 0
         self.nreflections = 0
+        self.npairs = 1
         self.nchannels = 0
         self.nsurfaces = 0
         self.ntriangles = 0
@@ -384,7 +385,7 @@ class Context:
         self._check(self.lib.rvb_synchronize(self.handle))
 
     def get_raw_diffuse(self):
-        out = np.zeros(getattr(self, "npairs", 1) * self.nrays * self.nreflections, dtype=IMPULSE)
+        out = np.zeros(self.npairs * self.nrays * self.nreflections, dtype=IMPULSE)
         self._check(self.lib.rvb_get_diffuse(self.handle, _ptr(out)))
         return out
 

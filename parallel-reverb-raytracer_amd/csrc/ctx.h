@@ -1,18 +1,24 @@
 // ctx.h — the context behind include/rvb_capi.h and what its translation units share:
 //   context.hip  life cycle, scene, directions, timings, diagnostics
-//   trace.hip    the trace in three steps, source patterns, its results, rvb_merge_images
+//   trace.hip    the trace in three steps, the tail steps a kept trace replays, its results, rvb_merge_images
+//   source.hip   source directivity (SourceDirectivity below, over source_state.h / source_state.hip): setters, upload, launches
 //   kept.hip     behind a kept trace: re-shading, its material gradients per surface and per triangle, a new microphone
 //   memory.hip   caller-owned device / pinned memory, staged host copies, the export stream
 //   sort.hip     the sorts the other stages call, "sorted list and bin boundaries"
 //   ir.hip       materialised attenuate / flatten, the fused impulse-response stage
 //   decay.hip    decay curves, reverberation times and the decay loss on the caller's device arrays
-// No compute happens in them and nothing falls back to the CPU: every entry point that produces results launches the HIP kernels
-// of trace_kernels.hip / image_kernels.hip / shadow_kernels.hip / reshade_kernels.hip / reshade_grad_kernels.hip / relisten_kernels.hip (the three over kept_tiles.h) / reshade_grad_map_kernels.hip / attenuate_kernels.hip / histogram_kernels.hip / exact_kernels.hip / decay_kernels.hip (and the sorts of rocprim_sort.hip / radix_sort.hip).
+// No compute happens in them and nothing falls back to the CPU: every entry point that produces results launches HIP kernels:
+//   the trace         trace_kernels.hip, image_kernels.hip, shadow_kernels.hip, source_kernels.hip
+//   a kept trace      reshade_kernels.hip, reshade_grad_kernels.hip, relisten_kernels.hip (the three over kept_tiles.h),
+//                     reshade_grad_map_kernels.hip
+//   the IR stage      attenuate_kernels.hip, histogram_kernels.hip, exact_kernels.hip, decay_kernels.hip
+//   the sorts         rocprim_sort.hip, radix_sort.hip
 #pragma once
 
 #include "../../include/rvb_capi.h"
 #include "hip_owned.h"
 #include "kernels.h"
+#include "source_state.h"
 
 #include <cmath>
 #include <cstddef>
@@ -50,12 +56,113 @@ static_assert(offsetof(SmallBlock, trace_range) == 32 && offsetof(SmallBlock, im
 static_assert(offsetof(SmallBlock, direct) == 64 && sizeof(SmallBlock) == 128, "small block layout");
 const size_t kFirstCandidates = 32;
 
-// What shades the records at the source end — a source has one directivity at a time —: nothing, the patterns of rvb_set_source_pattern
-// in their device form, or the table of rvb_set_source_table with this many orientations.
-struct SourceShading {
-    std::vector<SourcePatternDev> patterns;
-    uint32_t table_orientations = 0;
-    bool off() const { return patterns.empty() && table_orientations == 0; }
+// Source directivity, the device half over SourceState (source_state.h): what the last upload put on the device — it stays there
+// whatever is set afterwards, until the next trace or re-shade uploads: a kept trace may reflect it —, and the staging blocks it went through.
+struct SourceDirectivity : SourceState {
+    DevBuf patterns_dev;                        // [npatterns] SourcePatternDev
+    StagedBlock patterns_stage;
+    DevBuf table_dev;                           // [RVB_HRTF_ROWS][8] floats (the zero row last), then the bases, in one block
+    DevBuf gains;                               // ray_gains of the last launch that applied the table (apply_source_patterns sizes it)
+    StagedBlock table_stage;
+    // source.hip: whatever has changed since the last upload, up in stream order
+    hipError_t upload(hipStream_t stream);
+    const SourcePatternDev * patterns_on_device() const { return patterns_dev.as<SourcePatternDev>(); }
+    // the table on the device as the launchers take it, for `orientations` (SourceShading::table_orientations) of them
+    SourceTableDev table_on_device(uint32_t orientations) const
+    {
+        SourceTableDev d;
+        d.table = table_dev.as<const float>();
+        d.bases = reinterpret_cast<const float4 *>(d.table + (size_t) RVB_HRTF_ROWS * 8);
+        d.basis_stride = orientations > 1 ? 3u : 0u;
+        d.ray_gains = gains.as<float>();
+        return d;
+    }
+    // the gain rows of pair `pair`'s rays, as source_table_rays_kernel left them
+    const float * gains_of_pair(uint64_t pair, uint64_t rays_per_pair) const { return gains.as<const float>() + pair * rays_per_pair * 8; }
+};
+
+// The pinned staging block of a launch of several pairs, 40 * npairs bytes: [npairs] float4 microphones (x y z 0), [npairs] float4
+// sources, then [npairs][2] initial time-range words, 0xFFFFFFFF / 0.  The layout is written here and nowhere else.
+struct PairBlock {
+    static size_t mic_bytes(uint64_t npairs) { return 4 * npairs * sizeof(float); }
+    static size_t geom_bytes(uint64_t npairs) { return 2 * mic_bytes(npairs); }          // microphones, then sources
+    static size_t range_bytes(uint64_t npairs) { return 2 * npairs * sizeof(uint32_t); }
+    static size_t bytes(uint64_t npairs) { return geom_bytes(npairs) + range_bytes(npairs); }
+    static const void * ranges(const void * block, uint64_t npairs) { return static_cast<const char *>(block) + geom_bytes(npairs); }
+    // mics, sources: [npairs][3]
+    static void fill_mics(void * block, const float * mics, uint64_t npairs)
+    {
+        float * geom = static_cast<float *>(block);
+        for (uint64_t p = 0; p < npairs; ++p)
+            for (int i = 0; i < 3; ++i) geom[4 * p + i] = mics[3 * p + i];
+    }
+    static void fill(void * block, const float * mics, const float * sources, uint64_t npairs)
+    {
+        std::memset(block, 0, geom_bytes(npairs));
+        fill_mics(block, mics, npairs);
+        fill_mics(static_cast<char *>(block) + mic_bytes(npairs), sources, npairs);
+        uint32_t * init = static_cast<uint32_t *>(const_cast<void *>(ranges(block, npairs)));
+        for (uint64_t p = 0; p < npairs; ++p) { init[2 * p] = 0xFFFFFFFFu; init[2 * p + 1] = 0u; }
+    }
+};
+
+// The per-pair arrays of a launch of several pairs (rvb_trace_pairs; a launch of one pair uses the small block and stages nothing):
+// geometry, direct path and time range per pair live in arrays of their own, staged through pinned memory and copied in stream
+// order — no host synchronisation in front of the launch; the block is written again only after the copies of the previous launch
+// have left it.  Beside them their host mirrors and, for any number of pairs, the microphones of the last launch.
+struct PairLaunch {
+    DevBuf geom, direct, range;                 // mics + sources [2 * npairs] float4, direct [npairs] rvb_impulse, ranges [npairs][2]
+    StagedBlock block;                          // PairBlock
+    std::vector<float> mics_host;               // [npairs][3]
+    std::vector<rvb_impulse> direct_host;       // fetched once per trace (fetch_small)
+    std::vector<uint32_t> range_host;
+
+    // A launch of npairs > 1 pairs: the block filled and copied up, and the four pointers of `a` that then point here.
+    hipError_t stage(const float * mics, const float * sources, uint64_t npairs, hipStream_t stream, TraceArgs & a)
+    {
+        if (npairs <= 1) return hipSuccess;
+        hipError_t e = block.acquire(PairBlock::bytes(npairs), stream);
+        if (e != hipSuccess) return e;
+        PairBlock::fill(block.block.p, mics, sources, npairs);
+        if ((e = geom.ensure(PairBlock::geom_bytes(npairs))) != hipSuccess) return e;
+        if ((e = direct.ensure(npairs * sizeof(rvb_impulse))) != hipSuccess) return e;
+        if ((e = range.ensure(PairBlock::range_bytes(npairs))) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(geom.p, block.block.p, PairBlock::geom_bytes(npairs), hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
+        if ((e = reset_ranges(npairs, stream)) != hipSuccess) return e;
+        a.pair_mics = geom.as<float4>();
+        a.pair_sources = geom.as<float4>() + npairs;
+        a.direct = direct.as<rvb_impulse>();
+        a.time_range = range.as<uint32_t>();
+        return hipSuccess;
+    }
+    // rvb_relisten on a kept launch of npairs > 1 pairs: new microphones through the block — stage() sized it for this many pairs, and
+    // its sources and initial ranges stay —, copied in stream order (a kernel of the previous call may still read `geom`), and the
+    // direct slots back at zero.  reset_ranges, which follows, records the event.
+    hipError_t restage_mics(const float * mics, uint64_t npairs, hipStream_t stream)
+    {
+        hipError_t e = block.acquire(PairBlock::mic_bytes(npairs), stream);
+        if (e != hipSuccess) return e;
+        PairBlock::fill_mics(block.block.p, mics, npairs);
+        if ((e = hipMemcpyAsync(geom.p, block.block.p, PairBlock::mic_bytes(npairs), hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
+        return hipMemsetAsync(direct.p, 0, npairs * sizeof(rvb_impulse), stream);
+    }
+    // the time ranges back at "nothing seen", from the initial ranges that are still in the block: its next writer waits for the event recorded here
+    hipError_t reset_ranges(uint64_t npairs, hipStream_t stream)
+    {
+        hipError_t e = hipMemcpyAsync(range.p, PairBlock::ranges(block.block.p, npairs), PairBlock::range_bytes(npairs), hipMemcpyHostToDevice, stream);
+        return e == hipSuccess ? block.record(stream) : e;
+    }
+    // direct paths and time ranges into their host mirrors; the caller synchronises
+    hipError_t fetch(uint64_t npairs, hipStream_t stream)
+    {
+        direct_host.resize(npairs);
+        range_host.resize(2 * npairs);
+        hipError_t e = hipMemcpyAsync(direct_host.data(), direct.p, npairs * sizeof(rvb_impulse), hipMemcpyDeviceToHost, stream);
+        return e == hipSuccess ? hipMemcpyAsync(range_host.data(), range.p, PairBlock::range_bytes(npairs), hipMemcpyDeviceToHost, stream) : e;
+    }
+    const rvb_impulse & direct_of(uint64_t pair) const { return direct_host[pair]; }
+    const uint32_t * range_of(uint64_t pair) const { return range_host.data() + 2 * pair; }
+    const float * mic_of(uint64_t pair) const { return mics_host.data() + 3 * pair; }
 };
 
 struct Timing { std::string name; hipEvent_t start, stop; };       // (events of the context's pool)
@@ -153,37 +260,9 @@ struct rvb_ctx {
     float mic[3] = {0, 0, 0};
     // last trace: npairs (source, microphone) pairs x nrays rays each; the IR stage works on one pair's slice at a time
     uint64_t npairs = 1, traced_rays = 0, ir_pair = 0;
-    std::vector<float> pair_mics_host;          // [npairs][3]
-    DevBuf pair_geom, pair_direct, pair_range;   // device: mics+sources [2*npairs] float4, direct [npairs] Impulse, ranges [npairs][2]
-    StagedBlock pair_stage;                      // staging of the per-pair geometry and initial time ranges of a launch
-    std::vector<rvb_impulse> pair_direct_host;
-    std::vector<uint32_t> pair_range_host;
-    // directional sources (rvb_set_source_pattern): the patterns in their device form — empty: off —, uploaded in stream order by the
-    // first trace after they changed (through a pinned staging block of their own, as the per-pair geometry is)
-    std::vector<SourcePatternDev> source_patterns;
-    bool source_dirty = false;
-    DevBuf source_dev;
-    StagedBlock source_stage;
-    // the tabulated directivity (rvb_set_source_table) beside them: the host copy of the table — empty: off — and the bases of its
-    // orientations (rvb_source_table_basis), uploaded together in stream order by the first trace or re-shade after they changed; on the
-    // device [RVB_HRTF_ROWS][8] floats (the zero row last), then the bases.  `gains`: ray_gains of the last launch that applied the table.
-    struct SourceTable {
-        std::vector<float> table;               // [360 * 180][8]
-        std::vector<float> bases;               // [norientations][12]
-        bool dirty = false;
-        DevBuf dev, gains;
-        StagedBlock stage;
-        uint32_t norientations() const { return table.empty() ? 0u : (uint32_t) (bases.size() / 12); }
-    } source_table;
-    // what the traces and re-shades that follow apply
-    SourceShading source_shading() const
-    {
-        SourceShading s;
-        s.patterns = source_patterns;
-        s.table_orientations = source_table.norientations();
-        return s;
-    }
-    DevBuf image_items;                          // work list of the image-source check kernel
+    PairLaunch pairs;                           // the per-pair arrays of that launch, their host mirrors, its microphones
+    SourceDirectivity source;                   // rvb_set_source_pattern / rvb_set_source_table: what is set and what is on the device
+    DevBuf image_items;                         // work list of the image-source check kernel
     KeptTrace kept;                              // rvb_keep_paths: what rvb_reshade, rvb_reshade_grad and rvb_relisten work from
     // rvb_decay_* (csrc/decay.hip): per-tile sums and carries, per-row windows and results; nothing else lives here, so the decay calls
     // leave the sort buffers, the IR configuration and a prepared exact list alone
@@ -263,7 +342,7 @@ struct rvb_ctx {
     // them): what the host has fetched of them and what the IR stage has prepared from them is void.
     void void_fetched_results() { small_valid = false; ir_configured = false; exact.valid = false; }
     // the pair the IR stage works on, as a trace leaves it: the first, with its microphone
-    void select_first_pair() { ir_pair = 0; for (int i = 0; i < 3; ++i) mic[i] = pair_mics_host[i]; }
+    void select_first_pair() { ir_pair = 0; for (int i = 0; i < 3; ++i) mic[i] = pairs.mic_of(0)[i]; }
 };
 
 // ctx == NULL: the text of a failed rvb_create, per thread (rvb_last_error(NULL))
@@ -293,12 +372,12 @@ inline int key_bits_for(uint64_t nbins)
 // trace.hip: one synchronising 128-byte read per trace serves candidate count, direct path, time range, bounce count
 int fetch_small(rvb_ctx * ctx);
 // trace.hip: the steps of a trace that kept.hip replays (described where they are defined)
-int upload_source_patterns(rvb_ctx * ctx);
-int check_source_counts(rvb_ctx * ctx, const char * who, uint64_t npairs);
 int reset_time_ranges(rvb_ctx * ctx, const TraceArgs & a);
-int apply_source_patterns(rvb_ctx * ctx, const TraceArgs & a, const SourceShading & source, bool gains_stand = false);
 int launch_images_beside(rvb_ctx * ctx, TraceArgs & a);
 int launch_shadow_behind_images(rvb_ctx * ctx, const TraceArgs & a, const SourceShading & source, bool gains_stand = false);
+// source.hip: what a trace and a re-shade do about the source directivity (described where they are defined)
+int check_source_counts(rvb_ctx * ctx, const char * who, uint64_t npairs);
+int apply_source_patterns(rvb_ctx * ctx, const TraceArgs & a, const SourceShading & source, bool gains_stand = false);
 
 // sort.hip
 bool own_sort_enabled();

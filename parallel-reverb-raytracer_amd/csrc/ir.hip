@@ -496,7 +496,7 @@ int rvb_ir_time_range(rvb_ctx * ctx, float * min_nonzero_time, float * max_time)
         if (ctx->which & RVB_IR_DIFFUSE) {
             int rc = fetch_small(ctx);
             if (rc != RVB_OK) return rc;
-            if (ctx->npairs > 1) { got[0] = ctx->pair_range_host[2 * ctx->ir_pair]; got[1] = ctx->pair_range_host[2 * ctx->ir_pair + 1]; }
+            if (ctx->npairs > 1) { got[0] = ctx->pairs.range_of(ctx->ir_pair)[0]; got[1] = ctx->pairs.range_of(ctx->ir_pair)[1]; }
             else std::memcpy(got, ctx->small_host->trace_range, sizeof(got));
         }
     }

@@ -27,12 +27,12 @@ static ReshadeGradArgs grad_args(const rvb_ctx * ctx, float predelay, float samp
     g.sample_rate = sample_rate;
     g.first_ray = ctx->ir_pair * ctx->nrays;
     g.nrays = (uint32_t) ctx->nrays;
-    for (int i = 0; i < 3; ++i) g.mic[i] = ctx->pair_mics_host[3 * ctx->ir_pair + i];
+    for (int i = 0; i < 3; ++i) g.mic[i] = ctx->pairs.mic_of(ctx->ir_pair)[i];
     const std::vector<SourcePatternDev> & shaded_patterns = kept.shaded_source.patterns;
     g.has_pattern = !shaded_patterns.empty();
     g.pattern = g.has_pattern ? shaded_patterns[shaded_patterns.size() > 1 ? ctx->ir_pair : 0] : SourcePatternDev{};
     // a table shaded the records: the pair's rows of the gains that launch left (source_table_rays_kernel)
-    g.ray_gains = kept.shaded_source.table_orientations ? ctx->source_table.gains.as<const float>() + ctx->ir_pair * ctx->nrays * 8 : nullptr;
+    g.ray_gains = kept.shaded_source.table_orientations ? ctx->source.gains_of_pair(ctx->ir_pair, ctx->nrays) : nullptr;
     g.nsurfaces = ctx->nsurfaces;
     return g;
 }
@@ -83,17 +83,7 @@ int rvb_relisten(rvb_ctx * ctx, const float * mics, uint64_t npairs)
     // what the tail appends to or folds into, back where a trace starts; `executed` stays
     RVB_HIP(fail, ctx, hipMemsetAsync(&small->candidate_count, 0, sizeof(uint32_t), ctx->stream));
     RVB_HIP(fail, ctx, hipMemsetAsync(&small->image_item_count, 0, sizeof(SmallBlock) - offsetof(SmallBlock, image_item_count), ctx->stream));      // ... and the direct slot
-    if (npairs > 1) {
-        // the microphones through the launch's staging block (the sources and the initial ranges of the kept trace are still in it:
-        // trace_prepare is its only other writer, and it sized the block for this many pairs, so nothing grows here), copied in stream
-        // order: a kernel of the previous call may still read pair_geom.  reset_time_ranges, next, records the event.
-        RVB_HIP(fail, ctx, ctx->pair_stage.acquire(4 * npairs * sizeof(float), ctx->stream));
-        float * geom = ctx->pair_stage.host<float>();
-        for (uint64_t p = 0; p < npairs; ++p)
-            for (int i = 0; i < 3; ++i) geom[4 * p + i] = mics[3 * p + i];
-        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_geom.p, geom, 4 * npairs * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        RVB_HIP(fail, ctx, hipMemsetAsync(ctx->pair_direct.p, 0, npairs * sizeof(rvb_impulse), ctx->stream));
-    }
+    if (npairs > 1) RVB_HIP(fail, ctx, ctx->pairs.restage_mics(mics, npairs, ctx->stream));       // (reset_time_ranges, next, records the block's event)
     int rc = reset_time_ranges(ctx, a);
     if (rc != RVB_OK) return rc;
     ctx->begin_timing("relisten_records_kernel");
@@ -104,7 +94,7 @@ int rvb_relisten(rvb_ctx * ctx, const float * mics, uint64_t npairs)
     if ((rc = launch_shadow_behind_images(ctx, a, kept.shaded_source, true)) != RVB_OK) return rc;
     // the kept trace is now that of the new microphone(s): later rvb_reshade, rvb_reshade_grad and rvb_relisten start from here
     for (int i = 0; i < 3; ++i) kept.args.mic[i] = mics[i];
-    ctx->pair_mics_host.assign(mics, mics + 3 * npairs);
+    ctx->pairs.mics_host.assign(mics, mics + 3 * npairs);
     ctx->select_first_pair();
     return RVB_OK;
 }
@@ -128,10 +118,10 @@ int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces,
         a.scene.surfaces = ctx->scene.surfaces;
     }
     for (int i = 0; i < 8; ++i) a.air[i] = air_coefficient[i];
-    int rc = upload_source_patterns(ctx);
-    if (rc != RVB_OK) return rc;
+    RVB_HIP(fail, ctx, ctx->source.upload(ctx->stream));
     ctx->reset_timings();
-    if ((rc = reset_time_ranges(ctx, a)) != RVB_OK) return rc;
+    int rc = reset_time_ranges(ctx, a);
+    if (rc != RVB_OK) return rc;
     ctx->void_fetched_results();
     ctx->begin_timing("reshade_kernel");
     rvb_launch_reshade(a, kept.dev.paths.as<const float4>(), ctx->stream);
@@ -140,7 +130,7 @@ int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces,
     rvb_launch_reshade_images(a, ctx->stream);
     ctx->end_timing();
     RVB_HIP(fail, ctx, hipGetLastError());
-    const SourceShading source = ctx->source_shading();
+    const SourceShading source = ctx->source.shading();
     if ((rc = apply_source_patterns(ctx, a, source)) != RVB_OK) return rc;
     kept.note_shading(a, source);
     ctx->select_first_pair();

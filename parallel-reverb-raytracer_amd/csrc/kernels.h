@@ -1,4 +1,4 @@
-// kernels.h — launch interface between the C-ABI (trace.hip, kept.hip, sort.hip, ir.hip) and the HIP kernels.
+// kernels.h — launch interface between the C-ABI (trace.hip, source.hip, kept.hip, sort.hip, ir.hip) and the HIP kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -81,7 +81,7 @@ void rvb_launch_shadow(const TraceArgs & a, hipStream_t s);
 // patterns: device [npatterns] in their device form, npatterns 1 (every pair) or a.npairs.  Behind rvb_launch_shadow, on a stream that
 // has waited for rvb_launch_images.
 struct SourcePatternDev { float direction[4]; float shape[8]; };        // rvb_source_pattern with the direction normalised (w = 0)
-SourcePatternDev rvb_source_pattern_device_form(const rvb_source_pattern & p);                      // host
+SourcePatternDev rvb_source_pattern_device_form(const rvb_source_pattern & p);                      // host (source_state.hip)
 void rvb_launch_source_pattern(const TraceArgs & a, const SourcePatternDev * patterns, uint32_t npatterns, hipStream_t s);
 // The tabulated directivity (rvb_set_source_table of include/rvb_capi.h) at the same place: volume_b *= table[row(v)][b] with the row of
 // csrc/attenuation.h (hrtf_row with pos - mic replaced by v) in the source's basis.  rvb_launch_source_table_rays: one row selection per
@@ -95,7 +95,7 @@ struct SourceTableDev {
     uint32_t basis_stride;              // float4s between the bases of two pairs: 0 (one orientation for every pair) or 3
     float * ray_gains;                  // device [a.npairs][a.rays_per_pair][8]
 };
-// host: the basis of kernel.cpp:538-549 for (facing, up) as twelve floats (bx, by, bz; w = 0), with the device's operations; false where
+// host (source_state.hip): the basis of kernel.cpp:538-549 for (facing, up) as twelve floats (bx, by, bz; w = 0), with the device's operations; false where
 // normalize3(cross3(up, facing)) is zero or a value is not finite
 bool rvb_source_table_basis(const rvb_source_orientation & o, float basis[12]);
 void rvb_launch_source_table_rays(const TraceArgs & a, const SourceTableDev & t, hipStream_t s);

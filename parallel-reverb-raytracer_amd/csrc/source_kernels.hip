@@ -272,26 +272,7 @@ void launch_records(const TraceArgs & a, const SourcePatternDev * patterns, uint
 
 }  // namespace
 
-SourcePatternDev rvb_source_pattern_device_form(const rvb_source_pattern & p)
-{
-    SourcePatternDev d;
-    const v3 n = normalize3(mk3(p.direction[0], p.direction[1], p.direction[2]));       // kernel.cpp:511, with the device's operations
-    d.direction[0] = n.x; d.direction[1] = n.y; d.direction[2] = n.z; d.direction[3] = 0.0f;
-    for (int b = 0; b < 8; ++b) d.shape[b] = p.shape[b];
-    return d;
-}
-
-bool rvb_source_table_basis(const rvb_source_orientation & o, float basis[12])
-{
-    const v3 facing = mk3(o.facing[0], o.facing[1], o.facing[2]), up = mk3(o.up[0], o.up[1], o.up[2]);
-    const v3 bx = normalize3(cross3(up, facing));                   // kernel.cpp:538-549 (transform3, make_model), with the device's operations
-    const v3 by = cross3(facing, bx);
-    const float rows[12] = {bx.x, bx.y, bx.z, 0.0f, by.x, by.y, by.z, 0.0f, facing.x, facing.y, facing.z, 0.0f};
-    for (int i = 0; i < 12; ++i) basis[i] = rows[i];
-    bool finite = true;
-    for (int i = 0; i < 12; ++i) finite = finite && std::isfinite(rows[i]);
-    return finite && (bx.x != 0.0f || bx.y != 0.0f || bx.z != 0.0f);
-}
+// (the host forms of kernels.h, rvb_source_pattern_device_form and rvb_source_table_basis: source_state.hip)
 
 void rvb_launch_source_table_rays(const TraceArgs & a, const SourceTableDev & t, hipStream_t s)
 {

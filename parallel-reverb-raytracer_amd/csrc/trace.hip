@@ -1,6 +1,7 @@
 // trace.hip — the trace of include/rvb_capi.h: buffers, fills and kernel arguments; the path kernel; everything after it; then what a
 // trace leaves for the host (diffuse impulses, direct path, image-source candidates) and the image-source merge.  The steps that a kept
-// trace replays (kept.hip) come first: they are declared in ctx.h.
+// trace replays (kept.hip) come first: they are declared in ctx.h.  The source directivity is source.hip's, the per-pair arrays of a
+// launch are PairLaunch's (ctx.h).
 #include "ctx.h"
 
 #include <algorithm>
@@ -8,91 +9,15 @@
 #include <cstring>
 #include <map>
 
-// The patterns of rvb_set_source_pattern, where they have changed since the last upload: up in stream order, through a staging block
-// of their own.
-int upload_source_patterns(rvb_ctx * ctx)
-{
-    if (ctx->source_dirty && !ctx->source_patterns.empty()) {
-        RVB_HIP(fail, ctx, ctx->source_stage.upload(ctx->source_dev, ctx->source_patterns.data(), ctx->source_patterns.size() * sizeof(SourcePatternDev), ctx->stream));
-        ctx->source_dirty = false;
-    }
-    // ... and the table of rvb_set_source_table with the bases of its orientations behind it, in one block
-    rvb_ctx::SourceTable & t = ctx->source_table;
-    if (t.dirty && !t.table.empty()) {
-        const size_t table_floats = (size_t) RVB_HRTF_ROWS * 8, bytes = (table_floats + t.bases.size()) * sizeof(float);
-        RVB_HIP(fail, ctx, t.stage.acquire(bytes, ctx->stream, &t.dev));
-        float * host = t.stage.host<float>();
-        std::memcpy(host, t.table.data(), t.table.size() * sizeof(float));
-        std::memset(host + t.table.size(), 0, (table_floats - t.table.size()) * sizeof(float));           // the zero row
-        std::memcpy(host + table_floats, t.bases.data(), t.bases.size() * sizeof(float));
-        RVB_HIP(fail, ctx, hipMemcpyAsync(t.dev.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
-        RVB_HIP(fail, ctx, t.stage.record(ctx->stream));
-        t.dirty = false;
-    }
-    return RVB_OK;
-}
-
-// "n orientations / patterns for npairs pairs": one for all pairs, or one per pair
-int check_source_counts(rvb_ctx * ctx, const char * who, uint64_t npairs)
-{
-    if (ctx->source_patterns.size() > 1 && ctx->source_patterns.size() != npairs)
-        return fail(ctx, RVB_ERR_INVALID, std::string(who) + ": " + std::to_string(ctx->source_patterns.size()) + " source patterns for " + std::to_string(npairs) +
-                                          " pair(s): one for all pairs, or one per pair (rvb_set_source_pattern)");
-    if (ctx->source_table.norientations() > 1 && ctx->source_table.norientations() != npairs)
-        return fail(ctx, RVB_ERR_INVALID, std::string(who) + ": " + std::to_string(ctx->source_table.norientations()) + " source orientations for " +
-                                          std::to_string(npairs) + " pair(s): one for all pairs, or one per pair (rvb_set_source_table)");
-    return RVB_OK;
-}
-
 // The diffuse time range(s) of a launch back at "nothing seen": 0xFFFFFFFF / 0, per pair.
 int reset_time_ranges(rvb_ctx * ctx, const TraceArgs & a)
 {
     if (a.npairs > 1) {
-        // (the initial ranges are still in the launch's staging block: trace_prepare's next use of it waits for the event recorded here)
-        const uint32_t * init = reinterpret_cast<const uint32_t *>(ctx->pair_stage.host<float>() + 8 * (size_t) a.npairs);
-        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_range.p, init, 2 * (size_t) a.npairs * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        RVB_HIP(fail, ctx, ctx->pair_stage.record(ctx->stream));
+        RVB_HIP(fail, ctx, ctx->pairs.reset_ranges(a.npairs, ctx->stream));
     } else {
         RVB_HIP(fail, ctx, hipMemsetAsync(a.time_range, 0xFF, 4, ctx->stream));
         RVB_HIP(fail, ctx, hipMemsetAsync(a.time_range + 1, 0, 4, ctx->stream));
     }
-    return RVB_OK;
-}
-
-// Directional sources behind the kernel that wrote the final records (the shadow kernel of a trace, the re-shade kernels of rvb_reshade):
-// the records scaled once — this stream has waited for the image kernels, so the candidates are final too — and the diffuse time range
-// taken again, over the scaled records: it replaces that kernel's.
-// `source` names which directivity, the patterns of rvb_set_source_pattern or the table of rvb_set_source_table: what is on the device —
-// the context's after upload_source_patterns; rvb_relisten passes what the records reflect.  The table's diffuse gains are taken once per (pair, ray)
-// in front of the streaming pass; gains_stand: those of the launch that shaded the records last are still there (rvb_relisten: they do
-// not depend on the microphone).
-int apply_source_patterns(rvb_ctx * ctx, const TraceArgs & a, const SourceShading & source, bool gains_stand)
-{
-    if (source.off()) return RVB_OK;
-    rvb_ctx::SourceTable & t = ctx->source_table;
-    if (source.table_orientations && !gains_stand) RVB_HIP(fail, ctx, t.gains.ensure((size_t) a.nrays * 8 * sizeof(float)));
-    const int rc = reset_time_ranges(ctx, a);
-    if (rc != RVB_OK) return rc;
-    if (source.table_orientations) {
-        SourceTableDev d;
-        d.table = t.dev.as<const float>();
-        d.bases = reinterpret_cast<const float4 *>(d.table + (size_t) RVB_HRTF_ROWS * 8);
-        d.basis_stride = source.table_orientations > 1 ? 3u : 0u;
-        d.ray_gains = t.gains.as<float>();
-        if (!gains_stand) {
-            ctx->begin_timing("source_table_rays_kernel");
-            rvb_launch_source_table_rays(a, d, ctx->stream);
-            ctx->end_timing();
-        }
-        ctx->begin_timing("source_table_kernel");
-        rvb_launch_source_table(a, d, ctx->stream);
-        ctx->end_timing();
-    } else {
-        ctx->begin_timing("source_pattern_kernel");
-        rvb_launch_source_pattern(a, ctx->source_dev.as<SourcePatternDev>(), (uint32_t) source.patterns.size(), ctx->stream);
-        ctx->end_timing();
-    }
-    RVB_HIP(fail, ctx, hipGetLastError());
     return RVB_OK;
 }
 
@@ -186,30 +111,7 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     a.executed = &small->executed;
     a.time_range = small->trace_range;
     a.image_dist = kept.keep_paths ? kept.dev.image_dist.as<float>() : nullptr;
-    if (npairs > 1) {
-        // several pairs per launch: geometry, direct path and time range per pair live in arrays of their own
-        // staged through pinned memory and copied in stream order: no host synchronisation in front of the launch (the staging
-        // block is reused only after the copies of the previous launch have left it)
-        const size_t geom_floats = 8 * npairs, init_words = 2 * npairs;
-        const size_t stage_bytes = geom_floats * sizeof(float) + init_words * sizeof(uint32_t);
-        RVB_HIP(fail, ctx, ctx->pair_stage.acquire(stage_bytes, ctx->stream));
-        float * geom = ctx->pair_stage.host<float>();
-        uint32_t * init = reinterpret_cast<uint32_t *>(geom + geom_floats);
-        std::memset(geom, 0, geom_floats * sizeof(float));
-        for (uint64_t p = 0; p < npairs; ++p)
-            for (int i = 0; i < 3; ++i) { geom[4 * p + i] = mics[3 * p + i]; geom[4 * (npairs + p) + i] = sources[3 * p + i]; }
-        for (uint64_t p = 0; p < npairs; ++p) { init[2 * p] = 0xFFFFFFFFu; init[2 * p + 1] = 0u; }
-        RVB_HIP(fail, ctx, ctx->pair_geom.ensure(geom_floats * sizeof(float)));
-        RVB_HIP(fail, ctx, ctx->pair_direct.ensure(npairs * sizeof(rvb_impulse)));
-        RVB_HIP(fail, ctx, ctx->pair_range.ensure(npairs * 2 * sizeof(uint32_t)));
-        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_geom.p, geom, geom_floats * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_range.p, init, init_words * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        RVB_HIP(fail, ctx, ctx->pair_stage.record(ctx->stream));
-        a.pair_mics = ctx->pair_geom.as<float4>();
-        a.pair_sources = ctx->pair_geom.as<float4>() + npairs;
-        a.direct = ctx->pair_direct.as<rvb_impulse>();
-        a.time_range = ctx->pair_range.as<uint32_t>();
-    }
+    RVB_HIP(fail, ctx, ctx->pairs.stage(mics, sources, npairs, ctx->stream, a));        // several pairs per launch: the four above point to arrays per pair
     // record bucketing for coherent shadow rays (RVB_SHADOW_SORT=0 turns it off)
     static const bool sort_records = !(getenv("RVB_SHADOW_SORT") && getenv("RVB_SHADOW_SORT")[0] == '0');
     const uint64_t nrecords = nrays * nreflections;
@@ -246,8 +148,7 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     for (int i = 0; i < 3; ++i) { a.mic[i] = mic[i]; a.source[i] = source[i]; ctx->mic[i] = mic[i]; }
     for (int i = 0; i < 8; ++i) a.air[i] = air_coefficient[i];
 
-    const int rc = upload_source_patterns(ctx);
-    if (rc != RVB_OK) return rc;
+    RVB_HIP(fail, ctx, ctx->source.upload(ctx->stream));
 
     // diagnostic builds (RVB_STAMPS): [0..15] path_kernel, [16..31] shadow_kernel
     RVB_HIP(fail, ctx, ctx->stamps.ensure(32 * sizeof(unsigned long long)));
@@ -310,7 +211,7 @@ int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
         }
         ctx->end_timing();
     }
-    const SourceShading source = ctx->source_shading();
+    const SourceShading source = ctx->source.shading();
     if ((rc = launch_shadow_behind_images(ctx, a, source)) != RVB_OK) return rc;
     ctx->kept.take(a, source);
     ctx->nreflections = nreflections;
@@ -318,7 +219,7 @@ int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
     ctx->void_fetched_results();
     ctx->npairs = npairs;
     ctx->traced_rays = nrays;
-    ctx->pair_mics_host.assign(mics, mics + 3 * npairs);
+    ctx->pairs.mics_host.assign(mics, mics + 3 * npairs);
     ctx->select_first_pair();
     return RVB_OK;
 }
@@ -352,12 +253,8 @@ int fetch_small(rvb_ctx * ctx)
         RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->first_candidates, ctx->candidates.p,
                                           std::min(kFirstCandidates * sizeof(rvb_image_candidate), (size_t) ctx->traced_rays * 9 * sizeof(rvb_image_candidate)),
                                           hipMemcpyDeviceToHost, ctx->stream));
-    if (ctx->npairs > 1) {     // per-pair direct paths and time ranges
-        ctx->pair_direct_host.resize(ctx->npairs);
-        ctx->pair_range_host.resize(2 * ctx->npairs);
-        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_direct_host.data(), ctx->pair_direct.p, ctx->npairs * sizeof(rvb_impulse), hipMemcpyDeviceToHost, ctx->stream));
-        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->pair_range_host.data(), ctx->pair_range.p, ctx->npairs * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
+    if (ctx->npairs > 1)       // per-pair direct paths and time ranges
+        RVB_HIP(fail, ctx, ctx->pairs.fetch(ctx->npairs, ctx->stream));
     RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
     ctx->small_valid = true;
     return RVB_OK;
@@ -440,62 +337,6 @@ int rvb_trace_pairs(rvb_ctx * ctx, const float * mics, const float * sources, ui
     return trace_common(ctx, mics, sources, npairs, nreflections, air_coefficient, ray_offset);
 }
 
-int rvb_set_source_pattern(rvb_ctx * ctx, const rvb_source_pattern * patterns, uint64_t npatterns)
-{
-    if (!ctx) return RVB_ERR_INVALID;
-    if (!patterns) npatterns = 0;
-    std::vector<SourcePatternDev> form;
-    for (uint64_t p = 0; p < npatterns; ++p) {
-        bool finite = true;
-        for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(patterns[p].direction[i]);
-        for (int b = 0; b < 8; ++b) finite = finite && std::isfinite(patterns[p].shape[b]);
-        if (!finite) return fail(ctx, RVB_ERR_INVALID, "rvb_set_source_pattern: pattern " + std::to_string(p) + " holds a value that is not finite");
-        form.push_back(rvb_source_pattern_device_form(patterns[p]));
-        const float * d = form.back().direction;
-        // (a zero vector stays zero under normalize3; a length that overflows or underflows in binary32 does not give a unit vector either)
-        const float len2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-        if (!(len2 > 0.5f && len2 < 2.0f))
-            return fail(ctx, RVB_ERR_INVALID, "rvb_set_source_pattern: pattern " + std::to_string(p) + " has a direction of zero length (or one binary32 cannot normalise)");
-    }
-    ctx->source_table.table.clear();            // one directivity at a time: any accepted call turns the table off (what is on the device stays)
-    ctx->source_table.bases.clear();
-    // (the same patterns again — a pipeline sets them per job —: what is on the device stays)
-    if (form.size() == ctx->source_patterns.size() && (form.empty() || !std::memcmp(form.data(), ctx->source_patterns.data(), form.size() * sizeof(SourcePatternDev))))
-        return RVB_OK;
-    ctx->source_patterns.swap(form);
-    ctx->source_dirty = true;
-    return RVB_OK;
-}
-
-int rvb_set_source_table(rvb_ctx * ctx, const float * table, const rvb_source_orientation * orientations, uint64_t norientations)
-{
-    if (!ctx) return RVB_ERR_INVALID;
-    rvb_ctx::SourceTable & t = ctx->source_table;
-    if (!table) {                               // off: what is on the device stays (a kept trace may reflect it)
-        t.table.clear();
-        t.bases.clear();
-        return RVB_OK;
-    }
-    if (!orientations || norientations == 0) return fail(ctx, RVB_ERR_INVALID, "rvb_set_source_table: a table without orientations");
-    const size_t table_floats = (size_t) (RVB_HRTF_ROWS - 1) * 8;
-    for (size_t i = 0; i < table_floats; ++i)
-        if (!std::isfinite(table[i]))
-            return fail(ctx, RVB_ERR_INVALID, "rvb_set_source_table: row " + std::to_string(i / 8) + " of the table holds a value that is not finite");
-    std::vector<float> bases(12 * (size_t) norientations);
-    for (uint64_t p = 0; p < norientations; ++p) {
-        bool finite = true;
-        for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(orientations[p].facing[i]) && std::isfinite(orientations[p].up[i]);
-        if (!finite) return fail(ctx, RVB_ERR_INVALID, "rvb_set_source_table: orientation " + std::to_string(p) + " holds a value that is not finite");
-        if (!rvb_source_table_basis(orientations[p], bases.data() + 12 * p))
-            return fail(ctx, RVB_ERR_INVALID, "rvb_set_source_table: orientation " + std::to_string(p) + ": normalize3(cross3(up, facing)) is zero or not finite");
-    }
-    ctx->source_patterns.clear();               // one directivity at a time: the table turns any pattern off
-    t.table.assign(table, table + table_floats);
-    t.bases.swap(bases);
-    t.dirty = true;
-    return RVB_OK;
-}
-
 int rvb_ir_select_pair(rvb_ctx * ctx, uint64_t pair)
 {
     if (!ctx) return RVB_ERR_INVALID;
@@ -503,7 +344,7 @@ int rvb_ir_select_pair(rvb_ctx * ctx, uint64_t pair)
     if (pair >= ctx->npairs) return fail(ctx, RVB_ERR_INVALID, "rvb_ir_select_pair: pair out of range");
     ctx->ir_pair = pair;
     ctx->ir_configured = false;
-    for (int i = 0; i < 3; ++i) ctx->mic[i] = ctx->pair_mics_host[3 * pair + i];
+    for (int i = 0; i < 3; ++i) ctx->mic[i] = ctx->pairs.mic_of(pair)[i];
     return RVB_OK;
 }
 
@@ -537,7 +378,7 @@ int rvb_get_direct(rvb_ctx * ctx, rvb_impulse * out)
     RVB_BIND(ctx);
     int rc = fetch_small(ctx);
     if (rc != RVB_OK) return rc;
-    if (ctx->npairs > 1) *out = ctx->pair_direct_host[ctx->ir_pair];       // of the pair chosen with rvb_ir_select_pair
+    if (ctx->npairs > 1) *out = ctx->pairs.direct_of(ctx->ir_pair);      // of the pair chosen with rvb_ir_select_pair
     else *out = ctx->small_host->direct;
     return RVB_OK;
 }

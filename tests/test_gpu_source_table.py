@@ -342,15 +342,18 @@ def kept(kept_world):
     c.close()
 
 
-def fresh_state(world, surfaces, air, mic, dirs, nrefl, table, orient):
-    """A trace on a context of its own in the scene with the surface table `surfaces`."""
+def fresh_state(world, surfaces, air, mic, dirs, nrefl, table, orient, pattern=None, source=None):
+    """A trace on a context of its own in the scene with the surface table `surfaces`; pattern: (direction, shape) instead of a table;
+    source: another than the world's."""
     from parallel_reverb_raytracer_amd import capi
     c = capi.Context(0)
     try:
         c.set_scene((world["scene"][0], world["scene"][1], surfaces))
         if table is not None:
             c.set_source_table(table, *orient)
-        c.raytrace(mic, world["source"], dirs, nrefl, air)
+        if pattern is not None:
+            c.set_source_pattern(*pattern)
+        c.raytrace(mic, world["source"] if source is None else source, dirs, nrefl, air)
         return state_of(c, mic)
     finally:
         c.close()
@@ -408,6 +411,91 @@ def test_kept_traces_reshade_and_relisten_with_the_table(kept, kept_world):
             assert state_of(kept, w["mic"]) == want["A plain"]
     finally:
         kept.set_source_table(None)
+
+
+def test_kept_traces_across_pattern_and_table_and_changing_pair_counts(kept, kept_world):
+    """256 x 16, kept for materials and listeners, against fresh traces on contexts of their own, bit for bit.  (a) from a pattern to a
+    table and back on one kept trace: relisten shades with what the records reflect, whichever of the two has been set since, and the
+    next reshade takes up what is set.  (b) 3 pairs, 2 pairs and new microphones for them, 1 pair, 3 pairs again on one context, an
+    orientation per pair: every pair's diffuse slice, direct path and time range are those of that pair traced alone."""
+    w = kept_world
+    nrays, nrefl = 256, 16
+    dirs = scenes.sphere_directions(nrays, seed=23)
+    own, air = w["scene"][2], AIR_COEFFICIENTS
+    pattern = (FACING, SHAPES)
+    mics = np.array([w["mic"], (0.0, 12.0, 11.0), (-10.28, 3.85, -2.24)], np.float32)
+    sources = np.array([w["source"], (0.0, 12.5, 11.5), (-12.0, 2.5, 3.0)], np.float32)
+    new_mics = np.array([OTHER_MIC, w["mic"]], np.float32)
+    facings = np.array([ORIENT[0], OTHER_ORIENT[0], (0.6, 0.0, 0.8)], np.float32)
+    ups = np.array([ORIENT[1], OTHER_ORIENT[1], (0.0, 1.0, 0.0)], np.float32)
+
+    def pair_alone(p, mic):
+        return fresh_state(w, own, air, tuple(mic), dirs, nrefl, SPREAD, (facings[p], ups[p]), source=tuple(sources[p]))
+
+    want = {
+        "pattern": fresh_state(w, own, air, w["mic"], dirs, nrefl, None, None, pattern=pattern),
+        "pattern other mic": fresh_state(w, own, air, OTHER_MIC, dirs, nrefl, None, None, pattern=pattern),
+        "table": fresh_state(w, own, air, w["mic"], dirs, nrefl, SPREAD, ORIENT),
+        "table other mic": fresh_state(w, own, air, OTHER_MIC, dirs, nrefl, SPREAD, ORIENT),
+        "pair 1": pair_alone(1, mics[1]),
+        "pair 2": pair_alone(2, mics[2]),
+        "pair 1 new mic": pair_alone(1, new_mics[1]),
+    }
+    want["pair 0"], want["pair 0 new mic"] = want["table"], want["table other mic"]          # (pair 0 is the world's own, under ORIENT)
+    assert len({v[0] for v in want.values()}) == len(want) - 2
+    assert len({want[n][1] for n in ("pattern", "pattern other mic", "table", "table other mic")}) == 4, "the direct slot does not see the microphone or the directivity"
+    assert len({v[3] for v in want.values()}) > 1
+
+    def pairs_of(ctx, pair_mics):
+        """Per pair what state_of gives for a single pair, without the candidates: (diffuse slice, direct path, time range)."""
+        diffuse = ctx.get_raw_diffuse().reshape(len(pair_mics), -1)
+        out = []
+        for p, m in enumerate(pair_mics):
+            ctx.select_pair(p)
+            out.append((diffuse[p].tobytes(), ctx.get_direct().tobytes(), time_range(ctx, tuple(m))))
+        return out
+
+    def alone(*names):
+        return [(want[n][0], want[n][1], want[n][3]) for n in names]
+
+    try:
+        # (a)
+        kept.set_source_pattern(*pattern)
+        kept.raytrace(w["mic"], w["source"], dirs, nrefl, air)
+        assert state_of(kept, w["mic"]) == want["pattern"]
+        kept.set_source_table(SPREAD, *ORIENT)
+        kept.relisten(OTHER_MIC)
+        names = names_of(kept)          # (before state_of: the time-range query starts the timings again)
+        assert "source_pattern_kernel" in names and "source_table_kernel" not in names and "source_table_rays_kernel" not in names
+        assert state_of(kept, OTHER_MIC) == want["pattern other mic"]
+        kept.reshade(None, air)
+        assert state_of(kept, OTHER_MIC) == want["table other mic"]
+        kept.set_source_pattern(*pattern)
+        kept.relisten(w["mic"])
+        names = names_of(kept)
+        assert "source_table_kernel" in names and "source_table_rays_kernel" not in names and "source_pattern_kernel" not in names
+        assert state_of(kept, w["mic"]) == want["table"]
+        kept.reshade(None, air)
+        assert state_of(kept, w["mic"]) == want["pattern"]
+        # (b)
+        kept.set_source_table(SPREAD, facings, ups)
+        kept.trace_pairs(mics, sources, nrefl, air)
+        assert pairs_of(kept, mics) == alone("pair 0", "pair 1", "pair 2")
+        kept.set_source_table(SPREAD, facings[:2], ups[:2])
+        kept.trace_pairs(mics[:2], sources[:2], nrefl, air)
+        assert pairs_of(kept, mics[:2]) == alone("pair 0", "pair 1")
+        kept.relisten(new_mics)
+        assert pairs_of(kept, new_mics) == alone("pair 0 new mic", "pair 1 new mic")
+        kept.set_source_table(SPREAD, facings[2], ups[2])
+        kept.trace(mics[2], sources[2], nrefl, air)
+        assert state_of(kept, tuple(mics[2])) == want["pair 2"]
+        kept.set_source_table(SPREAD, facings, ups)
+        kept.trace_pairs(mics, sources, nrefl, air)
+        assert pairs_of(kept, mics) == alone("pair 0", "pair 1", "pair 2")
+    finally:
+        kept.set_source_table(None)
+        kept.set_source_pattern(None)
+        kept.npairs = 1
 
 
 BAND_FACTORS = np.array([0.5, 1.0, 2.0, 4.0, 0.25, 1.0, 2.0, 0.5], np.float32)
