@@ -462,6 +462,75 @@ int rvb_decay_times(rvb_ctx * ctx, const void * d_curve, uint64_t nrows, uint64_
 int rvb_decay_loss(rvb_ctx * ctx, const void * d_histogram, const void * d_curve, const void * d_target, const void * d_mask,
                    uint64_t nrows, uint64_t nbins, unsigned flags, double * loss_rows /* host [nrows] */, void * d_weights);
 
+/* ---- room acoustic parameters: EDT, T20, T30, C50, C80, D50, Ts of a curve, a loss against a measured table, its adjoint
+ *      (csrc/decay_params_kernels.hip) ---------------------------------------------------------------------------------------------------
+ * A room survey supplies the ISO 3382-1 single numbers per octave band, not a decay curve.  rvb_decay_params computes all seven for
+ * every row of a curve E in ONE sweep; rvb_decay_params_loss adds a weighted squared loss against a table of targets and the adjoint
+ * w = dL/dH, exactly the weights rvb_reshade_grad and rvb_reshade_grad_map take — the form rvb_decay_loss produces.  Shapes, row layout,
+ * scratch rules and the determinism promise are those of the decay calls above: any array of rows of bins; the context's device, stream,
+ * timings and decay scratch only; no scene, trace or IR configuration is needed, nothing is voided and no record is touched; all sums and
+ * logarithms are binary64 in an order fixed by (tile, chunk, bin); no atomics; each result is rounded to float once; two calls return
+ * identical bytes.  Both calls are synchronous.  No reference counterpart.
+ *
+ * DEFINITIONS.  All arithmetic is binary64 on the float32 values of E; fs is sample_rate widened to double; C10 = 10 / ln 10; the
+ * "not available" value is a quiet NaN.
+ *   EDT, T20, T30   exactly rvb_decay_times with (0, -10), (-5, -25), (-5, -35): the same thresholds, window [k0, k1), centred line and
+ *                   -60 / (slope * fs).  For every row the three floats are byte-equal to what rvb_decay_times returns for that pair.
+ *   C50, C80        ke = (uint64_t) (te * fs + 0.5), te the double literal 0.05 or 0.08; early = E[0] - E[ke], late = E[ke];
+ *                   C = C10 (ln early - ln late), in dB.  NaN unless E[0] > 0, ke < nbins, early > 0 and late > 0.
+ *   D50             D = (E[0] - E[k50]) / E[0].  NaN unless E[0] > 0 and k50 < nbins.
+ *   Ts              Ts = (sum_{k=1}^{nbins-1} E[k]) / (fs E[0]) = sum_j (j / fs) H_j^2 / sum_j H_j^2, the centre time with bin j at time
+ *                   j / fs, in seconds.  NaN unless E[0] > 0.
+ * LOSS.  Parameter p of row r counts when param_weights[r][p] > 0 and the model's value q (binary64, before its rounding to float) is
+ * finite; loss_rows[r] = sum_p weight (q - target)^2 over the counting parameters, in the order of the parameter numbers (a weight of
+ * 1 / target^2 gives relative errors).  An unavailable model value adds nothing; the caller sees it in `params`.
+ * ADJOINT.  With c_p = 2 weight (q - target) (0 when p does not count), g[k] = dL/dE[k] is the sum of
+ *   each time p, window [k0, k1), slope s, n = k1 - k0, Sxx = n (n^2 - 1) / 12, xc_k = (k - k0) - (n - 1) / 2:
+ *                   for k in the window  c_p (60 / (s^2 fs)) C10 xc_k / (Sxx E[k])   (the E[0] terms of the levels cancel: sum xc = 0; the
+ *                   window ends are held fixed — step functions of E, so this is the exact derivative almost everywhere);
+ *   C_te            g[0] += c C10 / early;  g[ke] -= c C10 (1 / early + 1 / late);
+ *   D50             g[k50] -= c / E[0];  g[0] += c E[k50] / E[0]^2;
+ *   Ts              g[k] += c / (fs E[0]) for every k >= 1;  g[0] -= c Ts / E[0];
+ * and d_weights[r][j] = 2 H[r][j] * sum_{k <= j} g[k] = dL/dH[r][j] for L = sum_r loss_rows[r], in H's layout: exactly 0 where H is 0,
+ * all-zero in a row with no counting parameter, no entry left unwritten.  The terms of one bin are added in the order of the parameter
+ * numbers, the three time terms first and under one division by E[k].  g is evaluated from E and a block of coefficients per row; no
+ * dense g array goes to memory.  d_weights == NULL: the loss (and params) only.  params may be NULL in rvb_decay_params_loss.
+ * REFUSALS, before any device is touched; a failed call writes nothing.  RVB_ERR_INVALID: a NULL ctx or required pointer (d_curve,
+ * params; for the loss d_histogram, d_curve, targets, param_weights, loss_rows), nrows == 0 or nbins == 0, a sample rate that is not
+ * finite and > 0, a param_weight that is not finite or is negative, a target that is not finite where its weight is > 0, d_weights
+ * overlapping the histogram or the curve.  RVB_ERR_CAPACITY as for rvb_decay_curve: more than 4096 rows, 2^32 bins or more.
+ * rvb_last_timings names the kernels of the call: "decay_params_find_kernel" (one pass over E for the five thresholds of the three
+ * windows), "decay_params_window_kernel", "decay_params_sums_kernel" (one pass over E: the three sums of xc * level, each where its window
+ * meets the tile, and sum E), "decay_params_fit_kernel" (the seven parameters, the row's loss and its coefficients); with d_weights also
+ * "decay_params_adjoint_sums_kernel", "decay_params_adjoint_carry_kernel", "decay_params_adjoint_scan_kernel".  The row's loss is left by
+ * the fit kernel, so that the call without d_weights ends there.
+ * MEASURED on one MI355X (profiles/decay_params_n1.txt, tools/decay_params_bench.py; medians of one run, calls by the host clock to the
+ * synchronisation, kernels by HIP events), at workload C2's stereo histogram, 16 x 846 741, and at 512 x 846 741 (64 channels):
+ *     rvb_decay_params          0.145 ms / 1.85 ms, where three rvb_decay_times calls take 0.343 ms / 3.03 ms and the pinned download of
+ *                               the curve that a host-side C80, D50 or Ts needs on top 0.98 ms / 30.4 ms (9.1 x / 18 x the call).  Kernels
+ *                               0.094 ms / 1.79 ms against a floor of 0.016 ms / 0.53 ms (E read twice, 6.6 TB/s): the find pass runs at
+ *                               1.9 x / 1.3 x its floor, the sums pass at 7.0 x / 5.4 x — the binary64 logarithm per bin of the windows'
+ *                               union (0 .. -35 dB, more than half the row here) bounds it, as it bounds decay_times_sums_kernel; at C2
+ *                               launches and the download of the results are a third of the call;
+ *     rvb_decay_params_loss     0.270 ms / 4.22 ms with weights, 0.170 ms / 2.16 ms without, beside rvb_decay_loss' 0.206 ms / 4.20 ms and
+ *                               0.119 ms / 2.23 ms in the same loop.  The three adjoint kernels 0.084 ms / 2.31 ms against a floor of
+ *                               0.033 ms / 1.05 ms (E read twice, H once, w written once): the sums pass at 4.0 x / 3.6 x its floor, the
+ *                               scan at 1.8 x / 1.7 x; the binary64 division per window bin and the binary64 scan are the candidates (no
+ *                               counter run has been made);
+ *     the older calls           rvb_decay_curve, rvb_decay_times and rvb_decay_loss of this build against a build of the commit before, the
+ *                               same loop in processes that take turns: medians differ by 0.000 / -0.013 ms, -0.001 / -0.033 ms and
+ *                               -0.001 / -0.17 ms, inside the difference between the parent's own two processes (0.001 / 0.015 ms,
+ *                               0.004 / 0.035 ms, 0.002 / 0.18 ms): their device code is unchanged.  (The logarithm-bound kernels follow
+ *                               the clock: rvb_decay_loss takes 3.7 ms in that loop and 4.2 ms in the loop that also runs the new calls.) */
+enum { RVB_DECAY_EDT = 0, RVB_DECAY_T20 = 1, RVB_DECAY_T30 = 2, RVB_DECAY_C50 = 3, RVB_DECAY_C80 = 4, RVB_DECAY_D50 = 5, RVB_DECAY_TS = 6 };
+#define RVB_DECAY_NPARAMS 7
+int rvb_decay_params(rvb_ctx * ctx, const void * d_curve, uint64_t nrows, uint64_t nbins, float sample_rate,
+                     float * params /* host [nrows][RVB_DECAY_NPARAMS] */);
+int rvb_decay_params_loss(rvb_ctx * ctx, const void * d_histogram, const void * d_curve, uint64_t nrows, uint64_t nbins, float sample_rate,
+                          const float * targets /* host [nrows][7] */, const float * param_weights /* host [nrows][7] */,
+                          double * loss_rows /* host [nrows] */, float * params /* host [nrows][7], may be NULL */,
+                          void * d_weights /* device [nrows][nbins], may be NULL */);
+
 /* Chooses the pair that rvb_get_direct and the rvb_ir_* calls below work on (pair 0 after a trace). */
 int rvb_ir_select_pair(rvb_ctx * ctx, uint64_t pair);
 

@@ -41,13 +41,15 @@ SYMBOLS = [
     "rvb_set_source_table",
     "rvb_set_source_pattern", "rvb_multi_set_source_pattern", "rvb_pipeline_set_source_pattern", "rvb_pipeline_submit_directed",
     "rvb_keep_paths", "rvb_reshade", "rvb_reshade_grad", "rvb_reshade_grad_map", "rvb_relisten",
-    "rvb_decay_curve", "rvb_decay_times", "rvb_decay_loss",
+    "rvb_decay_curve", "rvb_decay_times", "rvb_decay_loss", "rvb_decay_params", "rvb_decay_params_loss",
 ]
 
 PIPELINE_MAX_PAIRS = 8      # RVB_PIPELINE_MAX_PAIRS
 MAX_SPEAKERS = 64           # RVB_MAX_SPEAKERS
 DECAY_TILE = 4096           # RVB_DECAY_TILE
 DECAY_NORMALISED = 1        # RVB_DECAY_NORMALISED
+DECAY_EDT, DECAY_T20, DECAY_T30, DECAY_C50, DECAY_C80, DECAY_D50, DECAY_TS = range(7)     # RVB_DECAY_EDT .. RVB_DECAY_TS
+DECAY_NPARAMS = 7           # RVB_DECAY_NPARAMS
 GRAD_MAP_TILE = 1024        # RVB_GRAD_MAP_TILE
 KEEP_MATERIALS, KEEP_LISTENER = 1, 2     # RVB_KEEP_MATERIALS, RVB_KEEP_LISTENER
 
@@ -104,6 +106,10 @@ def load_library():
         lib.rvb_decay_times.argtypes = [_vp, _vp, _u64, _u64, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp]
         lib.rvb_decay_loss.restype = ctypes.c_int
         lib.rvb_decay_loss.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, _u64, ctypes.c_uint, _vp, _vp]
+        lib.rvb_decay_params.restype = ctypes.c_int
+        lib.rvb_decay_params.argtypes = [_vp, _vp, _u64, _u64, ctypes.c_float, _vp]
+        lib.rvb_decay_params_loss.restype = ctypes.c_int
+        lib.rvb_decay_params_loss.argtypes = [_vp, _vp, _vp, _u64, _u64, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]
         _lib = lib
     return _lib
 
@@ -589,6 +595,29 @@ class Context:
                                             _vp(device_weights_pointer) if device_weights_pointer else None))
         return loss_rows
 
+    def decay_params(self, device_curve_pointer, nrows, nbins, sample_rate):
+        """float32 [nrows][DECAY_NPARAMS]: EDT, T20, T30 (seconds), C50, C80 (dB), D50, Ts (seconds) of every row of a curve in one sweep
+        (rvb_decay_params; columns DECAY_EDT .. DECAY_TS); NaN where a parameter is not available.  Synchronous."""
+        params = np.zeros((int(nrows), DECAY_NPARAMS), dtype=np.float32)
+        self._check(self.lib.rvb_decay_params(self.handle, _vp(device_curve_pointer), _u64(nrows), _u64(nbins), ctypes.c_float(sample_rate),
+                                              _ptr(params)))
+        return params
+
+    def decay_params_loss(self, device_histogram_pointer, device_curve_pointer, nrows, nbins, sample_rate, targets, param_weights,
+                          device_weights_pointer=None):
+        """(loss_rows float64 [nrows], params float32 [nrows][DECAY_NPARAMS]): loss_rows = sum_p param_weights (q - targets)^2 over the
+        parameters with a weight > 0 and a finite model value q (rvb_decay_params_loss); targets and param_weights are host arrays
+        [nrows][DECAY_NPARAMS].  With device_weights_pointer the adjoint w = dL/dH goes there in H's layout: what reshade_grad takes.
+        Synchronous."""
+        targets = np.ascontiguousarray(targets, dtype=np.float32).reshape(int(nrows), DECAY_NPARAMS)
+        param_weights = np.ascontiguousarray(param_weights, dtype=np.float32).reshape(int(nrows), DECAY_NPARAMS)
+        loss_rows = np.zeros(int(nrows), dtype=np.float64)
+        params = np.zeros((int(nrows), DECAY_NPARAMS), dtype=np.float32)
+        self._check(self.lib.rvb_decay_params_loss(self.handle, _vp(device_histogram_pointer), _vp(device_curve_pointer), _u64(nrows), _u64(nbins),
+                                                   ctypes.c_float(sample_rate), _ptr(targets), _ptr(param_weights), _ptr(loss_rows), _ptr(params),
+                                                   _vp(device_weights_pointer) if device_weights_pointer else None))
+        return loss_rows, params
+
     @staticmethod
     def _decay_rows(tensor, *others):
         """(nrows, nbins) of a float32 CUDA tensor [..., nbins] whose leading dimensions are the rows; the others have its shape."""
@@ -625,6 +654,24 @@ class Context:
         loss = self.decay_loss(histogram.data_ptr(), curve.data_ptr(), target.data_ptr(), mask.data_ptr(), nrows, nbins, flags,
                                weights.data_ptr() if weights is not None else None)
         return loss.reshape(tuple(histogram.shape[:-1]))
+
+    def decay_params_tensor(self, curve, sample_rate):
+        """decay_params on a torch CUDA tensor [..., nbins]: float32 of the leading shape with DECAY_NPARAMS behind it — [nchannels][8][7]
+        for a curve [nchannels][8][nbins]."""
+        nrows, nbins = self._decay_rows(curve)
+        self.ir_accumulate_wait_for_torch()
+        return self.decay_params(curve.data_ptr(), nrows, nbins, sample_rate).reshape(tuple(curve.shape[:-1]) + (DECAY_NPARAMS,))
+
+    def decay_params_loss_tensor(self, histogram, curve, sample_rate, targets, param_weights, weights=None):
+        """decay_params_loss on torch CUDA tensors of one shape [..., nbins]: (losses float64 of the leading shape, params float32 of the
+        leading shape with DECAY_NPARAMS behind it); targets and param_weights are host arrays of the params' shape; `weights` (a tensor of
+        the histogram's shape, or None) receives dL/dH and is complete when the call returns."""
+        nrows, nbins = self._decay_rows(histogram, curve, *((weights,) if weights is not None else ()))
+        self.ir_accumulate_wait_for_torch()
+        loss, params = self.decay_params_loss(histogram.data_ptr(), curve.data_ptr(), nrows, nbins, sample_rate, targets, param_weights,
+                                              weights.data_ptr() if weights is not None else None)
+        lead = tuple(histogram.shape[:-1])
+        return loss.reshape(lead), params.reshape(lead + (DECAY_NPARAMS,))
 
     def ir_download(self, trim_predelay, sample_rate, mode=IR_FAST):
         """attenuate -> fixPredelay -> flattenImpulses (reference cmd/main.cpp:280-298) -> [nch][8][nbins]."""

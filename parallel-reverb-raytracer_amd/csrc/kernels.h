@@ -177,6 +177,34 @@ void rvb_launch_decay_loss_sums(const float * curve, const float * target, const
 void rvb_launch_decay_loss_carry(const float * curve, uint64_t nrows, uint64_t nbins, bool normalised, double * tiles, double * loss_rows, hipStream_t s);
 void rvb_launch_decay_loss_scan(const float * hist, const float * curve, const float * target, const float * mask, uint64_t nrows, uint64_t nbins,
                                 bool normalised, const double * tiles, float * weights, hipStream_t s);
+// Room acoustic parameters of a curve and their adjoint (decay_params_kernels.hip; rvb_decay_params / rvb_decay_params_loss), in the
+// tile shape of the decay kernels.  `first` is [5][nrows][tiles] bin numbers — the first bin at or below 0 dB, below -10 dB, at or below
+// -5 dB, below -25 dB, below -35 dB —, `window` [nrows][5] the same per row, `tiles` four planes of [nrows][tiles] doubles: sum xc level
+// of the EDT, T20 and T30 windows and sum E over the bins behind bin 0 (the adjoint reuses plane 0 for sum g).
+struct DecayParamsRatios { double r[5]; };                // 10^(db / 10) for 0, -10, -5, -25, -35 dB
+// What decay_params_fit_kernel leaves per row for the adjoint, with c_p = 2 weight (q - target), 0 for a parameter that does not count:
+// every term of g[k] = dL/dE[k] but for E[k] itself, so that the adjoint kernels evaluate g from E on the fly.
+struct DecayParamsRow {
+    double time_coef[3];      // EDT, T20, T30: c_p (60 / (s^2 fs)) C10 / Sxx; g[k] += time_coef xc_k / E[k] inside [k0, k1)
+    double centre[3];         // (n - 1) / 2: xc_k = (k - k0) - centre
+    double c_zero[2], c_at[2];// C50, C80: g[0] += c C10 / early; g[ke] -= c C10 (1 / early + 1 / late)
+    double d_zero, d_at;      // D50: g[0] += c E[k50] / E[0]^2; g[k50] -= c / E[0]
+    double ts_zero, ts_each;  // Ts: g[0] -= c Ts / E[0]; g[k] += c / (fs E[0]) for every k >= 1
+    uint32_t k0[3], k1[3];    // the windows; k0 == k1 == 0 where the time does not count
+    uint32_t ke[2];           // bin of 50 ms and of 80 ms; 0xFFFFFFFF: behind the row's end
+    uint32_t counts;          // any parameter of the row counts
+};
+void rvb_launch_decay_params_find(const float * curve, uint64_t nrows, uint64_t nbins, const DecayParamsRatios & ratios, uint32_t * first, hipStream_t s);
+void rvb_launch_decay_params_window(const uint32_t * first, uint64_t nrows, uint64_t nbins, uint32_t * window, hipStream_t s);
+void rvb_launch_decay_params_sums(const float * curve, uint64_t nrows, uint64_t nbins, const uint32_t * window, double * tiles, hipStream_t s);
+// ke50 / ke80: 0xFFFFFFFF where the bin lies behind the row's end; targets / param_weights: device [nrows][7], or both null (no loss)
+void rvb_launch_decay_params_fit(const float * curve, uint64_t nrows, uint64_t nbins, const uint32_t * window, const double * tiles, double sample_rate,
+                                 uint32_t ke50, uint32_t ke80, const float * targets, const float * param_weights, float * params,
+                                 DecayParamsRow * rows, double * loss_rows, hipStream_t s);
+void rvb_launch_decay_params_adjoint_sums(const float * curve, uint64_t nrows, uint64_t nbins, const DecayParamsRow * rows, double * tiles, hipStream_t s);
+void rvb_launch_decay_params_adjoint_carry(uint64_t nrows, uint64_t nbins, double * tiles, hipStream_t s);
+void rvb_launch_decay_params_adjoint_scan(const float * hist, const float * curve, uint64_t nrows, uint64_t nbins, const DecayParamsRow * rows,
+                                          const double * tiles, float * weights, hipStream_t s);
 // Grouping of the work records by the leaf position of the triangle they start from (rocprim_sort.hip):
 // order[] lists the records bucket by bucket and the shadow kernel walks that list.
 size_t rvb_group_records_temp_bytes(uint64_t n);

@@ -1,4 +1,4 @@
-"""Fitting materials to a measured decay: the loop a user of rvb_reshade / rvb_reshade_grad would otherwise write (include/rvb_capi.h).
+"""Fitting materials to a measured decay — a decay curve (fit_decay) or a table of room acoustic parameters (fit_params): the loop a user of rvb_reshade / rvb_reshade_grad would otherwise write (include/rvb_capi.h).
 
 One evaluation never leaves the device but for a few floats per row:
 
@@ -7,6 +7,7 @@ One evaluation never leaves the device but for a few floats per row:
     ir_accumulate(IR_EXACT) into a zeroed H      the exact mode adds in a fixed order: L is repeatable bit for bit
     decay_curve(H) -> E                          Schroeder integral
     decay_loss(H, E, target, mask) -> L, w       w = dL/dH in H's layout
+      or decay_params_loss(H, E, targets, param_weights) -> L, w, params      against measured EDT, T20, T30, C50, C80, D50, Ts
     reshade_grad(w) -> dL/dtable, dL/dair        chain rule through the binning
     (reshade_grad_map(w) -> dL/dtable per TRIANGLE: decay_sensitivity_map, "where on the walls"; needs keep_paths(True, listener=True))
 
@@ -33,19 +34,27 @@ def _on_device(x, shape):
     return x
 
 
-def _forward(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, want_weights):
-    """The evaluation up to the loss: (loss, curve, weights), the tensors [nchannels][8][nbins]; weights = dL/dH, or None."""
+def _histogram_and_curve(ctx, table, air, mic, speakers, sample_rate, predelay, nbins):
+    """The front of every evaluation: re-shade, bin exactly, integrate.  (hist, curve), tensors [nchannels][8][nbins]; the curve is
+    enqueued on the context's stream, where the loss calls find it."""
     import torch
     ctx.reshade(table, air)
     ctx.ir_configure_speakers(mic, speakers[0], speakers[1], capi.IR_DIFFUSE, None)
+    hist = torch.zeros((ctx.nchannels, 8, int(nbins)), dtype=torch.float32, device="cuda")
+    curve = torch.empty_like(hist)
+    ctx.ir_accumulate_tensor(predelay, sample_rate, nbins, capi.IR_EXACT, hist)      # (waits for torch's stream: the zero fill, the uploads)
+    ctx.decay_curve(hist.data_ptr(), ctx.nchannels * 8, nbins, curve.data_ptr())
+    return hist, curve
+
+
+def _forward(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, want_weights):
+    """The evaluation up to the loss: (loss, curve, weights), the tensors [nchannels][8][nbins]; weights = dL/dH, or None."""
+    import torch
     shape = (ctx.nchannels, 8, int(nbins))
     nrows = ctx.nchannels * 8
     target, mask = _on_device(target, shape), _on_device(mask, shape)
-    hist = torch.zeros(shape, dtype=torch.float32, device="cuda")
-    curve = torch.empty_like(hist)
+    hist, curve = _histogram_and_curve(ctx, table, air, mic, speakers, sample_rate, predelay, nbins)
     weights = torch.empty_like(hist) if want_weights else None
-    ctx.ir_accumulate_tensor(predelay, sample_rate, nbins, capi.IR_EXACT, hist)      # (waits for torch's stream: the zero fill, the uploads)
-    ctx.decay_curve(hist.data_ptr(), nrows, nbins, curve.data_ptr())
     loss_rows = ctx.decay_loss(hist.data_ptr(), curve.data_ptr(), target.data_ptr(), mask.data_ptr(), nrows, nbins,
                                capi.DECAY_NORMALISED if normalised else 0, weights.data_ptr() if want_weights else None)
     return float(loss_rows.sum()), curve, weights
@@ -94,23 +103,15 @@ ARMIJO_C = 1e-4
 MAX_HALVINGS = 30
 
 
-def fit_decay(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, free, steps, lower=0.01, upper=0.99,
-              normalised=True):
-    """Projected gradient descent on the coefficients of `table` that the boolean array `free` ([nsurfaces][16], the layout of
-    `coefficients`) marks; every other entry keeps its bits.  A step from theta with gradient g tries theta(t) = clip(theta - t g, lower,
-    upper) and halves t until the Armijo condition L(theta(t)) <= L(theta) - c g.(theta - theta(t)) holds, c = 1e-4 (without clipping
-    that is L - c t |g|^2); a step that never satisfies it within 30 halvings ends the fit.  Only steps that satisfy it are taken.  The
-    first t moves the steepest coefficient by 0.25; later steps start from twice the last accepted t.
-
-    Returns (table, record): the fitted table (a copy) and one dict per accepted step — loss_before, loss, step (the accepted t),
-    halvings, descent (g.(theta - theta(t))).  The air is held fixed.  Scope: see the module text."""
+def _fit(ctx, table, air, free, steps, lower, upper, loss_and_grad, loss_only):
+    """The projected-gradient / Armijo loop of fit_decay and fit_params: loss_and_grad(table) -> (loss, grad_surfaces),
+    loss_only(table) -> loss."""
     table = aligned_copy(np.ascontiguousarray(table, dtype=SURFACE))
     free = np.asarray(free, dtype=bool).reshape(table.shape[0], 16)
-    args = (air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised)
     record = []
     t = None
     for _ in range(int(steps)):
-        loss, grads, _, _ = _evaluate(ctx, table, *args, True)
+        loss, grads = loss_and_grad(table)
         theta = coefficients(table)
         g = np.where(free, coefficients(np.ascontiguousarray(grads)), np.float32(0.0)).astype(np.float64)
         steepest = np.abs(g).max()
@@ -123,7 +124,7 @@ def fit_decay(ctx, table, air, mic, speakers, target, mask, sample_rate, predela
             moved = np.clip(theta.astype(np.float64) - t * g, lower, upper).astype(np.float32)
             coefficients(trial)[free] = moved[free]
             descent = float((g * (theta.astype(np.float64) - coefficients(trial).astype(np.float64))).sum())
-            trial_loss = decay_loss(ctx, trial, *args[:-1], normalised=normalised)
+            trial_loss = loss_only(trial)
             if descent > 0 and trial_loss <= loss - ARMIJO_C * descent:
                 accepted = (trial, trial_loss, descent, halvings)
                 break
@@ -134,3 +135,63 @@ def fit_decay(ctx, table, air, mic, speakers, target, mask, sample_rate, predela
         record.append({"loss_before": loss, "loss": accepted[1], "step": t, "halvings": accepted[3], "descent": accepted[2]})
     ctx.reshade(table, air)
     return table, record
+
+
+def fit_decay(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, free, steps, lower=0.01, upper=0.99,
+              normalised=True):
+    """Projected gradient descent on the coefficients of `table` that the boolean array `free` ([nsurfaces][16], the layout of
+    `coefficients`) marks; every other entry keeps its bits.  A step from theta with gradient g tries theta(t) = clip(theta - t g, lower,
+    upper) and halves t until the Armijo condition L(theta(t)) <= L(theta) - c g.(theta - theta(t)) holds, c = 1e-4 (without clipping
+    that is L - c t |g|^2); a step that never satisfies it within 30 halvings ends the fit.  Only steps that satisfy it are taken.  The
+    first t moves the steepest coefficient by 0.25; later steps start from twice the last accepted t.
+
+    Returns (table, record): the fitted table (a copy) and one dict per accepted step — loss_before, loss, step (the accepted t),
+    halvings, descent (g.(theta - theta(t))).  The air is held fixed.  Scope: see the module text."""
+    args = (air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised)
+    return _fit(ctx, table, air, free, steps, lower, upper,
+                lambda candidate: _evaluate(ctx, candidate, *args, True)[:2], lambda candidate: _evaluate(ctx, candidate, *args, False)[0])
+
+
+# ---- fitting to a table of measured room acoustic parameters (rvb_decay_params_loss) ------------------------------------------------
+
+def _evaluate_params(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, want_grad):
+    import torch
+    hist, curve = _histogram_and_curve(ctx, table, air, mic, speakers, sample_rate, predelay, nbins)
+    weights = torch.empty_like(hist) if want_grad else None
+    shape = (ctx.nchannels * 8, capi.DECAY_NPARAMS)
+    loss_rows, params = ctx.decay_params_loss(hist.data_ptr(), curve.data_ptr(), ctx.nchannels * 8, nbins, sample_rate,
+                                              np.asarray(targets, dtype=np.float32).reshape(shape),
+                                              np.asarray(param_weights, dtype=np.float32).reshape(shape), weights.data_ptr() if want_grad else None)
+    params = params.reshape(ctx.nchannels, 8, capi.DECAY_NPARAMS)
+    if not want_grad:
+        return float(loss_rows.sum()), None, None, params
+    grads, grad_air = ctx.reshade_grad(predelay, sample_rate, nbins, weights.data_ptr())
+    return float(loss_rows.sum()), grads, grad_air, params
+
+
+def params_loss_and_grad(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins):
+    """(loss, grad_surfaces, grad_air, params) of the kept trace in `ctx` under the surface table `table` and the air coefficients `air`
+    against a measured table: targets and param_weights are [nchannels][8][7] (columns capi.DECAY_EDT .. capi.DECAY_TS: EDT, T20, T30 in
+    seconds, C50, C80 in dB, D50, Ts in seconds); loss = sum over the rows and parameters of param_weights (model - targets)^2
+    (rvb_decay_params_loss: a weight of 0 leaves a parameter out, 1 / target^2 gives relative errors, a parameter that the model's curve
+    does not yield adds nothing), its gradient as a SURFACE array and a float32[8] (rvb_reshade_grad), and the model's parameters, float32
+    [nchannels][8][7], NaN where not available.  speakers = (directions, coefficients).  Leaves the context re-shaded with `table`.
+
+    SCOPE: that of rvb_reshade_grad (see the module text) — the diffuse records only.  The early-energy parameters C50, C80, D50 and Ts
+    are therefore those of the DIFFUSE response: the direct sound and the image sources, which a measurement's early energy holds, are
+    not in the model's curve."""
+    return _evaluate_params(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, True)
+
+
+def params_loss(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins):
+    """The loss of params_loss_and_grad alone (no weights, no gradient), bit for bit: what a line search evaluates."""
+    return _evaluate_params(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, False)[0]
+
+
+def fit_params(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, free, steps, lower=0.01, upper=0.99):
+    """fit_decay's loop — projected gradient descent with Armijo steps on the coefficients that `free` marks, the same record — on the
+    loss of params_loss_and_grad: calibrates materials to a table of measured T30, EDT, C80, ...  Returns (table, record).  The air is
+    held fixed.  Scope: see params_loss_and_grad."""
+    args = (air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins)
+    return _fit(ctx, table, air, free, steps, lower, upper,
+                lambda candidate: _evaluate_params(ctx, candidate, *args, True)[:2], lambda candidate: _evaluate_params(ctx, candidate, *args, False)[0])

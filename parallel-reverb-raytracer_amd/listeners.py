@@ -6,24 +6,22 @@ One source, many microphones: the context holds ONE trace made with keep_paths(T
     ir_configure_speakers(..., IR_DIFFUSE)       (a relisten voids the IR configuration)
     ir_accumulate(mode) into a zeroed H          the exact mode adds in a fixed order: the times are repeatable bit for bit
     decay_curve(H) -> E                          Schroeder integral
-    decay_times(E)                               T30 (db_begin, db_end = -5, -35), EDT (0, -10), ...
+    decay_times(E)                               T30 (db_begin, db_end = -5, -35), EDT (0, -10), ...           (decay_map)
+      or decay_params(E)                         EDT, T20, T30, C50, C80, D50, Ts in one sweep                (parameter_map)
 
-and nothing leaves the device but eight floats per channel.  SCOPE: that of rvb_relisten — a single-pair trace on one context —, the
-diffuse records only (IR_DIFFUSE), the speaker model; the histogram starts at time 0 (no predelay), so that every listener's bins mean
-the same times."""
+and nothing leaves the device but eight (or 56) floats per channel.  SCOPE: that of rvb_relisten — a single-pair trace on one context
+—, the diffuse records only (IR_DIFFUSE), the speaker model; the histogram starts at time 0 (no predelay), so that every listener's
+bins mean the same times."""
 import numpy as np
 
 from . import capi
 
 
-def decay_map(ctx, mics, speakers, sample_rate, nbins, db_begin=-5.0, db_end=-35.0, mode=capi.IR_EXACT):
-    """float32 [nlisteners][nchannels][8]: the reverberation time in seconds of every (channel, band) row at every microphone of `mics`
-    ([nlisteners][3]), NaN where the curve does not reach db_end within nbins bins.  speakers = (directions, coefficients).  Leaves the
-    context relistened at the last microphone."""
+def _curves(ctx, mics, speakers, sample_rate, nbins, mode):
+    """Per listener (i, curve): the decay curve [nchannels][8][nbins] of the kept trace heard at mics[i], enqueued on the context's stream.
+    One histogram and one curve serve all listeners."""
     import torch
-    mics = np.asarray(mics, dtype=np.float32).reshape(-1, 3)
     nchannels = len(speakers[1])
-    out = np.zeros((mics.shape[0], nchannels, 8), dtype=np.float32)
     hist = torch.empty((nchannels, 8, int(nbins)), dtype=torch.float32, device="cuda")
     curve = torch.empty_like(hist)
     for i, mic in enumerate(mics):
@@ -32,5 +30,29 @@ def decay_map(ctx, mics, speakers, sample_rate, nbins, db_begin=-5.0, db_end=-35
         hist.zero_()
         ctx.ir_accumulate_tensor(0.0, sample_rate, nbins, mode, hist)       # (waits for torch's stream: the zero fill)
         ctx.decay_curve(hist.data_ptr(), nchannels * 8, nbins, curve.data_ptr())
+        yield i, curve
+
+
+def decay_map(ctx, mics, speakers, sample_rate, nbins, db_begin=-5.0, db_end=-35.0, mode=capi.IR_EXACT):
+    """float32 [nlisteners][nchannels][8]: the reverberation time in seconds of every (channel, band) row at every microphone of `mics`
+    ([nlisteners][3]), NaN where the curve does not reach db_end within nbins bins.  speakers = (directions, coefficients).  Leaves the
+    context relistened at the last microphone."""
+    mics = np.asarray(mics, dtype=np.float32).reshape(-1, 3)
+    nchannels = len(speakers[1])
+    out = np.zeros((mics.shape[0], nchannels, 8), dtype=np.float32)
+    for i, curve in _curves(ctx, mics, speakers, sample_rate, nbins, mode):
         out[i] = ctx.decay_times(curve.data_ptr(), nchannels * 8, nbins, sample_rate, db_begin, db_end).reshape(nchannels, 8)     # synchronous
+    return out
+
+
+def parameter_map(ctx, mics, speakers, sample_rate, nbins, mode=capi.IR_EXACT):
+    """float32 [nlisteners][nchannels][8][7]: EDT, T20, T30 (seconds), C50, C80 (dB), D50 and Ts (seconds) of every (channel, band) row at
+    every microphone of `mics` ([nlisteners][3]) in one sweep per listener (rvb_decay_params; columns capi.DECAY_EDT .. capi.DECAY_TS), NaN
+    where a parameter is not available.  The time columns are decay_map's for the same arguments, byte for byte; the early-energy
+    parameters are those of the diffuse response.  Leaves the context relistened at the last microphone."""
+    mics = np.asarray(mics, dtype=np.float32).reshape(-1, 3)
+    nchannels = len(speakers[1])
+    out = np.zeros((mics.shape[0], nchannels, 8, capi.DECAY_NPARAMS), dtype=np.float32)
+    for i, curve in _curves(ctx, mics, speakers, sample_rate, nbins, mode):
+        out[i] = ctx.decay_params(curve.data_ptr(), nchannels * 8, nbins, sample_rate).reshape(nchannels, 8, capi.DECAY_NPARAMS)     # synchronous
     return out
