@@ -17,6 +17,7 @@
 //                 listed twice, as the single-GPU tests do) are summed with peer copies and an add kernel instead.
 #include "../../include/rvb_capi.h"
 #include "hip_owned.h"
+#include "image_merge.h"
 
 #include <dlfcn.h>
 
@@ -284,23 +285,15 @@ int rvb_multi_get_diffuse(rvb_multi * m, rvb_impulse * out)
 static int merged_images(rvb_multi * m, int remove_direct, std::vector<rvb_impulse> & images)
 {
     std::vector<rvb_image_candidate> all;
-    for (Shard & s : m->shards) {
-        uint64_t n = 0;
-        int rc = rvb_get_image_candidates(s.ctx, nullptr, 0, &n);
-        if (rc != RVB_OK) return mfail(m, rc, rvb_last_error(s.ctx));
-        const size_t at = all.size();
-        all.resize(at + n);
-        if (n && (rc = rvb_get_image_candidates(s.ctx, all.data() + at, n, &n)) != RVB_OK) return mfail(m, rc, rvb_last_error(s.ctx));
-    }
+    int rc;
+    for (Shard & s : m->shards)
+        if ((rc = append_image_candidates(s.ctx, all)) != RVB_OK) return mfail(m, rc, rvb_last_error(s.ctx));
     rvb_impulse direct;
     std::memset(&direct, 0, sizeof(direct));
-    int rc = rvb_get_direct(m->shards[0].ctx, &direct);       // the same on every device
+    rc = rvb_get_direct(m->shards[0].ctx, &direct);           // the same on every device
     if (rc != RVB_OK) return mfail(m, rc, rvb_last_error(m->shards[0].ctx));
-    const rvb_impulse * direct_ptr = m->nrays ? &direct : nullptr;
-    uint64_t count = 0;
-    if ((rc = rvb_merge_images(all.data(), all.size(), direct_ptr, remove_direct, nullptr, 0, &count)) != RVB_OK) return mfail(m, rc, "rvb_merge_images");
-    images.resize(count);
-    if ((rc = rvb_merge_images(all.data(), all.size(), direct_ptr, remove_direct, images.data(), count, &count)) != RVB_OK) return mfail(m, rc, "rvb_merge_images");
+    // (no rays, no direct path)
+    if ((rc = merge_images(all.data(), all.size(), m->nrays ? &direct : nullptr, remove_direct, images)) != RVB_OK) return mfail(m, rc, "rvb_merge_images");
     return RVB_OK;
 }
 
