@@ -7,17 +7,10 @@ import re
 
 import numpy as np
 
+from host_lib import built_library
 from parallel_reverb_raytracer_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RVB_ERR_INVALID = 1
-
-
-def _lib():
-    if not os.path.exists(capi.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return capi.load_library()
 
 
 def test_header_declares_the_entry_points_and_the_contract():
@@ -38,22 +31,22 @@ def test_header_declares_the_entry_points_and_the_contract():
 
 
 def test_library_exports_the_entry_points():
-    lib = _lib()
+    lib = built_library()
     for name, nargs in (("rvb_decay_curve", 5), ("rvb_decay_times", 8), ("rvb_decay_loss", 10)):
         assert name in capi.SYMBOLS and hasattr(lib, name)
         assert getattr(lib, name).argtypes is not None and len(getattr(lib, name).argtypes) == nargs
 
 
 def test_a_null_handle_is_refused_and_the_host_outputs_stay():
-    lib = _lib()
+    lib = built_library()
     fake = [ctypes.c_void_p(4096 * (i + 1)) for i in range(5)]          # never dereferenced: the handle is looked at first
     seconds = np.full(4, 7.0, dtype=np.float32)
     losses = np.full(4, 7.0, dtype=np.float64)
-    assert lib.rvb_decay_curve(None, fake[0], 4, 100, fake[1]) == RVB_ERR_INVALID
-    assert lib.rvb_decay_times(None, fake[0], 4, 100, 44100.0, -5.0, -35.0, seconds.ctypes.data_as(ctypes.c_void_p)) == RVB_ERR_INVALID
+    assert lib.rvb_decay_curve(None, fake[0], 4, 100, fake[1]) == capi.ERR_INVALID
+    assert lib.rvb_decay_times(None, fake[0], 4, 100, 44100.0, -5.0, -35.0, seconds.ctypes.data_as(ctypes.c_void_p)) == capi.ERR_INVALID
     for weights in (fake[4], None):
         assert lib.rvb_decay_loss(None, fake[0], fake[1], fake[2], fake[3], 4, 100, capi.DECAY_NORMALISED,
-                                  losses.ctypes.data_as(ctypes.c_void_p), weights) == RVB_ERR_INVALID
+                                  losses.ctypes.data_as(ctypes.c_void_p), weights) == capi.ERR_INVALID
     assert (seconds == 7.0).all() and (losses == 7.0).all()
 
 

@@ -7,18 +7,11 @@ import re
 
 import numpy as np
 
+from host_lib import built_library
 from parallel_reverb_raytracer_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RVB_ERR_INVALID = 1
 NAMES = ("EDT", "T20", "T30", "C50", "C80", "D50", "TS")
-
-
-def _lib():
-    if not os.path.exists(capi.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return capi.load_library()
 
 
 def test_header_declares_the_entry_points_the_enum_and_the_contract():
@@ -41,23 +34,23 @@ def test_header_declares_the_entry_points_the_enum_and_the_contract():
 
 
 def test_library_exports_the_entry_points():
-    lib = _lib()
+    lib = built_library()
     for name, nargs in (("rvb_decay_params", 6), ("rvb_decay_params_loss", 11)):
         assert name in capi.SYMBOLS and hasattr(lib, name)
         assert getattr(lib, name).argtypes is not None and len(getattr(lib, name).argtypes) == nargs
 
 
 def test_a_null_handle_is_refused_and_the_host_outputs_stay():
-    lib = _lib()
+    lib = built_library()
     fake = [ctypes.c_void_p(4096 * (i + 1)) for i in range(3)]          # never dereferenced: the handle is looked at first
     params = np.full((4, 7), 7.0, dtype=np.float32)
     losses = np.full(4, 7.0, dtype=np.float64)
     targets, weights = np.ones((4, 7), dtype=np.float32), np.ones((4, 7), dtype=np.float32)
     pp, lp = params.ctypes.data_as(ctypes.c_void_p), losses.ctypes.data_as(ctypes.c_void_p)
     tp, wp = targets.ctypes.data_as(ctypes.c_void_p), weights.ctypes.data_as(ctypes.c_void_p)
-    assert lib.rvb_decay_params(None, fake[0], 4, 100, 44100.0, pp) == RVB_ERR_INVALID
+    assert lib.rvb_decay_params(None, fake[0], 4, 100, 44100.0, pp) == capi.ERR_INVALID
     for d_weights in (fake[2], None):
-        assert lib.rvb_decay_params_loss(None, fake[0], fake[1], 4, 100, 44100.0, tp, wp, lp, pp, d_weights) == RVB_ERR_INVALID
+        assert lib.rvb_decay_params_loss(None, fake[0], fake[1], 4, 100, 44100.0, tp, wp, lp, pp, d_weights) == capi.ERR_INVALID
     assert (params == 7.0).all() and (losses == 7.0).all()
 
 

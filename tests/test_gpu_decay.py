@@ -25,7 +25,6 @@ import decay_reference as ref
 
 pytestmark = pytest.mark.gpu
 
-RVB_ERR_INVALID, RVB_ERR_CAPACITY = 1, 5
 T = 4096
 ALL_BINS = [1, 2, 63, 64, 65, T - 1, T, T + 1, 2 * T + 63, 2 * T + 65]
 SHAPES = [(16, n) for n in ALL_BINS] + [(r, 2 * T + 65) for r in (1, 8, 72)]
@@ -264,7 +263,7 @@ def test_arguments(ctx):
     def loss(*a):
         return lib.rvb_decay_loss(handle, *a)
 
-    inv, cap = RVB_ERR_INVALID, RVB_ERR_CAPACITY
+    inv, cap = capi.ERR_INVALID, capi.ERR_CAPACITY
     assert curve(None, nrows, nbins, e) == inv and curve(h, nrows, nbins, None) == inv
     assert curve(h, 0, nbins, e) == inv and curve(h, nrows, 0, e) == inv
     assert curve(h, nrows, nbins, h) == inv and curve(h, nrows, nbins, h + 4 * (nrows * nbins - 1)) == inv and curve(h + 40, nrows, nbins, h) == inv

@@ -23,7 +23,6 @@ from test_gpu_decay import T, case, dev, exponential_curves, histogram, names_of
 
 pytestmark = pytest.mark.gpu
 
-RVB_ERR_INVALID, RVB_ERR_CAPACITY = 1, 5
 BIG = 2 * T + 65
 # 51200 Hz: k50 = 2560, k80 = T; 51187.5 / 51212.5: k80 = T - 1 / T + 1; 500 Hz at 65 bins: k50 = 25, k80 = 40; 25600 Hz at 8 x (T - 1):
 # k80 = 2048, one bin behind the start of row 1's zero tail (its C80 is NaN, its C50 is not); (2, 130 T + 5): the carry wave's rounds
@@ -150,6 +149,7 @@ def test_window_edges_on_tile_edges(ctx):
 def test_arguments(ctx):
     """Every refusal of the two calls; a failed call writes nothing, on the device or on the host."""
     import torch
+    from parallel_reverb_raytracer_amd import capi
     lib, handle = ctx.lib, ctx.handle
     nrows, nbins, fs = 4, 100, 44100.0
     bufs = [torch.full((nrows * nbins + 50,), 7.0, dtype=torch.float32, device="cuda") for _ in range(3)]
@@ -167,7 +167,7 @@ def test_arguments(ctx):
     def loss(*a):
         return lib.rvb_decay_params_loss(handle, *a)
 
-    inv, cap = RVB_ERR_INVALID, RVB_ERR_CAPACITY
+    inv, cap = capi.ERR_INVALID, capi.ERR_CAPACITY
     assert plain(None, nrows, nbins, fs, pp) == inv and plain(e, nrows, nbins, fs, None) == inv
     assert plain(e, 0, nbins, fs, pp) == inv and plain(e, nrows, 0, fs, pp) == inv
     assert plain(e, 4097, nbins, fs, pp) == cap and "4096" in lib.rvb_last_error(handle).decode()

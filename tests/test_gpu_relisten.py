@@ -17,7 +17,6 @@ from test_gpu_source_pattern import FACING, SHAPES, bits, expected_records, orac
 
 pytestmark = pytest.mark.gpu
 
-RVB_ERR_INVALID, RVB_ERR_STATE = 1, 4
 # A is the scene's own microphone (asserted in the fixture); the direct path is visible from A and C and hidden from B
 MICS = {"A": (14.0, 1.6, -0.9), "B": (9.12, 0.4, -8.33), "C": (-10.28, 3.85, -2.24)}
 SOURCE_2 = (-12.0, 2.5, 3.0)
@@ -221,7 +220,7 @@ def test_every_pair_of_trace_pairs_is_relistened(ctx, oracle, cathedral):
         assert_pairs([first["A"], second["C"]])
         with pytest.raises(capi.RvbError) as e:
             ctx.relisten(MICS["B"])                                  # one microphone for two pairs
-        assert e.value.code == RVB_ERR_INVALID
+        assert e.value.code == capi.ERR_INVALID
         ctx.relisten([MICS["B"], MICS["A"]])
         relisten_names(ctx)
         assert_pairs([first["B"], second["A"]])
@@ -309,25 +308,25 @@ def test_state_and_arguments(oracle, cathedral):
     c = capi.Context(0)
     try:
         c.set_scene(cathedral["scene"])
-        refused(c, RVB_ERR_STATE)                                    # before any trace
+        refused(c, capi.ERR_STATE)                                    # before any trace
         c.keep_paths(True)
         c.raytrace(a["mic"], a["source"], a["dirs"], 24, AIR_COEFFICIENTS)
-        assert "RVB_KEEP_LISTENER" in refused(c, RVB_ERR_STATE)      # kept for re-shading only
+        assert "RVB_KEEP_LISTENER" in refused(c, capi.ERR_STATE)      # kept for re-shading only
         assert_state(c, a)
         c.keep_paths(True, listener=True)
-        refused(c, RVB_ERR_STATE)                                    # switching it on afterwards does not change that
+        refused(c, capi.ERR_STATE)                                    # switching it on afterwards does not change that
         c.raytrace(a["mic"], a["source"], a["dirs"], 24, AIR_COEFFICIENTS)
-        refused(c, RVB_ERR_INVALID, [MICS["B"], MICS["C"]])          # two microphones for one pair
-        refused(c, RVB_ERR_INVALID, (1.0, float("nan"), 0.0))
-        refused(c, RVB_ERR_INVALID, (float("inf"), 0.0, 0.0))
+        refused(c, capi.ERR_INVALID, [MICS["B"], MICS["C"]])          # two microphones for one pair
+        refused(c, capi.ERR_INVALID, (1.0, float("nan"), 0.0))
+        refused(c, capi.ERR_INVALID, (float("inf"), 0.0, 0.0))
         assert_state(c, a)                                           # a failed relisten leaves the trace's results
         c.relisten(MICS["C"])
         assert_state(c, cases["C"])
         c.set_directions(a["dirs"])
-        refused(c, RVB_ERR_STATE)
+        refused(c, capi.ERR_STATE)
         c.trace(a["mic"], a["source"], 24, AIR_COEFFICIENTS)
         c.keep_paths(False)
-        refused(c, RVB_ERR_STATE)                                    # the side buffers are gone
+        refused(c, capi.ERR_STATE)                                    # the side buffers are gone
         assert_state(c, a)
     finally:
         c.close()

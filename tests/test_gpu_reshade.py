@@ -16,7 +16,6 @@ from test_gpu_speaker_arrays import fast_bound
 
 pytestmark = pytest.mark.gpu
 
-RVB_ERR_INVALID, RVB_ERR_STATE = 1, 4
 NEW_KERNELS = ("path_keep_kernel", "reshade_kernel", "reshade_images_kernel")
 # all eight differ from AIR_COEFFICIENTS
 AIR_B = (AIR_COEFFICIENTS * np.float32(1.7) - np.float32(1e-4)).astype(np.float32)
@@ -381,24 +380,24 @@ def test_state_and_arguments(oracle, cathedral):
     c = capi.Context(0)
     try:
         c.set_scene(cathedral["scene"])
-        refused(c, RVB_ERR_STATE)                                    # before any trace
+        refused(c, capi.ERR_STATE)                                    # before any trace
         c.raytrace(a["mic"], a["source"], a["dirs"], 24, AIR_COEFFICIENTS)
         names = [k for k, _ in c.last_timings()]
         assert names and not any(k in names for k in NEW_KERNELS)   # keeping off: no new kernel
-        refused(c, RVB_ERR_STATE)                                    # the trace was made without keeping
+        refused(c, capi.ERR_STATE)                                    # the trace was made without keeping
         c.keep_paths(True)
-        refused(c, RVB_ERR_STATE)                                    # ... and switching it on afterwards does not change that
+        refused(c, capi.ERR_STATE)                                    # ... and switching it on afterwards does not change that
         c.raytrace(a["mic"], a["source"], a["dirs"], 24, AIR_COEFFICIENTS)
-        refused(c, RVB_ERR_INVALID, cathedral["B"][:-1])             # wrong nsurfaces
+        refused(c, capi.ERR_INVALID, cathedral["B"][:-1])             # wrong nsurfaces
         assert_state(c, a)                                           # a failed re-shade leaves the trace's results
         c.set_directions(a["dirs"])
-        refused(c, RVB_ERR_STATE)
+        refused(c, capi.ERR_STATE)
         c.trace(a["mic"], a["source"], 24, AIR_COEFFICIENTS)
         c.set_scene(cathedral["scene"])
-        refused(c, RVB_ERR_STATE)
+        refused(c, capi.ERR_STATE)
         c.trace(a["mic"], a["source"], 24, AIR_COEFFICIENTS)
         c.keep_paths(False)
-        refused(c, RVB_ERR_STATE)                                    # the side buffers are gone
+        refused(c, capi.ERR_STATE)                                    # the side buffers are gone
         assert_state(c, a)
     finally:
         c.close()

@@ -20,7 +20,6 @@ from test_gpu_source_pattern import FACING, SHAPES
 
 pytestmark = pytest.mark.gpu
 
-RVB_ERR_INVALID, RVB_ERR_STATE = 1, 4
 SECONDS_PER_METER = np.float32(1.0 / 340.0)
 LN_E = float(np.log(np.float64(np.float32(np.e))))
 PROBE = 7          # surfaces per probe trace: bands 0..6 count their bounces, band 7 names the record's own surface
@@ -447,13 +446,13 @@ def test_side_effects_states_and_arguments(oracle, cathedral):
     c = capi.Context(0)
     try:
         c.set_scene(cathedral["scene"])
-        refused(c, RVB_ERR_STATE)                                    # before any trace
+        refused(c, capi.ERR_STATE)                                    # before any trace
         c.raytrace(mic, src, dirs, nrefl, AIR_COEFFICIENTS)
         c.ir_configure_speakers(mic, SPEAKERS[0], SPEAKERS[1], capi.IR_DIFFUSE, None)
-        assert "rvb_keep_paths" in refused(c, RVB_ERR_STATE)         # the trace was made without keeping
+        assert "rvb_keep_paths" in refused(c, capi.ERR_STATE)         # the trace was made without keeping
         c.keep_paths(True)
         c.raytrace(mic, src, dirs, nrefl, AIR_COEFFICIENTS)
-        refused(c, RVB_ERR_STATE)                                    # no IR configuration since the trace
+        refused(c, capi.ERR_STATE)                                    # no IR configuration since the trace
         before = snapshot(c, mic)
         _, nbins = binning_of(c, mic, SPEAKERS, sr)
         w = on_device(weights(2, nbins, 5))
@@ -464,17 +463,17 @@ def test_side_effects_states_and_arguments(oracle, cathedral):
         assert first[0]["specular"].any() and first[0]["diffuse"].any() and first[1].any()
         assert first[0].tobytes() == second[0].tobytes() and first[1].tobytes() == second[1].tobytes()      # one fixed order of summation
         assert snapshot(c, mic) == before                            # the records, the direct slot, the images, the time range
-        refused(c, RVB_ERR_INVALID, nbins=0)
-        refused(c, RVB_ERR_INVALID, rate=float("nan"))
+        refused(c, capi.ERR_INVALID, nbins=0)
+        refused(c, capi.ERR_INVALID, rate=float("nan"))
         c.ir_configure_hrtf(mic, scenes.hrtf_synthetic_table(), (0.0, 0.0, 1.0), (0.0, 1.0, 0.0), capi.IR_DIFFUSE, None)
-        assert "HRTF" in refused(c, RVB_ERR_STATE)
+        assert "HRTF" in refused(c, capi.ERR_STATE)
         c.ir_configure_speakers(mic, SPEAKERS[0], SPEAKERS[1], capi.IR_ALL, c.get_raw_images(False))
-        assert "RVB_IR_DIFFUSE" in refused(c, RVB_ERR_STATE)
+        assert "RVB_IR_DIFFUSE" in refused(c, capi.ERR_STATE)
         nine = ([(np.cos(i), 0.0, np.sin(i)) for i in range(9)], [0.5] * 9)
         c.ir_configure_speakers(mic, nine[0], nine[1], capi.IR_DIFFUSE, None)
-        assert "9 speaker" in refused(c, RVB_ERR_STATE)
+        assert "9 speaker" in refused(c, capi.ERR_STATE)
         assert snapshot(c, mic) == before                            # failed calls leave the results as they were
         c.set_directions(dirs)
-        refused(c, RVB_ERR_STATE)
+        refused(c, capi.ERR_STATE)
     finally:
         c.close()

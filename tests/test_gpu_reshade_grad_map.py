@@ -23,7 +23,6 @@ from test_gpu_source_table import ORIENT, SPREAD
 
 pytestmark = pytest.mark.gpu
 
-RVB_ERR_INVALID, RVB_ERR_STATE, RVB_ERR_CAPACITY = 1, 4, 5
 SR = 44100.0
 OTHER_MIC, OTHER_SOURCE = (0.0, 12.0, 11.0), (0.0, 12.5, 11.5)          # the second pair of tests/test_gpu_reshade_grad.py
 PLACE = np.array([0, 63, 64, 65, 3, 69, 6])                             # its seven surfaces in a table of 70
@@ -319,17 +318,17 @@ def test_side_effects_states_and_arguments(small):
         c.set_scene(small["scene"])
         out = nan_map(c)
         torch.cuda.synchronize()
-        refused(RVB_ERR_STATE)                                       # before any trace
+        refused(capi.ERR_STATE)                                       # before any trace
         c.raytrace(mic, src, dirs, nrefl, AIR_COEFFICIENTS)
         c.ir_configure_speakers(mic, SPEAKERS[0], SPEAKERS[1], capi.IR_DIFFUSE, None)
-        assert "RVB_KEEP_LISTENER" in refused(RVB_ERR_STATE)         # the trace was made without keeping
+        assert "RVB_KEEP_LISTENER" in refused(capi.ERR_STATE)         # the trace was made without keeping
         c.keep_paths(True)
         c.raytrace(mic, src, dirs, nrefl, AIR_COEFFICIENTS)
         c.ir_configure_speakers(mic, SPEAKERS[0], SPEAKERS[1], capi.IR_DIFFUSE, None)
-        assert "RVB_KEEP_LISTENER" in refused(RVB_ERR_STATE)         # kept for the materials alone
+        assert "RVB_KEEP_LISTENER" in refused(capi.ERR_STATE)         # kept for the materials alone
         c.keep_paths(True, listener=True)
         c.raytrace(mic, src, dirs, nrefl, AIR_COEFFICIENTS)
-        assert "configuration" in refused(RVB_ERR_STATE)             # no IR configuration since the trace
+        assert "configuration" in refused(capi.ERR_STATE)             # no IR configuration since the trace
         before = snapshot(c, mic)
         predelay, nbins = binning_of(c, mic, SPEAKERS, SR)
         w = on_device(weights(2, nbins, 5))
@@ -356,44 +355,44 @@ def test_side_effects_states_and_arguments(small):
         map_of(c, predelay, nbins, w)
         with pytest.raises(capi.RvbError) as e:
             c.ir_exact_fold_tensor(nbins, 0, nbins, folded)
-        assert e.value.code == RVB_ERR_STATE
+        assert e.value.code == capi.ERR_STATE
         # arguments
-        refused(RVB_ERR_INVALID, nbins=0)
-        refused(RVB_ERR_INVALID, rate=float("nan"))
-        refused(RVB_ERR_INVALID, predelay=float("inf"))
-        refused(RVB_ERR_INVALID, w=0)
-        refused(RVB_ERR_INVALID, m=None)
-        assert "816" in refused(RVB_ERR_INVALID, ntriangles=815)
-        refused(RVB_ERR_INVALID, ntriangles=817)
+        refused(capi.ERR_INVALID, nbins=0)
+        refused(capi.ERR_INVALID, rate=float("nan"))
+        refused(capi.ERR_INVALID, predelay=float("inf"))
+        refused(capi.ERR_INVALID, w=0)
+        refused(capi.ERR_INVALID, m=None)
+        assert "816" in refused(capi.ERR_INVALID, ntriangles=815)
+        refused(capi.ERR_INVALID, ntriangles=817)
         wide = torch.full((2 * 8 * 4096 + 816 * 16,), float("nan"), dtype=torch.float32, device="cuda")
         torch.cuda.synchronize()
         for offset in (0, 2 * 8 * 4096 - 1):                         # the map on the weights; its first float on their last
-            assert "overlaps" in refused(RVB_ERR_INVALID, w=wide.data_ptr(), m=wide.data_ptr() + 4 * offset)
+            assert "overlaps" in refused(capi.ERR_INVALID, w=wide.data_ptr(), m=wide.data_ptr() + 4 * offset)
         assert torch.isnan(wide).all()
         # states
         c.ir_configure_hrtf(mic, scenes.hrtf_synthetic_table(), (0.0, 0.0, 1.0), (0.0, 1.0, 0.0), capi.IR_DIFFUSE, None)
-        assert "HRTF" in refused(RVB_ERR_STATE)
+        assert "HRTF" in refused(capi.ERR_STATE)
         c.ir_configure_speakers(mic, SPEAKERS[0], SPEAKERS[1], capi.IR_ALL, c.get_raw_images(False))
-        assert "RVB_IR_DIFFUSE" in refused(RVB_ERR_STATE)
+        assert "RVB_IR_DIFFUSE" in refused(capi.ERR_STATE)
         nine = ([(np.cos(i), 0.0, np.sin(i)) for i in range(9)], [0.5] * 9)
         c.ir_configure_speakers(mic, nine[0], nine[1], capi.IR_DIFFUSE, None)
-        assert "9 speaker" in refused(RVB_ERR_STATE)
+        assert "9 speaker" in refused(capi.ERR_STATE)
         assert snapshot(c, mic) == before                            # failed calls leave the results as they were
         # more reflections than a ray's chain checkpoints in LDS hold (the other RVB_ERR_CAPACITY, 2^32 records of a pair, would take
         # 256 GB of term rows: not run)
         c.raytrace(mic, src, dirs[:8], 2049, AIR_COEFFICIENTS)
         c.ir_configure_speakers(mic, SPEAKERS[0], SPEAKERS[1], capi.IR_DIFFUSE, None)
-        assert "2048" in refused(RVB_ERR_CAPACITY)
+        assert "2048" in refused(capi.ERR_CAPACITY)
         c.set_directions(dirs)
-        assert "nothing traced" in refused(RVB_ERR_STATE)            # the directions changed since
+        assert "nothing traced" in refused(capi.ERR_STATE)            # the directions changed since
         # the scratch goes with the kept buffers
         c.raytrace(mic, src, dirs, nrefl, AIR_COEFFICIENTS)
         c.ir_configure_speakers(mic, SPEAKERS[0], SPEAKERS[1], capi.IR_DIFFUSE, None)
         assert map_of(c, predelay, nbins, w).tobytes() == first.tobytes()
         c.keep_paths(False)
-        assert "RVB_KEEP_LISTENER" in refused(RVB_ERR_STATE)
+        assert "RVB_KEEP_LISTENER" in refused(capi.ERR_STATE)
         c.set_scene(small["scene"])
-        assert "nothing traced" in refused(RVB_ERR_STATE)            # the scene changed since
+        assert "nothing traced" in refused(capi.ERR_STATE)            # the scene changed since
     finally:
         c.close()
 

@@ -23,7 +23,6 @@ from test_gpu_speaker_arrays import fast_bound
 
 pytestmark = pytest.mark.gpu
 
-RVB_ERR_INVALID = 1
 SPREAD = spread_table()[0]
 ORIENT = (OBLIQUE["facing"], OBLIQUE["up"])
 OTHER_ORIENT = ((0.0, -0.8, 0.6), (1.0, 0.0, 0.0))
@@ -93,19 +92,19 @@ def test_refusals_come_before_any_device_is_touched(ctx):
     lib, table = ctx.lib, np.ascontiguousarray(SPREAD, np.float32).reshape(-1)
     p = table.ctypes.data_as(ctypes.c_void_p)
     good = capi.make_source_orientations(*ORIENT)
-    assert lib.rvb_set_source_table(ctx.handle, p, None, ctypes.c_uint64(1)) == RVB_ERR_INVALID
-    assert lib.rvb_set_source_table(ctx.handle, p, good, ctypes.c_uint64(0)) == RVB_ERR_INVALID
+    assert lib.rvb_set_source_table(ctx.handle, p, None, ctypes.c_uint64(1)) == capi.ERR_INVALID
+    assert lib.rvb_set_source_table(ctx.handle, p, good, ctypes.c_uint64(0)) == capi.ERR_INVALID
     for bad_value in (np.nan, np.inf, -np.inf):
         bad = table.copy()
         bad[360 * 180 * 8 - 1] = bad_value
-        assert lib.rvb_set_source_table(ctx.handle, bad.ctypes.data_as(ctypes.c_void_p), good, ctypes.c_uint64(1)) == RVB_ERR_INVALID
+        assert lib.rvb_set_source_table(ctx.handle, bad.ctypes.data_as(ctypes.c_void_p), good, ctypes.c_uint64(1)) == capi.ERR_INVALID
         for facing, up in (((bad_value, 0.0, 1.0), (0.0, 1.0, 0.0)), ((0.0, 0.0, 1.0), (0.0, bad_value, 0.0))):
             o = capi.make_source_orientations(facing, up)
-            assert lib.rvb_set_source_table(ctx.handle, p, o, ctypes.c_uint64(1)) == RVB_ERR_INVALID
+            assert lib.rvb_set_source_table(ctx.handle, p, o, ctypes.c_uint64(1)) == capi.ERR_INVALID
     for facing, up in (((0.0, 1.0, 0.0), (0.0, 2.0, 0.0)), ((0.0, 0.0, 0.0), (0.0, 1.0, 0.0)), ((0.0, 0.0, 1.0), (0.0, 0.0, 0.0)),
                        ((1e-30, 0.0, 0.0), (0.0, 1e-30, 0.0)), ((3e38, 0.0, 0.0), (0.0, 3e38, 0.0))):
         two = capi.make_source_orientations([ORIENT[0], facing], [ORIENT[1], up])           # the second orientation is the bad one
-        assert lib.rvb_set_source_table(ctx.handle, p, two, ctypes.c_uint64(2)) == RVB_ERR_INVALID, (facing, up)
+        assert lib.rvb_set_source_table(ctx.handle, p, two, ctypes.c_uint64(2)) == capi.ERR_INVALID, (facing, up)
         assert "orientation 1" in lib.rvb_last_error(ctx.handle).decode()
 
 
@@ -263,10 +262,10 @@ def test_trace_pairs_takes_an_orientation_per_pair_or_one_for_all(ctx, cathedral
         ctx.set_source_table(SPREAD, np.concatenate([facings, facings[:1]]), np.concatenate([ups, ups[:1]]))
         with pytest.raises(capi.RvbError) as e:
             ctx.trace_pairs(mics, sources, nrefl, AIR_COEFFICIENTS)
-        assert e.value.code == RVB_ERR_INVALID, str(e.value)
+        assert e.value.code == capi.ERR_INVALID, str(e.value)
         with pytest.raises(capi.RvbError) as e:
             ctx.trace(mics[0], sources[0], nrefl, AIR_COEFFICIENTS)
-        assert e.value.code == RVB_ERR_INVALID, str(e.value)
+        assert e.value.code == capi.ERR_INVALID, str(e.value)
     finally:
         ctx.set_source_table(None)
         ctx.npairs = 1

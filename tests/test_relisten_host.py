@@ -7,17 +7,10 @@ import re
 
 import numpy as np
 
+from host_lib import built_library
 from parallel_reverb_raytracer_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RVB_ERR_INVALID = 1
-
-
-def _lib():
-    if not os.path.exists(capi.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return capi.load_library()
 
 
 def test_header_declares_the_entry_point_and_the_keep_bits():
@@ -38,16 +31,16 @@ def test_header_states_memory_and_scope():
 
 
 def test_library_exports_the_entry_point():
-    lib = _lib()
+    lib = built_library()
     assert "rvb_relisten" in capi.SYMBOLS and hasattr(lib, "rvb_relisten")
 
 
 def test_a_null_handle_is_refused():
-    lib = _lib()
+    lib = built_library()
     mic = np.array([1.0, 2.0, 3.0], np.float32)
-    assert lib.rvb_relisten(None, mic.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint64(1)) == RVB_ERR_INVALID
-    assert lib.rvb_relisten(None, None, ctypes.c_uint64(0)) == RVB_ERR_INVALID
-    assert lib.rvb_keep_paths(None, ctypes.c_int(capi.KEEP_MATERIALS | capi.KEEP_LISTENER)) == RVB_ERR_INVALID
+    assert lib.rvb_relisten(None, mic.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint64(1)) == capi.ERR_INVALID
+    assert lib.rvb_relisten(None, None, ctypes.c_uint64(0)) == capi.ERR_INVALID
+    assert lib.rvb_keep_paths(None, ctypes.c_int(capi.KEEP_MATERIALS | capi.KEEP_LISTENER)) == capi.ERR_INVALID
 
 
 def test_python_binding_and_listener_loop_exist():

@@ -6,18 +6,11 @@ import re
 
 import numpy as np
 
+from host_lib import built_library
 from parallel_reverb_raytracer_amd import capi
 from parallel_reverb_raytracer_amd.dtypes import SURFACE
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RVB_ERR_INVALID = 1
-
-
-def _lib():
-    if not os.path.exists(capi.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return capi.load_library()
 
 
 def test_header_declares_the_entry_point():
@@ -31,19 +24,19 @@ def test_header_declares_the_entry_point():
 
 
 def test_library_exports_the_entry_point():
-    lib = _lib()
+    lib = built_library()
     assert "rvb_reshade_grad" in capi.SYMBOLS and hasattr(lib, "rvb_reshade_grad")
     assert lib.rvb_reshade_grad.argtypes is not None and len(lib.rvb_reshade_grad.argtypes) == 7
 
 
 def test_a_null_handle_is_refused():
-    lib = _lib()
+    lib = built_library()
     grads = np.zeros(3, dtype=SURFACE)
     air = np.zeros(8, dtype=np.float32)
     fake_weights = ctypes.c_void_p(64)          # never dereferenced: the handle is looked at first
     args = (ctypes.c_float(0.0), ctypes.c_float(44100.0), ctypes.c_uint64(16), fake_weights, grads.ctypes.data_as(ctypes.c_void_p))
-    assert lib.rvb_reshade_grad(None, *args, air.ctypes.data_as(ctypes.c_void_p)) == RVB_ERR_INVALID
-    assert lib.rvb_reshade_grad(None, *args, None) == RVB_ERR_INVALID
+    assert lib.rvb_reshade_grad(None, *args, air.ctypes.data_as(ctypes.c_void_p)) == capi.ERR_INVALID
+    assert lib.rvb_reshade_grad(None, *args, None) == capi.ERR_INVALID
     assert not grads.view(np.uint8).any() and not air.any()
 
 

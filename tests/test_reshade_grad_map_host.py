@@ -7,18 +7,11 @@ import re
 
 import numpy as np
 
+from host_lib import built_library
 from parallel_reverb_raytracer_amd import capi, fitting
 from parallel_reverb_raytracer_amd.dtypes import SURFACE, TRIANGLE
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RVB_ERR_INVALID = 1
-
-
-def _lib():
-    if not os.path.exists(capi.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return capi.load_library()
 
 
 def test_header_declares_the_entry_point_and_the_tile():
@@ -35,16 +28,16 @@ def test_header_declares_the_entry_point_and_the_tile():
 
 
 def test_library_exports_the_entry_point():
-    lib = _lib()
+    lib = built_library()
     assert "rvb_reshade_grad_map" in capi.SYMBOLS and hasattr(lib, "rvb_reshade_grad_map")
     assert lib.rvb_reshade_grad_map.argtypes is not None and len(lib.rvb_reshade_grad_map.argtypes) == 7
 
 
 def test_a_null_handle_is_refused():
-    lib = _lib()
+    lib = built_library()
     fake_weights, fake_map = ctypes.c_void_p(64), ctypes.c_void_p(1 << 20)          # never dereferenced: the handle is looked at first
     assert lib.rvb_reshade_grad_map(None, ctypes.c_float(0.0), ctypes.c_float(44100.0), ctypes.c_uint64(16), fake_weights, fake_map,
-                                    ctypes.c_uint64(12)) == RVB_ERR_INVALID
+                                    ctypes.c_uint64(12)) == capi.ERR_INVALID
 
 
 def test_python_layers_offer_the_map():

@@ -7,19 +7,12 @@ import re
 
 import numpy as np
 
+from host_lib import built_library
 from parallel_reverb_raytracer_amd import capi, scenes
 from parallel_reverb_raytracer_amd.dtypes import AIR_COEFFICIENTS, SURFACE
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ["rvb_keep_paths", "rvb_reshade"]
-RVB_ERR_INVALID = 1
-
-
-def _lib():
-    if not os.path.exists(capi.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return capi.load_library()
 
 
 def test_header_declares_the_entry_points():
@@ -30,19 +23,19 @@ def test_header_declares_the_entry_points():
 
 
 def test_library_exports_the_entry_points():
-    lib = _lib()
+    lib = built_library()
     for name in NEW_SYMBOLS:
         assert name in capi.SYMBOLS and hasattr(lib, name), name
 
 
 def test_null_handles_are_refused():
-    lib = _lib()
+    lib = built_library()
     table, count = capi.surface_table(scenes.shoebox()[2])
     air = (ctypes.c_float * 8)(*[float(x) for x in AIR_COEFFICIENTS])
-    assert lib.rvb_keep_paths(None, ctypes.c_int(1)) == RVB_ERR_INVALID
-    assert lib.rvb_keep_paths(None, ctypes.c_int(0)) == RVB_ERR_INVALID
-    assert lib.rvb_reshade(None, table.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint64(count), air) == RVB_ERR_INVALID
-    assert lib.rvb_reshade(None, None, ctypes.c_uint64(0), air) == RVB_ERR_INVALID
+    assert lib.rvb_keep_paths(None, ctypes.c_int(1)) == capi.ERR_INVALID
+    assert lib.rvb_keep_paths(None, ctypes.c_int(0)) == capi.ERR_INVALID
+    assert lib.rvb_reshade(None, table.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint64(count), air) == capi.ERR_INVALID
+    assert lib.rvb_reshade(None, None, ctypes.c_uint64(0), air) == capi.ERR_INVALID
 
 
 def test_python_binding_marshals_a_surface_table_and_none():

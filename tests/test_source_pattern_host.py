@@ -2,36 +2,28 @@
 entry points, each refuses a NULL handle with RVB_ERR_INVALID before it touches a device, and the Python mirror of the pattern is the
 header's 48 bytes."""
 import ctypes
-import os
 
+from host_lib import built_library
 from parallel_reverb_raytracer_amd import capi
 
 NEW_SYMBOLS = ["rvb_set_source_pattern", "rvb_multi_set_source_pattern", "rvb_pipeline_set_source_pattern", "rvb_pipeline_submit_directed"]
-RVB_ERR_INVALID = 1
-
-
-def _lib():
-    if not os.path.exists(capi.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return capi.load_library()
 
 
 def test_library_exports_the_source_pattern_entry_points():
-    lib = _lib()
+    lib = built_library()
     for name in NEW_SYMBOLS:
         assert name in capi.SYMBOLS and hasattr(lib, name), name
 
 
 def test_null_handles_are_refused():
-    lib = _lib()
+    lib = built_library()
     pattern = capi.make_source_patterns([(1.0, 0.0, 0.0)], 0.5)
     f3, f8 = (ctypes.c_float * 3)(1.0, 0.0, 0.0), (ctypes.c_float * 8)(*([0.5] * 8))
-    assert lib.rvb_set_source_pattern(None, pattern, ctypes.c_uint64(1)) == RVB_ERR_INVALID
-    assert lib.rvb_set_source_pattern(None, None, ctypes.c_uint64(0)) == RVB_ERR_INVALID
-    assert lib.rvb_multi_set_source_pattern(None, pattern) == RVB_ERR_INVALID
-    assert lib.rvb_pipeline_set_source_pattern(None, f8, f3) == RVB_ERR_INVALID
-    assert lib.rvb_pipeline_submit_directed(None, f3, f3, None, None, f3) == RVB_ERR_INVALID
+    assert lib.rvb_set_source_pattern(None, pattern, ctypes.c_uint64(1)) == capi.ERR_INVALID
+    assert lib.rvb_set_source_pattern(None, None, ctypes.c_uint64(0)) == capi.ERR_INVALID
+    assert lib.rvb_multi_set_source_pattern(None, pattern) == capi.ERR_INVALID
+    assert lib.rvb_pipeline_set_source_pattern(None, f8, f3) == capi.ERR_INVALID
+    assert lib.rvb_pipeline_submit_directed(None, f3, f3, None, None, f3) == capi.ERR_INVALID
 
 
 def test_python_mirror_of_the_pattern_is_48_bytes():

@@ -10,16 +10,8 @@ import numpy as np
 
 from attenuation_edges import CANONICAL, OBLIQUE, listener_angles
 from conftest import ROOT
+from host_lib import built_library
 from parallel_reverb_raytracer_amd import capi, directivity
-
-RVB_ERR_INVALID = 1
-
-
-def _lib():
-    if not os.path.exists(capi.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return capi.load_library()
 
 
 def test_header_declares_the_entry_point_and_its_contract():
@@ -38,7 +30,7 @@ def test_header_declares_the_entry_point_and_its_contract():
 
 
 def test_library_exports_the_entry_point_and_the_binding_knows_it():
-    lib = _lib()
+    lib = built_library()
     assert "rvb_set_source_table" in capi.SYMBOLS and hasattr(lib, "rvb_set_source_table")
     assert ctypes.sizeof(capi.SourceOrientation) == 32 and capi.SourceOrientation.up.offset == 16
     o = capi.make_source_orientations([(0.0, 0.0, 1.0), (0.6, 0.0, 0.8)], (0.0, 1.0, 0.0))
@@ -47,13 +39,13 @@ def test_library_exports_the_entry_point_and_the_binding_knows_it():
 
 
 def test_a_null_handle_is_refused_whatever_else_is_passed():
-    lib = _lib()
+    lib = built_library()
     table = np.ones(360 * 180 * 8, np.float32)
     o = capi.make_source_orientations((0.0, 0.0, 1.0), (0.0, 1.0, 0.0))
     bad = capi.make_source_orientations((0.0, 1.0, 0.0), (0.0, 1.0, 0.0))         # up parallel to facing
     p = table.ctypes.data_as(ctypes.c_void_p)
     for args in ((p, o, 1), (None, None, 0), (p, None, 0), (p, o, 0), (p, bad, 1)):
-        assert lib.rvb_set_source_table(None, args[0], args[1], ctypes.c_uint64(args[2])) == RVB_ERR_INVALID, args[2:]
+        assert lib.rvb_set_source_table(None, args[0], args[1], ctypes.c_uint64(args[2])) == capi.ERR_INVALID, args[2:]
 
 
 def unit_directions(n, seed):
