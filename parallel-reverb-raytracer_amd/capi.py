@@ -310,15 +310,17 @@ class Context(_Handle):
         self.nrays = 0
         self.nreflections = 0
         self.npairs = 1
+        self.ray_offset = 0
         self.nchannels = 0
         self.nsurfaces = 0
         self.ntriangles = 0
         self._keep = []
         self._events = collections.deque(maxlen=2)     # the torch events of the last TWO waits, whichever method made them
 
-    def _traced(self, nreflections, npairs):
+    def _traced(self, nreflections, npairs, ray_offset):
         self.nreflections = int(nreflections)
         self.npairs = int(npairs)
+        self.ray_offset = int(ray_offset)
 
     # ---- Raytracer ------------------------------------------------------------------------------
     def set_scene(self, scene):
@@ -364,8 +366,8 @@ class Context(_Handle):
         s = np.ascontiguousarray(np.asarray(sources, dtype=np.float32).reshape(n, 3))
         offs = (ctypes.c_uint64 * n)(*[int(o) for o in (ray_offsets if ray_offsets is not None else [0] * n)])
         contexts[0]._check(contexts[0].lib.rvb_trace_group(handles, n, _ptr(m), _ptr(s), nreflections, _f8(air), offs))
-        for c in contexts:
-            c._traced(nreflections, 1)
+        for c, offset in zip(contexts, offs):
+            c._traced(nreflections, 1, offset)
 
     def set_concurrent_traces(self, traces):
         """Hint: traces of this size the caller keeps in flight on the device at a time (rvb_set_concurrent_traces)."""
@@ -438,7 +440,7 @@ class Context(_Handle):
 
     def trace(self, mic, source, nreflections, air, ray_offset=0):
         self._check(self.lib.rvb_trace(self.handle, _f3(mic), _f3(source), nreflections, _f8(air), ray_offset))
-        self._traced(nreflections, 1)
+        self._traced(nreflections, 1, ray_offset)
 
     def trace_pairs(self, mics, sources, nreflections, air, ray_offset=0):
         """Several (source, microphone) pairs in one launch (rvb_trace_pairs): [npairs][3] each; every pair uses the rays set on
@@ -447,16 +449,18 @@ class Context(_Handle):
         s_ = np.ascontiguousarray(np.asarray(sources, dtype=np.float32).reshape(-1, 3))
         assert m.shape == s_.shape and m.shape[0] >= 1
         self._check(self.lib.rvb_trace_pairs(self.handle, _ptr(m), _ptr(s_), m.shape[0], nreflections, _f8(air), ray_offset))
-        self._traced(nreflections, m.shape[0])
+        self._traced(nreflections, m.shape[0], ray_offset)
 
     def select_pair(self, pair):
         self._check(self.lib.rvb_ir_select_pair(self.handle, pair))
 
     def get_pair_candidates(self, pair, candidates=None):
-        """Image-source candidates of one pair of a trace_pairs launch, ray numbers relative to the pair."""
+        """Image-source candidates of one pair of a trace_pairs launch, ray numbers relative to the pair (the candidates carry the trace's
+        ray_offset: ray = ray_offset + pair * nrays + the ray's number within the pair)."""
         cand = self.get_image_candidates() if candidates is None else candidates
-        mine = cand[(cand["ray"] // np.uint64(self.nrays)) == np.uint64(pair)].copy()
-        mine["ray"] -= np.uint64(pair * self.nrays)
+        in_launch = cand["ray"] - np.uint64(self.ray_offset)
+        mine = cand[(in_launch // np.uint64(self.nrays)) == np.uint64(pair)].copy()
+        mine["ray"] -= np.uint64(self.ray_offset + pair * self.nrays)
         return mine
 
     def raytrace(self, mic, source, directions, nreflections, air):
