@@ -141,6 +141,7 @@ private:
     // RVB_DEVICES=N (N > 1): the trace is sharded over GPUs 0 .. N-1 of the node (rvb_multi_*, ray-range shards; results are the
     // bytes one device gives).  The reference itself drives one device (rayverb.cpp:163).
     std::shared_ptr<rvb_multi> multi_;
+    void check_multi(int rc, const char * where) const;     // rvb_multi status -> cl::Error
 
     const unsigned long nreflections;
     unsigned long nrays;

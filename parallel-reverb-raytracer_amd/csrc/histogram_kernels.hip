@@ -123,6 +123,13 @@ __global__ __launch_bounds__(256) void histogram_transpose_kernel(const float * 
     }
 }
 
+// acc += x: one device's histogram added to another's (the peer-copy sum of csrc/multi.hip's fast mode)
+__global__ __launch_bounds__(256) void add_kernel(float * __restrict__ acc, const float * __restrict__ x, uint64_t n)
+{
+    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x)
+        acc[i] += x[i];
+}
+
 }  // namespace
 
 void rvb_launch_histogram_fast(const AttenuationModel & m, const rvb_impulse * in, uint64_t n, float predelay,
@@ -137,4 +144,9 @@ void rvb_launch_histogram_transpose(const float * acc, float * out, uint32_t nch
 {
     hipLaunchKernelGGL(histogram_transpose_kernel, dim3(stream_blocks((nbins + TR_BINS - 1) / TR_BINS * 256, 256)), dim3(256), 0, s,
                        acc, out, nchannels, nbins);
+}
+
+void rvb_launch_add(float * acc, const float * x, uint64_t n, hipStream_t s)
+{
+    hipLaunchKernelGGL(add_kernel, dim3(4096), dim3(256), 0, s, acc, x, n);
 }

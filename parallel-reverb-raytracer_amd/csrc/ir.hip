@@ -1,5 +1,6 @@
 // ir.hip — from impulses to histograms: the materialised steps of the reference (attenuate per channel, fix the predelay, flatten) and
 // the fused impulse-response stage (configure, time range, binning in fast or exact mode, download / export).
+#include "bin_blocks.h"
 #include "ctx.h"
 
 #include <algorithm>
@@ -291,9 +292,9 @@ int ir_accumulate_impl(rvb_ctx * ctx, float predelay, float sample_rate, uint64_
             int rc = exact_prepare(ctx, predelay, sample_rate, nbins);
             if (rc != RVB_OK) return rc;
             const uint32_t parts = pinned_dst ? slices : 1u;
-            const uint64_t per = ((nbins + parts - 1) / parts + 15) & ~15ull;      // whole 64-byte segments
-            for (uint64_t b0 = 0; b0 < nbins; b0 += per) {
-                const uint64_t b1 = std::min(nbins, b0 + per);
+            const BinBlocks pieces(nbins, parts);                                  // whole 64-byte segments
+            for (uint64_t k = 0; k < pieces.count(); ++k) {
+                const uint64_t b0 = pieces.range(k).b0, b1 = pieces.range(k).b1;
                 rc = exact_fold(ctx, b0, b1, hist);
                 if (rc == RVB_OK && pinned_dst && parts > 1) rc = export_bin_range(ctx, pinned_dst, hist, (uint64_t) m.nchannels * 8, nbins, b0, b1);
                 if (rc != RVB_OK) return rc;

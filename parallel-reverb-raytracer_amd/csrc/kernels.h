@@ -1,4 +1,4 @@
-// kernels.h — launch interface between the C-ABI (trace.hip, source.hip, kept.hip, sort.hip, ir.hip) and the HIP kernels.
+// kernels.h — launch interface between the C-ABI (trace.hip, source.hip, kept.hip, sort.hip, ir.hip, multi.hip) and the HIP kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -239,6 +239,8 @@ void rvb_launch_histogram_fast(const AttenuationModel & m, const rvb_impulse * i
                                float sample_rate, uint64_t nbins, float * acc, hipStream_t s);
 // acc[bin][channel][band] -> hist[channel][band][bin] (added to what is there)
 void rvb_launch_histogram_transpose(const float * acc, float * hist, uint32_t nchannels, uint64_t nbins, hipStream_t s);
+// acc[i] += x[i], i < n: a whole histogram of another device added to this one's (csrc/multi.hip, the fast mode without RCCL)
+void rvb_launch_add(float * acc, const float * x, uint64_t n, hipStream_t s);
 // exact mode helpers: per-impulse bin keys (`sentinel` = nbins marks impulses that add nothing), then the ordered per-bin
 // summation of `nchannels` channels that share the sorted list, added to what hist [all channels][8][nbins] holds
 void rvb_launch_bin_keys(const AttenuationModel & m, uint32_t channel, const rvb_impulse * in, uint64_t n, uint64_t index_base,

@@ -15,11 +15,14 @@
 //   RVB_IR_FAST   every device bins its shard at once (float atomics), then ONE sum over devices: RCCL ncclAllReduce over
 //                 xGMI, loaded from librccl.so at run time; devices that RCCL cannot put in one communicator (the same GPU
 //                 listed twice, as the single-GPU tests do) are summed with peer copies and an add kernel instead.
+// Host code only (the add kernel is histogram_kernels.hip's, behind rvb_launch_add; RCCL's binding is rccl_binding.h): the order of
+// its calls is pinned without a GPU by tests/cpp/multi_order.cpp, which stands in for everything this file calls.
 #include "../../include/rvb_capi.h"
+#include "bin_blocks.h"
 #include "hip_owned.h"
 #include "image_merge.h"
-
-#include <dlfcn.h>
+#include "kernels.h"
+#include "rccl_binding.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -30,49 +33,6 @@
 #include <vector>
 
 namespace {
-
-// ---- the four RCCL entry points used, bound at run time (prototypes: /opt/rocm/include/rccl/rccl.h:236, :260, :339, :611, :919) ----
-typedef struct ncclComm * ncclComm_t;
-struct Rccl {
-    void * lib = nullptr;
-    int (*CommInitAll)(ncclComm_t *, int, const int *) = nullptr;
-    int (*CommDestroy)(ncclComm_t) = nullptr;
-    const char * (*GetErrorString)(int) = nullptr;
-    int (*AllReduce)(const void *, void *, size_t, int, int, ncclComm_t, hipStream_t) = nullptr;
-    int (*GroupStart)() = nullptr;
-    int (*GroupEnd)() = nullptr;
-    bool ok() const { return CommInitAll && CommDestroy && GetErrorString && AllReduce && GroupStart && GroupEnd; }
-};
-const int kNcclFloat = 7, kNcclSum = 0;       // rccl.h:466, :448
-
-Rccl & rccl()
-{
-    static Rccl r = [] {
-        Rccl x;
-        const char * names[] = {getenv("RVB_RCCL_LIB"), "librccl.so.1", "/opt/rocm/lib/librccl.so.1", "librccl.so"};
-        for (const char * n : names) {
-            if (!n) continue;
-            x.lib = dlopen(n, RTLD_NOW | RTLD_LOCAL);
-            if (x.lib) break;
-        }
-        if (x.lib) {
-            x.CommInitAll = reinterpret_cast<int (*)(ncclComm_t *, int, const int *)>(dlsym(x.lib, "ncclCommInitAll"));
-            x.CommDestroy = reinterpret_cast<int (*)(ncclComm_t)>(dlsym(x.lib, "ncclCommDestroy"));
-            x.GetErrorString = reinterpret_cast<const char * (*)(int)>(dlsym(x.lib, "ncclGetErrorString"));
-            x.AllReduce = reinterpret_cast<int (*)(const void *, void *, size_t, int, int, ncclComm_t, hipStream_t)>(dlsym(x.lib, "ncclAllReduce"));
-            x.GroupStart = reinterpret_cast<int (*)()>(dlsym(x.lib, "ncclGroupStart"));
-            x.GroupEnd = reinterpret_cast<int (*)()>(dlsym(x.lib, "ncclGroupEnd"));
-        }
-        return x;
-    }();
-    return r;
-}
-
-__global__ __launch_bounds__(256) void add_kernel(float * __restrict__ acc, const float * __restrict__ x, uint64_t n)
-{
-    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x)
-        acc[i] += x[i];
-}
 
 struct Shard {
     rvb_ctx * ctx = nullptr;
@@ -123,6 +83,8 @@ int mfail(rvb_multi * m, int code, const std::string & what)
     if (m) m->error = what;
     return code;
 }
+// fail with this context's last error
+int ctx_fail(rvb_multi * m, int code, const rvb_ctx * ctx) { return mfail(m, code, rvb_last_error(ctx)); }
 
 // f(shard) on one host thread per device; the first failure is reported
 template <class F>
@@ -287,11 +249,11 @@ static int merged_images(rvb_multi * m, int remove_direct, std::vector<rvb_impul
     std::vector<rvb_image_candidate> all;
     int rc;
     for (Shard & s : m->shards)
-        if ((rc = append_image_candidates(s.ctx, all)) != RVB_OK) return mfail(m, rc, rvb_last_error(s.ctx));
+        if ((rc = append_image_candidates(s.ctx, all)) != RVB_OK) return ctx_fail(m, rc, s.ctx);
     rvb_impulse direct;
     std::memset(&direct, 0, sizeof(direct));
     rc = rvb_get_direct(m->shards[0].ctx, &direct);           // the same on every device
-    if (rc != RVB_OK) return mfail(m, rc, rvb_last_error(m->shards[0].ctx));
+    if (rc != RVB_OK) return ctx_fail(m, rc, m->shards[0].ctx);
     // (no rays, no direct path)
     if ((rc = merge_images(all.data(), all.size(), m->nrays ? &direct : nullptr, remove_direct, images)) != RVB_OK) return mfail(m, rc, "rvb_merge_images");
     return RVB_OK;
@@ -311,157 +273,235 @@ int rvb_multi_get_images(rvb_multi * m, int remove_direct, rvb_impulse * out, ui
     return RVB_OK;
 }
 
-// model: speakers != NULL -> speaker channels, else HRTF (table, facing, up)
-static int multi_ir(rvb_multi * m, const float mic[3], const rvb_speaker * speakers, uint64_t nspeakers,
-                    const float * table, const float * facing, const float * up,
-                    int which, int remove_direct, int trim_predelay, float sample_rate, int mode,
-                    float * out, uint64_t capacity_bins, uint64_t * nbins)
-{
-    if (!m || !nbins) return RVB_ERR_INVALID;
-    if (!m->traced) return mfail(m, RVB_ERR_STATE, "rvb_multi_ir: nothing traced");
-    if (which < 1 || which > 3) return mfail(m, RVB_ERR_INVALID, "rvb_multi_ir: which must be 1..3");
-    const uint32_t nch = speakers ? (uint32_t) nspeakers : 2u;
-    auto configure = [&](rvb_ctx * ctx, int w, const rvb_impulse * images, uint64_t nimages) {
+// One rvb_multi_ir_* call: the model (speakers != NULL -> speaker channels, else HRTF: table, facing, up) and what to bin how
+struct IrRequest {
+    const float * mic;
+    const rvb_speaker * speakers;
+    uint64_t nspeakers;
+    const float * table, * facing, * up;
+    int which, remove_direct, trim_predelay, mode;
+    float sample_rate;
+    uint32_t nchannels() const { return speakers ? (uint32_t) nspeakers : 2u; }
+    bool diffuse() const { return (which & RVB_IR_DIFFUSE) != 0; }
+    int configure(rvb_ctx * ctx, int w, const rvb_impulse * images, uint64_t nimages) const
+    {
         return speakers ? rvb_ir_configure_speakers(ctx, mic, speakers, nspeakers, w, images, nimages)
                         : rvb_ir_configure_hrtf(ctx, mic, table, facing, up, w, images, nimages);
-    };
-    // 1. merged image sources (host, a few dozen records); time range of every shard and of the images
-    m->images.clear();
-    if (which & RVB_IR_IMAGES) {
-        const int rc = merged_images(m, remove_direct, m->images);
+    }
+};
+// what the time range of all shards makes of it: [nchannels][8][bins] floats on every device
+struct IrLayout {
+    float predelay = 0.0f;
+    uint64_t bins = 0, rows = 0;
+    size_t count() const { return (size_t) (bins * rows); }
+    size_t bytes() const { return count() * sizeof(float); }
+};
+
+// 1. merged image sources (host, a few dozen records); time range of every shard and of the images -> predelay, bins
+static int images_and_range(rvb_multi & m, const IrRequest & q, IrLayout & l)
+{
+    m.images.clear();
+    if (q.which & RVB_IR_IMAGES) {
+        const int rc = merged_images(&m, q.remove_direct, m.images);
         if (rc != RVB_OK) return rc;
     }
-    std::vector<float> lo(m->shards.size() + 1, 0.0f), hi(m->shards.size() + 1, 0.0f);
-    if (which & RVB_IR_DIFFUSE) {
-        const int rc = for_each_shard(m, [&](Shard & s) {
-            const size_t g = (size_t) (&s - m->shards.data());
-            int r = configure(s.ctx, RVB_IR_DIFFUSE, nullptr, 0);
+    std::vector<float> lo(m.shards.size() + 1, 0.0f), hi(m.shards.size() + 1, 0.0f);
+    if (q.diffuse()) {
+        const int rc = for_each_shard(&m, [&](Shard & s) {
+            const size_t g = (size_t) (&s - m.shards.data());
+            int r = q.configure(s.ctx, RVB_IR_DIFFUSE, nullptr, 0);
             return r != RVB_OK ? r : rvb_ir_time_range(s.ctx, &lo[g], &hi[g]);
         });
         if (rc != RVB_OK) return rc;
     }
-    Shard & last = m->shards.back();
-    if (!m->images.empty()) {
-        int rc = configure(last.ctx, RVB_IR_IMAGES, m->images.data(), m->images.size());
+    Shard & last = m.shards.back();
+    if (!m.images.empty()) {
+        int rc = q.configure(last.ctx, RVB_IR_IMAGES, m.images.data(), m.images.size());
         if (rc == RVB_OK) rc = rvb_ir_time_range(last.ctx, &lo.back(), &hi.back());
-        if (rc != RVB_OK) return mfail(m, rc, rvb_last_error(last.ctx));
+        if (rc != RVB_OK) return ctx_fail(&m, rc, last.ctx);
     }
     float min_nonzero = 0.0f, max_time = 0.0f;                 // findPredelay / MAX_SAMPLE inputs over all shards
     for (size_t i = 0; i < lo.size(); ++i) {
         if (lo[i] > 0.0f && (min_nonzero == 0.0f || lo[i] < min_nonzero)) min_nonzero = lo[i];
         max_time = std::max(max_time, hi[i]);
     }
-    const float predelay = trim_predelay ? min_nonzero : 0.0f;
-    const uint64_t bins = rvb_ir_bins(max_time, predelay, sample_rate);
-    *nbins = bins;
+    l.predelay = q.trim_predelay ? min_nonzero : 0.0f;
+    l.bins = rvb_ir_bins(max_time, l.predelay, q.sample_rate);
+    l.rows = (uint64_t) q.nchannels() * 8;
+    return RVB_OK;
+}
+
+static int ensure_histograms(rvb_multi & m, size_t bytes)
+{
+    for (Shard & s : m.shards) { RVB_HIP(mfail, &m, hipSetDevice(s.device)); RVB_HIP(mfail, &m, s.hist.ensure(bytes)); }
+    return RVB_OK;
+}
+
+// 2a. RVB_IR_EXACT, the systolic chain of the banner.  The blocks are whole 64-byte segments of every [channel][band] row.  Everything
+// is enqueued from the caller's thread in dependency order: an event is recorded before the wait that names it is enqueued
+// (tests/cpp/multi_order.cpp checks that, and that every device folds every block once, in order, behind its arrival).  The host
+// waits once, at the end.
+static int ensure_chain_events(rvb_multi & m, uint64_t nblocks)
+{
+    for (Shard & s : m.shards) {
+        RVB_HIP(mfail, &m, hipSetDevice(s.device));
+        for (std::vector<Event> * events : {&s.arrived, &s.folded})
+            while (events->size() < nblocks) { Event e; RVB_HIP(mfail, &m, hipEventCreateWithFlags(&e.h, hipEventDisableTiming)); events->push_back(std::move(e)); }
+    }
+    return RVB_OK;
+}
+
+// (configured again: the range step may have left the last shard configured for the images)
+static int prepare_shards(rvb_multi & m, const IrRequest & q, const IrLayout & l)
+{
+    return for_each_shard(&m, [&](Shard & s) {
+        if (!q.diffuse() || !s.count) return (int) RVB_OK;
+        int r = q.configure(s.ctx, RVB_IR_DIFFUSE, nullptr, 0);
+        return r != RVB_OK ? r : rvb_ir_exact_prepare(s.ctx, l.predelay, q.sample_rate, l.bins);
+    });
+}
+
+// device g: block by block, wait for the device before, fetch the block, fold this shard's impulses on top, say so
+static int enqueue_device(rvb_multi & m, const IrRequest & q, const IrLayout & l, const BinBlocks & blocks, size_t g)
+{
+    Shard & s = m.shards[g];
+    const uint64_t bins = l.bins;
+    const bool folds = q.diffuse() && s.count;
+    RVB_HIP(mfail, &m, hipSetDevice(s.device));
+    if (g == 0) RVB_HIP(mfail, &m, hipMemsetAsync(s.histogram(), 0, l.bytes(), s.stream));
+    for (uint64_t k = 0; k < blocks.count(); ++k) {
+        const uint64_t b0 = blocks.range(k).b0, b1 = blocks.range(k).b1;
+        if (g > 0) {
+            Shard & prev = m.shards[g - 1];
+            RVB_HIP(mfail, &m, hipStreamWaitEvent(s.stream, prev.folded[k], 0));
+            if (prev.device == s.device) {
+                RVB_HIP(mfail, &m, hipMemcpy2DAsync(s.histogram() + b0, bins * sizeof(float), prev.histogram() + b0, bins * sizeof(float), (b1 - b0) * sizeof(float), l.rows,
+                                                    hipMemcpyDeviceToDevice, s.stream));
+            } else {
+                for (uint64_t r = 0; r < l.rows; ++r)     // (a row's piece of the block is contiguous: one peer copy each)
+                    RVB_HIP(mfail, &m, hipMemcpyPeerAsync(s.histogram() + r * bins + b0, s.device, prev.histogram() + r * bins + b0, prev.device, (b1 - b0) * sizeof(float), s.stream));
+            }
+        }
+        RVB_HIP(mfail, &m, hipEventRecord(s.arrived[k], s.stream));
+        if (folds) {
+            int rc = rvb_wait_for_event(s.ctx, s.arrived[k]);
+            if (rc == RVB_OK) rc = rvb_ir_exact_fold(s.ctx, bins, b0, b1, s.histogram());
+            if (rc == RVB_OK) rc = rvb_record_event(s.ctx, s.folded[k]);
+            if (rc != RVB_OK) return ctx_fail(&m, rc, s.ctx);
+        } else {
+            RVB_HIP(mfail, &m, hipEventRecord(s.folded[k], s.stream));          // nothing to add here: the block passes through
+        }
+    }
+    return RVB_OK;
+}
+
+static int exact_chain(rvb_multi & m, const IrRequest & q, const IrLayout & l)
+{
+    const BinBlocks blocks(l.bins, std::max<uint64_t>(1, std::min<uint64_t>(m.chain_blocks, (l.bins + 15) / 16)));
+    int rc = ensure_chain_events(m, blocks.count());
+    if (rc == RVB_OK) rc = prepare_shards(m, q, l);
+    for (size_t g = 0; g < m.shards.size() && rc == RVB_OK; ++g) rc = enqueue_device(m, q, l, blocks, g);
+    if (rc != RVB_OK) return rc;
+    // the last device's folds are the end of the chain (a device without impulses only passed blocks on its own stream)
+    Shard & last = m.shards.back();
+    RVB_HIP(mfail, &m, hipSetDevice(last.device));
+    RVB_HIP(mfail, &m, hipStreamSynchronize(last.stream));
+    rc = rvb_synchronize(last.ctx);
+    return rc == RVB_OK ? rc : ctx_fail(&m, rc, last.ctx);
+}
+
+// 2b. RVB_IR_FAST: all shards at once, then one sum over the devices
+static int fast_bin_all(rvb_multi & m, const IrRequest & q, const IrLayout & l)
+{
+    return for_each_shard(&m, [&](Shard & s) {
+        if (hipSetDevice(s.device) != hipSuccess || hipMemsetAsync(s.histogram(), 0, l.bytes(), s.stream) != hipSuccess ||
+            hipStreamSynchronize(s.stream) != hipSuccess)
+            return (int) RVB_ERR_HIP;
+        if (!q.diffuse() || !s.count) return (int) RVB_OK;
+        int r = q.configure(s.ctx, RVB_IR_DIFFUSE, nullptr, 0);
+        if (r == RVB_OK) r = rvb_ir_accumulate(s.ctx, l.predelay, q.sample_rate, l.bins, RVB_IR_FAST, s.histogram());
+        return r != RVB_OK ? r : rvb_synchronize(s.ctx);
+    });
+}
+
+// RCCL over xGMI: [channels][8][nbins] floats, in place on every device (rccl.h:611)
+static int sum_rccl(rvb_multi & m, size_t count)
+{
+    int e = rccl().GroupStart();
+    for (size_t g = 0; g < m.shards.size() && e == 0; ++g) {
+        RVB_HIP(mfail, &m, hipSetDevice(m.shards[g].device));
+        e = rccl().AllReduce(m.shards[g].histogram(), m.shards[g].histogram(), count, kNcclFloat, kNcclSum, m.comms[g], m.shards[g].stream);
+    }
+    const int e2 = rccl().GroupEnd();
+    if (e != 0 || e2 != 0) return mfail(&m, RVB_ERR_HIP, std::string("ncclAllReduce: ") + rccl().GetErrorString(e ? e : e2));
+    for (Shard & s : m.shards) { RVB_HIP(mfail, &m, hipSetDevice(s.device)); RVB_HIP(mfail, &m, hipStreamSynchronize(s.stream)); }
+    m.rccl_used_last = true;
+    return RVB_OK;
+}
+
+// no communicator for this device list: gather on shard 0 with peer copies, add there
+static int sum_peer(rvb_multi & m, const IrLayout & l)
+{
+    Shard & root = m.shards[0];
+    RVB_HIP(mfail, &m, hipSetDevice(root.device));
+    RVB_HIP(mfail, &m, root.peer.ensure(l.bytes()));
+    for (size_t g = 1; g < m.shards.size(); ++g) {
+        RVB_HIP(mfail, &m, hipMemcpyPeerAsync(root.peer.as<float>(), root.device, m.shards[g].histogram(), m.shards[g].device, l.bytes(), root.stream));
+        rvb_launch_add(root.histogram(), root.peer.as<float>(), (uint64_t) l.count(), root.stream);
+        RVB_HIP(mfail, &m, hipGetLastError());
+    }
+    RVB_HIP(mfail, &m, hipStreamSynchronize(root.stream));
+    return RVB_OK;
+}
+
+// one sum over the devices: RCCL where it serves the device list, else peer copies; a single device has nothing to sum
+static int sum_over_devices(rvb_multi & m, const IrLayout & l)
+{
+    const bool force = (m.flags & RVB_MULTI_REHEARSE_RCCL) != 0;
+    if ((m.shards.size() > 1 || force) && ensure_rccl(&m)) return sum_rccl(m, l.count());
+    return m.shards.size() > 1 ? sum_peer(m, l) : (int) RVB_OK;
+}
+
+// 3. the merged image sources go last (reference order: diffuse, then images — rayverb.cpp:708-714)
+static int images_last(rvb_multi & m, const IrRequest & q, const IrLayout & l, Shard & result)
+{
+    if (m.images.empty()) return RVB_OK;
+    int rc = q.configure(result.ctx, RVB_IR_IMAGES, m.images.data(), m.images.size());
+    if (rc == RVB_OK) rc = rvb_ir_accumulate(result.ctx, l.predelay, q.sample_rate, l.bins, q.mode, result.histogram());
+    if (rc == RVB_OK) rc = rvb_synchronize(result.ctx);
+    return rc == RVB_OK ? rc : ctx_fail(&m, rc, result.ctx);
+}
+
+static int download(rvb_multi & m, Shard & result, float * out, size_t bytes)
+{
+    return rvb_copy_to_host(result.ctx, out, result.histogram(), bytes) == RVB_OK ? (int) RVB_OK : ctx_fail(&m, RVB_ERR_HIP, result.ctx);
+}
+
+static int multi_ir(rvb_multi * m, const IrRequest & q, float * out, uint64_t capacity_bins, uint64_t * nbins)
+{
+    if (!m || !nbins) return RVB_ERR_INVALID;
+    if (!m->traced) return mfail(m, RVB_ERR_STATE, "rvb_multi_ir: nothing traced");
+    if (q.which < 1 || q.which > 3) return mfail(m, RVB_ERR_INVALID, "rvb_multi_ir: which must be 1..3");
+    IrLayout l;
+    int rc = images_and_range(*m, q, l);
+    if (rc != RVB_OK) return rc;
+    *nbins = l.bins;
     if (!out) return RVB_OK;
-    if (capacity_bins < bins) return mfail(m, RVB_ERR_CAPACITY, "rvb_multi_ir: capacity_bins too small");
-    const size_t count = (size_t) bins * nch * 8, bytes = count * sizeof(float);
-    for (Shard & s : m->shards) { RVB_HIP(mfail, m, hipSetDevice(s.device)); RVB_HIP(mfail, m, s.hist.ensure(bytes)); }
+    if (capacity_bins < l.bins) return mfail(m, RVB_ERR_CAPACITY, "rvb_multi_ir: capacity_bins too small");
+    rc = ensure_histograms(*m, l.bytes());
+    if (rc != RVB_OK) return rc;
     m->rccl_used_last = false;
-    Shard * result = nullptr;
-    if (mode == RVB_IR_EXACT) {
-        // 2a. the chain, systolic: every device keys and sorts its impulses at once; the histogram then travels in B bin-range blocks
-        // (whole 64-byte segments of every [channel][band] row): device g folds block k behind its arrival from device g - 1, while
-        // device g + 1 folds block k - 1.  Everything is enqueued from this thread in dependency order (an event is recorded before the
-        // wait that names it is enqueued); the host waits once, at the end.
-        const uint64_t rows = (uint64_t) nch * 8;
-        const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>(m->chain_blocks, (bins + 15) / 16));
-        const uint64_t per = ((bins + blocks - 1) / blocks + 15) & ~15ull;
-        const uint64_t nblocks = (bins + per - 1) / per;
-        for (Shard & s : m->shards) {
-            RVB_HIP(mfail, m, hipSetDevice(s.device));
-            for (std::vector<Event> * events : {&s.arrived, &s.folded})
-                while (events->size() < nblocks) { Event e; RVB_HIP(mfail, m, hipEventCreateWithFlags(&e.h, hipEventDisableTiming)); events->push_back(std::move(e)); }
-        }
-        const int rc_prep = for_each_shard(m, [&](Shard & s) {
-            if (!(which & RVB_IR_DIFFUSE) || !s.count) return (int) RVB_OK;
-            int r = configure(s.ctx, RVB_IR_DIFFUSE, nullptr, 0);
-            return r != RVB_OK ? r : rvb_ir_exact_prepare(s.ctx, predelay, sample_rate, bins);
-        });
-        if (rc_prep != RVB_OK) return rc_prep;
-        for (size_t g = 0; g < m->shards.size(); ++g) {
-            Shard & s = m->shards[g];
-            const bool folds = (which & RVB_IR_DIFFUSE) && s.count;
-            RVB_HIP(mfail, m, hipSetDevice(s.device));
-            if (g == 0) RVB_HIP(mfail, m, hipMemsetAsync(s.histogram(), 0, bytes, s.stream));
-            for (uint64_t k = 0; k < nblocks; ++k) {
-                const uint64_t b0 = k * per, b1 = std::min<uint64_t>(bins, b0 + per);
-                if (g > 0) {
-                    Shard & prev = m->shards[g - 1];
-                    RVB_HIP(mfail, m, hipStreamWaitEvent(s.stream, prev.folded[k], 0));
-                    if (prev.device == s.device) {
-                        RVB_HIP(mfail, m, hipMemcpy2DAsync(s.histogram() + b0, bins * sizeof(float), prev.histogram() + b0, bins * sizeof(float), (b1 - b0) * sizeof(float), rows,
-                                                           hipMemcpyDeviceToDevice, s.stream));
-                    } else {
-                        for (uint64_t r = 0; r < rows; ++r)     // (a row's piece of the block is contiguous: one peer copy each)
-                            RVB_HIP(mfail, m, hipMemcpyPeerAsync(s.histogram() + r * bins + b0, s.device, prev.histogram() + r * bins + b0, prev.device, (b1 - b0) * sizeof(float), s.stream));
-                    }
-                }
-                RVB_HIP(mfail, m, hipEventRecord(s.arrived[k], s.stream));
-                if (folds) {
-                    int rc = rvb_wait_for_event(s.ctx, s.arrived[k]);
-                    if (rc == RVB_OK) rc = rvb_ir_exact_fold(s.ctx, bins, b0, b1, s.histogram());
-                    if (rc == RVB_OK) rc = rvb_record_event(s.ctx, s.folded[k]);
-                    if (rc != RVB_OK) return mfail(m, rc, rvb_last_error(s.ctx));
-                } else {
-                    RVB_HIP(mfail, m, hipEventRecord(s.folded[k], s.stream));          // nothing to add here: the block passes through
-                }
-            }
-        }
-        // the last device's folds are the end of the chain (a device without impulses only passed blocks on its own stream)
-        RVB_HIP(mfail, m, hipSetDevice(last.device));
-        RVB_HIP(mfail, m, hipStreamSynchronize(last.stream));
-        { const int rc = rvb_synchronize(last.ctx); if (rc != RVB_OK) return mfail(m, rc, rvb_last_error(last.ctx)); }
-        result = &last;
-    } else if (mode == RVB_IR_FAST) {
-        // 2b. all shards at once, then one sum over the devices
-        int rc = for_each_shard(m, [&](Shard & s) {
-            if (hipSetDevice(s.device) != hipSuccess || hipMemsetAsync(s.histogram(), 0, bytes, s.stream) != hipSuccess ||
-                hipStreamSynchronize(s.stream) != hipSuccess)
-                return (int) RVB_ERR_HIP;
-            if (!(which & RVB_IR_DIFFUSE) || !s.count) return (int) RVB_OK;
-            int r = configure(s.ctx, RVB_IR_DIFFUSE, nullptr, 0);
-            if (r == RVB_OK) r = rvb_ir_accumulate(s.ctx, predelay, sample_rate, bins, RVB_IR_FAST, s.histogram());
-            return r != RVB_OK ? r : rvb_synchronize(s.ctx);
-        });
-        if (rc != RVB_OK) return rc;
-        const bool force = (m->flags & RVB_MULTI_REHEARSE_RCCL) != 0;
-        if ((m->shards.size() > 1 || force) && ensure_rccl(m)) {
-            // RCCL over xGMI: [channels][8][nbins] floats, in place on every device (rccl.h:611)
-            int e = rccl().GroupStart();
-            for (size_t g = 0; g < m->shards.size() && e == 0; ++g) {
-                RVB_HIP(mfail, m, hipSetDevice(m->shards[g].device));
-                e = rccl().AllReduce(m->shards[g].histogram(), m->shards[g].histogram(), count, kNcclFloat, kNcclSum, m->comms[g], m->shards[g].stream);
-            }
-            const int e2 = rccl().GroupEnd();
-            if (e != 0 || e2 != 0) return mfail(m, RVB_ERR_HIP, std::string("ncclAllReduce: ") + rccl().GetErrorString(e ? e : e2));
-            for (Shard & s : m->shards) { RVB_HIP(mfail, m, hipSetDevice(s.device)); RVB_HIP(mfail, m, hipStreamSynchronize(s.stream)); }
-            m->rccl_used_last = true;
-        } else if (m->shards.size() > 1) {
-            // no communicator for this device list: gather on shard 0 with peer copies, add there
-            Shard & root = m->shards[0];
-            RVB_HIP(mfail, m, hipSetDevice(root.device));
-            RVB_HIP(mfail, m, root.peer.ensure(bytes));
-            for (size_t g = 1; g < m->shards.size(); ++g) {
-                RVB_HIP(mfail, m, hipMemcpyPeerAsync(root.peer.as<float>(), root.device, m->shards[g].histogram(), m->shards[g].device, bytes, root.stream));
-                hipLaunchKernelGGL(add_kernel, dim3(4096), dim3(256), 0, root.stream, root.histogram(), root.peer.as<float>(), (uint64_t) count);
-                RVB_HIP(mfail, m, hipGetLastError());
-            }
-            RVB_HIP(mfail, m, hipStreamSynchronize(root.stream));
-        }
-        result = &m->shards[0];
+    if (q.mode == RVB_IR_EXACT) {
+        rc = exact_chain(*m, q, l);
+    } else if (q.mode == RVB_IR_FAST) {
+        rc = fast_bin_all(*m, q, l);
+        if (rc == RVB_OK) rc = sum_over_devices(*m, l);
     } else {
         return mfail(m, RVB_ERR_INVALID, "rvb_multi_ir: unknown mode");
     }
-    // 3. the merged image sources go last (reference order: diffuse, then images — rayverb.cpp:708-714)
-    if (!m->images.empty()) {
-        int rc = configure(result->ctx, RVB_IR_IMAGES, m->images.data(), m->images.size());
-        if (rc == RVB_OK) rc = rvb_ir_accumulate(result->ctx, predelay, sample_rate, bins, mode, result->histogram());
-        if (rc == RVB_OK) rc = rvb_synchronize(result->ctx);
-        if (rc != RVB_OK) return mfail(m, rc, rvb_last_error(result->ctx));
-    }
-    return rvb_copy_to_host(result->ctx, out, result->histogram(), bytes) == RVB_OK ? (int) RVB_OK : mfail(m, RVB_ERR_HIP, rvb_last_error(result->ctx));
+    Shard & result = q.mode == RVB_IR_EXACT ? m->shards.back() : m->shards[0];      // the end of the chain / the root of the sum
+    if (rc == RVB_OK) rc = images_last(*m, q, l, result);
+    return rc == RVB_OK ? download(*m, result, out, l.bytes()) : rc;
 }
 
 int rvb_multi_ir_speakers(rvb_multi * m, const float mic[3], const rvb_speaker * speakers, uint64_t nspeakers, int which, int remove_direct,
@@ -469,7 +509,7 @@ int rvb_multi_ir_speakers(rvb_multi * m, const float mic[3], const rvb_speaker *
 {
     if (!m) return RVB_ERR_INVALID;
     if (!mic || !speakers || nspeakers == 0 || nspeakers > RVB_MAX_SPEAKERS) return mfail(m, RVB_ERR_INVALID, "rvb_multi_ir_speakers: 1.." RVB_STR(RVB_MAX_SPEAKERS) " speakers required");
-    return multi_ir(m, mic, speakers, nspeakers, nullptr, nullptr, nullptr, which, remove_direct, trim_predelay, sample_rate, mode, out, capacity_bins, nbins);
+    return multi_ir(m, IrRequest{mic, speakers, nspeakers, nullptr, nullptr, nullptr, which, remove_direct, trim_predelay, mode, sample_rate}, out, capacity_bins, nbins);
 }
 
 int rvb_multi_ir_hrtf(rvb_multi * m, const float mic[3], const float * table, const float facing[3], const float up[3], int which, int remove_direct,
@@ -477,7 +517,7 @@ int rvb_multi_ir_hrtf(rvb_multi * m, const float mic[3], const float * table, co
 {
     if (!m) return RVB_ERR_INVALID;
     if (!mic || !table || !facing || !up) return mfail(m, RVB_ERR_INVALID, "rvb_multi_ir_hrtf: null argument");
-    return multi_ir(m, mic, nullptr, 0, table, facing, up, which, remove_direct, trim_predelay, sample_rate, mode, out, capacity_bins, nbins);
+    return multi_ir(m, IrRequest{mic, nullptr, 0, table, facing, up, which, remove_direct, trim_predelay, mode, sample_rate}, out, capacity_bins, nbins);
 }
 
 }  // extern "C"

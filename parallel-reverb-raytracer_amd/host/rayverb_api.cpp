@@ -256,6 +256,12 @@ void ContextProvider::check(int rc, const char * where) const
         throw cl::Error(rc, (std::string(where) + ": " + rvb_last_error(ctx_.get())).c_str());
 }
 
+void Raytracer::check_multi(int rc, const char * where) const
+{
+    if (rc != RVB_OK)
+        throw cl::Error(rc, (std::string(where) + ": " + rvb_multi_last_error(multi_.get())).c_str());
+}
+
 KernelLoader::KernelLoader() : KernelLoader(false) {}
 
 KernelLoader::KernelLoader(bool verbose)
@@ -428,11 +434,10 @@ void Raytracer::upload(std::vector<Triangle> & triangles, std::vector<cl_float3>
         if (rc != RVB_OK)
             throw cl::Error(rc, rvb_last_error(nullptr));
         multi_ = std::shared_ptr<rvb_multi>(raw, rvb_multi_destroy);
-        const int rc2 = rvb_multi_set_scene(raw, reinterpret_cast<const rvb_triangle *>(triangles.data()), triangles.size(),
-                                            reinterpret_cast<const rvb_float3 *>(vertices.data()), vertices.size(),
-                                            reinterpret_cast<const rvb_surface *>(surfaces.data()), surfaces.size());
-        if (rc2 != RVB_OK)
-            throw cl::Error(rc2, (std::string("rvb_multi_set_scene: ") + rvb_multi_last_error(raw)).c_str());
+        check_multi(rvb_multi_set_scene(raw, reinterpret_cast<const rvb_triangle *>(triangles.data()), triangles.size(),
+                                        reinterpret_cast<const rvb_float3 *>(vertices.data()), vertices.size(),
+                                        reinterpret_cast<const rvb_surface *>(surfaces.data()), surfaces.size()),
+                    "rvb_multi_set_scene");
         return;
     }
     check(rvb_set_scene(context(), reinterpret_cast<const rvb_triangle *>(triangles.data()), triangles.size(),
@@ -476,8 +481,7 @@ void Raytracer::raytrace(const cl_float3 & micpos, const cl_float3 & source, con
     if (multi_) {
         int rc = rvb_multi_set_directions(multi_.get(), reinterpret_cast<const rvb_float3 *>(directions.data()), directions.size());
         if (rc == RVB_OK) rc = rvb_multi_trace(multi_.get(), micpos.s, source.s, nreflections, air);     // blocking, every device at once
-        if (rc != RVB_OK)
-            throw cl::Error(rc, (std::string("rvb_multi_trace: ") + rvb_multi_last_error(multi_.get())).c_str());
+        check_multi(rc, "rvb_multi_trace");
         return;
     }
     check(rvb_set_directions(context(), reinterpret_cast<const rvb_float3 *>(directions.data()), directions.size()), "rvb_set_directions");
@@ -491,9 +495,7 @@ void Raytracer::setSourcePattern(const cl_float3 & direction, const std::array<f
     for (int i = 0; i < 4; ++i) p.direction[i] = direction.s[i];
     for (int b = 0; b < 8; ++b) p.shape[b] = shape[(size_t) b];
     if (multi_) {
-        const int rc = rvb_multi_set_source_pattern(multi_.get(), &p);
-        if (rc != RVB_OK)
-            throw cl::Error(rc, (std::string("rvb_multi_set_source_pattern: ") + rvb_multi_last_error(multi_.get())).c_str());
+        check_multi(rvb_multi_set_source_pattern(multi_.get(), &p), "rvb_multi_set_source_pattern");
         return;
     }
     check(rvb_set_source_pattern(context(), &p, 1), "rvb_set_source_pattern");
@@ -510,9 +512,7 @@ void Raytracer::fetchDiffuse(std::vector<Impulse> & out)
 {
     const size_t n = nrays * nreflections;
     if (multi_) {                              // every device writes its slice of the array; no single device copy to remember
-        const int rc = rvb_multi_get_diffuse(multi_.get(), reinterpret_cast<rvb_impulse *>(out.data()));
-        if (rc != RVB_OK)
-            throw cl::Error(rc, (std::string("rvb_multi_get_diffuse: ") + rvb_multi_last_error(multi_.get())).c_str());
+        check_multi(rvb_multi_get_diffuse(multi_.get(), reinterpret_cast<rvb_impulse *>(out.data())), "rvb_multi_get_diffuse");
         return;
     }
     check(rvb_get_diffuse(context(), reinterpret_cast<rvb_impulse *>(out.data())), "rvb_get_diffuse");
@@ -534,8 +534,7 @@ std::vector<Impulse> Raytracer::mergedImages(bool removeDirect)
         int rc = rvb_multi_get_images(multi_.get(), removeDirect, nullptr, 0, &count);
         std::vector<Impulse> ret(count);
         if (rc == RVB_OK) rc = rvb_multi_get_images(multi_.get(), removeDirect, reinterpret_cast<rvb_impulse *>(ret.data()), count, &count);
-        if (rc != RVB_OK)
-            throw cl::Error(rc, (std::string("rvb_multi_get_images: ") + rvb_multi_last_error(multi_.get())).c_str());
+        check_multi(rc, "rvb_multi_get_images");
         return ret;
     }
     uint64_t ncand = 0;
