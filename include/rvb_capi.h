@@ -94,7 +94,11 @@ int rvb_scene_info(rvb_ctx * ctx, uint64_t * nodes, uint64_t * kept_triangles, u
 /* ---- ray directions: replaces the per-group cl::copy of rayverb.cpp:593-598 ---------------- */
 /* Directions are unit vectors (reference getRandomDirections, helpers.cpp:63-81); RVB_ERR_INVALID for a direction that is not
  * finite or whose length is outside [0.5, 2] (the range the pruning margins of the acceleration structure are derived for).
- * The device variant borrows the caller's buffer and does not inspect it: the same contract is the caller's to keep. */
+ * The device variant borrows the caller's buffer and does not inspect it: the same contract is the caller's to keep.
+ * rvb_set_scene, rvb_share_scene and rvb_set_directions* void the last trace and everything made from it: until the next trace the
+ * fetches (rvb_get_*, rvb_diffuse_device), rvb_ir_select_pair and rvb_ir_configure_* return RVB_ERR_STATE, an IR configuration and a
+ * prepared exact list are void (rvb_ir_time_range*, rvb_ir_accumulate*, rvb_ir_exact_*, rvb_ir_download: RVB_ERR_STATE), and a kept trace
+ * is no longer usable (rvb_reshade, rvb_relisten). */
 int rvb_set_directions(rvb_ctx * ctx, const rvb_float3 * directions, uint64_t nrays);          /* host */
 int rvb_set_directions_device(rvb_ctx * ctx, const void * d_directions, uint64_t nrays);        /* device, borrowed */
 /* A hint, never a change of results: how many traces of this size the caller keeps in flight on the device at a time (several
@@ -531,7 +535,9 @@ int rvb_decay_params_loss(rvb_ctx * ctx, const void * d_histogram, const void * 
                           double * loss_rows /* host [nrows] */, float * params /* host [nrows][7], may be NULL */,
                           void * d_weights /* device [nrows][nbins], may be NULL */);
 
-/* Chooses the pair that rvb_get_direct and the rvb_ir_* calls below work on (pair 0 after a trace). */
+/* Chooses the pair that rvb_get_direct and the rvb_ir_* calls below work on (pair 0 after a trace).  RVB_ERR_STATE: nothing traced;
+ * RVB_ERR_INVALID: no such pair.  A successful call voids the IR configuration and a prepared exact list, which were made for the
+ * records of the pair selected before (rvb_ir_configure_* again), also when it names the pair that is selected already. */
 int rvb_ir_select_pair(rvb_ctx * ctx, uint64_t pair);
 
 /* ---- raw results: replace getRawDiffuse / getRawImages (rayverb.cpp:687-714) ---------------- */
@@ -552,7 +558,10 @@ int rvb_merge_images(const rvb_image_candidate * candidates, uint64_t ncandidate
 /* ---- attenuation, materialised: replace SpeakerAttenuator::attenuate (rayverb.cpp:856-892 +
  * kernel attenuate, kernel.cpp:505-535) and HrtfAttenuator::attenuate (rayverb.cpp:765-818 +
  * kernel hrtf, kernel.cpp:537-625) for ONE channel.  Host in, host out.  Impulses whose volume
- * is all-zero give {0, 0} (the reference leaves them uninitialised, quirk Q2). */
+ * is all-zero give {0, 0} (the reference leaves them uninitialised, quirk Q2).
+ * rvb_attenuate_speaker* leave the IR configuration, a prepared exact list and the sort buffers alone.  rvb_attenuate_hrtf* put their
+ * one ear's table where the table of rvb_ir_configure_hrtf lives: they void the IR configuration (whichever model it names) and a
+ * prepared exact list, and a following rvb_ir_configure_hrtf with table == NULL returns RVB_ERR_STATE. */
 int rvb_attenuate_speaker(rvb_ctx * ctx, const float mic[3], const rvb_impulse * in, uint64_t n,
                           const rvb_speaker * speaker, rvb_attenuated_impulse * out);
 /* The same kernel on device-resident buffers (e.g. rvb_diffuse_device): d_in / d_out are HBM arrays of n Impulse /
@@ -610,7 +619,10 @@ enum { RVB_IR_FAST = 0, RVB_IR_EXACT = 1 };
 int rvb_ir_configure_speakers(rvb_ctx * ctx, const float mic[3], const rvb_speaker * speakers, uint64_t nspeakers,
                               int which, const rvb_impulse * images, uint64_t nimages);
 /* table == NULL: the table of this context's previous rvb_ir_configure_hrtf call stays on the device (many listeners, one table: 4 MB
- * uploaded once instead of per impulse response); RVB_ERR_STATE if there is none. */
+ * uploaded once instead of per impulse response); RVB_ERR_STATE if there is none.  A call with a table that fails with RVB_ERR_STATE
+ * because nothing is traced has uploaded its table all the same: it is the table a later call with table == NULL finds.  Every
+ * successful rvb_ir_configure_* copies the images, replaces the previous configuration as a whole (model, channels, `which`, images) and
+ * voids a prepared exact list. */
 int rvb_ir_configure_hrtf(rvb_ctx * ctx, const float mic[3], const float * table /* [2][360*180*8] or NULL */,
                           const float facing[3], const float up[3],
                           int which, const rvb_impulse * images, uint64_t nimages);
@@ -641,7 +653,10 @@ int rvb_ir_accumulate_export(rvb_ctx * ctx, float predelay, float sample_rate, u
  *   rvb_ir_exact_fold      bins [bin_begin, bin_end): each bin's impulses added in impulse order on top of what d_histogram holds
  *                          (rayverb.cpp:67-74) — folding all bins once equals rvb_ir_accumulate(..., RVB_IR_EXACT, ...).
  * The prepared list lives in the context's sort buffers: a call that reuses them (rvb_ir_configure_*, rvb_trace, rvb_flatten*,
- * rvb_ir_accumulate) voids it and rvb_ir_exact_fold then fails with RVB_ERR_STATE.  Both are asynchronous on the context's stream. */
+ * a successful rvb_ir_accumulate* in either mode and with any nbins, rvb_ir_download, rvb_reshade_grad_map) or that changes what the list was made
+ * from (rvb_reshade, rvb_relisten, rvb_ir_select_pair, rvb_attenuate_hrtf*, rvb_set_scene, rvb_share_scene, rvb_set_directions*)
+ * voids it and rvb_ir_exact_fold then fails with RVB_ERR_STATE, as it does for an nbins other than the prepared one.  A second
+ * rvb_ir_exact_prepare replaces the list.  Both are asynchronous on the context's stream. */
 int rvb_ir_exact_prepare(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins);
 int rvb_ir_exact_fold(rvb_ctx * ctx, uint64_t nbins, uint64_t bin_begin, uint64_t bin_end, void * d_histogram);
 /* Convenience for one GPU: steps 1-3 done, histogram copied to host memory [nchannels][8][*nbins]. */

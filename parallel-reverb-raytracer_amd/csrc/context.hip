@@ -128,7 +128,7 @@ int rvb_set_scene(rvb_ctx * ctx, const rvb_triangle * triangles, uint64_t ntrian
         return fail(ctx, err.find("stack") != std::string::npos ? RVB_ERR_CAPACITY : RVB_ERR_INVALID, "rvb_set_scene: " + err);
     RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
     ctx->have_scene = false;
-    ctx->traced = false;
+    ctx->void_trace();
     // a store other contexts hold stays theirs: this context gets a new one (buffers it holds alone are reused)
     if (!ctx->store || ctx->store.use_count() > 1) {
         ctx->store = std::make_shared<SceneStore>();
@@ -184,7 +184,7 @@ int rvb_share_scene(rvb_ctx * ctx, rvb_ctx * from)
     ctx->nsurfaces = from->nsurfaces;
     ctx->ntriangles = from->ntriangles;
     ctx->have_scene = true;
-    ctx->traced = false;
+    ctx->void_trace();
     return RVB_OK;
 }
 
@@ -220,7 +220,7 @@ int rvb_set_directions(rvb_ctx * ctx, const rvb_float3 * directions, uint64_t nr
         RVB_HIP(fail, ctx, hipMemcpy(ctx->directions_own.p, directions, nrays * sizeof(rvb_float3), hipMemcpyHostToDevice));
     ctx->directions = ctx->directions_own.as<const float4>();
     ctx->nrays = nrays;
-    ctx->traced = false;
+    ctx->void_trace();
     return RVB_OK;
 }
 
@@ -230,7 +230,7 @@ int rvb_set_directions_device(rvb_ctx * ctx, const void * d_directions, uint64_t
     if (nrays && !d_directions) return fail(ctx, RVB_ERR_INVALID, "rvb_set_directions_device: null directions");
     ctx->directions = reinterpret_cast<const float4 *>(d_directions);
     ctx->nrays = nrays;
-    ctx->traced = false;
+    ctx->void_trace();
     return RVB_OK;
 }
 

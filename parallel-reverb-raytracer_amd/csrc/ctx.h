@@ -341,6 +341,9 @@ struct rvb_ctx {
     // From here on the results are no longer the last trace's (a trace has finished, rvb_reshade or rvb_relisten is about to rewrite
     // them): what the host has fetched of them and what the IR stage has prepared from them is void.
     void void_fetched_results() { small_valid = false; ir_configured = false; exact.valid = false; }
+    // The trace is gone (rvb_set_scene, rvb_share_scene, rvb_set_directions*, a trace that begins): nrays or the scene no longer describe
+    // the records in `impulses`, so an IR configuration or a prepared exact list made for them must not be used either.
+    void void_trace() { traced = false; ir_configured = false; exact.valid = false; }
     // the pair the IR stage works on, as a trace leaves it: the first, with its microphone
     void select_first_pair() { ir_pair = 0; for (int i = 0; i < 3; ++i) mic[i] = pairs.mic_of(0)[i]; }
 };

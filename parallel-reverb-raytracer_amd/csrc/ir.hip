@@ -53,6 +53,7 @@ int set_one_ear_table(rvb_ctx * ctx, const float * table, uint64_t channel)
     if (rc != RVB_OK) return rc;
     ctx->hrtf_table_ears = 1;                 // (one ear's table in its slot: not what rvb_ir_configure_hrtf(table == NULL) may reuse)
     ctx->ir_configured = false;
+    ctx->exact.valid = false;                 // (a prepared list of the HRTF model folds with the table image that has just been replaced)
     return RVB_OK;
 }
 
@@ -525,7 +526,9 @@ uint64_t rvb_ir_bins(float max_time, float predelay, float sample_rate)
 
 int rvb_ir_accumulate(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins, int mode, void * d_histogram)
 {
-    return ir_accumulate_impl(ctx, predelay, sample_rate, nbins, mode, d_histogram, nullptr, 1);
+    const int rc = ir_accumulate_impl(ctx, predelay, sample_rate, nbins, mode, d_histogram, nullptr, 1);
+    if (ctx && rc == RVB_OK) ctx->exact.valid = false;        // include/rvb_capi.h: rvb_ir_accumulate voids a prepared list, whatever its mode and its nbins
+    return rc;
 }
 
 int rvb_ir_accumulate_export(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins, int mode, void * d_histogram,
@@ -535,7 +538,9 @@ int rvb_ir_accumulate_export(rvb_ctx * ctx, float predelay, float sample_rate, u
     // Default: ONE piece.  Measured at workload C2 (profiles/r04_export_slices_n1.txt): 1 / 2 / 4 / 8 bin ranges leave one impulse response
     // on the host after 6.98 / 7.04 / 7.02 / 7.00 ms (5.88 ms to HBM: the 54 MB need 1.1 ms of the link whenever they start, and the fold they
     // could overlap is 0.27 ms split into launches that cost what the overlap gains) and the pipeline at 4.82 / 4.81 / 4.80 / 4.96 ms per IR.
-    return ir_accumulate_impl(ctx, predelay, sample_rate, nbins, mode, d_histogram, static_cast<float *>(pinned_dst), slices ? slices : 1u);
+    const int rc = ir_accumulate_impl(ctx, predelay, sample_rate, nbins, mode, d_histogram, static_cast<float *>(pinned_dst), slices ? slices : 1u);
+    if (ctx && rc == RVB_OK) ctx->exact.valid = false;
+    return rc;
 }
 
 int rvb_ir_exact_prepare(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins)

@@ -67,7 +67,7 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     if (check_source_counts(ctx, "rvb_trace", npairs) != RVB_OK) return RVB_ERR_INVALID;
     const float * mic = mics, * source = sources;
     RVB_BIND(ctx);
-    ctx->traced = false;                              // (until trace_finish: a failure below must not leave the last trace's results half reset)
+    ctx->void_trace();                                // (until trace_finish: a failure below must not leave the last trace's results half reset)
     ctx->kept.void_all();
     const uint64_t nrays = ctx->nrays * npairs;       // rays of this launch
     const size_t imp_bytes = (size_t) nrays * nreflections * sizeof(rvb_impulse);
@@ -344,6 +344,7 @@ int rvb_ir_select_pair(rvb_ctx * ctx, uint64_t pair)
     if (pair >= ctx->npairs) return fail(ctx, RVB_ERR_INVALID, "rvb_ir_select_pair: pair out of range");
     ctx->ir_pair = pair;
     ctx->ir_configured = false;
+    ctx->exact.valid = false;                 // (a prepared list names the records of the pair it was made for; the fold reads ir_diffuse)
     for (int i = 0; i < 3; ++i) ctx->mic[i] = ctx->pairs.mic_of(pair)[i];
     return RVB_OK;
 }
