@@ -135,6 +135,14 @@ _SIGNATURES = {
     "rvb_executed_bounces": (_i, _vp, _vp),
 }
 SYMBOLS = list(_SIGNATURES)
+# ... and of include/rvb_capi_images.h, the image sources of a kept trace on the device: a table of its own beside the first
+# (tests/test_images_header_host.py holds it against that header)
+_IMAGE_SIGNATURES = {
+    "rvb_ir_configure_speakers_merged": (_i, _vp, _vp, _vp, _u64, _i, _i, _vp),
+    "rvb_ir_configure_hrtf_merged": (_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp),
+    "rvb_reshade_grad_images": (_i, _vp, _f, _f, _u64, _vp, _vp, _vp),
+}
+IMAGE_SYMBOLS = list(_IMAGE_SIGNATURES)
 _lib = None
 
 
@@ -160,9 +168,10 @@ def load_library():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (restype, *argtypes) in _SIGNATURES.items():
-            function = getattr(lib, name)
-            function.restype, function.argtypes = restype, argtypes
+        for table in (_SIGNATURES, _IMAGE_SIGNATURES):
+            for name, (restype, *argtypes) in table.items():
+                function = getattr(lib, name)
+                function.restype, function.argtypes = restype, argtypes
         _lib = lib
     return _lib
 
@@ -423,6 +432,16 @@ class Context(_Handle):
         self._check(self.lib.rvb_reshade_grad(self.handle, predelay, sample_rate, nbins, device_weights_pointer, _ptr(grads), _ptr(grad_air)))
         return grads, grad_air
 
+    def reshade_grad_images(self, predelay, sample_rate, nbins, device_weights_pointer):
+        """(grads, grad_air) of the IMAGE part of L = sum w * H (rvb_reshade_grad_images of include/rvb_capi_images.h): what
+        ir_accumulate(predelay, sample_rate, nbins, IR_FAST) adds for the images of a configuration made with ir_configure_speakers_merged
+        (IR_IMAGES or IR_ALL, at most 8 channels).  grads holds dL/dspecular, its diffuse entries are +0; the direct sound adds to grad_air
+        alone.  L is a sum over impulses: add reshade_grad's result (under an IR_DIFFUSE configuration) for the whole of IR_ALL.  Synchronous."""
+        grads = np.zeros(self.nsurfaces, dtype=SURFACE)
+        grad_air = np.zeros(8, dtype=np.float32)
+        self._check(self.lib.rvb_reshade_grad_images(self.handle, predelay, sample_rate, nbins, device_weights_pointer, _ptr(grads), _ptr(grad_air)))
+        return grads, grad_air
+
     def reshade_grad_map(self, predelay, sample_rate, nbins, device_weights_pointer, out=None):
         """The gradient of reshade_grad per TRIANGLE (rvb_reshade_grad_map): a float32 CUDA tensor [ntriangles][16], row t the derivatives of
         L with respect to a private copy of the coefficients of triangle t's surface — specular 0..7, then diffuse 8..15 —, t the index of
@@ -562,6 +581,25 @@ class Context(_Handle):
         img = _images(images)
         self._check(self.lib.rvb_ir_configure_hrtf(self.handle, _f3(mic), _ptr(t), _f3(facing), _f3(up), which, _ptr(img), img.shape[0]))
         self.nchannels = 2
+
+    def ir_configure_speakers_merged(self, mic, directions, coefficients, which=IR_ALL, remove_direct=False):
+        """ir_configure_speakers with images = get_raw_images(remove_direct) of the selected pair, made on the device
+        (rvb_ir_configure_speakers_merged of include/rvb_capi_images.h): which candidate wins each key of the merge is decided once per
+        trace or relisten, so after a reshade the call costs one gather kernel.  Returns the number of images."""
+        sp = make_speakers(directions, coefficients)
+        nimages = _u64(0)
+        self._check(self.lib.rvb_ir_configure_speakers_merged(self.handle, _f3(mic), _ptr(sp), sp.shape[0], which, int(remove_direct), ctypes.byref(nimages)))
+        self.nchannels = sp.shape[0]
+        return nimages.value
+
+    def ir_configure_hrtf_merged(self, mic, table, facing, up, which=IR_ALL, remove_direct=False):
+        """ir_configure_hrtf with images = get_raw_images(remove_direct) of the selected pair, made on the device
+        (rvb_ir_configure_hrtf_merged); table None as in ir_configure_hrtf.  Returns the number of images."""
+        t = _gain_table(table, ears=2) if table is not None else None
+        nimages = _u64(0)
+        self._check(self.lib.rvb_ir_configure_hrtf_merged(self.handle, _f3(mic), _ptr(t), _f3(facing), _f3(up), which, int(remove_direct), ctypes.byref(nimages)))
+        self.nchannels = 2
+        return nimages.value
 
     def ir_time_range(self):
         lo, hi = ctypes.c_float(0), ctypes.c_float(0)

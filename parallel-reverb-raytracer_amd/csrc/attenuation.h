@@ -135,6 +135,19 @@ __device__ __forceinline__ int64_t hrtf_row(const ModelDev & m, v3 pos)
     return row_of(az, el);
 }
 
+// The table row of a tabulated source directivity (source_kernels.hip, image_grad_kernels.hip) for the departure vector `v`: hrtf_row
+// with pos - mic replaced by v — the listener's basis is the source's (bx, by, bz of rvb_source_table_basis), the margin scheme of angle_deg and quirk Q5 of row_of included.  A row outside the table
+// (finite inputs give none) reads the zero row: no address outside the table is formed.
+__device__ __forceinline__ uint32_t departure_row(const float4 bx, const float4 by, const float4 bz, const v3 v)
+{
+    const v3 d = normalize3(v);
+    const v3 t = mk3(dot3(mk3(bx.x, bx.y, bx.z), d), dot3(mk3(by.x, by.y, by.z), d), dot3(mk3(bz.x, bz.y, bz.z), d));
+    const float az = angle_deg(t.x, t.z, 180.0f, false);
+    const float el = angle_deg(t.y, sqrtf(t.x * t.x + t.z * t.z), 0.0f, false);
+    const int64_t row = row_of(az, el);
+    return row >= 0 && row < RVB_HRTF_ROWS ? (uint32_t) row : (uint32_t) (RVB_HRTF_ROWS - 1);
+}
+
 // The same row for two neighbouring lanes that share one impulse (a quad of attenuate_kernel, the two lanes of a bin in
 // ordered_sum_hrtf_kernel): azimuth and elevation are both atan2(y, x) of different arguments, so the even lane evaluates the
 // azimuth and the odd lane the elevation with ONE call, then they swap by DPP.  Same operations on the same operands as hrtf_row.

@@ -7,10 +7,12 @@
 //   sort.hip     the sorts the other stages call, "sorted list and bin boundaries"
 //   ir.hip       materialised attenuate / flatten, the fused impulse-response stage
 //   decay.hip    decay curves, reverberation times and the decay loss on the caller's device arrays
+//   images.hip   include/rvb_capi_images.h: the merged image list made on the device, the image-source part of the material gradient
 // No compute happens in them and nothing falls back to the CPU: every entry point that produces results launches HIP kernels:
 //   the trace         trace_kernels.hip, image_kernels.hip, shadow_kernels.hip, source_kernels.hip
 //   a kept trace      reshade_kernels.hip, reshade_grad_kernels.hip, relisten_kernels.hip (the three over kept_tiles.h),
 //                     reshade_grad_map_kernels.hip
+//   the image list    image_grad_kernels.hip
 //   the IR stage      attenuate_kernels.hip, histogram_kernels.hip, exact_kernels.hip, decay_kernels.hip
 //   the sorts         rocprim_sort.hip, radix_sort.hip
 #pragma once
@@ -223,6 +225,21 @@ struct KeptTrace {
     void release() { Buffers freed(std::move(dev)); }
 };
 
+// The merged image list made on the device (rvb_ir_configure_*_merged, images.hip).  Which candidate wins each key of rvb_merge_images
+// depends on geometry and microphone only: `winners` holds, per output impulse in the merge's order, the device position of the candidate
+// it is copied from, or RVB_IMAGE_WINNER_DIRECT for the pair's direct slot.  Made once per (trace or relisten, pair, remove_direct) from
+// one download of the candidates, uploaded once; a re-shade, a source setter and rvb_ir_select_pair leave it alone.
+struct MergedImages {
+    bool valid = false;                          // `winners` describes the candidates on the device
+    uint64_t pair = 0;
+    bool remove_direct = false;
+    uint64_t count = 0;
+    bool configured = false;                     // the current IR configuration was made from the list: ctx->images is its gather
+    DevBuf winners;                              // [count] uint32_t
+    DevBuf grad_scratch;                         // rvb_reshade_grad_images: the term rows, then the result
+    void void_list() { valid = false; }
+};
+
 struct rvb_ctx {
     int device = 0;
     // (declared first: destroyed last, after everything that work on them may use)
@@ -260,6 +277,7 @@ struct rvb_ctx {
     float mic[3] = {0, 0, 0};
     // last trace: npairs (source, microphone) pairs x nrays rays each; the IR stage works on one pair's slice at a time
     uint64_t npairs = 1, traced_rays = 0, ir_pair = 0;
+    uint64_t trace_ray_offset = 0;              // ... and its ray_offset: a candidate's ray is trace_ray_offset + pair * nrays + the ray's number
     PairLaunch pairs;                           // the per-pair arrays of that launch, their host mirrors, its microphones
     SourceDirectivity source;                   // rvb_set_source_pattern / rvb_set_source_table: what is set and what is on the device
     DevBuf image_items;                         // work list of the image-source check kernel
@@ -293,6 +311,8 @@ struct rvb_ctx {
     DevBuf own_sort_temp, own_sort_keys, own_sort_values;      // csrc/radix_sort.hip: tile counters, the intermediate (key, value) pair
     uint64_t nimages = 0;
     std::vector<rvb_impulse> images_host;
+    bool images_host_stale = false;             // `images` was gathered on the device: images_host is fetched when a reader asks (ir_images_on_host)
+    MergedImages merged;
     DevBuf speakers;                             // more than 8 speakers: AttenuationModel::speaker_table, uploaded in stream order at configure
     std::vector<float4> speakers_host;
     // exact mode in two steps (rvb_ir_exact_prepare / rvb_ir_exact_fold): what the sorted list in keys_b / vals_b / bin_starts was prepared for
@@ -343,7 +363,7 @@ struct rvb_ctx {
     void void_fetched_results() { small_valid = false; ir_configured = false; exact.valid = false; }
     // The trace is gone (rvb_set_scene, rvb_share_scene, rvb_set_directions*, a trace that begins): nrays or the scene no longer describe
     // the records in `impulses`, so an IR configuration or a prepared exact list made for them must not be used either.
-    void void_trace() { traced = false; ir_configured = false; exact.valid = false; }
+    void void_trace() { traced = false; ir_configured = false; exact.valid = false; merged.void_list(); }
     // the pair the IR stage works on, as a trace leaves it: the first, with its microphone
     void select_first_pair() { ir_pair = 0; for (int i = 0; i < 3; ++i) mic[i] = pairs.mic_of(0)[i]; }
 };
@@ -381,6 +401,18 @@ int launch_shadow_behind_images(rvb_ctx * ctx, const TraceArgs & a, const Source
 // source.hip: what a trace and a re-shade do about the source directivity (described where they are defined)
 int check_source_counts(rvb_ctx * ctx, const char * who, uint64_t npairs);
 int apply_source_patterns(rvb_ctx * ctx, const TraceArgs & a, const SourceShading & source, bool gains_stand = false);
+
+// trace.hip: the merge rule of rvb_merge_images on its own — per output impulse, in the merge's (std::map key) order, the position in
+// `candidates` of the candidate it is copied from, or RVB_IMAGE_WINNER_DIRECT for the direct slot.  RVB_ERR_INVALID for a slot out of range.
+int merge_image_winners(const rvb_image_candidate * candidates, uint64_t ncandidates, bool have_direct, bool remove_direct, std::vector<uint32_t> & winners);
+// ir.hip: the halves of rvb_ir_configure_speakers / rvb_ir_configure_hrtf — the model; what both refuse; the image list and the
+// configuration's state (gathered: the caller enqueues the gather into ctx->images, no host list is uploaded) — and the host copy of the
+// image list for the readers that need one
+int ir_speaker_model(rvb_ctx * ctx, const float mic[3], const rvb_speaker * speakers, uint64_t nspeakers);
+int ir_hrtf_model(rvb_ctx * ctx, const float mic[3], const float * table, const float facing[3], const float up[3]);
+int ir_configure_refusals(rvb_ctx * ctx, int which);
+int ir_configure_images(rvb_ctx * ctx, int which, const rvb_impulse * images, uint64_t nimages, bool gathered);
+int ir_images_on_host(rvb_ctx * ctx);
 
 // sort.hip
 bool own_sort_enabled();

@@ -120,25 +120,97 @@ int flatten_finish(rvb_ctx * ctx, const rvb_attenuated_impulse * d_in, uint64_t 
 
 // ---- fused impulse-response stage ----------------------------------------------------------------
 
-int configure_common(rvb_ctx * ctx, int which, const rvb_impulse * images, uint64_t nimages)
+}  // namespace
+
+int ir_configure_refusals(rvb_ctx * ctx, int which)
 {
     if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_ir_configure: nothing traced");
     if (which < 1 || which > 3) return fail(ctx, RVB_ERR_INVALID, "rvb_ir_configure: which must be 1..3");
-    if (nimages && !images) return fail(ctx, RVB_ERR_INVALID, "rvb_ir_configure: null images");
+    return RVB_OK;
+}
+
+// (behind ir_configure_refusals, which every caller has passed)
+int ir_configure_images(rvb_ctx * ctx, int which, const rvb_impulse * images, uint64_t nimages, bool gathered)
+{
+    if (!gathered && nimages && !images) return fail(ctx, RVB_ERR_INVALID, "rvb_ir_configure: null images");
     if (nimages * sizeof(rvb_impulse) > ctx->images.cap)
         RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));          // the buffer is about to be replaced
     RVB_HIP(fail, ctx, ctx->images.ensure(nimages * sizeof(rvb_impulse)));
     ctx->nimages = nimages;
-    ctx->images_host.assign(images, images + nimages);
-    // in stream order (kernels of an earlier configuration that read the old images run before it); the source is the
-    // context's own copy, which lives until the next configure
-    if (nimages) RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->images.p, ctx->images_host.data(), nimages * sizeof(rvb_impulse), hipMemcpyHostToDevice, ctx->stream));
+    if (gathered) {
+        ctx->images_host.clear();
+    } else {
+        ctx->images_host.assign(images, images + nimages);
+        // in stream order (kernels of an earlier configuration that read the old images run before it); the source is the
+        // context's own copy, which lives until the next configure
+        if (nimages) RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->images.p, ctx->images_host.data(), nimages * sizeof(rvb_impulse), hipMemcpyHostToDevice, ctx->stream));
+    }
+    ctx->images_host_stale = gathered;
+    ctx->merged.configured = gathered;
     ctx->which = which;
     ctx->ir_configured = true;
     ctx->exact.valid = false;
     ctx->range_pending = false;
     return RVB_OK;
 }
+
+// A list gathered on the device (rvb_ir_configure_*_merged): its host copy, fetched once per configuration by the first reader.
+int ir_images_on_host(rvb_ctx * ctx)
+{
+    if (!ctx->images_host_stale) return RVB_OK;
+    ctx->images_host.resize(ctx->nimages);
+    if (ctx->nimages)
+        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->images_host.data(), ctx->images.p, ctx->nimages * sizeof(rvb_impulse), hipMemcpyDeviceToHost, ctx->stream));
+    RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
+    ctx->images_host_stale = false;
+    return RVB_OK;
+}
+
+int ir_speaker_model(rvb_ctx * ctx, const float mic[3], const rvb_speaker * speakers, uint64_t nspeakers)
+{
+    if (!mic || !speakers || nspeakers == 0 || nspeakers > RVB_MAX_SPEAKERS)
+        return fail(ctx, RVB_ERR_INVALID, "rvb_ir_configure_speakers: 1.." RVB_STR(RVB_MAX_SPEAKERS) " speakers required");
+    RVB_BIND(ctx);
+    AttenuationModel m;
+    m.hrtf = 0;
+    m.nchannels = (uint32_t) nspeakers;
+    for (int i = 0; i < 3; ++i) m.mic[i] = mic[i];
+    for (uint64_t s = 0; s < nspeakers && s < 8; ++s) m.speakers[s] = speakers[s];
+    if (nspeakers > 8) {
+        // the wide kernels read their speakers from device memory: uploaded in stream order like the images (kernels of an earlier
+        // configuration that read the old table run before the copy; the source is the context's own copy, alive until the next configure)
+        if (nspeakers * sizeof(float4) > ctx->speakers.cap)
+            RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));          // the buffer is about to be replaced
+        RVB_HIP(fail, ctx, ctx->speakers.ensure(RVB_MAX_SPEAKERS * sizeof(float4)));
+        ctx->speakers_host.resize(nspeakers);
+        rvb_make_speaker_table(speakers, nspeakers, ctx->speakers_host.data());
+        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->speakers.p, ctx->speakers_host.data(), nspeakers * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+        m.speaker_table = ctx->speakers.as<const float4>();
+    }
+    ctx->model = m;
+    return RVB_OK;
+}
+
+int ir_hrtf_model(rvb_ctx * ctx, const float mic[3], const float * table, const float facing[3], const float up[3])
+{
+    if (!mic || !facing || !up) return fail(ctx, RVB_ERR_INVALID, "rvb_ir_configure_hrtf: null argument");
+    RVB_BIND(ctx);
+    if (table) {
+        // (the table on the device may still be read by kernels enqueued under the previous configuration)
+        RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
+        int rc = upload_hrtf_table(ctx, table, 0, 2);
+        if (rc != RVB_OK) return rc;
+        ctx->hrtf_table_ears = 2;
+    } else if (ctx->hrtf_table_ears != 2) {
+        // table == NULL: the two-ear table of the previous rvb_ir_configure_hrtf on this context stays (a caller that configures many
+        // listeners with one table — the pipeline — uploads its 4 MB once, not per impulse response)
+        return fail(ctx, RVB_ERR_STATE, "rvb_ir_configure_hrtf: table == NULL needs an earlier call with a table on this context");
+    }
+    ctx->model = hrtf_model(ctx, mic, facing, up);
+    return RVB_OK;
+}
+
+namespace {
 
 // HRTF model: the attenuated time of an impulse differs per ear (kernel.cpp:616-622), so the range needs a pass over the impulses; the
 // pass and the copy of its two words to pinned host memory are ENQUEUED here and waited for in rvb_ir_time_range — a caller with several
@@ -424,48 +496,18 @@ int rvb_ir_configure_speakers(rvb_ctx * ctx, const float mic[3], const rvb_speak
                               int which, const rvb_impulse * images, uint64_t nimages)
 {
     if (!ctx) return RVB_ERR_INVALID;
-    if (!mic || !speakers || nspeakers == 0 || nspeakers > RVB_MAX_SPEAKERS)
-        return fail(ctx, RVB_ERR_INVALID, "rvb_ir_configure_speakers: 1.." RVB_STR(RVB_MAX_SPEAKERS) " speakers required");
-    RVB_BIND(ctx);
-    AttenuationModel m;
-    m.hrtf = 0;
-    m.nchannels = (uint32_t) nspeakers;
-    for (int i = 0; i < 3; ++i) m.mic[i] = mic[i];
-    for (uint64_t s = 0; s < nspeakers && s < 8; ++s) m.speakers[s] = speakers[s];
-    if (nspeakers > 8) {
-        // the wide kernels read their speakers from device memory: uploaded in stream order like the images (kernels of an earlier
-        // configuration that read the old table run before the copy; the source is the context's own copy, alive until the next configure)
-        if (nspeakers * sizeof(float4) > ctx->speakers.cap)
-            RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));          // the buffer is about to be replaced
-        RVB_HIP(fail, ctx, ctx->speakers.ensure(RVB_MAX_SPEAKERS * sizeof(float4)));
-        ctx->speakers_host.resize(nspeakers);
-        rvb_make_speaker_table(speakers, nspeakers, ctx->speakers_host.data());
-        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->speakers.p, ctx->speakers_host.data(), nspeakers * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-        m.speaker_table = ctx->speakers.as<const float4>();
-    }
-    ctx->model = m;
-    return configure_common(ctx, which, images, nimages);
+    int rc = ir_speaker_model(ctx, mic, speakers, nspeakers);
+    if (rc == RVB_OK) rc = ir_configure_refusals(ctx, which);
+    return rc == RVB_OK ? ir_configure_images(ctx, which, images, nimages, false) : rc;
 }
 
 int rvb_ir_configure_hrtf(rvb_ctx * ctx, const float mic[3], const float * table, const float facing[3], const float up[3],
                           int which, const rvb_impulse * images, uint64_t nimages)
 {
     if (!ctx) return RVB_ERR_INVALID;
-    if (!mic || !facing || !up) return fail(ctx, RVB_ERR_INVALID, "rvb_ir_configure_hrtf: null argument");
-    RVB_BIND(ctx);
-    if (table) {
-        // (the table on the device may still be read by kernels enqueued under the previous configuration)
-        RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
-        int rc = upload_hrtf_table(ctx, table, 0, 2);
-        if (rc != RVB_OK) return rc;
-        ctx->hrtf_table_ears = 2;
-    } else if (ctx->hrtf_table_ears != 2) {
-        // table == NULL: the two-ear table of the previous rvb_ir_configure_hrtf on this context stays (a caller that configures many
-        // listeners with one table — the pipeline — uploads its 4 MB once, not per impulse response)
-        return fail(ctx, RVB_ERR_STATE, "rvb_ir_configure_hrtf: table == NULL needs an earlier call with a table on this context");
-    }
-    ctx->model = hrtf_model(ctx, mic, facing, up);
-    return configure_common(ctx, which, images, nimages);
+    int rc = ir_hrtf_model(ctx, mic, table, facing, up);
+    if (rc == RVB_OK) rc = ir_configure_refusals(ctx, which);
+    return rc == RVB_OK ? ir_configure_images(ctx, which, images, nimages, false) : rc;
 }
 
 int rvb_ir_time_range_begin(rvb_ctx * ctx)
@@ -506,7 +548,9 @@ int rvb_ir_time_range(rvb_ctx * ctx, float * min_nonzero_time, float * max_time)
     bool have_lo = got[0] != 0xFFFFFFFFu;
     if (have_lo) std::memcpy(&lo, &got[0], 4);
     std::memcpy(&hi, &got[1], 4);
-    if (!ctx->model.hrtf && (ctx->which & RVB_IR_IMAGES))
+    if (!ctx->model.hrtf && (ctx->which & RVB_IR_IMAGES)) {
+        const int rc = ir_images_on_host(ctx);                  // (a list gathered on the device comes down once)
+        if (rc != RVB_OK) return rc;
         for (const rvb_impulse & im : ctx->images_host) {
             bool nonzero = false;
             for (int b = 0; b < 8; ++b) nonzero = nonzero || im.volume[b] != 0.0f;
@@ -514,6 +558,7 @@ int rvb_ir_time_range(rvb_ctx * ctx, float * min_nonzero_time, float * max_time)
             if (im.time != 0.0f && (!have_lo || im.time < lo)) { lo = im.time; have_lo = true; }
             if (im.time > hi) hi = im.time;
         }
+    }
     if (min_nonzero_time) *min_nonzero_time = have_lo ? lo : 0.0f;
     if (max_time) *max_time = hi;
     return RVB_OK;

@@ -80,6 +80,7 @@ int rvb_relisten(rvb_ctx * ctx, const float * mics, uint64_t npairs)
     SmallBlock * small = ctx->small_dev();
     ctx->reset_timings();
     ctx->void_fetched_results();
+    ctx->merged.void_list();                      // (the image kernels find other candidates: which of them win is decided anew)
     // what the tail appends to or folds into, back where a trace starts; `executed` stays
     RVB_HIP(fail, ctx, hipMemsetAsync(&small->candidate_count, 0, sizeof(uint32_t), ctx->stream));
     RVB_HIP(fail, ctx, hipMemsetAsync(&small->image_item_count, 0, sizeof(SmallBlock) - offsetof(SmallBlock, image_item_count), ctx->stream));      // ... and the direct slot

@@ -158,6 +158,35 @@ void rvb_launch_reshade_grad_map_terms(const TraceArgs & a, const float4 * kept,
 void rvb_launch_reshade_grad_map_fold(const uint32_t * sorted_keys, const uint32_t * sorted_values, uint64_t n, uint32_t ntriangles, const float * terms,
                                       double * partials, float * map, hipStream_t s);
 void rvb_launch_reshade_grad_map_combine(const uint32_t * starts, const uint32_t * ends, uint32_t ntriangles, const double * partials, float * map, hipStream_t s);
+// The merged image list on the device and the image-source part of the material gradient (image_grad_kernels.hip;
+// include/rvb_capi_images.h).  winners[i]: the position in a.candidates of the candidate that output impulse i is copied from, or
+// RVB_IMAGE_WINNER_DIRECT for `direct`, the selected pair's direct slot.
+#define RVB_IMAGE_WINNER_DIRECT 0xFFFFFFFFu
+#define RVB_IMAGE_GRAD_STEPS 8u          // a candidate's chain: the bounces 0 .. slot - 2, slot <= RVB_NUM_IMAGE_SOURCE - 1
+#define RVB_IMAGE_GRAD_ROW 80u           // words of a term row: the chain's surfaces [8] (0xFFFFFFFF: no step), the steps' terms [8][8], the air terms [8]
+void rvb_launch_image_gather(const rvb_image_candidate * candidates, const rvb_impulse * direct, const uint32_t * winners, uint64_t n,
+                             rvb_impulse * images, hipStream_t s);
+// rvb_reshade_grad_images.  `a`: the kept trace's arguments under the table and air that the records reflect now; `direct_dist`: the
+// place of the pair's direct slot in a.image_dist; weights: device [nchannels][8][nbins], read in place; pattern / table: the source
+// directivity that the records reflect (at most one; table_basis: the pair's three float4).  The terms kernel leaves `rows`
+// [n][RVB_IMAGE_GRAD_ROW]; the reduce kernel adds them per surface and band in binary64 — thread t of the surface's workgroup the images
+// t, t + 256, ... in list order and chain order, then a fixed tree — and writes out[nsurfaces * 16 + 8] floats, the diffuse entries +0.
+struct ImageGradArgs {
+    const uint32_t * winners;
+    const rvb_impulse * images;         // the gathered list: position and time of image i
+    uint64_t n;
+    uint64_t direct_dist;
+    const float * weights;
+    uint64_t nbins;
+    float predelay, sample_rate;
+    float mic[3];                       // the pair's microphone in the trace
+    bool has_pattern;
+    SourcePatternDev pattern;
+    const float * table;                // null: no source table
+    const float4 * table_basis;
+};
+void rvb_launch_reshade_grad_images(const TraceArgs & a, const AttenuationModel & model, const ImageGradArgs & g, uint32_t * rows, hipStream_t s);
+void rvb_launch_reshade_grad_images_reduce(const uint32_t * rows, uint64_t n, uint64_t nsurfaces, float * out, hipStream_t s);
 // Decay curves (decay_kernels.hip; rvb_decay_curve / rvb_decay_times / rvb_decay_loss of include/rvb_capi.h) on nrows rows of nbins floats.
 // Every phase is a launch of its own — a value per tile of RVB_DECAY_TILE bins, one wave per row over the row's tiles, the tile again on
 // top of its carry —; `tiles` is [nrows][rvb_decay_tiles(nbins)] doubles (three such planes for the loss: m d^2, 2 m d, g), `first`

@@ -134,18 +134,7 @@ __global__ __launch_bounds__(256) void source_pattern_images_kernel(rvb_image_ca
 //   source_table_kernel            source_pattern_kernel's sibling: volume_b *= ray_gains[pair][ray][b], the time range of the scaled records
 //   source_table_images_kernel     candidates and direct slot(s): v = mic - position, the row per record, gathered from the table
 
-// The table row for the departure vector `v`: hrtf_row of attenuation.h with pos - mic replaced by v — the listener's basis is the
-// source's (bx, by, bz of rvb_source_table_basis), the margin scheme of angle_deg and quirk Q5 of row_of included.  A row outside the table
-// (finite inputs give none) reads the zero row: no address outside the table is formed.
-__device__ __forceinline__ uint32_t departure_row(const float4 bx, const float4 by, const float4 bz, const v3 v)
-{
-    const v3 d = normalize3(v);
-    const v3 t = mk3(dot3(mk3(bx.x, bx.y, bx.z), d), dot3(mk3(by.x, by.y, by.z), d), dot3(mk3(bz.x, bz.y, bz.z), d));
-    const float az = angle_deg(t.x, t.z, 180.0f, false);
-    const float el = angle_deg(t.y, sqrtf(t.x * t.x + t.z * t.z), 0.0f, false);
-    const int64_t row = row_of(az, el);
-    return row >= 0 && row < RVB_HRTF_ROWS ? (uint32_t) row : (uint32_t) (RVB_HRTF_ROWS - 1);
-}
+// (the table row for a departure vector: departure_row of attenuation.h)
 
 // One lane per (pair, ray).
 __global__ __launch_bounds__(256) void source_table_rays_kernel(const float4 * __restrict__ directions, const float4 * __restrict__ table,

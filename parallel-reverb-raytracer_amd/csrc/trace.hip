@@ -1,5 +1,6 @@
 // trace.hip — the trace of include/rvb_capi.h: buffers, fills and kernel arguments; the path kernel; everything after it; then what a
-// trace leaves for the host (diffuse impulses, direct path, image-source candidates) and the image-source merge.  The steps that a kept
+// trace leaves for the host (diffuse impulses, direct path, image-source candidates) and the image-source merge (its rule on its own:
+// merge_image_winners, which images.hip shares).  The steps that a kept
 // trace replays (kept.hip) come first: they are declared in ctx.h.  The source directivity is source.hip's, the per-pair arrays of a
 // launch are PairLaunch's (ctx.h).
 #include "ctx.h"
@@ -219,6 +220,7 @@ int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
     ctx->void_fetched_results();
     ctx->npairs = npairs;
     ctx->traced_rays = nrays;
+    ctx->trace_ray_offset = a.ray_offset;
     ctx->pairs.mics_host.assign(mics, mics + 3 * npairs);
     ctx->select_first_pair();
     return RVB_OK;
@@ -257,6 +259,44 @@ int fetch_small(rvb_ctx * ctx)
         RVB_HIP(fail, ctx, ctx->pairs.fetch(ctx->npairs, ctx->stream));
     RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
     ctx->small_valid = true;
+    return RVB_OK;
+}
+
+int merge_image_winners(const rvb_image_candidate * candidates, uint64_t ncandidates, bool have_direct, bool remove_direct, std::vector<uint32_t> & winners)
+{
+    // reference rayverb.cpp:654-676: for each ray j and k = 1..10 the key is the first k entries of
+    // the ray's index row; inserted if absent when k == 1 or the last entry is non-zero.  Entries
+    // are zero except where a candidate exists, so rows are rebuilt from the candidates alone.
+    std::vector<uint32_t> sorted((size_t) ncandidates);
+    for (size_t i = 0; i < sorted.size(); ++i) sorted[i] = (uint32_t) i;
+    std::sort(sorted.begin(), sorted.end(), [&](uint32_t x, uint32_t y) { return by_ray_and_slot(candidates[x], candidates[y]); });
+    std::map<std::vector<unsigned long>, uint32_t> tally;
+    if (have_direct)
+        tally[std::vector<unsigned long>(1, 0)] = RVB_IMAGE_WINNER_DIRECT;      // k == 1: key {0} from ray 0
+    size_t i = 0;
+    while (i < sorted.size()) {
+        size_t j = i;
+        unsigned long row[RVB_NUM_IMAGE_SOURCE] = {0};
+        while (j < sorted.size() && candidates[sorted[j]].ray == candidates[sorted[i]].ray) {
+            const rvb_image_candidate & c = candidates[sorted[j]];
+            if (c.slot == 0 || c.slot >= RVB_NUM_IMAGE_SOURCE)
+                return RVB_ERR_INVALID;
+            row[c.slot] = c.index;
+            ++j;
+        }
+        for (size_t c = i; c < j; ++c) {
+            std::vector<unsigned long> key(row, row + candidates[sorted[c]].slot + 1);
+            if (tally.find(key) == tally.end())
+                tally[key] = sorted[c];
+        }
+        i = j;
+    }
+    if (remove_direct)
+        tally.erase(std::vector<unsigned long>(1, 0));          // rayverb.cpp:695-696
+    winners.clear();
+    winners.reserve(tally.size());
+    for (const auto & kv : tally)
+        winners.push_back(kv.second);
     return RVB_OK;
 }
 
@@ -413,41 +453,16 @@ int rvb_merge_images(const rvb_image_candidate * candidates, uint64_t ncandidate
 {
     if (!count || (ncandidates && !candidates))
         return RVB_ERR_INVALID;
-    // reference rayverb.cpp:654-676: for each ray j and k = 1..10 the key is the first k entries of
-    // the ray's index row; inserted if absent when k == 1 or the last entry is non-zero.  Entries
-    // are zero except where a candidate exists, so rows are rebuilt from the candidates alone.
-    std::vector<rvb_image_candidate> sorted(candidates, candidates + ncandidates);
-    std::sort(sorted.begin(), sorted.end(), by_ray_and_slot);
-    std::map<std::vector<unsigned long>, rvb_impulse> tally;
-    if (direct)
-        tally[std::vector<unsigned long>(1, 0)] = *direct;      // k == 1: key {0} from ray 0
-    size_t i = 0;
-    while (i < sorted.size()) {
-        size_t j = i;
-        unsigned long row[RVB_NUM_IMAGE_SOURCE] = {0};
-        while (j < sorted.size() && sorted[j].ray == sorted[i].ray) {
-            if (sorted[j].slot == 0 || sorted[j].slot >= RVB_NUM_IMAGE_SOURCE)
-                return RVB_ERR_INVALID;
-            row[sorted[j].slot] = sorted[j].index;
-            ++j;
-        }
-        for (size_t c = i; c < j; ++c) {
-            std::vector<unsigned long> key(row, row + sorted[c].slot + 1);
-            if (tally.find(key) == tally.end())
-                tally[key] = sorted[c].impulse;
-        }
-        i = j;
-    }
-    if (remove_direct)
-        tally.erase(std::vector<unsigned long>(1, 0));          // rayverb.cpp:695-696
-    *count = tally.size();
+    std::vector<uint32_t> winners;
+    const int rc = merge_image_winners(candidates, ncandidates, direct != nullptr, remove_direct != 0, winners);
+    if (rc != RVB_OK) return rc;
+    *count = winners.size();
     if (!out)
         return RVB_OK;
-    if (capacity < tally.size())
+    if (capacity < winners.size())
         return RVB_ERR_CAPACITY;
-    size_t w = 0;
-    for (const auto & kv : tally)
-        out[w++] = kv.second;
+    for (size_t w = 0; w < winners.size(); ++w)
+        out[w] = winners[w] == RVB_IMAGE_WINNER_DIRECT ? *direct : candidates[winners[w]].impulse;
     return RVB_OK;
 }
 

@@ -11,8 +11,14 @@ One evaluation never leaves the device but for a few floats per row:
     reshade_grad(w) -> dL/dtable, dL/dair        chain rule through the binning
     (reshade_grad_map(w) -> dL/dtable per TRIANGLE: decay_sensitivity_map, "where on the walls"; needs keep_paths(True, listener=True))
 
-SCOPE: that of rvb_reshade_grad — a context that holds a trace made with keep_paths(True), the diffuse records only (IR_DIFFUSE), the
-speaker model with at most 8 channels; no image sources, no HRTF.  The target and the mask are float32 CUDA tensors [nchannels][8][nbins]
+With which=IR_ALL (or IR_IMAGES) the direct sound and the image sources take part (include/rvb_capi_images.h): the second line becomes
+ir_configure_speakers_merged(which) — the merged image list made on the device, after a re-shade one gather kernel — and the gradient
+is reshade_grad_images(w), for IR_ALL plus reshade_grad(w) under an IR_DIFFUSE configuration: L is a sum over impulses, the two are
+added in binary64 and rounded to float once, for surfaces and air alike.
+
+SCOPE: that of rvb_reshade_grad and rvb_reshade_grad_images — a context that holds a trace made with keep_paths(True), the speaker model
+with at most 8 channels, no HRTF; by default the diffuse records only (which=IR_DIFFUSE, the calls of earlier versions one for one),
+with which=IR_ALL the whole response; the per-triangle map takes IR_DIFFUSE only.  The target and the mask are float32 CUDA tensors [nchannels][8][nbins]
 (numpy arrays are uploaded): the target a decay curve in linear energy, the mask >= 0 and zero outside the evaluation range."""
 import numpy as np
 
@@ -34,12 +40,20 @@ def _on_device(x, shape):
     return x
 
 
-def _histogram_and_curve(ctx, table, air, mic, speakers, sample_rate, predelay, nbins):
+def _configure(ctx, mic, speakers, which, remove_direct):
+    if which == capi.IR_DIFFUSE:
+        ctx.ir_configure_speakers(mic, speakers[0], speakers[1], capi.IR_DIFFUSE, None)
+    else:
+        ctx.ir_configure_speakers_merged(mic, speakers[0], speakers[1], which, remove_direct)
+
+
+def _histogram_and_curve(ctx, table, air, mic, speakers, sample_rate, predelay, nbins, which=capi.IR_DIFFUSE, remove_direct=False):
     """The front of every evaluation: re-shade, bin exactly, integrate.  (hist, curve), tensors [nchannels][8][nbins]; the curve is
     enqueued on the context's stream, where the loss calls find it."""
     import torch
+    assert which in (capi.IR_DIFFUSE, capi.IR_IMAGES, capi.IR_ALL)
     ctx.reshade(table, air)
-    ctx.ir_configure_speakers(mic, speakers[0], speakers[1], capi.IR_DIFFUSE, None)
+    _configure(ctx, mic, speakers, which, remove_direct)
     hist = torch.zeros((ctx.nchannels, 8, int(nbins)), dtype=torch.float32, device="cuda")
     curve = torch.empty_like(hist)
     ctx.ir_accumulate_tensor(predelay, sample_rate, nbins, capi.IR_EXACT, hist)      # (waits for torch's stream: the zero fill, the uploads)
@@ -47,45 +61,69 @@ def _histogram_and_curve(ctx, table, air, mic, speakers, sample_rate, predelay, 
     return hist, curve
 
 
-def _forward(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, want_weights):
+def _gradient(ctx, mic, speakers, predelay, sample_rate, nbins, weights, which, remove_direct):
+    """(grad_surfaces, grad_air) of the configuration that _histogram_and_curve left: reshade_grad for the diffuse records,
+    reshade_grad_images for the images, for IR_ALL their binary64 sum rounded to float once."""
+    if which == capi.IR_DIFFUSE:
+        return ctx.reshade_grad(predelay, sample_rate, nbins, weights.data_ptr())
+    grads, grad_air = ctx.reshade_grad_images(predelay, sample_rate, nbins, weights.data_ptr())
+    if which == capi.IR_IMAGES:
+        return grads, grad_air
+    ctx.ir_configure_speakers(mic, speakers[0], speakers[1], capi.IR_DIFFUSE, None)
+    diffuse, diffuse_air = ctx.reshade_grad(predelay, sample_rate, nbins, weights.data_ptr())
+    total = np.zeros_like(grads)
+    coefficients(total)[:] = (coefficients(grads).astype(np.float64) + coefficients(diffuse).astype(np.float64)).astype(np.float32)
+    return total, (grad_air.astype(np.float64) + diffuse_air.astype(np.float64)).astype(np.float32)
+
+
+def _forward(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, want_weights, which=capi.IR_DIFFUSE,
+             remove_direct=False):
     """The evaluation up to the loss: (loss, curve, weights), the tensors [nchannels][8][nbins]; weights = dL/dH, or None."""
     import torch
     shape = (ctx.nchannels, 8, int(nbins))
     nrows = ctx.nchannels * 8
     target, mask = _on_device(target, shape), _on_device(mask, shape)
-    hist, curve = _histogram_and_curve(ctx, table, air, mic, speakers, sample_rate, predelay, nbins)
+    hist, curve = _histogram_and_curve(ctx, table, air, mic, speakers, sample_rate, predelay, nbins, which, remove_direct)
     weights = torch.empty_like(hist) if want_weights else None
     loss_rows = ctx.decay_loss(hist.data_ptr(), curve.data_ptr(), target.data_ptr(), mask.data_ptr(), nrows, nbins,
                                capi.DECAY_NORMALISED if normalised else 0, weights.data_ptr() if want_weights else None)
     return float(loss_rows.sum()), curve, weights
 
 
-def _evaluate(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, want_grad):
-    loss, curve, weights = _forward(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, want_grad)
+def _evaluate(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, want_grad, which=capi.IR_DIFFUSE,
+              remove_direct=False):
+    loss, curve, weights = _forward(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, want_grad, which,
+                                    remove_direct)
     if not want_grad:
         return loss, None, None, None
     times = ctx.decay_times(curve.data_ptr(), ctx.nchannels * 8, nbins, sample_rate).reshape(ctx.nchannels, 8)
-    grads, grad_air = ctx.reshade_grad(predelay, sample_rate, nbins, weights.data_ptr())
+    grads, grad_air = _gradient(ctx, mic, speakers, predelay, sample_rate, nbins, weights, which, remove_direct)
     return loss, grads, grad_air, times
 
 
-def decay_loss_and_grad(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised=True):
+def decay_loss_and_grad(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised=True, which=capi.IR_DIFFUSE,
+                        remove_direct=False):
     """(loss, grad_surfaces, grad_air, times) of the kept trace in `ctx` under the surface table `table` and the air coefficients `air`:
     loss = sum over the rows of sum_k mask (ln E - ln target - the difference at bin 0 if normalised)^2 (rvb_decay_loss), its gradient as a
     SURFACE array and a float32[8] (rvb_reshade_grad), and the T30 of every row of the current curve, float32 [nchannels][8], NaN where
-    the curve does not reach -35 dB.  speakers = (directions, coefficients).  Leaves the context re-shaded with `table`."""
-    return _evaluate(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, True)
+    the curve does not reach -35 dB.  speakers = (directions, coefficients).  which: IR_DIFFUSE, IR_IMAGES or IR_ALL (with the direct
+    sound unless remove_direct), see the module text.  Leaves the context re-shaded with `table`."""
+    return _evaluate(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, True, which, remove_direct)
 
 
-def decay_loss(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised=True):
+def decay_loss(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised=True, which=capi.IR_DIFFUSE,
+               remove_direct=False):
     """The loss of decay_loss_and_grad alone (no weights, no gradient): what a line search evaluates."""
-    return _evaluate(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, False)[0]
+    return _evaluate(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, False, which, remove_direct)[0]
 
 
-def decay_sensitivity_map(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised=True):
+def decay_sensitivity_map(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised=True, which=capi.IR_DIFFUSE):
     """(loss, map): the loss of decay_loss_and_grad, bit for bit, and its gradient per TRIANGLE (rvb_reshade_grad_map) as a SURFACE array
     [ntriangles] — where on the walls a change of the coefficients changes this decay at this microphone; entry t belongs to triangle t of
-    the scene given to set_scene.  Needs a trace kept with keep_paths(True, listener=True).  Leaves the context re-shaded with `table`."""
+    the scene given to set_scene.  Needs a trace kept with keep_paths(True, listener=True).  Leaves the context re-shaded with `table`.
+    The map is that of the diffuse records: ValueError for which != IR_DIFFUSE (the image sources have no per-triangle gradient)."""
+    if which != capi.IR_DIFFUSE:
+        raise ValueError("decay_sensitivity_map: which must be IR_DIFFUSE (rvb_reshade_grad_map takes the diffuse records only)")
     loss, _, weights = _forward(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, True)
     per_triangle = ctx.reshade_grad_map(predelay, sample_rate, nbins, weights.data_ptr())
     return loss, np.ascontiguousarray(per_triangle.cpu().numpy()).view(SURFACE).reshape(-1)
@@ -138,7 +176,7 @@ def _fit(ctx, table, air, free, steps, lower, upper, loss_and_grad, loss_only):
 
 
 def fit_decay(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, free, steps, lower=0.01, upper=0.99,
-              normalised=True):
+              normalised=True, which=capi.IR_DIFFUSE, remove_direct=False):
     """Projected gradient descent on the coefficients of `table` that the boolean array `free` ([nsurfaces][16], the layout of
     `coefficients`) marks; every other entry keeps its bits.  A step from theta with gradient g tries theta(t) = clip(theta - t g, lower,
     upper) and halves t until the Armijo condition L(theta(t)) <= L(theta) - c g.(theta - theta(t)) holds, c = 1e-4 (without clipping
@@ -149,14 +187,16 @@ def fit_decay(ctx, table, air, mic, speakers, target, mask, sample_rate, predela
     halvings, descent (g.(theta - theta(t))).  The air is held fixed.  Scope: see the module text."""
     args = (air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised)
     return _fit(ctx, table, air, free, steps, lower, upper,
-                lambda candidate: _evaluate(ctx, candidate, *args, True)[:2], lambda candidate: _evaluate(ctx, candidate, *args, False)[0])
+                lambda candidate: _evaluate(ctx, candidate, *args, True, which, remove_direct)[:2],
+                lambda candidate: _evaluate(ctx, candidate, *args, False, which, remove_direct)[0])
 
 
 # ---- fitting to a table of measured room acoustic parameters (rvb_decay_params_loss) ------------------------------------------------
 
-def _evaluate_params(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, want_grad):
+def _evaluate_params(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, want_grad, which=capi.IR_DIFFUSE,
+                     remove_direct=False):
     import torch
-    hist, curve = _histogram_and_curve(ctx, table, air, mic, speakers, sample_rate, predelay, nbins)
+    hist, curve = _histogram_and_curve(ctx, table, air, mic, speakers, sample_rate, predelay, nbins, which, remove_direct)
     weights = torch.empty_like(hist) if want_grad else None
     shape = (ctx.nchannels * 8, capi.DECAY_NPARAMS)
     loss_rows, params = ctx.decay_params_loss(hist.data_ptr(), curve.data_ptr(), ctx.nchannels * 8, nbins, sample_rate,
@@ -165,11 +205,12 @@ def _evaluate_params(ctx, table, air, mic, speakers, targets, param_weights, sam
     params = params.reshape(ctx.nchannels, 8, capi.DECAY_NPARAMS)
     if not want_grad:
         return float(loss_rows.sum()), None, None, params
-    grads, grad_air = ctx.reshade_grad(predelay, sample_rate, nbins, weights.data_ptr())
+    grads, grad_air = _gradient(ctx, mic, speakers, predelay, sample_rate, nbins, weights, which, remove_direct)
     return float(loss_rows.sum()), grads, grad_air, params
 
 
-def params_loss_and_grad(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins):
+def params_loss_and_grad(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, which=capi.IR_DIFFUSE,
+                         remove_direct=False):
     """(loss, grad_surfaces, grad_air, params) of the kept trace in `ctx` under the surface table `table` and the air coefficients `air`
     against a measured table: targets and param_weights are [nchannels][8][7] (columns capi.DECAY_EDT .. capi.DECAY_TS: EDT, T20, T30 in
     seconds, C50, C80 in dB, D50, Ts in seconds); loss = sum over the rows and parameters of param_weights (model - targets)^2
@@ -177,21 +218,24 @@ def params_loss_and_grad(ctx, table, air, mic, speakers, targets, param_weights,
     does not yield adds nothing), its gradient as a SURFACE array and a float32[8] (rvb_reshade_grad), and the model's parameters, float32
     [nchannels][8][7], NaN where not available.  speakers = (directions, coefficients).  Leaves the context re-shaded with `table`.
 
-    SCOPE: that of rvb_reshade_grad (see the module text) — the diffuse records only.  The early-energy parameters C50, C80, D50 and Ts
-    are therefore those of the DIFFUSE response: the direct sound and the image sources, which a measurement's early energy holds, are
-    not in the model's curve."""
-    return _evaluate_params(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, True)
+    SCOPE: see the module text.  By default (which=IR_DIFFUSE) the diffuse records only: the early-energy parameters C50, C80, D50 and Ts
+    are then those of the DIFFUSE response, without the direct sound and the image sources that a measurement's early energy holds.
+    which=IR_ALL puts them into the model's curve (remove_direct: without the direct sound) and into the gradient
+    (rvb_reshade_grad_images): what a fit to measured clarity, definition or EDT wants."""
+    return _evaluate_params(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, True, which, remove_direct)
 
 
-def params_loss(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins):
+def params_loss(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, which=capi.IR_DIFFUSE, remove_direct=False):
     """The loss of params_loss_and_grad alone (no weights, no gradient), bit for bit: what a line search evaluates."""
-    return _evaluate_params(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, False)[0]
+    return _evaluate_params(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, False, which, remove_direct)[0]
 
 
-def fit_params(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, free, steps, lower=0.01, upper=0.99):
+def fit_params(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, free, steps, lower=0.01, upper=0.99,
+               which=capi.IR_DIFFUSE, remove_direct=False):
     """fit_decay's loop — projected gradient descent with Armijo steps on the coefficients that `free` marks, the same record — on the
     loss of params_loss_and_grad: calibrates materials to a table of measured T30, EDT, C80, ...  Returns (table, record).  The air is
     held fixed.  Scope: see params_loss_and_grad."""
     args = (air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins)
     return _fit(ctx, table, air, free, steps, lower, upper,
-                lambda candidate: _evaluate_params(ctx, candidate, *args, True)[:2], lambda candidate: _evaluate_params(ctx, candidate, *args, False)[0])
+                lambda candidate: _evaluate_params(ctx, candidate, *args, True, which, remove_direct)[:2],
+                lambda candidate: _evaluate_params(ctx, candidate, *args, False, which, remove_direct)[0])
