@@ -4,8 +4,9 @@
 //   source.hip   source directivity (SourceDirectivity below, over source_state.h / source_state.hip): setters, upload, launches
 //   kept.hip     behind a kept trace: re-shading, its material gradients per surface and per triangle, a new microphone
 //   memory.hip   caller-owned device / pinned memory, staged host copies, the export stream
-//   sort.hip     the sorts the other stages call, "sorted list and bin boundaries"
-//   ir.hip       materialised attenuate / flatten, the fused impulse-response stage
+//   sort.hip     the sorts the other stages call, their buffers (SortBuffers below), "sorted list and bin boundaries"
+//   ir.hip       the fused impulse-response stage (IrStage below, over ir_state.h): configure, time range, binning, download / export
+//   flatten.hip  the materialised steps of the reference: attenuate per channel, fix the predelay, flatten
 //   decay.hip    decay curves, reverberation times and the decay loss on the caller's device arrays
 //   images.hip   include/rvb_capi_images.h: the merged image list made on the device, the image-source part of the material gradient
 // No compute happens in them and nothing falls back to the CPU: every entry point that produces results launches HIP kernels:
@@ -19,6 +20,7 @@
 
 #include "../../include/rvb_capi.h"
 #include "hip_owned.h"
+#include "ir_state.h"
 #include "kernels.h"
 #include "source_state.h"
 
@@ -175,7 +177,7 @@ struct Timing { std::string name; hipEvent_t start, stop; };       // (events of
 // (ray, bounce) too, {own-plane threshold, triangle} (csrc/relisten_kernels.hip).  The buffers exist only while keeping is on.
 // The kept state is valid while rvb_ctx::traced holds and nothing has voided it: a trace voids it first (void_all) and takes it last (take).
 // The grouping order of the records is kept where the trace left it: `sort_order` is written by the record grouping of a trace and by
-// nothing else (the binning stages sort in keys_a / keys_b / vals_a / vals_b), and the next trace voids the kept state before it
+// nothing else (the binning stages sort in SortBuffers), and the next trace voids the kept state before it
 // regroups; args.sort_order points there (null: the trace grouped nothing).
 struct KeptTrace {
     bool keep_paths = false, keep_listener = false;      // asked for: the buffers come with the next trace, sized for it
@@ -234,10 +236,30 @@ struct MergedImages {
     uint64_t pair = 0;
     bool remove_direct = false;
     uint64_t count = 0;
-    bool configured = false;                     // the current IR configuration was made from the list: ctx->images is its gather
     DevBuf winners;                              // [count] uint32_t
     DevBuf grad_scratch;                         // rvb_reshade_grad_images: the term rows, then the result
     void void_list() { valid = false; }
+};
+
+// The impulse-response stage, the device half over IrState (ir_state.h): the model and the image list of the configuration, the HRTF
+// table image, and the stage's scratch.
+struct IrStage : IrState {
+    AttenuationModel model;
+    DevBuf images;                               // [nimages()] rvb_impulse
+    std::vector<rvb_impulse> images_host;        // its host copy; of a list gathered on the device once a reader has asked (ir_images_on_host)
+    DevBuf hrtf_table;
+    DevBuf speakers;                             // more than 8 speakers: AttenuationModel::speaker_table, uploaded in stream order at configure
+    std::vector<float4> speakers_host;
+    DevBuf acc, hist, scratch_in, scratch_out;
+    DevBuf flat_in;                              // rvb_flatten's upload: a buffer of its own, so that no other entry point overwrites it between a size query and the fill
+};
+
+// sort.hip's: the (key, value) list of a binning pass in keys_a / vals_a, sorted into keys_b / vals_b with bin_starts beside it
+// (sort_and_bin).  Whoever fills them calls ensure_sort_buffers first; what they hold is IrState::tenant.  own_*: csrc/radix_sort.hip's
+// tile counters and intermediate (key, value) pair.
+struct SortBuffers {
+    DevBuf keys_a, keys_b, vals_a, vals_b, temp, bin_starts;
+    DevBuf own_temp, own_keys, own_values;
 };
 
 struct rvb_ctx {
@@ -270,8 +292,6 @@ struct rvb_ctx {
     uint64_t nrays = 0;
     uint32_t concurrent_traces = 1;             // rvb_set_concurrent_traces
     uint32_t path_lanes = 0;                    // rvb_set_path_lanes: 0 = chosen per launch (rvb_path_lanes_for)
-    bool range_pending = false;                 // rvb_ir_time_range_begin has enqueued the HRTF time-range pass of the current configuration
-    int hrtf_table_ears = 0;                    // ears of the HRTF table on the device: 2 after rvb_ir_configure_hrtf, 1 after the one-ear attenuate calls
     bool traced = false;
     uint64_t nreflections = 0;
     float mic[3] = {0, 0, 0};
@@ -302,31 +322,13 @@ struct rvb_ctx {
     bool timing_failed = false;                 // an event could not be created: timings are dropped, the work itself is unaffected
     bool timing_open = false;
 
-    // impulse-response stage
-    bool ir_configured = false;
-    AttenuationModel model;
-    int which = RVB_IR_ALL;
-    DevBuf images, hrtf_table, acc, keys_a, keys_b, vals_a, vals_b, sort_temp, scratch_in, scratch_out, hist, bin_starts;
-    DevBuf flat_in;                              // rvb_flatten's upload: a buffer of its own, so that no other entry point overwrites it between a size query and the fill
-    DevBuf own_sort_temp, own_sort_keys, own_sort_values;      // csrc/radix_sort.hip: tile counters, the intermediate (key, value) pair
-    uint64_t nimages = 0;
-    std::vector<rvb_impulse> images_host;
-    bool images_host_stale = false;             // `images` was gathered on the device: images_host is fetched when a reader asks (ir_images_on_host)
+    IrStage ir;                                 // the impulse-response stage: configuration, model, image list, what the sort buffers hold
     MergedImages merged;
-    DevBuf speakers;                             // more than 8 speakers: AttenuationModel::speaker_table, uploaded in stream order at configure
-    std::vector<float4> speakers_host;
-    // exact mode in two steps (rvb_ir_exact_prepare / rvb_ir_exact_fold): what the sorted list in keys_b / vals_b / bin_starts was prepared for
-    struct ExactState { bool valid = false; bool hrtf_combined = false; uint64_t nbins = 0, n = 0, ndiffuse = 0, nimages = 0; } exact;
+    SortBuffers sort;
 
     // staged host copies (rvb_copy_to_host / rvb_copy_to_device): per worker thread a stream and two pinned bounce buffers
     struct CopyLane { Stream stream; PinnedBuf pinned[2]; Event done[2]; };
     std::vector<CopyLane> copy_lanes;
-    // rvb_flatten remembers what it uploaded for a size query, so that the fill that follows does not upload and key it again.
-    // The array sits in flat_in (written by rvb_flatten only), its keys in keys_a / vals_a: every other writer of those two
-    // (rvb_ir_accumulate in exact mode, rvb_flatten_device) clears flat_host, and so does a reallocation of the sort buffers.
-    const void * flat_host = nullptr;
-    uint64_t flat_n = 0, flat_bins = 0;
-    float flat_rate = 0.0f;
 
     ~rvb_ctx()
     {
@@ -360,10 +362,10 @@ struct rvb_ctx {
     void reset_timings() { timings.clear(); events_used = 0; }
     // From here on the results are no longer the last trace's (a trace has finished, rvb_reshade or rvb_relisten is about to rewrite
     // them): what the host has fetched of them and what the IR stage has prepared from them is void.
-    void void_fetched_results() { small_valid = false; ir_configured = false; exact.valid = false; }
+    void void_fetched_results() { small_valid = false; ir.drop_configuration(); }
     // The trace is gone (rvb_set_scene, rvb_share_scene, rvb_set_directions*, a trace that begins): nrays or the scene no longer describe
     // the records in `impulses`, so an IR configuration or a prepared exact list made for them must not be used either.
-    void void_trace() { traced = false; ir_configured = false; exact.valid = false; merged.void_list(); }
+    void void_trace() { traced = false; ir.drop_configuration(); merged.void_list(); }
     // the pair the IR stage works on, as a trace leaves it: the first, with its microphone
     void select_first_pair() { ir_pair = 0; for (int i = 0; i < 3; ++i) mic[i] = pairs.mic_of(0)[i]; }
 };
@@ -376,6 +378,12 @@ int fail(rvb_ctx * ctx, int code, const std::string & what);
 inline const rvb_impulse * ir_diffuse(const rvb_ctx * ctx)
 {
     return ctx->impulses.as<rvb_impulse>() + ctx->ir_pair * ctx->nrays * ctx->nreflections;
+}
+// ... and how many of them, and of the images, the configuration's `which` takes
+struct IrCounts { uint64_t ndiffuse, nimages; };
+inline IrCounts ir_counts(const rvb_ctx * ctx)
+{
+    return {(ctx->ir.which() & RVB_IR_DIFFUSE) ? ctx->nrays * ctx->nreflections : 0, (ctx->ir.which() & RVB_IR_IMAGES) ? ctx->ir.nimages() : 0};
 }
 
 inline uint64_t bins_for(float max_time, float predelay, float sample_rate)
@@ -406,13 +414,15 @@ int apply_source_patterns(rvb_ctx * ctx, const TraceArgs & a, const SourceShadin
 // `candidates` of the candidate it is copied from, or RVB_IMAGE_WINNER_DIRECT for the direct slot.  RVB_ERR_INVALID for a slot out of range.
 int merge_image_winners(const rvb_image_candidate * candidates, uint64_t ncandidates, bool have_direct, bool remove_direct, std::vector<uint32_t> & winners);
 // ir.hip: the halves of rvb_ir_configure_speakers / rvb_ir_configure_hrtf — the model; what both refuse; the image list and the
-// configuration's state (gathered: the caller enqueues the gather into ctx->images, no host list is uploaded) — and the host copy of the
-// image list for the readers that need one
+// configuration's state (gathered: the caller enqueues the gather into ctx->ir.images, no host list is uploaded) — and the host copy of the
+// image list for the readers that need one; the HRTF table image and the model over it, which flatten.hip's one-ear calls use too
 int ir_speaker_model(rvb_ctx * ctx, const float mic[3], const rvb_speaker * speakers, uint64_t nspeakers);
 int ir_hrtf_model(rvb_ctx * ctx, const float mic[3], const float * table, const float facing[3], const float up[3]);
 int ir_configure_refusals(rvb_ctx * ctx, int which);
 int ir_configure_images(rvb_ctx * ctx, int which, const rvb_impulse * images, uint64_t nimages, bool gathered);
 int ir_images_on_host(rvb_ctx * ctx);
+int upload_hrtf_table(rvb_ctx * ctx, const float * table, int first_ear, int ears);
+AttenuationModel hrtf_model(const rvb_ctx * ctx, const float mic[3], const float facing[3], const float up[3]);
 
 // sort.hip
 bool own_sort_enabled();

@@ -36,7 +36,7 @@ int ensure_winners(rvb_ctx * ctx, bool remove_direct)
     // From here on the list on the device is no longer the one a configuration may have been made from: that configuration goes with
     // it (a failure above has left both as they were).
     merged.valid = false;
-    if (merged.configured) { ctx->ir_configured = false; ctx->exact.valid = false; merged.configured = false; }
+    if (ctx->ir.from_merged_list()) ctx->ir.drop_configuration();
     RVB_HIP(fail, ctx, merged.winners.ensure(winners.size() * sizeof(uint32_t)));
     if (!winners.empty()) RVB_HIP(fail, ctx, hipMemcpy(merged.winners.p, winners.data(), winners.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     merged.count = winners.size();
@@ -63,7 +63,7 @@ int configure_merged(rvb_ctx * ctx, int which, int remove_direct, uint64_t * nim
     ctx->reset_timings();
     ctx->begin_timing("image_gather_kernel");
     rvb_launch_image_gather(ctx->candidates.as<rvb_image_candidate>(), direct_slot(ctx), ctx->merged.winners.as<uint32_t>(), n,
-                            ctx->images.as<rvb_impulse>(), ctx->stream);
+                            ctx->ir.images.as<rvb_impulse>(), ctx->stream);
     ctx->end_timing();
     RVB_HIP(fail, ctx, hipGetLastError());
     if (nimages) *nimages = n;
@@ -99,22 +99,22 @@ int rvb_reshade_grad_images(rvb_ctx * ctx, float predelay, float sample_rate, ui
     if (!std::isfinite(predelay) || !std::isfinite(sample_rate)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_images: predelay or sample rate is not finite");
     if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: nothing traced (or the scene or the directions have changed since)");
     if (!ctx->kept.valid) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: the last trace was made without rvb_keep_paths(ctx, 1)");
-    if (!ctx->ir_configured)
+    if (!ctx->ir.configured())
         return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: no IR configuration (rvb_ir_configure_speakers_merged after the trace, re-shade or relisten)");
-    if (ctx->model.hrtf) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: the HRTF model is configured; this version takes the speaker model only");
-    if (!ctx->merged.configured || !ctx->merged.valid)
+    if (ctx->ir.model.hrtf) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: the HRTF model is configured; this version takes the speaker model only");
+    if (!ctx->ir.from_merged_list() || !ctx->merged.valid)
         return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: the caller's list has lost its chains: configure with rvb_ir_configure_speakers_merged");
-    if (ctx->which == RVB_IR_DIFFUSE)
+    if (ctx->ir.which() == RVB_IR_DIFFUSE)
         return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: configured with which == RVB_IR_DIFFUSE: no image takes part (rvb_reshade_grad has that gradient)");
-    if (ctx->model.nchannels > 8)
-        return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: " + std::to_string(ctx->model.nchannels) + " speaker channels configured; this version takes 1 to 8");
+    if (ctx->ir.model.nchannels > 8)
+        return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: " + std::to_string(ctx->ir.model.nchannels) + " speaker channels configured; this version takes 1 to 8");
     if (ctx->nsurfaces >= (1ull << 27)) return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad_images: too many surfaces");
     RVB_BIND(ctx);
     KeptTrace & kept = ctx->kept;
     MergedImages & merged = ctx->merged;
     TraceArgs a = kept.shaded_args();
     a.scene.stamps = nullptr;
-    const uint64_t n = ctx->nimages, entries = ctx->nsurfaces * 16 + 8;
+    const uint64_t n = ctx->ir.nimages(), entries = ctx->nsurfaces * 16 + 8;
     // the term rows, then the result
     const size_t row_bytes = (size_t) n * RVB_IMAGE_GRAD_ROW * sizeof(uint32_t);
     RVB_HIP(fail, ctx, merged.grad_scratch.ensure(row_bytes + entries * sizeof(float)));
@@ -122,7 +122,7 @@ int rvb_reshade_grad_images(rvb_ctx * ctx, float predelay, float sample_rate, ui
     float * d_out = reinterpret_cast<float *>(merged.grad_scratch.as<char>() + row_bytes);
     ImageGradArgs g = {};
     g.winners = merged.winners.as<const uint32_t>();
-    g.images = ctx->images.as<const rvb_impulse>();
+    g.images = ctx->ir.images.as<const rvb_impulse>();
     g.n = n;
     g.direct_dist = a.nrays * (RVB_NUM_IMAGE_SOURCE - 1) + ctx->ir_pair;
     g.weights = reinterpret_cast<const float *>(d_weights);
@@ -141,7 +141,7 @@ int rvb_reshade_grad_images(rvb_ctx * ctx, float predelay, float sample_rate, ui
     }
     ctx->reset_timings();
     ctx->begin_timing("reshade_grad_images_kernel");
-    rvb_launch_reshade_grad_images(a, ctx->model, g, rows, ctx->stream);
+    rvb_launch_reshade_grad_images(a, ctx->ir.model, g, rows, ctx->stream);
     ctx->end_timing();
     ctx->begin_timing("reshade_grad_images_reduce_kernel");
     rvb_launch_reshade_grad_images_reduce(rows, n, ctx->nsurfaces, d_out, ctx->stream);

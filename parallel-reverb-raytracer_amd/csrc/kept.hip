@@ -21,7 +21,7 @@ static ReshadeGradArgs grad_args(const rvb_ctx * ctx, float predelay, float samp
 {
     const KeptTrace & kept = ctx->kept;
     ReshadeGradArgs g;
-    g.weights = ctx->acc.as<float>();
+    g.weights = ctx->ir.acc.as<float>();
     g.nbins = nbins;
     g.predelay = predelay;
     g.sample_rate = sample_rate;
@@ -147,33 +147,33 @@ int rvb_reshade_grad(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t 
     if (!std::isfinite(predelay) || !std::isfinite(sample_rate)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: predelay or sample rate is not finite");
     if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: nothing traced (or the scene or the directions have changed since)");
     if (!ctx->kept.valid) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: the last trace was made without rvb_keep_paths(ctx, 1)");
-    if (!ctx->ir_configured) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: no IR configuration (rvb_ir_configure_speakers after the trace or re-shade)");
-    if (ctx->model.hrtf) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: the HRTF model is configured; this version takes the speaker model only");
-    if (ctx->which != RVB_IR_DIFFUSE) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: configured with image sources; this version takes which == RVB_IR_DIFFUSE only");
-    if (ctx->model.nchannels > 8)
-        return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: " + std::to_string(ctx->model.nchannels) + " speaker channels configured; this version takes 1 to 8");
+    if (!ctx->ir.configured()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: no IR configuration (rvb_ir_configure_speakers after the trace or re-shade)");
+    if (ctx->ir.model.hrtf) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: the HRTF model is configured; this version takes the speaker model only");
+    if (ctx->ir.which() != RVB_IR_DIFFUSE) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: configured with image sources; this version takes which == RVB_IR_DIFFUSE only");
+    if (ctx->ir.model.nchannels > 8)
+        return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: " + std::to_string(ctx->ir.model.nchannels) + " speaker channels configured; this version takes 1 to 8");
     if (ctx->nreflections > RVB_RESHADE_GRAD_MAX_REFLECTIONS)
         return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad: more than " RVB_STR(RVB_RESHADE_GRAD_MAX_REFLECTIONS) " reflections");
     if (ctx->nsurfaces >= (1ull << 27)) return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad: too many surfaces");
     RVB_BIND(ctx);
     KeptTrace & kept = ctx->kept;
     const TraceArgs a = for_record_pass(ctx, kept.shaded_args());
-    const uint32_t nchannels = ctx->model.nchannels;
+    const uint32_t nchannels = ctx->ir.model.nchannels;
     const uint64_t entries = ctx->nsurfaces * 16 + 8;
     const uint32_t blocks = rvb_reshade_grad_blocks(ctx->nrays, ctx->nsurfaces);
     // the weights in the accumulation image's layout go where that image goes; the result (floats), then the partial tables (doubles)
     const size_t out_bytes = (entries * sizeof(float) + 15) & ~(size_t) 15;
-    RVB_HIP(fail, ctx, ctx->acc.ensure((size_t) nbins * nchannels * 8 * sizeof(float)));
+    RVB_HIP(fail, ctx, ctx->ir.acc.ensure((size_t) nbins * nchannels * 8 * sizeof(float)));
     RVB_HIP(fail, ctx, kept.dev.grad_scratch.ensure(out_bytes + (size_t) blocks * entries * sizeof(double)));
     float * d_out = kept.dev.grad_scratch.as<float>();
     double * partials = reinterpret_cast<double *>(kept.dev.grad_scratch.as<char>() + out_bytes);
     const ReshadeGradArgs g = grad_args(ctx, predelay, sample_rate, nbins);
     ctx->reset_timings();
     ctx->begin_timing("reshade_grad_weights_kernel");
-    rvb_launch_reshade_grad_weights(reinterpret_cast<const float *>(d_weights), ctx->acc.as<float>(), nchannels, nbins, ctx->stream);
+    rvb_launch_reshade_grad_weights(reinterpret_cast<const float *>(d_weights), ctx->ir.acc.as<float>(), nchannels, nbins, ctx->stream);
     ctx->end_timing();
     ctx->begin_timing("reshade_grad_kernel");
-    rvb_launch_reshade_grad(a, kept.dev.paths.as<const float4>(), ctx->model, g, partials, blocks, ctx->stream);
+    rvb_launch_reshade_grad(a, kept.dev.paths.as<const float4>(), ctx->ir.model, g, partials, blocks, ctx->stream);
     ctx->end_timing();
     ctx->begin_timing("reshade_grad_reduce_kernel");
     rvb_launch_reshade_grad_reduce(partials, blocks, ctx->nsurfaces, d_out, ctx->stream);
@@ -201,11 +201,11 @@ int rvb_reshade_grad_map(rvb_ctx * ctx, float predelay, float sample_rate, uint6
     if (!ctx->kept.valid || !ctx->kept.listener_valid)
         return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: the last trace was made without rvb_keep_paths(ctx, RVB_KEEP_MATERIALS | RVB_KEEP_LISTENER): "
                                         "a record's triangle is in its listener record");
-    if (!ctx->ir_configured) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: no IR configuration (rvb_ir_configure_speakers after the trace or re-shade)");
-    if (ctx->model.hrtf) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: the HRTF model is configured; this version takes the speaker model only");
-    if (ctx->which != RVB_IR_DIFFUSE)
+    if (!ctx->ir.configured()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: no IR configuration (rvb_ir_configure_speakers after the trace or re-shade)");
+    if (ctx->ir.model.hrtf) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: the HRTF model is configured; this version takes the speaker model only");
+    if (ctx->ir.which() != RVB_IR_DIFFUSE)
         return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: configured with image sources; this version takes which == RVB_IR_DIFFUSE only");
-    const uint32_t nchannels = ctx->model.nchannels;
+    const uint32_t nchannels = ctx->ir.model.nchannels;
     if (nchannels > 8) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: " + std::to_string(nchannels) + " speaker channels configured; this version takes 1 to 8");
     {
         const uintptr_t m0 = (uintptr_t) d_map, m1 = m0 + ntriangles * sizeof(rvb_surface);
@@ -228,29 +228,28 @@ int rvb_reshade_grad_map(rvb_ctx * ctx, float predelay, float sample_rate, uint6
     // the term rows, then the fold's partials; the (key, value) list in the sort buffers, which voids a prepared exact list and the keys
     // that a size query of rvb_flatten left
     const size_t term_bytes = (size_t) n * 16 * sizeof(float);
-    RVB_HIP(fail, ctx, ctx->acc.ensure((size_t) nbins * nchannels * 8 * sizeof(float)));
+    RVB_HIP(fail, ctx, ctx->ir.acc.ensure((size_t) nbins * nchannels * 8 * sizeof(float)));
     RVB_HIP(fail, ctx, kept.dev.map_scratch.ensure(term_bytes + (size_t) rvb_grad_map_tiles(n) * 2 * 16 * sizeof(double)));
     int rc = ensure_sort_buffers(ctx, n);
     if (rc != RVB_OK) return rc;
-    ctx->flat_host = nullptr;
     float * terms = kept.dev.map_scratch.as<float>();
     double * partials = reinterpret_cast<double *>(kept.dev.map_scratch.as<char>() + term_bytes);
     const ReshadeGradArgs g = grad_args(ctx, predelay, sample_rate, nbins);
     ctx->reset_timings();
     ctx->begin_timing("reshade_grad_weights_kernel");
-    rvb_launch_reshade_grad_weights(reinterpret_cast<const float *>(d_weights), ctx->acc.as<float>(), nchannels, nbins, ctx->stream);
+    rvb_launch_reshade_grad_weights(reinterpret_cast<const float *>(d_weights), ctx->ir.acc.as<float>(), nchannels, nbins, ctx->stream);
     ctx->end_timing();
     ctx->begin_timing("reshade_grad_map_terms_kernel");
-    rvb_launch_reshade_grad_map_terms(a, kept.dev.paths.as<const float4>(), kept.dev.listen.as<const uint2>(), ctx->model, g, (uint32_t) ntriangles, terms,
-                                      ctx->keys_a.as<uint32_t>(), ctx->vals_a.as<uint32_t>(), ctx->stream);
+    rvb_launch_reshade_grad_map_terms(a, kept.dev.paths.as<const float4>(), kept.dev.listen.as<const uint2>(), ctx->ir.model, g, (uint32_t) ntriangles, terms,
+                                      ctx->sort.keys_a.as<uint32_t>(), ctx->sort.vals_a.as<uint32_t>(), ctx->stream);
     ctx->end_timing();
     ctx->begin_timing("reshade_grad_map_sort");
     rc = sort_and_bin(ctx, n, ntriangles + 1, key_bits_for(ntriangles), true);     // (values are the entry numbers: either sort)
     ctx->end_timing();
     if (rc != RVB_OK) return rc;
-    const uint32_t * starts = ctx->bin_starts.as<uint32_t>();
+    const uint32_t * starts = ctx->sort.bin_starts.as<uint32_t>();
     ctx->begin_timing("reshade_grad_map_fold_kernel");
-    rvb_launch_reshade_grad_map_fold(ctx->keys_b.as<uint32_t>(), ctx->vals_b.as<uint32_t>(), n, (uint32_t) ntriangles, terms, partials,
+    rvb_launch_reshade_grad_map_fold(ctx->sort.keys_b.as<uint32_t>(), ctx->sort.vals_b.as<uint32_t>(), n, (uint32_t) ntriangles, terms, partials,
                                      reinterpret_cast<float *>(d_map), ctx->stream);
     ctx->end_timing();
     ctx->begin_timing("reshade_grad_map_combine_kernel");

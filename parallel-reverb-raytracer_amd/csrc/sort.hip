@@ -20,20 +20,20 @@ int own_sort(rvb_ctx * ctx, const uint32_t * keys, uint32_t value_base, uint64_t
 {
     if (n == 0 || end_bit <= begin_bit) return RVB_OK;
     const int passes = (end_bit - begin_bit + 7) / 8;
-    RVB_HIP(fail, ctx, ctx->own_sort_temp.ensure(rvb_radix_sort_temp_bytes(n)));
+    RVB_HIP(fail, ctx, ctx->sort.own_temp.ensure(rvb_radix_sort_temp_bytes(n)));
     uint32_t * tmp_k = nullptr, * tmp_v = nullptr;
     if (passes > 1) {
-        RVB_HIP(fail, ctx, ctx->own_sort_keys.ensure(n * 4));
-        RVB_HIP(fail, ctx, ctx->own_sort_values.ensure(n * 4));
-        tmp_k = ctx->own_sort_keys.as<uint32_t>();
-        tmp_v = ctx->own_sort_values.as<uint32_t>();
+        RVB_HIP(fail, ctx, ctx->sort.own_keys.ensure(n * 4));
+        RVB_HIP(fail, ctx, ctx->sort.own_values.ensure(n * 4));
+        tmp_k = ctx->sort.own_keys.as<uint32_t>();
+        tmp_v = ctx->sort.own_values.as<uint32_t>();
     }
     // passes alternate A, B, A, ...: the last one must land in the caller's buffers
     const bool last_in_b = ((passes - 1) & 1) != 0;
     uint32_t * ka = last_in_b ? tmp_k : keys_out, * va = last_in_b ? tmp_v : values_out;
     uint32_t * kb = last_in_b ? keys_out : tmp_k, * vb = last_in_b ? values_out : tmp_v;
     const uint32_t * ks = nullptr, * vs = nullptr;
-    RVB_HIP(fail, ctx, rvb_radix_sort_pairs(ctx->own_sort_temp.p, ctx->own_sort_temp.cap, keys, nullptr, value_base, ka, va, kb, vb, n,
+    RVB_HIP(fail, ctx, rvb_radix_sort_pairs(ctx->sort.own_temp.p, ctx->sort.own_temp.cap, keys, nullptr, value_base, ka, va, kb, vb, n,
                                             begin_bit, end_bit, want_keys, &ks, &vs, ctx->stream));
     if (vs != values_out || (want_keys && ks != keys_out)) return fail(ctx, RVB_ERR_HIP, "internal error: radix sort result in the wrong buffer");
     return RVB_OK;
@@ -41,13 +41,13 @@ int own_sort(rvb_ctx * ctx, const uint32_t * keys, uint32_t value_base, uint64_t
 
 int ensure_sort_buffers(rvb_ctx * ctx, uint64_t n)
 {
-    if (n * 4 > ctx->keys_a.cap || n * 4 > ctx->vals_a.cap) ctx->flat_host = nullptr;      // the keys of a size query are about to be freed
-    ctx->exact.valid = false;                 // (every caller rewrites the sort buffers)
-    RVB_HIP(fail, ctx, ctx->keys_a.ensure(n * 4));
-    RVB_HIP(fail, ctx, ctx->keys_b.ensure(n * 4));
-    RVB_HIP(fail, ctx, ctx->vals_a.ensure(n * 4));
-    RVB_HIP(fail, ctx, ctx->vals_b.ensure(n * 4));
-    RVB_HIP(fail, ctx, ctx->sort_temp.ensure(rvb_sort_temp_bytes(n)));
+    SortBuffers & b = ctx->sort;
+    ctx->ir.sort_buffers_claimed();           // (every caller rewrites the sort buffers: the keys of a size query or a prepared list go)
+    RVB_HIP(fail, ctx, b.keys_a.ensure(n * 4));
+    RVB_HIP(fail, ctx, b.keys_b.ensure(n * 4));
+    RVB_HIP(fail, ctx, b.vals_a.ensure(n * 4));
+    RVB_HIP(fail, ctx, b.vals_b.ensure(n * 4));
+    RVB_HIP(fail, ctx, b.temp.ensure(rvb_sort_temp_bytes(n)));
     return RVB_OK;
 }
 
@@ -56,16 +56,17 @@ int ensure_sort_buffers(rvb_ctx * ctx, uint64_t n)
 // sort (may_sort_own) where the key pass wrote the entry numbers 0 .. n-1 as values; every other list is rocPRIM's.
 int sort_and_bin(rvb_ctx * ctx, uint64_t n, uint64_t nkeys, int key_bits, bool may_sort_own)
 {
-    RVB_HIP(fail, ctx, ctx->bin_starts.ensure(nkeys * 8));
-    uint32_t * starts = ctx->bin_starts.as<uint32_t>();
+    SortBuffers & b = ctx->sort;
+    RVB_HIP(fail, ctx, b.bin_starts.ensure(nkeys * 8));
+    uint32_t * starts = b.bin_starts.as<uint32_t>();
     if (may_sort_own && own_sort_enabled()) {
-        const int rc = own_sort(ctx, ctx->keys_a.as<uint32_t>(), 0u, n, 0, key_bits, ctx->keys_b.as<uint32_t>(), ctx->vals_b.as<uint32_t>(), true);
+        const int rc = own_sort(ctx, b.keys_a.as<uint32_t>(), 0u, n, 0, key_bits, b.keys_b.as<uint32_t>(), b.vals_b.as<uint32_t>(), true);
         if (rc != RVB_OK) return rc;
     } else {
-        rvb_sort_pairs(ctx->sort_temp.p, ctx->sort_temp.cap, ctx->keys_a.as<uint32_t>(), ctx->keys_b.as<uint32_t>(),
-                       ctx->vals_a.as<uint32_t>(), ctx->vals_b.as<uint32_t>(), n, key_bits, ctx->stream);
+        rvb_sort_pairs(b.temp.p, b.temp.cap, b.keys_a.as<uint32_t>(), b.keys_b.as<uint32_t>(),
+                       b.vals_a.as<uint32_t>(), b.vals_b.as<uint32_t>(), n, key_bits, ctx->stream);
     }
     RVB_HIP(fail, ctx, hipMemsetAsync(starts, 0xFF, nkeys * 4, ctx->stream));
-    rvb_launch_bin_starts(ctx->keys_b.as<uint32_t>(), n, nkeys, starts, starts + nkeys, ctx->stream);
+    rvb_launch_bin_starts(b.keys_b.as<uint32_t>(), n, nkeys, starts, starts + nkeys, ctx->stream);
     return RVB_OK;
 }

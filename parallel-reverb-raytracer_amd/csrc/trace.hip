@@ -383,8 +383,7 @@ int rvb_ir_select_pair(rvb_ctx * ctx, uint64_t pair)
     if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_ir_select_pair: nothing traced");
     if (pair >= ctx->npairs) return fail(ctx, RVB_ERR_INVALID, "rvb_ir_select_pair: pair out of range");
     ctx->ir_pair = pair;
-    ctx->ir_configured = false;
-    ctx->exact.valid = false;                 // (a prepared list names the records of the pair it was made for; the fold reads ir_diffuse)
+    ctx->ir.drop_configuration();             // (a prepared list names the records of the pair it was made for; the fold reads ir_diffuse)
     for (int i = 0; i < 3; ++i) ctx->mic[i] = ctx->pairs.mic_of(pair)[i];
     return RVB_OK;
 }

@@ -1,8 +1,9 @@
 """The walks of tests/context_model.py can see what they are for — shown without a GPU.
 
 LedgerContext has the method surface of capi.Context over the CPU oracle (in the manner of tests/oracle_tracer.py) and keeps the same
-caches and flags as rvb_ctx, function by function as csrc/ does: the fetched small block, the residency of a flatten size query and what
-the sort buffers hold, the prepared list, its own copy of the images, the ear count of the table, the kept state, the selected pair.
+caches and flags as rvb_ctx, function by function as csrc/ does: the fetched small block, the tenant of the sort buffers (the keys of a
+flatten size query or a prepared list: IrState of csrc/ir_state.h) beside what the buffers really hold, its own copy of the images, the
+ear count of the table, the kept state, the selected pair.
 `forget=<site>` leaves out exactly one invalidation of the code.  The conditions below: the model and the complete stand-in agree on
 every walk; every forgotten invalidation is flagged by a directed sequence and by a quarter of the seeds; the seeds cover every
 operation, every refusal and every nbins class, and every seed shrinks and grows every buffer."""
@@ -16,25 +17,21 @@ from context_model import Disagreement, Rec, Walk
 from parallel_reverb_raytracer_amd import capi
 from parallel_reverb_raytracer_amd.dtypes import IMPULSE
 
-# the invalidation sites of csrc/, "function:what it clears"
+# the invalidation sites of csrc/, "function:what it clears" or "function:the transition of IrState it calls"
 FORGETS = (
-    "ensure_sort_buffers:exact.valid", "exact_begin:flat_host", "configure_common:exact.valid", "configure_common:range_pending",
-    "set_one_ear_table:hrtf_table_ears", "set_one_ear_table:ir_configured", "set_one_ear_table:exact.valid",
+    "ensure_sort_buffers:tenant", "configure_common:exact.valid", "configure_common:range_pending",
+    "set_one_ear_table:hrtf_table_ears", "set_one_ear_table:drop_configuration", "drop_configuration:configured", "drop_configuration:exact.valid",
     "trace_finish:void_fetched_results", "trace_finish:select_first_pair", "trace_finish:kept", "reshade:void_fetched_results",
-    "relisten:void_fetched_results", "set_scene:traced", "set_directions:traced", "void_trace:ir_configured", "keep_paths(0):release",
-    "select_pair:exact.valid", "accumulate:exact.valid", "flatten_fill:keys consumed", "reshade_grad_map:flat_host",
+    "relisten:void_fetched_results", "set_scene:traced", "set_directions:traced", "void_trace:drop_configuration", "keep_paths(0):release",
+    "select_pair:drop_configuration", "accumulate:exact.valid", "flatten_fill:keys consumed",
 )
-# ensure_sort_buffers also clears flat_host when it reallocates keys_a.  Every caller clears flat_host itself before (rvb_flatten,
-# rvb_flatten_device, exact_begin) or behind it (rvb_reshade_grad_map), so no sequence of calls can observe that line alone: it is a second
-# line of defence, and the stand-in shows exactly that.
-SHADOWED = ("ensure_sort_buffers:flat_host",)
 # NOT SHOWN here: "share_scene: traced".  rvb_share_scene needs a second context and is no operation of the walks, so the stand-in has no
 # such site and nothing here says that a walk would notice that line missing.
 
 
 class LedgerContext:
     def __init__(self, world, forget=None):
-        assert forget is None or forget in FORGETS + SHADOWED, forget
+        assert forget is None or forget in FORGETS, forget
         self.w, self.forget = world, forget
         self.scene = self.nrays = None
         self.traced, self.dev, self.npairs, self.ir_pair = False, None, 1, 0
@@ -45,9 +42,8 @@ class LedgerContext:
         self.nchannels = 0
         self.hrtf_table, self.hrtf_table_ears = None, 0
         self.range_pending, self.range_host = False, (0.0, 0.0)
-        self.exact = {"valid": False}
-        self.sort_cap, self.sort_keys = 0, "nothing"                  # capacity of keys_a, and whose keys it holds
-        self.flat_host, self.flat_n, self.flat_rate, self.flat_bins = None, 0, 0.0, 0
+        self.tenant, self.query, self.exact = "nothing", None, None   # IrState: "nothing" / "flatten query" / "exact list", and the two payloads
+        self.sort_cap, self.sort_keys = 0, "nothing"                  # capacity of keys_a, and whose keys it really holds
         self._chans = {}
 
     def forgot(self, site):
@@ -60,13 +56,23 @@ class LedgerContext:
     def synchronize(self):
         pass
 
+    # ---- ir_state.h ------------------------------------------------------------------------------------------------------------------
+    def void_exact_list(self):
+        if self.tenant == "exact list":
+            self.tenant = "nothing"
+
+    def drop_configuration(self):
+        if not self.forgot("drop_configuration:configured"):
+            self.ir_configured = False
+        if not self.forgot("drop_configuration:exact.valid"):
+            self.void_exact_list()
+
     # ---- context.hip -----------------------------------------------------------------------------------------------------------------
     def void_trace(self, site):
         if not self.forgot(site):
             self.traced = False
-        if not self.forgot("void_trace:ir_configured"):
-            self.ir_configured = False
-        self.exact["valid"] = False
+        if not self.forgot("void_trace:drop_configuration"):
+            self.drop_configuration()
 
     def set_scene(self, scene):
         self.scene = next(name for name in cm.SCENES if self.w.scene(name) is scene)
@@ -83,8 +89,8 @@ class LedgerContext:
     def void_fetched_results(self, site):
         if self.forgot(site):
             return
-        self.small_valid, self.ir_configured = False, False
-        self.exact["valid"] = False
+        self.small_valid = False
+        self.drop_configuration()
 
     def _index(self, what, xyz):
         return next(i for i, v in enumerate(self.w.scenes[self.scene][what]) if np.allclose(v, xyz))
@@ -120,9 +126,9 @@ class LedgerContext:
             self.fail(capi.ERR_STATE, "rvb_ir_select_pair: nothing traced")
         if pair >= self.npairs:
             self.fail(capi.ERR_INVALID, "rvb_ir_select_pair: pair out of range")
-        self.ir_pair, self.ir_configured = pair, False
-        if not self.forgot("select_pair:exact.valid"):
-            self.exact["valid"] = False
+        self.ir_pair = pair
+        if not self.forgot("select_pair:drop_configuration"):
+            self.drop_configuration()
 
     def _pair_diffuse(self):
         """ir_diffuse(): the slice of the selected pair — beyond the launch there is no record of this trace"""
@@ -183,8 +189,6 @@ class LedgerContext:
         if self.model[0] == "hrtf" or self.which != capi.IR_DIFFUSE or self.nchannels > 8:
             self.fail(capi.ERR_STATE, "rvb_reshade_grad_map: speakers, RVB_IR_DIFFUSE, 1 to 8 channels only")
         self.ensure_sort_buffers(self.dev.ndirs * self.dev.nrefl)
-        if not self.forgot("reshade_grad_map:flat_host"):
-            self.flat_host = None
         self.sort_keys = "a gradient map's list"
         out.zero_()                                                       # (zero weights: every entry written, every entry 0)
         return out
@@ -215,32 +219,26 @@ class LedgerContext:
     # ---- sort.hip --------------------------------------------------------------------------------------------------------------------
     def ensure_sort_buffers(self, n):
         if n > self.sort_cap:
-            if not self.forgot("ensure_sort_buffers:flat_host"):
-                self.flat_host = None
             self.sort_cap, self.sort_keys = n, "a fresh allocation"
-        if not self.forgot("ensure_sort_buffers:exact.valid"):
-            self.exact["valid"] = False
+        if not self.forgot("ensure_sort_buffers:tenant"):                 # on every call: whoever asks rewrites the buffers
+            self.tenant = "nothing"
 
-    # ---- ir.hip ----------------------------------------------------------------------------------------------------------------------
+    # ---- flatten.hip -----------------------------------------------------------------------------------------------------------------
     def flatten_keys(self, array, sample_rate):
-        self.ensure_sort_buffers(array.shape[0])
+        self.ensure_sort_buffers(array.shape[0])                          # (in front of the upload into flat_in)
         self.sort_keys = ("flat", id(array), sample_rate)
         return self.w.oracle.flatten(array, sample_rate).shape[1]
 
     def flatten_query(self, array, sample_rate):
-        self.flat_host = None
         bins = self.flatten_keys(array, sample_rate)
-        self.flat_n, self.flat_rate, self.flat_bins, self.flat_host = array.shape[0], sample_rate, bins, id(array)
+        self.tenant, self.query = "flatten query", (id(array), array.shape[0], sample_rate, bins)
         return bins
 
     def flatten_fill(self, array, sample_rate, capacity):
-        resident = self.flat_host == id(array) and self.flat_n == array.shape[0] and self.flat_rate == sample_rate
-        bins = self.flat_bins
-        if not resident:
-            self.flat_host = None
-            bins = self.flatten_keys(array, sample_rate)
+        resident = self.tenant == "flatten query" and self.query[:3] == (id(array), array.shape[0], sample_rate)
+        bins = self.query[3] if resident else self.flatten_keys(array, sample_rate)
         if not self.forgot("flatten_fill:keys consumed"):
-            self.flat_host = None
+            self.tenant = "nothing"
         if capacity < bins:
             self.fail(capi.ERR_CAPACITY, "rvb_flatten: capacity_bins too small")
         # the ordered sum follows the keys that ARE in the sort buffers: another call's keys bin this array wrongly
@@ -254,12 +252,11 @@ class LedgerContext:
     def attenuate_hrtf(self, mic, impulses, table_channel, facing, up, channel):
         if not self.forgot("set_one_ear_table:hrtf_table_ears"):          # set_one_ear_table
             self.hrtf_table_ears = 1
-        if not self.forgot("set_one_ear_table:ir_configured"):
-            self.ir_configured = False
-        if not self.forgot("set_one_ear_table:exact.valid"):
-            self.exact["valid"] = False
+        if not self.forgot("set_one_ear_table:drop_configuration"):
+            self.drop_configuration()
         return self.w.oracle.attenuate_hrtf(mic, impulses, table_channel, facing, up, channel)
 
+    # ---- ir.hip ----------------------------------------------------------------------------------------------------------------------
     def configure_common(self, kind, layout, which, images):
         if not self.traced:
             self.fail(capi.ERR_STATE, "rvb_ir_configure: nothing traced")
@@ -268,7 +265,7 @@ class LedgerContext:
         self.model, self.which, self.ir_configured = (kind, layout), which, True
         self.nchannels = 2 if kind == "hrtf" else len(cm.LAYOUTS[layout])
         if not self.forgot("configure_common:exact.valid"):
-            self.exact["valid"] = False
+            self.void_exact_list()
         if not self.forgot("configure_common:range_pending"):
             self.range_pending = False
 
@@ -322,11 +319,9 @@ class LedgerContext:
 
     def exact_prepare(self, predelay, sample_rate, nbins):
         chans = self.channels()
-        if not self.forgot("exact_begin:flat_host"):                      # exact_begin
-            self.flat_host = None
-        self.ensure_sort_buffers(chans[0].shape[0] * (2 if self.model[0] == "hrtf" else 1))
+        self.ensure_sort_buffers(chans[0].shape[0] * (2 if self.model[0] == "hrtf" else 1))          # exact_begin
         self.sort_keys = "an exact list"
-        self.exact = {"valid": True, "nbins": nbins, "chans": chans, "predelay": predelay, "rate": sample_rate}
+        self.tenant, self.exact = "exact list", {"nbins": nbins, "chans": chans, "predelay": predelay, "rate": sample_rate}
 
     def exact_fold(self, b0, b1, hist):
         e = self.exact
@@ -343,7 +338,7 @@ class LedgerContext:
             self.exact_prepare(predelay, sample_rate, nbins)
             self.exact_fold(0, nbins, hist)
         if not self.forgot("accumulate:exact.valid"):
-            self.exact["valid"] = False
+            self.void_exact_list()
 
     def ir_exact_prepare(self, predelay, sample_rate, nbins):
         if not self.ir_configured:
@@ -351,7 +346,7 @@ class LedgerContext:
         self.exact_prepare(predelay, sample_rate, nbins)
 
     def ir_exact_fold_tensor(self, nbins, bin_begin, bin_end, tensor):
-        if not self.exact["valid"] or self.exact["nbins"] != nbins:
+        if self.tenant != "exact list" or self.exact["nbins"] != nbins:
             self.fail(capi.ERR_STATE, "rvb_ir_exact_fold: rvb_ir_exact_prepare with this nbins first")
         hist = tensor.numpy()
         if hist.shape[0] != len(self.exact["chans"]):                   # (a list of another channel count: the fold would write other rows)
@@ -443,11 +438,6 @@ def test_a_forgotten_invalidation_is_flagged(world, complete, forget):
             seeds.append(seed)
     print("%s: flagged by the directed sequence %s and by the seeds %s" % (forget, directed, seeds))
     assert 4 * len(seeds) >= len(cm.SEEDS), "only seeds %s notice %s" % (seeds, forget)
-
-
-@pytest.mark.parametrize("forget", SHADOWED)
-def test_a_shadowed_line_cannot_be_observed(world, complete, forget):
-    assert not any(flagged(world, ops_of(kind, name), forget) for kind, name in WALKS)
 
 
 OPERATIONS = ("set_scene", "set_directions", "keep_paths", "set_source_pattern", "trace", "trace_pairs", "select_pair", "reshade", "relisten",
