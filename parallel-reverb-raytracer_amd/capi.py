@@ -30,6 +30,7 @@ DECAY_NORMALISED = 1
 DECAY_EDT, DECAY_T20, DECAY_T30, DECAY_C50, DECAY_C80, DECAY_D50, DECAY_TS = range(7)
 DECAY_NPARAMS = 7
 GRAD_MAP_TILE = 1024
+LIVE_TILE = 1024
 KEEP_MATERIALS, KEEP_LISTENER = 1, 2
 MULTI_REHEARSE_RCCL = 1
 TABLE_FLOATS = 360 * 180 * NUM_BANDS     # one ear of the HRTF table; a source table
@@ -143,6 +144,11 @@ _IMAGE_SIGNATURES = {
     "rvb_reshade_grad_images": (_i, _vp, _f, _f, _u64, _vp, _vp, _vp),
 }
 IMAGE_SYMBOLS = list(_IMAGE_SIGNATURES)
+# ... and of include/rvb_capi_live.h, the diagnostic of exact mode's live list (tests/test_live_header_host.py)
+_LIVE_SIGNATURES = {
+    "rvb_ir_exact_list_info": (_i, _vp, _vp, _vp, _vp),
+}
+LIVE_SYMBOLS = list(_LIVE_SIGNATURES)
 _lib = None
 
 
@@ -168,7 +174,7 @@ def load_library():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _IMAGE_SIGNATURES):
+        for table in (_SIGNATURES, _IMAGE_SIGNATURES, _LIVE_SIGNATURES):
             for name, (restype, *argtypes) in table.items():
                 function = getattr(lib, name)
                 function.restype, function.argtypes = restype, argtypes
@@ -649,6 +655,12 @@ class Context(_Handle):
         assert tensor.is_cuda and tensor.is_contiguous() and tensor.numel() == self.nchannels * 8 * nbins
         self.ir_accumulate_wait_for_torch()
         self._check(self.lib.rvb_ir_exact_fold(self.handle, nbins, bin_begin, bin_end, tensor.data_ptr()))
+
+    def ir_exact_list_info(self):
+        """(listed, live_on_device, count_valid) of the last exact-mode list of this context (rvb_ir_exact_list_info)."""
+        listed, live, valid = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int(0)
+        self._check(self.lib.rvb_ir_exact_list_info(self.handle, ctypes.byref(listed), ctypes.byref(live), ctypes.byref(valid)))
+        return listed.value, live.value, bool(valid.value)
 
     def export_tensor_to_host(self, tensor, pinned_host_tensor):
         """Enqueues, behind the binning, the copy of a device tensor (the histogram ir_accumulate_tensor filled) into a PINNED host

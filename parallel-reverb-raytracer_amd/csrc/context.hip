@@ -57,6 +57,7 @@ int rvb_create(rvb_ctx ** out, int device, unsigned flags)
     ctx->small_host = ctx->host_block.as<SmallBlock>();
     ctx->first_candidates = reinterpret_cast<rvb_image_candidate *>(ctx->small_host + 1);
     ctx->range_host = reinterpret_cast<uint32_t *>(ctx->first_candidates + kFirstCandidates);
+    ctx->live_overflow_host = ctx->range_host + 2;
     *out = ctx.release();
     return RVB_OK;
 }

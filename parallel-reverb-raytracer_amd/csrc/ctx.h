@@ -50,13 +50,15 @@ struct SmallBlock {
     uint32_t max_time_bits;             // rvb_flatten: latest attenuated time
     uint32_t pad1_;
     uint32_t trace_range[2];            // float bits: time range of the traced diffuse impulses (shadow_kernel)
+    uint32_t live_count;                // traced diffuse impulses that carry volume (live_sum_kernel behind the shadow kernel; right behind the range)
     uint32_t image_item_count;          // entries of the image-source work list (image_plan_kernel)
-    uint32_t pad2_[5];
+    uint32_t pad2_[4];
     rvb_impulse direct;
 };
 static_assert(offsetof(SmallBlock, candidate_count) == 0 && offsetof(SmallBlock, executed) == 8, "small block layout");
 static_assert(offsetof(SmallBlock, range) == 16 && offsetof(SmallBlock, max_time_bits) == 24, "small block layout");
-static_assert(offsetof(SmallBlock, trace_range) == 32 && offsetof(SmallBlock, image_item_count) == 40, "small block layout");
+static_assert(offsetof(SmallBlock, trace_range) == 32 && offsetof(SmallBlock, live_count) == 40, "small block layout");
+static_assert(offsetof(SmallBlock, image_item_count) == 44, "small block layout");
 static_assert(offsetof(SmallBlock, direct) == 64 && sizeof(SmallBlock) == 128, "small block layout");
 const size_t kFirstCandidates = 32;
 
@@ -115,11 +117,14 @@ struct PairBlock {
 // order — no host synchronisation in front of the launch; the block is written again only after the copies of the previous launch
 // have left it.  Beside them their host mirrors and, for any number of pairs, the microphones of the last launch.
 struct PairLaunch {
-    DevBuf geom, direct, range;                 // mics + sources [2 * npairs] float4, direct [npairs] rvb_impulse, ranges [npairs][2]
+    // mics + sources [2 * npairs] float4, direct [npairs] rvb_impulse, ranges [npairs][2] and behind them the live counts [npairs]
+    // (live_sum_kernel, shadow_kernels.hip)
+    DevBuf geom, direct, range;
     StagedBlock block;                          // PairBlock
     std::vector<float> mics_host;               // [npairs][3]
     std::vector<rvb_impulse> direct_host;       // fetched once per trace (fetch_small)
-    std::vector<uint32_t> range_host;
+    std::vector<uint32_t> range_host;           // ranges, then live counts
+    static size_t live_bytes(uint64_t npairs) { return npairs * sizeof(uint32_t); }
 
     // A launch of npairs > 1 pairs: the block filled and copied up, and the four pointers of `a` that then point here.
     hipError_t stage(const float * mics, const float * sources, uint64_t npairs, hipStream_t stream, TraceArgs & a)
@@ -130,9 +135,10 @@ struct PairLaunch {
         PairBlock::fill(block.block.p, mics, sources, npairs);
         if ((e = geom.ensure(PairBlock::geom_bytes(npairs))) != hipSuccess) return e;
         if ((e = direct.ensure(npairs * sizeof(rvb_impulse))) != hipSuccess) return e;
-        if ((e = range.ensure(PairBlock::range_bytes(npairs))) != hipSuccess) return e;
+        if ((e = range.ensure(PairBlock::range_bytes(npairs) + live_bytes(npairs))) != hipSuccess) return e;
         if ((e = hipMemcpyAsync(geom.p, block.block.p, PairBlock::geom_bytes(npairs), hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
         if ((e = reset_ranges(npairs, stream)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(range.as<char>() + PairBlock::range_bytes(npairs), 0, live_bytes(npairs), stream)) != hipSuccess) return e;
         a.pair_mics = geom.as<float4>();
         a.pair_sources = geom.as<float4>() + npairs;
         a.direct = direct.as<rvb_impulse>();
@@ -156,16 +162,17 @@ struct PairLaunch {
         hipError_t e = hipMemcpyAsync(range.p, PairBlock::ranges(block.block.p, npairs), PairBlock::range_bytes(npairs), hipMemcpyHostToDevice, stream);
         return e == hipSuccess ? block.record(stream) : e;
     }
-    // direct paths and time ranges into their host mirrors; the caller synchronises
+    // direct paths, time ranges and live counts into their host mirrors; the caller synchronises
     hipError_t fetch(uint64_t npairs, hipStream_t stream)
     {
         direct_host.resize(npairs);
-        range_host.resize(2 * npairs);
+        range_host.resize(3 * npairs);
         hipError_t e = hipMemcpyAsync(direct_host.data(), direct.p, npairs * sizeof(rvb_impulse), hipMemcpyDeviceToHost, stream);
-        return e == hipSuccess ? hipMemcpyAsync(range_host.data(), range.p, PairBlock::range_bytes(npairs), hipMemcpyDeviceToHost, stream) : e;
+        return e == hipSuccess ? hipMemcpyAsync(range_host.data(), range.p, PairBlock::range_bytes(npairs) + live_bytes(npairs), hipMemcpyDeviceToHost, stream) : e;
     }
     const rvb_impulse & direct_of(uint64_t pair) const { return direct_host[pair]; }
     const uint32_t * range_of(uint64_t pair) const { return range_host.data() + 2 * pair; }
+    uint32_t live_of(uint64_t pair) const { return range_host[range_host.size() / 3 * 2 + pair]; }
     const float * mic_of(uint64_t pair) const { return mics_host.data() + 3 * pair; }
 };
 
@@ -257,9 +264,11 @@ struct IrStage : IrState {
 // sort.hip's: the (key, value) list of a binning pass in keys_a / vals_a, sorted into keys_b / vals_b with bin_starts beside it
 // (sort_and_bin).  Whoever fills them calls ensure_sort_buffers first; what they hold is IrState::tenant.  own_*: csrc/radix_sort.hip's
 // tile counters and intermediate (key, value) pair.
+// live: the exact mode's live list (live_list below) — LiveHeader, then a word per tile of RVB_LIVE_TILE records.
 struct SortBuffers {
     DevBuf keys_a, keys_b, vals_a, vals_b, temp, bin_starts;
     DevBuf own_temp, own_keys, own_values;
+    DevBuf live;
 };
 
 struct rvb_ctx {
@@ -306,6 +315,7 @@ struct rvb_ctx {
     // leave the sort buffers, the IR configuration and a prepared exact list alone
     DevBuf decay_scratch;
     DevBuf impulses, early, candidates, small, stamps, sort_keys, sort_scratch, sort_order, group_temp;       // small: one SmallBlock
+    DevBuf live_stripes;                        // TraceArgs::live_stripes: zeroed when allocated, put back to zero by every launch that adds to it
     // host mirror of `small`, fetched once per trace together with the first few image-source candidates (usually all of them).
     // One PINNED block: a device-to-host copy into pageable memory is staged by the runtime and blocks the host per call (three
     // round trips of 30-160 us between the shadow kernel and the binning stage in a kernel trace); into pinned memory the copies
@@ -314,7 +324,14 @@ struct rvb_ctx {
     SmallBlock * small_host = nullptr;          // the start of host_block
     rvb_image_candidate * first_candidates = nullptr;   // [kFirstCandidates], behind small_host in the same block
     uint32_t * range_host = nullptr;            // [2] behind them: where the HRTF time-range pass lands (rvb_ir_time_range_begin)
+    // behind them: set by live_compact_kernel, straight into this pinned word, if a live list ever held more than its count allowed
+    // (the excess was dropped); fetch_small reports it
+    uint32_t * live_overflow_host = nullptr;
     bool small_valid = false;
+    // The live counts that came with the small block (SmallBlock::live_count, PairLaunch::live_of) bound the diffuse impulses that
+    // carry volume: a trace sets it; whatever rewrites the records behind the shadow kernel without counting clears it
+    // (apply_source_patterns, rvb_reshade, rvb_relisten), and the exact mode then lists every record.
+    bool live_count_valid = false;
     bool stamps_cleared = false;
     std::vector<Timing> timings;
     std::vector<Event> event_pool;

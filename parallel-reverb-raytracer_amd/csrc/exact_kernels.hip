@@ -59,6 +59,140 @@ __global__ __launch_bounds__(256) void bin_keys_hrtf_kernel(ModelDev m, const rv
     }
 }
 
+// ---- the live list: only the impulses that carry volume are sorted (a third of workload C2's shadow rays is blocked) ----
+// Three plain launches, no workgroup waits for another:
+//   live_keys_kernel      a raw key per impulse at the impulse's own position — its bin, the sentinel behind the histogram's end,
+//                         LIVE_DEAD without volume — and per tile of RVB_LIVE_TILE consecutive impulses how many carry volume;
+//   live_offsets_kernel   one workgroup: the tile counts become where each tile's live impulses start, and their total;
+//   live_compact_kernel   (key, impulse number) of every live impulse at its tile's start + its rank within the tile, then sentinel
+//                         entries from the total up to the list's length `listed`.
+// The impulses are numbered as the fold gathers them: the diffuse ones, then the images.  Tile t is impulses [t, t + 1) * RVB_LIVE_TILE
+// whatever the grid; one wave walks it in rounds of 64 consecutive impulses, so a rank is a prefix count of a ballot and the list keeps
+// the impulses in their order — with the stable sort, what the fold's sums need.  `listed` comes from the trace's count and bounds the
+// live impulses by contract; an entry that would land behind it is dropped and *overflow set, so that a broken count cannot write
+// out of bounds (the host reports it: fetch_small).
+#define LIVE_DEAD 0xFFFFFFFFu
+#define LIVE_ROUNDS (RVB_LIVE_TILE / 64)
+#define LIVE_WAVES 4                // tiles (waves) per workgroup of the key and the compaction kernel
+static_assert(RVB_LIVE_TILE % 64 == 0, "a wave walks a tile in whole rounds");
+
+struct LiveHeader { uint32_t total, pad_[3]; };          // in front of the tile words (SortBuffers::live)
+
+__device__ __forceinline__ uint32_t lanes_below(const unsigned long long mask)
+{
+    return __builtin_amdgcn_mbcnt_hi((uint32_t) (mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mask, 0u));
+}
+
+// HRTF: both ears' raw keys from one pass, ear 1's at n + the impulse's number, as bin_keys_hrtf_kernel keys them.
+template <bool HRTF>
+__global__ __launch_bounds__(64 * LIVE_WAVES) void live_keys_kernel(ModelDev m, const rvb_impulse * __restrict__ diffuse, uint64_t ndiffuse,
+                                                                    const rvb_impulse * __restrict__ images, uint64_t n, float predelay,
+                                                                    float sample_rate, uint32_t nbins, uint32_t * __restrict__ raw,
+                                                                    uint32_t * __restrict__ tile_counts)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = (uint64_t) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    const uint64_t ntiles = (n + RVB_LIVE_TILE - 1) / RVB_LIVE_TILE;
+    for (uint64_t tile = (uint64_t) blockIdx.x * LIVE_WAVES + wave; tile < ntiles; tile += (uint64_t) gridDim.x * LIVE_WAVES) {
+        uint32_t live = 0;
+#pragma unroll 4
+        for (uint32_t r = 0; r < LIVE_ROUNDS; ++r) {
+            const uint64_t j = tile * RVB_LIVE_TILE + r * 64u + lane;
+            const uint64_t jj = j < n ? j : n - 1;            // (behind the end: the last impulse again, its verdict dropped)
+            const float4 * rec = reinterpret_cast<const float4 *>(jj < ndiffuse ? diffuse + jj : images + (jj - ndiffuse));
+            const float4 v0 = rec[0], v1 = rec[1], p = rec[2];
+            const float time = rec[3].x;
+            const bool nonzero = j < n && ANY_VOLUME(v0, v1);
+            if (j < n) {
+                const v3 pos = mk3(p.x, p.y, p.z);
+                if (HRTF) {
+                    raw[j] = nonzero ? min(time_bin(hrtf_time(m, 0, pos, time), predelay, sample_rate), nbins) : LIVE_DEAD;
+                    raw[n + j] = nonzero ? nbins + 1u + min(time_bin(hrtf_time(m, 1, pos, time), predelay, sample_rate), nbins) : LIVE_DEAD;
+                } else {
+                    raw[j] = nonzero ? min(time_bin(time, predelay, sample_rate), nbins) : LIVE_DEAD;      // speaker channels keep the input time
+                }
+            }
+            live += (uint32_t) __popcll(__ballot(nonzero));
+        }
+        if (lane == 0) tile_counts[tile] = live;
+    }
+}
+
+// (Four waves, not sixteen: in the pipeline, beside the other contexts' path kernels, a workgroup of 1024 waited 0.7 ms for a CU with
+// room for all of its waves at once.)
+#define LIVE_OFFSET_THREADS 256
+__global__ __launch_bounds__(LIVE_OFFSET_THREADS) void live_offsets_kernel(uint32_t * __restrict__ tiles, uint64_t ntiles, LiveHeader * __restrict__ head)
+{
+    __shared__ uint32_t wave_sums[LIVE_OFFSET_THREADS / 64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    // a run of consecutive tiles per lane
+    const uint64_t per = (ntiles + LIVE_OFFSET_THREADS - 1) / LIVE_OFFSET_THREADS;
+    const uint64_t first = (uint64_t) threadIdx.x * per < ntiles ? (uint64_t) threadIdx.x * per : ntiles, last = first + per < ntiles ? first + per : ntiles;
+    uint32_t sum = 0;
+    for (uint64_t k = first; k < last; ++k) sum += tiles[k];
+    uint32_t upto = sum;                                       // ... through this lane, within the wave
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t below = (uint32_t) __shfl_up((int) upto, off);
+        if (lane >= (uint32_t) off) upto += below;
+    }
+    if (lane == 63u) wave_sums[wave] = upto;
+    __syncthreads();
+    uint32_t at = upto - sum;
+    for (uint32_t w = 0; w < wave; ++w) at += wave_sums[w];
+    for (uint64_t k = first; k < last; ++k) {
+        const uint32_t count = tiles[k];
+        tiles[k] = at;
+        at += count;
+    }
+    if (threadIdx.x == LIVE_OFFSET_THREADS - 1u) head->total = at;          // (the last lane's run ends with the last tile)
+}
+
+template <bool HRTF>
+__global__ __launch_bounds__(64 * LIVE_WAVES) void live_compact_kernel(const uint32_t * __restrict__ raw, uint64_t n,
+                                                                       const uint32_t * __restrict__ tile_starts,
+                                                                       const LiveHeader * __restrict__ head, uint64_t listed, uint32_t nbins,
+                                                                       uint32_t * __restrict__ keys, uint32_t * __restrict__ values,
+                                                                       uint32_t * overflow)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = (uint64_t) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    const uint64_t ntiles = (n + RVB_LIVE_TILE - 1) / RVB_LIVE_TILE;
+    for (uint64_t tile = (uint64_t) blockIdx.x * LIVE_WAVES + wave; tile < ntiles; tile += (uint64_t) gridDim.x * LIVE_WAVES) {
+        uint64_t at = tile_starts[tile];
+#pragma unroll 4
+        for (uint32_t r = 0; r < LIVE_ROUNDS; ++r) {
+            const uint64_t j = tile * RVB_LIVE_TILE + r * 64u + lane;
+            const uint32_t key = j < n ? raw[j] : LIVE_DEAD;
+            const bool live = key != LIVE_DEAD;
+            const unsigned long long mask = __ballot(live);
+            if (live) {
+                const uint64_t to = at + lanes_below(mask);
+                if (to < listed) {
+                    keys[to] = key;
+                    values[to] = (uint32_t) j;
+                    if (HRTF) {
+                        keys[listed + to] = raw[n + j];
+                        values[listed + to] = (uint32_t) j;
+                    }
+                } else {
+                    *overflow = 1u;
+                }
+            }
+            at += (uint64_t) __popcll(mask);
+        }
+    }
+    // the rest of the list: entries that match no bin (sorted last, never gathered)
+    const uint64_t total = head->total < listed ? head->total : listed;
+    for (uint64_t k = total + (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; k < listed; k += (uint64_t) gridDim.x * blockDim.x) {
+        keys[k] = nbins;
+        values[k] = 0u;
+        if (HRTF) {
+            keys[listed + k] = 2u * nbins + 1u;
+            values[listed + k] = 0u;
+        }
+    }
+}
+
 // Where each bin's run starts in the sorted key list: starts[key] = first position of that key (entries of absent keys keep
 // the caller's 0xFFFFFFFF fill).  One coalesced pass over the keys replaces a 23-step binary search per bin — 19 M dependent
 // random reads at workload C2, which made the summation kernel fetch 3 GB for 0.5 GB of impulses.
@@ -334,6 +468,32 @@ void rvb_launch_bin_starts(const uint32_t * sorted_keys, uint64_t n, uint64_t nb
 {
     if (n == 0) return;
     hipLaunchKernelGGL(bin_starts_kernel, dim3(stream_blocks(n, 256)), dim3(256), 0, s, sorted_keys, n, nbins, starts, ends);
+}
+
+size_t rvb_live_scratch_bytes(uint64_t n)
+{
+    return sizeof(LiveHeader) + (size_t) ((n + RVB_LIVE_TILE - 1) / RVB_LIVE_TILE) * sizeof(uint32_t);
+}
+
+void rvb_launch_live_list(const AttenuationModel & m, const rvb_impulse * diffuse, uint64_t ndiffuse, const rvb_impulse * images, uint64_t n,
+                          float predelay, float sample_rate, uint32_t nbins, uint64_t listed, uint32_t * raw, void * scratch,
+                          uint32_t * keys, uint32_t * values, uint32_t * overflow, hipStream_t s)
+{
+    if (n == 0) return;
+    LiveHeader * head = static_cast<LiveHeader *>(scratch);
+    uint32_t * tiles = reinterpret_cast<uint32_t *>(head + 1);
+    const uint64_t ntiles = (n + RVB_LIVE_TILE - 1) / RVB_LIVE_TILE;
+    const dim3 grid(stream_blocks(ntiles, LIVE_WAVES)), block(64 * LIVE_WAVES);
+    const ModelDev md = make_model(m);
+    if (m.hrtf) {
+        hipLaunchKernelGGL(live_keys_kernel<true>, grid, block, 0, s, md, diffuse, ndiffuse, images, n, predelay, sample_rate, nbins, raw, tiles);
+        hipLaunchKernelGGL(live_offsets_kernel, dim3(1), dim3(LIVE_OFFSET_THREADS), 0, s, tiles, ntiles, head);
+        hipLaunchKernelGGL(live_compact_kernel<true>, grid, block, 0, s, raw, n, tiles, head, listed, nbins, keys, values, overflow);
+    } else {
+        hipLaunchKernelGGL(live_keys_kernel<false>, grid, block, 0, s, md, diffuse, ndiffuse, images, n, predelay, sample_rate, nbins, raw, tiles);
+        hipLaunchKernelGGL(live_offsets_kernel, dim3(1), dim3(LIVE_OFFSET_THREADS), 0, s, tiles, ntiles, head);
+        hipLaunchKernelGGL(live_compact_kernel<false>, grid, block, 0, s, raw, n, tiles, head, listed, nbins, keys, values, overflow);
+    }
 }
 
 void rvb_launch_ordered_sum(const AttenuationModel & m, uint32_t first_channel, uint32_t nchannels, const rvb_impulse * diffuse,

@@ -3,6 +3,7 @@
 #include "bin_blocks.h"
 #include "ctx.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -147,7 +148,28 @@ int exact_begin(rvb_ctx * ctx, uint64_t nbins, uint64_t lists, ExactList & in)
     in.n = in.ndiffuse + in.nimages;
     if (in.n >= (1ull << 31)) return fail(ctx, RVB_ERR_CAPACITY, "rvb_ir_accumulate: too many impulses for exact mode");
     if (nbins >= 0x7FFFFFF0ull) return fail(ctx, RVB_ERR_CAPACITY, "rvb_ir_accumulate: too many bins for exact mode");
+    in.listed = in.n;
     return ensure_sort_buffers(ctx, lists * in.n);
+}
+
+// The live list (exact_kernels.hip) in keys_a / vals_a: `in.listed` entries per ear — the trace's count of live diffuse impulses, which
+// came down with the small block, and every image; all n where the count no longer holds (same launches, only the list is padded).
+// The raw keys pass through keys_b, which the sort overwrites afterwards.
+int live_list(rvb_ctx * ctx, ExactList & in, float predelay, float sample_rate, uint64_t nbins)
+{
+    in.compacted = true;
+    in.count_valid = ctx->live_count_valid;
+    if (in.count_valid && in.ndiffuse) {
+        const int rc = fetch_small(ctx);                // (the caller's rvb_ir_time_range or image merge has waited for it already)
+        if (rc != RVB_OK) return rc;
+        const uint64_t live = ctx->npairs > 1 ? ctx->pairs.live_of(ctx->ir_pair) : ctx->small_host->live_count;
+        in.listed = std::min(live, in.ndiffuse) + in.nimages;
+    }
+    RVB_HIP(fail, ctx, ctx->sort.live.ensure(rvb_live_scratch_bytes(in.n)));
+    rvb_launch_live_list(ctx->ir.model, ir_diffuse(ctx), in.ndiffuse, ctx->ir.images.as<rvb_impulse>(), in.n, predelay, sample_rate, (uint32_t) nbins,
+                         in.listed, ctx->sort.keys_b.as<uint32_t>(), ctx->sort.live.p, ctx->sort.keys_a.as<uint32_t>(), ctx->sort.vals_a.as<uint32_t>(),
+                         ctx->live_overflow_host, ctx->stream);
+    return RVB_OK;
 }
 
 // One channel's list: keys are bins, nbins itself marks "adds nothing" (key_bits_for(nbins) bits cover 0 .. nbins); sorted, with bin boundaries.
@@ -169,16 +191,15 @@ int exact_prepare(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbi
     int rc = exact_begin(ctx, nbins, m.hrtf ? 2 : 1, in);
     if (rc != RVB_OK) return rc;
     if (m.hrtf) {
-        uint32_t * keys = ctx->sort.keys_a.as<uint32_t>(), * values = ctx->sort.vals_a.as<uint32_t>();
-        const uint64_t nkeys = 2 * (nbins + 1);
-        rvb_launch_bin_keys_hrtf(m, ir_diffuse(ctx), in.ndiffuse, 0, in.n, predelay, sample_rate, (uint32_t) nbins, keys, values, ctx->stream);
-        rvb_launch_bin_keys_hrtf(m, ctx->ir.images.as<rvb_impulse>(), in.nimages, in.ndiffuse, in.n, predelay, sample_rate, (uint32_t) nbins, keys, values, ctx->stream);
         // (explicit values — the two halves carry the same impulse numbers — and always rocPRIM's sort: RVB_SORT=own takes identity values only.
         // Values derived from the entry's position by a transform iterator instead of an array: 1.52 -> 1.58 ms, and 0.85 -> 0.88 ms for the
         // one-list speaker form; rocPRIM's first pass reads an array faster than it evaluates an iterator.)
-        rc = sort_and_bin(ctx, 2 * in.n, nkeys, key_bits_for(nkeys - 1), false);
+        const uint64_t nkeys = 2 * (nbins + 1);
+        if ((rc = live_list(ctx, in, predelay, sample_rate, nbins)) == RVB_OK) rc = sort_and_bin(ctx, 2 * in.listed, nkeys, key_bits_for(nkeys - 1), false);
+    } else if (own_sort_enabled()) {
+        rc = exact_list(ctx, in, 0, predelay, sample_rate, nbins, true);          // identity values: the list of every impulse
     } else {
-        rc = exact_list(ctx, in, 0, predelay, sample_rate, nbins, true);
+        if ((rc = live_list(ctx, in, predelay, sample_rate, nbins)) == RVB_OK) rc = sort_and_bin(ctx, in.listed, nbins, key_bits_for(nbins), false);
     }
     if (rc != RVB_OK) return rc;
     RVB_HIP(fail, ctx, hipGetLastError());
@@ -200,10 +221,10 @@ int exact_fold(rvb_ctx * ctx, uint64_t b0, uint64_t b1, float * hist)
                                     ctx->sort.bin_starts.as<uint32_t>(), ctx->sort.bin_starts.as<uint32_t>() + nkeys, e.nbins, hist, ctx->stream, b0, b1);
     } else if (m.nchannels > 8) {
         rvb_launch_ordered_sum_wide(m, ir_diffuse(ctx), e.ndiffuse, ctx->ir.images.as<rvb_impulse>(), ctx->sort.vals_b.as<uint32_t>(),
-                                    ctx->sort.bin_starts.as<uint32_t>(), ctx->sort.bin_starts.as<uint32_t>() + e.nbins, e.n, e.nbins, hist, ctx->stream, b0, b1);
+                                    ctx->sort.bin_starts.as<uint32_t>(), ctx->sort.bin_starts.as<uint32_t>() + e.nbins, e.listed, e.nbins, hist, ctx->stream, b0, b1);
     } else {
         rvb_launch_ordered_sum(m, 0, m.nchannels, ir_diffuse(ctx), e.ndiffuse, ctx->ir.images.as<rvb_impulse>(), ctx->sort.vals_b.as<uint32_t>(),
-                               ctx->sort.bin_starts.as<uint32_t>(), ctx->sort.bin_starts.as<uint32_t>() + e.nbins, e.n, e.nbins, hist, ctx->stream, b0, b1);
+                               ctx->sort.bin_starts.as<uint32_t>(), ctx->sort.bin_starts.as<uint32_t>() + e.nbins, e.listed, e.nbins, hist, ctx->stream, b0, b1);
     }
     RVB_HIP(fail, ctx, hipGetLastError());
     return RVB_OK;
@@ -348,7 +369,13 @@ int rvb_ir_time_range(rvb_ctx * ctx, float * min_nonzero_time, float * max_time)
             if (rc != RVB_OK) return rc;
         }
         ctx->ir.range_taken();
-        RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
+        // (the wait takes the trace's small block along where nothing has fetched it yet: the exact mode sizes its list from it)
+        if (ctx->small_valid) {
+            RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
+        } else {
+            const int rc = fetch_small(ctx);
+            if (rc != RVB_OK) return rc;
+        }
         std::memcpy(got, ctx->range_host, sizeof(got));
     } else {
         // Speaker channels keep the input time (kernel.cpp:530-533), so the range is that of the raw
@@ -422,6 +449,25 @@ int rvb_ir_exact_fold(rvb_ctx * ctx, uint64_t nbins, uint64_t bin_begin, uint64_
     if (bin_begin > bin_end) return fail(ctx, RVB_ERR_INVALID, "rvb_ir_exact_fold: bin range");
     RVB_BIND(ctx);
     return exact_fold(ctx, bin_begin, bin_end, static_cast<float *>(d_histogram));
+}
+
+int rvb_ir_exact_list_info(rvb_ctx * ctx, uint64_t * listed, uint64_t * live_on_device, int * count_valid)
+{
+    if (!ctx) return RVB_ERR_INVALID;
+    if (!ctx->ir.ever_listed()) return fail(ctx, RVB_ERR_STATE, "rvb_ir_exact_list_info: no exact-mode list has been made on this context");
+    const ExactList & e = ctx->ir.exact();
+    if (listed) *listed = e.listed;
+    if (count_valid) *count_valid = e.count_valid ? 1 : 0;
+    if (live_on_device) {
+        uint32_t total = (uint32_t) e.listed;           // (the list of every impulse counts nothing)
+        if (e.compacted && e.n) {
+            RVB_BIND(ctx);
+            RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
+            RVB_HIP(fail, ctx, hipMemcpy(&total, ctx->sort.live.p, sizeof(total), hipMemcpyDeviceToHost));       // LiveHeader::total
+        }
+        *live_on_device = total;
+    }
+    return RVB_OK;
 }
 
 int rvb_ir_download(rvb_ctx * ctx, int trim_predelay, float sample_rate, int mode,

@@ -18,9 +18,13 @@ struct FlattenQuery {
 };
 
 // Exact mode in two steps (rvb_ir_exact_prepare / rvb_ir_exact_fold): what the sorted list in keys_b / vals_b / bin_starts was prepared for.
+// `listed` entries per ear: the impulses that carry volume and a tail that matches no bin (live_list, ir.hip), listed <= n; the full
+// list of RVB_SORT=own has listed == n and !compacted.  count_valid: the trace's live count sized the list.
 struct ExactList {
     bool hrtf_combined = false;
     uint64_t nbins = 0, n = 0, ndiffuse = 0, nimages = 0;
+    uint64_t listed = 0;
+    bool count_valid = false, compacted = false;
 };
 
 class IrState {
@@ -49,6 +53,8 @@ public:
         return tenant_ == FLATTEN_QUERY && in != nullptr && query_.host == in && query_.n == n && query_.sample_rate == sample_rate;
     }
     bool prepared() const { return tenant_ == EXACT_LIST; }
+    // exact() describes a list that was made, prepared still or not (rvb_ir_exact_list_info)
+    bool ever_listed() const { return ever_listed_; }
     bool prepared_for(uint64_t nbins) const { return prepared() && exact_.nbins == nbins; }
 
     // A successful rvb_ir_configure_*: replaces the previous configuration as a whole.  gathered: the list comes from the merged list
@@ -89,13 +95,13 @@ public:
     }
     // the fill's sort consumes the keys
     void flatten_filled() { tenant_ = NOTHING; }
-    void exact_prepared(const ExactList & list) { tenant_ = EXACT_LIST; exact_ = list; }
+    void exact_prepared(const ExactList & list) { tenant_ = EXACT_LIST; exact_ = list; ever_listed_ = true; }
     // include/rvb_capi.h: rvb_ir_accumulate voids a prepared list, whatever its mode and its nbins.  The keys of a size query stay:
     // RVB_IR_FAST with up to 8 speakers does not touch the sort buffers.
     void void_exact_list() { if (tenant_ == EXACT_LIST) tenant_ = NOTHING; }
 
 private:
-    bool configured_ = false, from_merged_list_ = false, host_images_stale_ = false, range_pending_ = false;
+    bool configured_ = false, from_merged_list_ = false, host_images_stale_ = false, range_pending_ = false, ever_listed_ = false;
     int which_ = 3;                              // RVB_IR_ALL
     int table_ears_ = 0;
     uint64_t nimages_ = 0;

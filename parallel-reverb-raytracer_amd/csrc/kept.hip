@@ -80,10 +80,11 @@ int rvb_relisten(rvb_ctx * ctx, const float * mics, uint64_t npairs)
     SmallBlock * small = ctx->small_dev();
     ctx->reset_timings();
     ctx->void_fetched_results();
+    ctx->live_count_valid = false;                // (a trace alone vouches for a count: after a replay exact mode lists every impulse)
     ctx->merged.void_list();                      // (the image kernels find other candidates: which of them win is decided anew)
     // what the tail appends to or folds into, back where a trace starts; `executed` stays
     RVB_HIP(fail, ctx, hipMemsetAsync(&small->candidate_count, 0, sizeof(uint32_t), ctx->stream));
-    RVB_HIP(fail, ctx, hipMemsetAsync(&small->image_item_count, 0, sizeof(SmallBlock) - offsetof(SmallBlock, image_item_count), ctx->stream));      // ... and the direct slot
+    RVB_HIP(fail, ctx, hipMemsetAsync(&small->live_count, 0, sizeof(SmallBlock) - offsetof(SmallBlock, live_count), ctx->stream));      // ... and the direct slot
     if (npairs > 1) RVB_HIP(fail, ctx, ctx->pairs.restage_mics(mics, npairs, ctx->stream));       // (reset_time_ranges, next, records the block's event)
     int rc = reset_time_ranges(ctx, a);
     if (rc != RVB_OK) return rc;
@@ -124,6 +125,7 @@ int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces,
     int rc = reset_time_ranges(ctx, a);
     if (rc != RVB_OK) return rc;
     ctx->void_fetched_results();
+    ctx->live_count_valid = false;                // (the re-shade kernels rewrite every volume and count nothing)
     ctx->begin_timing("reshade_kernel");
     rvb_launch_reshade(a, kept.dev.paths.as<const float4>(), ctx->stream);
     ctx->end_timing();

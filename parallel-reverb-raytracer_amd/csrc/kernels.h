@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/rvb_capi.h"
+#include "../../include/rvb_capi_live.h"
 #include "bvh.h"
 
 struct SceneDev {                       // device pointers of the current scene
@@ -38,7 +39,8 @@ struct TraceArgs {
                                         // (path kernels; needs nreflections % 32 == 0); exactly one of sort_keys / sort_keys16 is set, or neither
     uint32_t key_shift;
     uint32_t * sort_order;              // [nrays * nreflections] record indices grouped by bucket
-    uint32_t * time_range;              // [2] float bits: min non-zero / max time of non-zero diffuse impulses
+    uint32_t * time_range;              // [2] float bits: min non-zero / max time of non-zero diffuse impulses; behind the pairs' ranges a count
+                                        // per pair of the diffuse impulses that carry volume (rvb_launch_shadow only: live_sum_kernel)
     uint64_t nrays;
     uint32_t nreflections;
     uint32_t stack_entries;             // LDS traversal stack entries per lane (BuiltScene::stack_need)
@@ -56,7 +58,12 @@ struct TraceArgs {
     float air[8];
     float * image_dist;                 // rvb_keep_paths only, else null: [nrays * 9 + npairs] INIT_DIST of candidates[i] at i, then of the direct path of every
                                         // pair (negative: hidden) — what rvb_reshade cannot recover from an image impulse
+    // [RVB_LIVE_STRIPES][npairs] partial counts of the diffuse impulses that carry volume, all zero between launches: the shadow kernel's
+    // waves add to the stripe of their workgroup (one address for all 65 536 of them: shadow_pair_kernel 1.25 -> 5.84 ms at workload C2),
+    // and live_sum_kernel behind it adds the stripes up, zeroes them and leaves the counts behind the time ranges
+    uint32_t * live_stripes;
 };
+#define RVB_LIVE_STRIPES 1024
 
 // ---- the trace: trace_kernels.hip (path stage), image_kernels.hip, shadow_kernels.hip; their shared device code: traversal.h ----
 // Phase A (trace_kernels.hip): one lane per ray, the sequential closest-hit / reflect chain (kernel.cpp:359-375,
@@ -291,6 +298,16 @@ void rvb_launch_bin_keys_hrtf(const AttenuationModel & m, const rvb_impulse * in
 void rvb_launch_ordered_sum_hrtf(const AttenuationModel & m, const rvb_impulse * diffuse, uint64_t ndiffuse, const rvb_impulse * images,
                                  const uint32_t * sorted_values, const uint32_t * starts, const uint32_t * ends, uint64_t nbins, float * hist,
                                  hipStream_t s, uint64_t bin_begin = 0, uint64_t bin_end = ~0ull);
+// The live list of exact mode, in place of rvb_launch_bin_keys* and their identity values: only the impulses that carry volume are
+// listed (numbered as the fold gathers them: diffuse, then images), in their order, and sentinel entries fill the list up to `listed`
+// entries — per ear for the HRTF model, ear 1's half from `listed` on.  `listed` bounds the live impulses by contract (the trace's
+// count + every image); what would land behind it is dropped and *overflow (any memory the device can write) set.  raw: n words (2 n:
+// HRTF) for the raw keys; scratch: rvb_live_scratch_bytes(n) — the total of live impulses in its first word once the launches have
+// run, then a word per tile of RVB_LIVE_TILE impulses.  Three launches, none waits for another's workgroups.
+size_t rvb_live_scratch_bytes(uint64_t n);
+void rvb_launch_live_list(const AttenuationModel & m, const rvb_impulse * diffuse, uint64_t ndiffuse, const rvb_impulse * images, uint64_t n,
+                          float predelay, float sample_rate, uint32_t nbins, uint64_t listed, uint32_t * raw, void * scratch,
+                          uint32_t * keys, uint32_t * values, uint32_t * overflow, hipStream_t s);
 // starts[key] / ends[key] = first position of `key` in the sorted list / one past its last (starts[] pre-filled with 0xFFFFFFFF by
 // the caller, nbins entries each; ends[] is only read where starts[] was written)
 void rvb_launch_bin_starts(const uint32_t * sorted_keys, uint64_t n, uint64_t nbins, uint32_t * starts, uint32_t * ends, hipStream_t s);

@@ -26,6 +26,7 @@ struct ShadowJob {
     float diff, new_dist, mag;
     uint32_t surface;
     float tmin, tmax_seen;               // arrival-time range of the non-zero impulses this lane's quad produced
+    bool live;                           // the record that done() finished carries volume
     uint32_t pair;                       // pair of the current record (several pairs per launch only)
     lds_float4_ptr surf_lds;             // surface table in LDS; unused when !SURF_LDS
     uint32_t skip;                       // own-plane subtree of the triangle the shadow ray starts on, RVB_BVH_EMPTY = none
@@ -98,6 +99,8 @@ struct ShadowJob {
         // takes part iff any band is non-zero (kernel.cpp:524)
         const bool nonzero = quad_any(c < 2 && (o.x != 0.0f || o.y != 0.0f || o.z != 0.0f || o.w != 0.0f));
         note_time(a, nonzero, c == 0, pair, seconds_per_meter() * dist, tmin, tmax_seen);
+        live = nonzero;
+        if (a.npairs > 1 && nonzero && c == 0) live_count_of_pair(a, pair);
     }
 };
 
@@ -123,12 +126,15 @@ __global__ __launch_bounds__(WAVE, RVB_SHADOW_WAVES) void shadow_kernel(TraceArg
     // one record per quad per pass: the 16 quads of the wave start and finish a pass together
     v3 o, d;
     float tmax;
+    uint32_t live = 0;
     while (job.next(o, d, tmax)) {
         Hit h;
         const bool blocked = traverse_quad<true>(a.scene, o, d, tmax, stack_lds + q, h, job.skip);
         job.done(blocked, h);
+        live_count_step(a, job.live && c == 0, live);
     }
     time_range_of_wave(a, job.tmin, job.tmax_seen);
+    live_count_of_wave(a, live);
 }
 
 // shadow_kernel with two lanes per record: lane 0 carries chunks 0 and 2 of the 64-byte record (bands 0-3; hit point, DIFF), lane 1
@@ -145,7 +151,9 @@ __global__ __launch_bounds__(WAVE, RVB_SHADOW_PAIR_WAVES) void shadow_pair_kerne
     v3 mic = ld3(a.mic);
     const float air0 = a.air[4 * h], air1 = a.air[4 * h + 1], air2 = a.air[4 * h + 2], air3 = a.air[4 * h + 3];
     float tmin = __builtin_inff(), tmax_seen = 0.0f;
-    for (uint64_t g = (uint64_t) blockIdx.x * PAIRS_PER_BLOCK + q; g < total; g += stride) {
+    uint32_t live = 0, nonzero = 0;             // live records of this wave so far (live_count_step); this record's verdict
+    for (uint64_t g = (uint64_t) blockIdx.x * PAIRS_PER_BLOCK + q; g < total; g += stride, live_count_step(a, nonzero && h == 0, live)) {
+        nonzero = 0u;
         float4 * rec = reinterpret_cast<float4 *>(a.impulses + (a.sort_order ? (uint64_t) a.sort_order[g] : g));
         const float4 vol = load_stream(rec + h), aux = load_stream(rec + h + 2);
         // (from here to `skip` the three kernels differ in the gathers only; a shared aim helper moved instructions in this one and in shadow_kernel)
@@ -183,7 +191,7 @@ __global__ __launch_bounds__(WAVE, RVB_SHADOW_PAIR_WAVES) void shadow_pair_kerne
         store_stream(rec + h, o);
         store_stream(rec + h + 2, h == 0 ? make_float4(p.x, p.y, p.z, 0.0f) : make_float4(t, 0.0f, 0.0f, 0.0f));
         // inputs of findPredelay / MAX_SAMPLE (rayverb.h:49-74, rayverb.cpp:54-57): an impulse takes part iff any band is non-zero
-        uint32_t nonzero = (o.x != 0.0f || o.y != 0.0f || o.z != 0.0f || o.w != 0.0f) ? 1u : 0u;
+        nonzero = (o.x != 0.0f || o.y != 0.0f || o.z != 0.0f || o.w != 0.0f) ? 1u : 0u;
         nonzero |= dpp_u<QP_SWAP1>(nonzero);
         if (nonzero) {
             if (a.npairs > 1) {
@@ -191,6 +199,7 @@ __global__ __launch_bounds__(WAVE, RVB_SHADOW_PAIR_WAVES) void shadow_pair_kerne
                     const volatile uint32_t * seen = a.time_range + 2u * pair;
                     if (t != 0.0f && __float_as_uint(t) < seen[0]) atomicMin(a.time_range + 2u * pair, __float_as_uint(t));
                     if (__float_as_uint(t) > seen[1]) atomicMax(a.time_range + 2u * pair + 1u, __float_as_uint(t));
+                    live_count_of_pair(a, pair);
                 }
             } else {
                 if (t != 0.0f) tmin = fminf(tmin, t);
@@ -199,6 +208,7 @@ __global__ __launch_bounds__(WAVE, RVB_SHADOW_PAIR_WAVES) void shadow_pair_kerne
         }
     }
     time_range_of_wave(a, tmin, tmax_seen);
+    live_count_of_wave(a, live);
 }
 
 // shadow_pair_kernel with ONE lane per record (round 4, RVB_SHADOW_LANES=1): 64 records per wave pass, every lane walks its own any-hit
@@ -222,7 +232,10 @@ __global__ __launch_bounds__(WAVE, RVB_LANE_WAVES) void shadow_lane_kernel(Trace
     const lds_u32_ptr bottom = (lds_u32_ptr) stack_lds + lane;
     v3 mic = ld3(a.mic);
     float tmin = __builtin_inff(), tmax_seen = 0.0f;
-    for (uint64_t g = (uint64_t) blockIdx.x * LANE_RAYS + lane; g < total; g += stride) {
+    uint32_t live = 0;
+    bool nonzero = false;
+    for (uint64_t g = (uint64_t) blockIdx.x * LANE_RAYS + lane; g < total; g += stride, live_count_step(a, nonzero, live)) {
+        nonzero = false;
         float4 * rec = reinterpret_cast<float4 *>(a.impulses + (a.sort_order ? (uint64_t) a.sort_order[g] : g));
         const float4 vol_lo = load_stream(rec + 0), vol_hi = load_stream(rec + 1), geo = load_stream(rec + 2), aux = load_stream(rec + 3);
         const uint32_t tag = __float_as_uint(aux.w);
@@ -319,11 +332,31 @@ __global__ __launch_bounds__(WAVE, RVB_LANE_WAVES) void shadow_lane_kernel(Trace
         store_stream(rec + 1, o_hi);
         store_stream(rec + 2, make_float4(p.x, p.y, p.z, 0.0f));
         store_stream(rec + 3, make_float4(t, 0.0f, 0.0f, 0.0f));
-        const bool nonzero = o_lo.x != 0.0f || o_lo.y != 0.0f || o_lo.z != 0.0f || o_lo.w != 0.0f
-                          || o_hi.x != 0.0f || o_hi.y != 0.0f || o_hi.z != 0.0f || o_hi.w != 0.0f;
+        nonzero = o_lo.x != 0.0f || o_lo.y != 0.0f || o_lo.z != 0.0f || o_lo.w != 0.0f
+               || o_hi.x != 0.0f || o_hi.y != 0.0f || o_hi.z != 0.0f || o_hi.w != 0.0f;
         note_time(a, nonzero, true, pair, t, tmin, tmax_seen);
+        if (a.npairs > 1 && nonzero) live_count_of_pair(a, pair);
     }
     time_range_of_wave(a, tmin, tmax_seen);
+    live_count_of_wave(a, live);
+}
+
+// One wave behind a shadow kernel: pair by pair, lane t takes the stripes t, t + 64, ... of a.live_stripes — their partial counts, which
+// it puts back to zero for the next launch — and the wave's sum is the pair's count, written (not added) behind the launch's time
+// ranges.  (One wave, not a workgroup of 1024: in the pipeline, beside the other contexts' path kernels, sixteen waves that must fit
+// one CU together waited 47 us for their place.)
+__global__ __launch_bounds__(WAVE) void live_sum_kernel(uint32_t * __restrict__ stripes, uint32_t npairs, uint32_t * __restrict__ counts)
+{
+    for (uint32_t pair = 0; pair < npairs; ++pair) {
+        uint32_t sum = 0;
+        for (uint32_t stripe = threadIdx.x; stripe < RVB_LIVE_STRIPES; stripe += WAVE) {
+            sum += stripes[stripe * npairs + pair];
+            stripes[stripe * npairs + pair] = 0u;
+        }
+        for (int off = 32; off > 0; off >>= 1)
+            sum += (uint32_t) __shfl_xor((int) sum, off);
+        if (threadIdx.x == 0) counts[pair] = sum;
+    }
 }
 
 }  // namespace
@@ -352,4 +385,6 @@ void rvb_launch_shadow(const TraceArgs & a, hipStream_t s)
     if (lanes == 1) launch_by_surfaces(shadow_lane_kernel<true>, shadow_lane_kernel<false>, a.lds_surfaces, blocks, lds, s, a);
     else if (lanes == 2) launch_by_surfaces(shadow_pair_kernel<true>, shadow_pair_kernel<false>, a.lds_surfaces, blocks, lds, s, a);
     else launch_by_surfaces(shadow_kernel<true>, shadow_kernel<false>, a.lds_surfaces, blocks, lds, s, a);
+    const uint32_t npairs = a.npairs > 1 ? a.npairs : 1u;
+    hipLaunchKernelGGL(live_sum_kernel, dim3(1), dim3(WAVE), 0, s, a.live_stripes, npairs, a.time_range + 2u * npairs);
 }

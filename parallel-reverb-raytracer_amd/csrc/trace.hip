@@ -69,6 +69,7 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     const float * mic = mics, * source = sources;
     RVB_BIND(ctx);
     ctx->void_trace();                                // (until trace_finish: a failure below must not leave the last trace's results half reset)
+    ctx->live_count_valid = false;
     ctx->kept.void_all();
     const uint64_t nrays = ctx->nrays * npairs;       // rays of this launch
     const size_t imp_bytes = (size_t) nrays * nreflections * sizeof(rvb_impulse);
@@ -77,6 +78,12 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     RVB_HIP(fail, ctx, ctx->early.ensure(early_bytes));
     RVB_HIP(fail, ctx, ctx->candidates.ensure((size_t) nrays * 9 * sizeof(rvb_image_candidate)));
     RVB_HIP(fail, ctx, ctx->image_items.ensure(((size_t) nrays * 9 + npairs) * 3 * sizeof(uint32_t)));      // (ray, bounce) entries, then a state word each
+    const size_t stripe_bytes = (size_t) RVB_LIVE_STRIPES * npairs * sizeof(uint32_t);
+    if (stripe_bytes > ctx->live_stripes.cap) {
+        RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));          // (a launch that still adds to the old block)
+        RVB_HIP(fail, ctx, ctx->live_stripes.ensure(stripe_bytes));
+        RVB_HIP(fail, ctx, hipMemsetAsync(ctx->live_stripes.p, 0, stripe_bytes, ctx->stream));
+    }
     KeptTrace & kept = ctx->kept;
     if (kept.keep_paths) {                            // rvb_keep_paths: what rvb_reshade needs beside the results
         RVB_HIP(fail, ctx, kept.dev.paths.ensure((size_t) nrays * nreflections * sizeof(float4)));
@@ -112,6 +119,7 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     a.executed = &small->executed;
     a.time_range = small->trace_range;
     a.image_dist = kept.keep_paths ? kept.dev.image_dist.as<float>() : nullptr;
+    a.live_stripes = ctx->live_stripes.as<uint32_t>();
     RVB_HIP(fail, ctx, ctx->pairs.stage(mics, sources, npairs, ctx->stream, a));        // several pairs per launch: the four above point to arrays per pair
     // record bucketing for coherent shadow rays (RVB_SHADOW_SORT=0 turns it off)
     static const bool sort_records = !(getenv("RVB_SHADOW_SORT") && getenv("RVB_SHADOW_SORT")[0] == '0');
@@ -213,6 +221,7 @@ int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
         ctx->end_timing();
     }
     const SourceShading source = ctx->source.shading();
+    ctx->live_count_valid = true;               // the shadow stage leaves the count (a directivity pass behind it clears this: apply_source_patterns)
     if ((rc = launch_shadow_behind_images(ctx, a, source)) != RVB_OK) return rc;
     ctx->kept.take(a, source);
     ctx->nreflections = nreflections;
@@ -258,6 +267,10 @@ int fetch_small(rvb_ctx * ctx)
     if (ctx->npairs > 1)       // per-pair direct paths and time ranges
         RVB_HIP(fail, ctx, ctx->pairs.fetch(ctx->npairs, ctx->stream));
     RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
+    if (*ctx->live_overflow_host) {            // (the lists behind this point are sound again: the word is reported once)
+        *ctx->live_overflow_host = 0;
+        return fail(ctx, RVB_ERR_HIP, "internal error: an exact-mode list held more live impulses than the trace had counted; the histogram made from it lacks the excess");
+    }
     ctx->small_valid = true;
     return RVB_OK;
 }

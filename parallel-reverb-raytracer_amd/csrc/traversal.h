@@ -853,6 +853,42 @@ __device__ __forceinline__ void time_range_of_wave(const TraceArgs & a, float tm
     }
 }
 
+// How many diffuse impulses of a pair carry volume (the shadow stage only): the exact mode lists no more than these (SmallBlock::live_count,
+// PairLaunch).  The waves add to a.live_stripes, the stripe of their workgroup; live_sum_kernel (shadow_kernels.hip) makes the counts.
+__device__ __forceinline__ uint32_t * live_count_of(const TraceArgs & a, const uint32_t pair)
+{
+    const uint32_t stripe = blockIdx.x & (RVB_LIVE_STRIPES - 1u);
+    return a.live_stripes + (a.npairs > 1 ? stripe * a.npairs + pair : stripe);
+}
+// One pair: the wave counts in the step of its record loop, where the lanes that skipped a record are back — `nz_writer` is set in one
+// lane per live record, so the count is a population count of a ballot and needs no vector register inside the loop —, and adds once
+// at the kernel's end.  The lanes still in the loop take a step together, so the lane that leaves last has taken every step and holds
+// the wave's count: the largest of the lanes' values.
+__device__ __forceinline__ void live_count_step(const TraceArgs & a, const bool nz_writer, uint32_t & live)
+{
+    if (a.npairs <= 1) live += (uint32_t) __popcll(__ballot(nz_writer));
+}
+__device__ __forceinline__ void live_count_of_wave(const TraceArgs & a, uint32_t live)
+{
+    for (int off = 32; off > 0; off >>= 1)
+        live = max(live, (uint32_t) __shfl_xor((int) live, off));
+    if (threadIdx.x == 0 && a.npairs <= 1 && live) atomicAdd(live_count_of(a, 0), live);
+}
+// Several pairs per launch: called by the writer lane of a live record; one add per pair among them (a wave's records are neighbours in
+// grouped order: nearly always one pair).
+__device__ __forceinline__ void live_count_of_pair(const TraceArgs & a, const uint32_t pair)
+{
+    for (;;) {
+        const uint32_t p = (uint32_t) __builtin_amdgcn_readfirstlane((int) pair);
+        const unsigned long long same = __ballot(pair == p);
+        if (pair == p) {
+            if ((uint32_t) __builtin_amdgcn_mbcnt_hi((uint32_t) (same >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) same, 0u)) == 0u)
+                atomicAdd(live_count_of(a, p), (uint32_t) __popcll(same));
+            break;
+        }
+    }
+}
+
 // kernel.cpp:480-485 for one band: newVol * attenuation * diffuse * DIFF, left to right.  (One band at a time: a float4 form changes all three kernels.)
 __device__ __forceinline__ float band_product(const float vol, const float att, const float dc, const float diff) { return ((vol * att) * dc) * diff; }
 
