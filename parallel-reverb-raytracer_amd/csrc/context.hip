@@ -40,7 +40,6 @@ int rvb_create(rvb_ctx ** out, int device, unsigned flags)
     // The side stream (image_kernel) runs at the lowest priority: the record grouping on the main stream is the critical
     // path between path_kernel and shadow_kernel and must not queue behind image_kernel's 14 k workgroups.
     int prio_least = 0, prio_greatest = 0;
-    const size_t host_bytes = sizeof(SmallBlock) + kFirstCandidates * sizeof(rvb_image_candidate) + 16;
     if ((e = hipSetDevice(device)) != hipSuccess || (e = hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest)) != hipSuccess ||
         (e = hipStreamCreateWithPriority(&ctx->stream.h, hipStreamNonBlocking, prio_greatest)) != hipSuccess ||
         (e = hipStreamCreateWithPriority(&ctx->side_stream.h, hipStreamNonBlocking, prio_least)) != hipSuccess ||
@@ -50,14 +49,8 @@ int rvb_create(rvb_ctx ** out, int device, unsigned flags)
         (e = hipEventCreateWithFlags(&ctx->side_done.h, hipEventDisableTiming)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&ctx->prep_done.h, hipEventDisableTiming)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&ctx->group_done.h, hipEventDisableTiming)) != hipSuccess ||
-        (e = ctx->small.ensure(sizeof(SmallBlock))) != hipSuccess ||
-        (e = ctx->host_block.ensure(host_bytes)) != hipSuccess)
+        (e = ctx->trace.create()) != hipSuccess)
         return fail(nullptr, RVB_ERR_HIP, std::string("rvb_create: ") + hipGetErrorString(e));
-    std::memset(ctx->host_block.p, 0, host_bytes);
-    ctx->small_host = ctx->host_block.as<SmallBlock>();
-    ctx->first_candidates = reinterpret_cast<rvb_image_candidate *>(ctx->small_host + 1);
-    ctx->range_host = reinterpret_cast<uint32_t *>(ctx->first_candidates + kFirstCandidates);
-    ctx->live_overflow_host = ctx->range_host + 2;
     *out = ctx.release();
     return RVB_OK;
 }
@@ -277,11 +270,11 @@ int rvb_last_timings(rvb_ctx * ctx, char * names, uint64_t names_capacity, float
 int rvb_debug_stamps(rvb_ctx * ctx, uint64_t * out, uint64_t capacity)
 {
     if (!ctx || !out) return RVB_ERR_INVALID;
-    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_debug_stamps: nothing traced");
+    if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_debug_stamps: nothing traced");
     RVB_BIND(ctx);
     RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
     unsigned long long v[32];
-    RVB_HIP(fail, ctx, hipMemcpy(v, ctx->stamps.p, sizeof(v), hipMemcpyDeviceToHost));
+    RVB_HIP(fail, ctx, hipMemcpy(v, ctx->trace.stamps.p, sizeof(v), hipMemcpyDeviceToHost));
     for (uint64_t i = 0; i < capacity && i < 32; ++i) out[i] = v[i];
     return RVB_OK;
 }
@@ -289,11 +282,11 @@ int rvb_debug_stamps(rvb_ctx * ctx, uint64_t * out, uint64_t capacity)
 int rvb_executed_bounces(rvb_ctx * ctx, uint64_t * bounces)
 {
     if (!ctx || !bounces) return RVB_ERR_INVALID;
-    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_executed_bounces: nothing traced");
+    if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_executed_bounces: nothing traced");
     RVB_BIND(ctx);
     int rc = fetch_small(ctx);
     if (rc != RVB_OK) return rc;
-    *bounces = ctx->small_host->executed;
+    *bounces = ctx->trace.host->small.executed;
     return RVB_OK;
 }
 

@@ -1,6 +1,6 @@
 // ctx.h — the context behind include/rvb_capi.h and what its translation units share:
 //   context.hip  life cycle, scene, directions, timings, diagnostics
-//   trace.hip    the trace in three steps, the tail steps a kept trace replays, its results, rvb_merge_images
+//   trace.hip    the trace in three steps (TraceStage below, over trace_state.h), the tail steps a kept trace replays, its results, rvb_merge_images
 //   source.hip   source directivity (SourceDirectivity below, over source_state.h / source_state.hip): setters, upload, launches
 //   kept.hip     behind a kept trace: re-shading, its material gradients per surface and per triangle, a new microphone
 //   memory.hip   caller-owned device / pinned memory, staged host copies, the export stream
@@ -23,9 +23,11 @@
 #include "ir_state.h"
 #include "kernels.h"
 #include "source_state.h"
+#include "trace_state.h"
 
 #include <cmath>
 #include <cstddef>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <utility>
@@ -61,6 +63,22 @@ static_assert(offsetof(SmallBlock, trace_range) == 32 && offsetof(SmallBlock, li
 static_assert(offsetof(SmallBlock, image_item_count) == 44, "small block layout");
 static_assert(offsetof(SmallBlock, direct) == 64 && sizeof(SmallBlock) == 128, "small block layout");
 const size_t kFirstCandidates = 32;
+
+// The host mirror of `small`, fetched once per trace together with the first few image-source candidates (usually all of them).
+// One PINNED block: a device-to-host copy into pageable memory is staged by the runtime and blocks the host per call (three
+// round trips of 30-160 us between the shadow kernel and the binning stage in a kernel trace); into pinned memory the copies
+// are asynchronous and the host waits once.
+struct TraceHostBlock {
+    SmallBlock small;
+    rvb_image_candidate first[kFirstCandidates];
+    uint32_t hrtf_range[2];                     // where the HRTF time-range pass lands (rvb_ir_time_range_begin)
+    // set by live_compact_kernel, straight into this pinned word, if a live list ever held more than its count allowed
+    // (the excess was dropped); fetch_small reports it
+    uint32_t live_overflow;
+};
+static_assert(offsetof(TraceHostBlock, first) == sizeof(SmallBlock), "host block layout: the candidates right behind the small block");
+static_assert(offsetof(TraceHostBlock, hrtf_range) == sizeof(SmallBlock) + kFirstCandidates * sizeof(rvb_image_candidate), "host block layout");
+static_assert(offsetof(TraceHostBlock, live_overflow) == offsetof(TraceHostBlock, hrtf_range) + 8, "host block layout: the word handed to live_compact_kernel");
 
 // Source directivity, the device half over SourceState (source_state.h): what the last upload put on the device — it stays there
 // whatever is set afterwards, until the next trace or re-shade uploads: a kept trace may reflect it —, and the staging blocks it went through.
@@ -122,8 +140,8 @@ struct PairLaunch {
     DevBuf geom, direct, range;
     StagedBlock block;                          // PairBlock
     std::vector<float> mics_host;               // [npairs][3]
-    std::vector<rvb_impulse> direct_host;       // fetched once per trace (fetch_small)
-    std::vector<uint32_t> range_host;           // ranges, then live counts
+    std::vector<rvb_impulse> direct_mirror;     // fetched once per trace (fetch_small)
+    std::vector<uint32_t> range_mirror;         // ranges, then live counts
     static size_t live_bytes(uint64_t npairs) { return npairs * sizeof(uint32_t); }
 
     // A launch of npairs > 1 pairs: the block filled and copied up, and the four pointers of `a` that then point here.
@@ -165,15 +183,80 @@ struct PairLaunch {
     // direct paths, time ranges and live counts into their host mirrors; the caller synchronises
     hipError_t fetch(uint64_t npairs, hipStream_t stream)
     {
-        direct_host.resize(npairs);
-        range_host.resize(3 * npairs);
-        hipError_t e = hipMemcpyAsync(direct_host.data(), direct.p, npairs * sizeof(rvb_impulse), hipMemcpyDeviceToHost, stream);
-        return e == hipSuccess ? hipMemcpyAsync(range_host.data(), range.p, PairBlock::range_bytes(npairs) + live_bytes(npairs), hipMemcpyDeviceToHost, stream) : e;
+        direct_mirror.resize(npairs);
+        range_mirror.resize(3 * npairs);
+        hipError_t e = hipMemcpyAsync(direct_mirror.data(), direct.p, npairs * sizeof(rvb_impulse), hipMemcpyDeviceToHost, stream);
+        return e == hipSuccess ? hipMemcpyAsync(range_mirror.data(), range.p, PairBlock::range_bytes(npairs) + live_bytes(npairs), hipMemcpyDeviceToHost, stream) : e;
     }
-    const rvb_impulse & direct_of(uint64_t pair) const { return direct_host[pair]; }
-    const uint32_t * range_of(uint64_t pair) const { return range_host.data() + 2 * pair; }
-    uint32_t live_of(uint64_t pair) const { return range_host[range_host.size() / 3 * 2 + pair]; }
+    const rvb_impulse & direct_of(uint64_t pair) const { return direct_mirror[pair]; }
+    const uint32_t * range_of(uint64_t pair) const { return range_mirror.data() + 2 * pair; }
+    uint32_t live_of(uint64_t npairs, uint64_t pair) const { return range_mirror[2 * npairs + pair]; }
     const float * mic_of(uint64_t pair) const { return mics_host.data() + 3 * pair; }
+};
+
+// The trace stage, the device half over TraceState (trace_state.h): the buffers a trace writes, those of its record grouping, the
+// per-pair arrays, the pinned host mirror, and the selected pair's results — the fork between the small block (one pair) and the
+// per-pair arrays (several) is written here, once per quantity.
+struct TraceStage : TraceState {
+    DevBuf impulses, early, candidates, small, stamps;          // small: one SmallBlock
+    DevBuf image_items;                         // work list of the image-source check kernel
+    DevBuf live_stripes;                        // TraceArgs::live_stripes: zeroed when allocated, put back to zero by every launch that adds to it
+    DevBuf sort_keys, sort_scratch, sort_order, group_temp;     // the record grouping of a trace
+    bool stamps_cleared = false;
+    PairLaunch pairs;                           // the per-pair arrays of the last launch, their host mirrors, its microphones
+    PinnedBuf host_block;
+    TraceHostBlock * host = nullptr;            // host_block, zeroed (rvb_create)
+
+    SmallBlock * small_dev() const { return small.as<SmallBlock>(); }
+    hipError_t create()
+    {
+        hipError_t e = small.ensure(sizeof(SmallBlock));
+        if (e == hipSuccess) e = host_block.ensure(sizeof(TraceHostBlock));
+        if (e == hipSuccess) std::memset(host = host_block.as<TraceHostBlock>(), 0, sizeof(TraceHostBlock));
+        return e;
+    }
+    static size_t early_bytes(uint64_t nrays) { return (size_t) nrays * 9 * sizeof(uint32_t); }
+    // entries of the image work list: a (ray, bounce) per candidate slot and one per pair
+    static size_t image_entries(uint64_t nrays, uint64_t npairs) { return (size_t) nrays * 9 + npairs; }
+    // The buffers of a launch of nrays rays in npairs pairs; new stripes start at zero.
+    hipError_t ensure_launch(uint64_t nrays, uint64_t npairs, uint64_t nreflections, hipStream_t stream)
+    {
+        hipError_t e;
+        if ((e = impulses.ensure((size_t) nrays * nreflections * sizeof(rvb_impulse))) != hipSuccess) return e;
+        if ((e = early.ensure(early_bytes(nrays))) != hipSuccess) return e;
+        if ((e = candidates.ensure((size_t) nrays * 9 * sizeof(rvb_image_candidate))) != hipSuccess) return e;
+        if ((e = image_items.ensure(image_entries(nrays, npairs) * 3 * sizeof(uint32_t))) != hipSuccess) return e;      // (ray, bounce) entries, then a state word each
+        const size_t stripe_bytes = (size_t) RVB_LIVE_STRIPES * npairs * sizeof(uint32_t);
+        if (stripe_bytes <= live_stripes.cap) return hipSuccess;
+        if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;          // (a launch that still adds to the old block)
+        if ((e = live_stripes.ensure(stripe_bytes)) != hipSuccess) return e;
+        return hipMemsetAsync(live_stripes.p, 0, stripe_bytes, stream);
+    }
+    // ... and where its kernels find them: one pair's results in the small block (PairLaunch::stage repoints those of several pairs)
+    void point(TraceArgs & a, uint64_t nrays, uint64_t npairs) const
+    {
+        SmallBlock * s = small_dev();
+        a.impulses = impulses.as<rvb_impulse>();
+        a.early = early.as<uint32_t>();
+        a.candidates = candidates.as<rvb_image_candidate>();
+        a.candidate_count = &s->candidate_count;
+        a.image_items = reinterpret_cast<ImageItem *>(image_items.p);
+        a.image_state = image_items.as<uint32_t>() + image_entries(nrays, npairs) * 2;
+        a.image_item_count = &s->image_item_count;
+        a.direct = &s->direct;
+        a.pair_mics = nullptr;
+        a.pair_sources = nullptr;
+        a.executed = &s->executed;
+        a.time_range = s->trace_range;
+        a.live_stripes = live_stripes.as<uint32_t>();
+    }
+
+    // The selected pair's results.  The host's need fetch_small first.
+    const rvb_impulse & direct() const { return npairs() > 1 ? pairs.direct_of(pair()) : host->small.direct; }
+    const rvb_impulse * direct_slot() const { return npairs() > 1 ? pairs.direct.as<rvb_impulse>() + pair() : &small_dev()->direct; }
+    const uint32_t * diffuse_range() const { return npairs() > 1 ? pairs.range_of(pair()) : host->small.trace_range; }     // float bits [2]
+    uint32_t live_count() const { return npairs() > 1 ? pairs.live_of(npairs(), pair()) : host->small.live_count; }
+    const float * mic() const { return pairs.mic_of(pair()); }
 };
 
 struct Timing { std::string name; hipEvent_t start, stop; };       // (events of the context's pool)
@@ -182,7 +265,7 @@ struct Timing { std::string name; hipEvent_t start, stop; };       // (events of
 // per (ray, bounce) (SideRecord of csrc/kept_tiles.h) and the INIT_DIST of every image impulse (csrc/reshade_kernels.hip), and `args` remembers its kernel arguments:
 // microphones, sources, air, ray offset and every buffer of the launch.  With RVB_KEEP_LISTENER it leaves an 8-byte listener record per
 // (ray, bounce) too, {own-plane threshold, triangle} (csrc/relisten_kernels.hip).  The buffers exist only while keeping is on.
-// The kept state is valid while rvb_ctx::traced holds and nothing has voided it: a trace voids it first (void_all) and takes it last (take).
+// The kept state is valid while TraceState::traced() holds and nothing has voided it: a trace voids it first (void_all) and takes it last (take).
 // The grouping order of the records is kept where the trace left it: `sort_order` is written by the record grouping of a trace and by
 // nothing else (the binning stages sort in SortBuffers), and the next trace voids the kept state before it
 // regroups; args.sort_order points there (null: the trace grouped nothing).
@@ -301,38 +384,13 @@ struct rvb_ctx {
     uint64_t nrays = 0;
     uint32_t concurrent_traces = 1;             // rvb_set_concurrent_traces
     uint32_t path_lanes = 0;                    // rvb_set_path_lanes: 0 = chosen per launch (rvb_path_lanes_for)
-    bool traced = false;
-    uint64_t nreflections = 0;
-    float mic[3] = {0, 0, 0};
-    // last trace: npairs (source, microphone) pairs x nrays rays each; the IR stage works on one pair's slice at a time
-    uint64_t npairs = 1, traced_rays = 0, ir_pair = 0;
-    uint64_t trace_ray_offset = 0;              // ... and its ray_offset: a candidate's ray is trace_ray_offset + pair * nrays + the ray's number
-    PairLaunch pairs;                           // the per-pair arrays of that launch, their host mirrors, its microphones
+    // the last trace: npairs() (source, microphone) pairs x nrays rays each; the IR stage works on one pair's slice at a time
+    TraceStage trace;
     SourceDirectivity source;                   // rvb_set_source_pattern / rvb_set_source_table: what is set and what is on the device
-    DevBuf image_items;                         // work list of the image-source check kernel
     KeptTrace kept;                              // rvb_keep_paths: what rvb_reshade, rvb_reshade_grad and rvb_relisten work from
     // rvb_decay_* (csrc/decay.hip): per-tile sums and carries, per-row windows and results; nothing else lives here, so the decay calls
     // leave the sort buffers, the IR configuration and a prepared exact list alone
     DevBuf decay_scratch;
-    DevBuf impulses, early, candidates, small, stamps, sort_keys, sort_scratch, sort_order, group_temp;       // small: one SmallBlock
-    DevBuf live_stripes;                        // TraceArgs::live_stripes: zeroed when allocated, put back to zero by every launch that adds to it
-    // host mirror of `small`, fetched once per trace together with the first few image-source candidates (usually all of them).
-    // One PINNED block: a device-to-host copy into pageable memory is staged by the runtime and blocks the host per call (three
-    // round trips of 30-160 us between the shadow kernel and the binning stage in a kernel trace); into pinned memory the copies
-    // are asynchronous and the host waits once.
-    PinnedBuf host_block;
-    SmallBlock * small_host = nullptr;          // the start of host_block
-    rvb_image_candidate * first_candidates = nullptr;   // [kFirstCandidates], behind small_host in the same block
-    uint32_t * range_host = nullptr;            // [2] behind them: where the HRTF time-range pass lands (rvb_ir_time_range_begin)
-    // behind them: set by live_compact_kernel, straight into this pinned word, if a live list ever held more than its count allowed
-    // (the excess was dropped); fetch_small reports it
-    uint32_t * live_overflow_host = nullptr;
-    bool small_valid = false;
-    // The live counts that came with the small block (SmallBlock::live_count, PairLaunch::live_of) bound the diffuse impulses that
-    // carry volume: a trace sets it; whatever rewrites the records behind the shadow kernel without counting clears it
-    // (apply_source_patterns, rvb_reshade, rvb_relisten), and the exact mode then lists every record.
-    bool live_count_valid = false;
-    bool stamps_cleared = false;
     std::vector<Timing> timings;
     std::vector<Event> event_pool;
     size_t events_used = 0;
@@ -354,7 +412,6 @@ struct rvb_ctx {
             if (s) (void) hipStreamSynchronize(s);
     }
 
-    SmallBlock * small_dev() const { return small.as<SmallBlock>(); }
     hipEvent_t next_event()
     {
         if (events_used == event_pool.size()) {
@@ -377,14 +434,12 @@ struct rvb_ctx {
     }
     void end_timing(hipStream_t on = nullptr) { if (timing_open) (void) hipEventRecord(timings.back().stop, on ? on : stream.h); timing_open = false; }
     void reset_timings() { timings.clear(); events_used = 0; }
-    // From here on the results are no longer the last trace's (a trace has finished, rvb_reshade or rvb_relisten is about to rewrite
-    // them): what the host has fetched of them and what the IR stage has prepared from them is void.
-    void void_fetched_results() { small_valid = false; ir.drop_configuration(); }
+    // From here on the results are no longer the last trace's (rvb_reshade or rvb_relisten is about to rewrite them): what the host
+    // has fetched of them, their live count and what the IR stage has prepared from them is void, and the first pair is selected.
+    void void_fetched_results() { trace.records_rewritten(); ir.drop_configuration(); }
     // The trace is gone (rvb_set_scene, rvb_share_scene, rvb_set_directions*, a trace that begins): nrays or the scene no longer describe
     // the records in `impulses`, so an IR configuration or a prepared exact list made for them must not be used either.
-    void void_trace() { traced = false; ir.drop_configuration(); merged.void_list(); }
-    // the pair the IR stage works on, as a trace leaves it: the first, with its microphone
-    void select_first_pair() { ir_pair = 0; for (int i = 0; i < 3; ++i) mic[i] = pairs.mic_of(0)[i]; }
+    void void_trace() { trace.inputs_changed(); ir.drop_configuration(); merged.void_list(); }
 };
 
 // ctx == NULL: the text of a failed rvb_create, per thread (rvb_last_error(NULL))
@@ -394,13 +449,13 @@ int fail(rvb_ctx * ctx, int code, const std::string & what);
 // the diffuse impulses the IR stage works on: the slice of the pair chosen with rvb_ir_select_pair (pair 0 of 1 otherwise)
 inline const rvb_impulse * ir_diffuse(const rvb_ctx * ctx)
 {
-    return ctx->impulses.as<rvb_impulse>() + ctx->ir_pair * ctx->nrays * ctx->nreflections;
+    return ctx->trace.impulses.as<rvb_impulse>() + ctx->trace.pair() * ctx->nrays * ctx->trace.nreflections();
 }
 // ... and how many of them, and of the images, the configuration's `which` takes
 struct IrCounts { uint64_t ndiffuse, nimages; };
 inline IrCounts ir_counts(const rvb_ctx * ctx)
 {
-    return {(ctx->ir.which() & RVB_IR_DIFFUSE) ? ctx->nrays * ctx->nreflections : 0, (ctx->ir.which() & RVB_IR_IMAGES) ? ctx->ir.nimages() : 0};
+    return {(ctx->ir.which() & RVB_IR_DIFFUSE) ? ctx->nrays * ctx->trace.nreflections() : 0, (ctx->ir.which() & RVB_IR_IMAGES) ? ctx->ir.nimages() : 0};
 }
 
 inline uint64_t bins_for(float max_time, float predelay, float sample_rate)

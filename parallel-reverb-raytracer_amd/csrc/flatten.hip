@@ -54,7 +54,7 @@ int attenuate_host(rvb_ctx * ctx, const AttenuationModel & m, uint32_t channel, 
 // keys + max time of a device-resident AttenuatedImpulse array -> *bins, in the sort buffers the caller has claimed
 int flatten_keys(rvb_ctx * ctx, const rvb_attenuated_impulse * d_in, uint64_t n, float sample_rate, uint64_t * bins)
 {
-    uint32_t * max_bits = &ctx->small_dev()->max_time_bits;
+    uint32_t * max_bits = &ctx->trace.small_dev()->max_time_bits;
     RVB_HIP(fail, ctx, hipMemsetAsync(max_bits, 0, 4, ctx->stream));
     rvb_launch_flat_keys(d_in, n, sample_rate, ctx->sort.keys_a.as<uint32_t>(), ctx->sort.vals_a.as<uint32_t>(), max_bits, ctx->stream);
     uint32_t bits = 0;

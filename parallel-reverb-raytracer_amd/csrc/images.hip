@@ -12,18 +12,18 @@ namespace {
 int ensure_winners(rvb_ctx * ctx, bool remove_direct)
 {
     MergedImages & merged = ctx->merged;
-    if (merged.valid && merged.pair == ctx->ir_pair && merged.remove_direct == remove_direct) return RVB_OK;
+    if (merged.valid && merged.pair == ctx->trace.pair() && merged.remove_direct == remove_direct) return RVB_OK;
     int rc = fetch_small(ctx);
     if (rc != RVB_OK) return rc;
     RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));        // the candidates are final, and no kernel reads the list that is about to be replaced
-    const uint32_t ncand = ctx->small_host->candidate_count;
+    const uint32_t ncand = ctx->trace.host->small.candidate_count;
     std::vector<rvb_image_candidate> all(ncand);
-    if (ncand) RVB_HIP(fail, ctx, hipMemcpy(all.data(), ctx->candidates.p, (size_t) ncand * sizeof(rvb_image_candidate), hipMemcpyDeviceToHost));
+    if (ncand) RVB_HIP(fail, ctx, hipMemcpy(all.data(), ctx->trace.candidates.p, (size_t) ncand * sizeof(rvb_image_candidate), hipMemcpyDeviceToHost));
     // the selected pair's candidates (a candidate's ray: ray_offset + pair * nrays + the ray's number within the pair), device positions kept
     std::vector<rvb_image_candidate> mine;
     std::vector<uint32_t> position;
     for (uint32_t i = 0; i < ncand; ++i) {
-        if (ctx->npairs > 1 && ctx->nrays && (all[i].ray - ctx->trace_ray_offset) / ctx->nrays != ctx->ir_pair) continue;
+        if (ctx->trace.npairs() > 1 && ctx->nrays && (all[i].ray - ctx->trace.ray_offset()) / ctx->nrays != ctx->trace.pair()) continue;
         mine.push_back(all[i]);
         position.push_back(i);
     }
@@ -40,16 +40,10 @@ int ensure_winners(rvb_ctx * ctx, bool remove_direct)
     RVB_HIP(fail, ctx, merged.winners.ensure(winners.size() * sizeof(uint32_t)));
     if (!winners.empty()) RVB_HIP(fail, ctx, hipMemcpy(merged.winners.p, winners.data(), winners.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     merged.count = winners.size();
-    merged.pair = ctx->ir_pair;
+    merged.pair = ctx->trace.pair();
     merged.remove_direct = remove_direct;
     merged.valid = true;
     return RVB_OK;
-}
-
-// the selected pair's direct slot on the device
-const rvb_impulse * direct_slot(const rvb_ctx * ctx)
-{
-    return ctx->npairs > 1 ? ctx->pairs.direct.as<rvb_impulse>() + ctx->ir_pair : &ctx->small_dev()->direct;
 }
 
 // behind the model: the list, the configuration's state, the gather in stream order
@@ -62,7 +56,7 @@ int configure_merged(rvb_ctx * ctx, int which, int remove_direct, uint64_t * nim
     if ((rc = ir_configure_images(ctx, which, nullptr, n, true)) != RVB_OK) return rc;
     ctx->reset_timings();
     ctx->begin_timing("image_gather_kernel");
-    rvb_launch_image_gather(ctx->candidates.as<rvb_image_candidate>(), direct_slot(ctx), ctx->merged.winners.as<uint32_t>(), n,
+    rvb_launch_image_gather(ctx->trace.candidates.as<rvb_image_candidate>(), ctx->trace.direct_slot(), ctx->merged.winners.as<uint32_t>(), n,
                             ctx->ir.images.as<rvb_impulse>(), ctx->stream);
     ctx->end_timing();
     RVB_HIP(fail, ctx, hipGetLastError());
@@ -97,7 +91,7 @@ int rvb_reshade_grad_images(rvb_ctx * ctx, float predelay, float sample_rate, ui
     if (!d_weights || !grad_surfaces) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_images: null weights or null output");
     if (nbins == 0 || nbins >= (1ull << 32)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_images: no bins (or more than 32-bit bin numbers reach)");
     if (!std::isfinite(predelay) || !std::isfinite(sample_rate)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_images: predelay or sample rate is not finite");
-    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: nothing traced (or the scene or the directions have changed since)");
+    if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: nothing traced (or the scene or the directions have changed since)");
     if (!ctx->kept.valid) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: the last trace was made without rvb_keep_paths(ctx, 1)");
     if (!ctx->ir.configured())
         return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: no IR configuration (rvb_ir_configure_speakers_merged after the trace, re-shade or relisten)");
@@ -124,20 +118,20 @@ int rvb_reshade_grad_images(rvb_ctx * ctx, float predelay, float sample_rate, ui
     g.winners = merged.winners.as<const uint32_t>();
     g.images = ctx->ir.images.as<const rvb_impulse>();
     g.n = n;
-    g.direct_dist = a.nrays * (RVB_NUM_IMAGE_SOURCE - 1) + ctx->ir_pair;
+    g.direct_dist = a.nrays * (RVB_NUM_IMAGE_SOURCE - 1) + ctx->trace.pair();
     g.weights = reinterpret_cast<const float *>(d_weights);
     g.nbins = nbins;
     g.predelay = predelay;
     g.sample_rate = sample_rate;
-    for (int i = 0; i < 3; ++i) g.mic[i] = ctx->pairs.mic_of(ctx->ir_pair)[i];
+    for (int i = 0; i < 3; ++i) g.mic[i] = ctx->trace.mic()[i];
     // the source directivity that the records reflect now, for the selected pair
     const SourceShading & shaded = kept.shaded_source;
     g.has_pattern = !shaded.patterns.empty();
-    if (g.has_pattern) g.pattern = shaded.patterns[shaded.patterns.size() > 1 ? ctx->ir_pair : 0];
+    if (g.has_pattern) g.pattern = shaded.patterns[shaded.patterns.size() > 1 ? ctx->trace.pair() : 0];
     if (shaded.table_orientations) {
         const SourceTableDev t = ctx->source.table_on_device(shaded.table_orientations);
         g.table = t.table;
-        g.table_basis = t.bases + ctx->ir_pair * t.basis_stride;
+        g.table_basis = t.bases + ctx->trace.pair() * t.basis_stride;
     }
     ctx->reset_timings();
     ctx->begin_timing("reshade_grad_images_kernel");

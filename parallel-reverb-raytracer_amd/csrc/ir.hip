@@ -33,7 +33,7 @@ AttenuationModel hrtf_model(const rvb_ctx * ctx, const float mic[3], const float
 
 int ir_configure_refusals(rvb_ctx * ctx, int which)
 {
-    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_ir_configure: nothing traced");
+    if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_ir_configure: nothing traced");
     if (which < 1 || which > 3) return fail(ctx, RVB_ERR_INVALID, "rvb_ir_configure: which must be 1..3");
     return RVB_OK;
 }
@@ -122,18 +122,18 @@ namespace {
 // contexts enqueues all of them (rvb_ir_time_range_begin) before it waits for the first.
 int time_range_enqueue(rvb_ctx * ctx)
 {
-    uint32_t * range = ctx->small_dev()->range;
+    uint32_t * range = ctx->trace.small_dev()->range;
     RVB_HIP(fail, ctx, hipMemsetAsync(range, 0xFF, 4, ctx->stream));
     RVB_HIP(fail, ctx, hipMemsetAsync(range + 1, 0, 4, ctx->stream));
     ctx->reset_timings();
     ctx->begin_timing("time_range_kernel");
     if (ctx->ir.which() & RVB_IR_DIFFUSE)
-        rvb_launch_time_range(ctx->ir.model, ir_diffuse(ctx), ctx->nrays * ctx->nreflections, range, ctx->stream);
+        rvb_launch_time_range(ctx->ir.model, ir_diffuse(ctx), ctx->nrays * ctx->trace.nreflections(), range, ctx->stream);
     if (ctx->ir.which() & RVB_IR_IMAGES)
         rvb_launch_time_range(ctx->ir.model, ctx->ir.images.as<rvb_impulse>(), ctx->ir.nimages(), range, ctx->stream);
     ctx->end_timing();
     RVB_HIP(fail, ctx, hipGetLastError());
-    RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->range_host, range, 8, hipMemcpyDeviceToHost, ctx->stream));
+    RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->trace.host->hrtf_range, range, 8, hipMemcpyDeviceToHost, ctx->stream));
     ctx->ir.range_enqueued();
     return RVB_OK;
 }
@@ -158,17 +158,16 @@ int exact_begin(rvb_ctx * ctx, uint64_t nbins, uint64_t lists, ExactList & in)
 int live_list(rvb_ctx * ctx, ExactList & in, float predelay, float sample_rate, uint64_t nbins)
 {
     in.compacted = true;
-    in.count_valid = ctx->live_count_valid;
+    in.count_valid = ctx->trace.live_count_holds();
     if (in.count_valid && in.ndiffuse) {
         const int rc = fetch_small(ctx);                // (the caller's rvb_ir_time_range or image merge has waited for it already)
         if (rc != RVB_OK) return rc;
-        const uint64_t live = ctx->npairs > 1 ? ctx->pairs.live_of(ctx->ir_pair) : ctx->small_host->live_count;
-        in.listed = std::min(live, in.ndiffuse) + in.nimages;
+        in.listed = std::min<uint64_t>(ctx->trace.live_count(), in.ndiffuse) + in.nimages;
     }
     RVB_HIP(fail, ctx, ctx->sort.live.ensure(rvb_live_scratch_bytes(in.n)));
     rvb_launch_live_list(ctx->ir.model, ir_diffuse(ctx), in.ndiffuse, ctx->ir.images.as<rvb_impulse>(), in.n, predelay, sample_rate, (uint32_t) nbins,
                          in.listed, ctx->sort.keys_b.as<uint32_t>(), ctx->sort.live.p, ctx->sort.keys_a.as<uint32_t>(), ctx->sort.vals_a.as<uint32_t>(),
-                         ctx->live_overflow_host, ctx->stream);
+                         &ctx->trace.host->live_overflow, ctx->stream);
     return RVB_OK;
 }
 
@@ -370,13 +369,13 @@ int rvb_ir_time_range(rvb_ctx * ctx, float * min_nonzero_time, float * max_time)
         }
         ctx->ir.range_taken();
         // (the wait takes the trace's small block along where nothing has fetched it yet: the exact mode sizes its list from it)
-        if (ctx->small_valid) {
+        if (ctx->trace.fetched()) {
             RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
         } else {
             const int rc = fetch_small(ctx);
             if (rc != RVB_OK) return rc;
         }
-        std::memcpy(got, ctx->range_host, sizeof(got));
+        std::memcpy(got, ctx->trace.host->hrtf_range, sizeof(got));
     } else {
         // Speaker channels keep the input time (kernel.cpp:530-533), so the range is that of the raw
         // impulses: the diffuse part was reduced inside shadow_kernel, the few images are scanned below.
@@ -384,8 +383,7 @@ int rvb_ir_time_range(rvb_ctx * ctx, float * min_nonzero_time, float * max_time)
         if (ctx->ir.which() & RVB_IR_DIFFUSE) {
             int rc = fetch_small(ctx);
             if (rc != RVB_OK) return rc;
-            if (ctx->npairs > 1) { got[0] = ctx->pairs.range_of(ctx->ir_pair)[0]; got[1] = ctx->pairs.range_of(ctx->ir_pair)[1]; }
-            else std::memcpy(got, ctx->small_host->trace_range, sizeof(got));
+            std::memcpy(got, ctx->trace.diffuse_range(), sizeof(got));
         }
     }
     float lo = 0.0f, hi = 0.0f;

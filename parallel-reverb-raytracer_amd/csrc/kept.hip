@@ -25,14 +25,14 @@ static ReshadeGradArgs grad_args(const rvb_ctx * ctx, float predelay, float samp
     g.nbins = nbins;
     g.predelay = predelay;
     g.sample_rate = sample_rate;
-    g.first_ray = ctx->ir_pair * ctx->nrays;
+    g.first_ray = ctx->trace.pair() * ctx->nrays;
     g.nrays = (uint32_t) ctx->nrays;
-    for (int i = 0; i < 3; ++i) g.mic[i] = ctx->pairs.mic_of(ctx->ir_pair)[i];
+    for (int i = 0; i < 3; ++i) g.mic[i] = ctx->trace.mic()[i];
     const std::vector<SourcePatternDev> & shaded_patterns = kept.shaded_source.patterns;
     g.has_pattern = !shaded_patterns.empty();
-    g.pattern = g.has_pattern ? shaded_patterns[shaded_patterns.size() > 1 ? ctx->ir_pair : 0] : SourcePatternDev{};
+    g.pattern = g.has_pattern ? shaded_patterns[shaded_patterns.size() > 1 ? ctx->trace.pair() : 0] : SourcePatternDev{};
     // a table shaded the records: the pair's rows of the gains that launch left (source_table_rays_kernel)
-    g.ray_gains = kept.shaded_source.table_orientations ? ctx->source.gains_of_pair(ctx->ir_pair, ctx->nrays) : nullptr;
+    g.ray_gains = kept.shaded_source.table_orientations ? ctx->source.gains_of_pair(ctx->trace.pair(), ctx->nrays) : nullptr;
     g.nsurfaces = ctx->nsurfaces;
     return g;
 }
@@ -62,11 +62,11 @@ int rvb_relisten(rvb_ctx * ctx, const float * mics, uint64_t npairs)
     if (!mics) return fail(ctx, RVB_ERR_INVALID, "rvb_relisten: null microphones");
     for (uint64_t i = 0; i < 3 * npairs; ++i)
         if (!std::isfinite(mics[i])) return fail(ctx, RVB_ERR_INVALID, "rvb_relisten: microphone " + std::to_string(i / 3) + " holds a coordinate that is not finite");
-    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_relisten: nothing traced (or the scene or the directions have changed since)");
+    if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_relisten: nothing traced (or the scene or the directions have changed since)");
     if (!ctx->kept.listener_valid)
         return fail(ctx, RVB_ERR_STATE, "rvb_relisten: the last trace was made without rvb_keep_paths(ctx, RVB_KEEP_MATERIALS | RVB_KEEP_LISTENER)");
-    if (npairs != ctx->npairs)
-        return fail(ctx, RVB_ERR_INVALID, "rvb_relisten: " + std::to_string(npairs) + " microphone(s) for a kept trace of " + std::to_string(ctx->npairs) + " pair(s)");
+    if (npairs != ctx->trace.npairs())
+        return fail(ctx, RVB_ERR_INVALID, "rvb_relisten: " + std::to_string(npairs) + " microphone(s) for a kept trace of " + std::to_string(ctx->trace.npairs()) + " pair(s)");
     RVB_BIND(ctx);
     KeptTrace & kept = ctx->kept;
     // the table, the air and the source directivity are those the records reflect now (the scene's own after the kept trace, those of the
@@ -77,15 +77,14 @@ int rvb_relisten(rvb_ctx * ctx, const float * mics, uint64_t npairs)
     // measurements only (tools/relisten_bench.py): the shadow kernel walks the records in natural order instead of the trace's grouping
     static const bool natural_order = getenv("RVB_RELISTEN_ORDER") && getenv("RVB_RELISTEN_ORDER")[0] == '0';
     if (natural_order) a.sort_order = nullptr;
-    SmallBlock * small = ctx->small_dev();
+    SmallBlock * small = ctx->trace.small_dev();
     ctx->reset_timings();
-    ctx->void_fetched_results();
-    ctx->live_count_valid = false;                // (a trace alone vouches for a count: after a replay exact mode lists every impulse)
+    ctx->void_fetched_results();                  // (a trace alone vouches for a live count: after a replay exact mode lists every impulse)
     ctx->merged.void_list();                      // (the image kernels find other candidates: which of them win is decided anew)
     // what the tail appends to or folds into, back where a trace starts; `executed` stays
     RVB_HIP(fail, ctx, hipMemsetAsync(&small->candidate_count, 0, sizeof(uint32_t), ctx->stream));
     RVB_HIP(fail, ctx, hipMemsetAsync(&small->live_count, 0, sizeof(SmallBlock) - offsetof(SmallBlock, live_count), ctx->stream));      // ... and the direct slot
-    if (npairs > 1) RVB_HIP(fail, ctx, ctx->pairs.restage_mics(mics, npairs, ctx->stream));       // (reset_time_ranges, next, records the block's event)
+    if (npairs > 1) RVB_HIP(fail, ctx, ctx->trace.pairs.restage_mics(mics, npairs, ctx->stream));       // (reset_time_ranges, next, records the block's event)
     int rc = reset_time_ranges(ctx, a);
     if (rc != RVB_OK) return rc;
     ctx->begin_timing("relisten_records_kernel");
@@ -96,8 +95,7 @@ int rvb_relisten(rvb_ctx * ctx, const float * mics, uint64_t npairs)
     if ((rc = launch_shadow_behind_images(ctx, a, kept.shaded_source, true)) != RVB_OK) return rc;
     // the kept trace is now that of the new microphone(s): later rvb_reshade, rvb_reshade_grad and rvb_relisten start from here
     for (int i = 0; i < 3; ++i) kept.args.mic[i] = mics[i];
-    ctx->pairs.mics_host.assign(mics, mics + 3 * npairs);
-    ctx->select_first_pair();
+    ctx->trace.pairs.mics_host.assign(mics, mics + 3 * npairs);
     return RVB_OK;
 }
 
@@ -105,11 +103,11 @@ int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces,
 {
     if (!ctx) return RVB_ERR_INVALID;
     if (!air_coefficient) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade: null air coefficient");
-    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_reshade: nothing traced (or the scene or the directions have changed since)");
+    if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade: nothing traced (or the scene or the directions have changed since)");
     if (!ctx->kept.valid) return fail(ctx, RVB_ERR_STATE, "rvb_reshade: the last trace was made without rvb_keep_paths(ctx, 1)");
     if (surfaces && nsurfaces != ctx->nsurfaces)
         return fail(ctx, RVB_ERR_INVALID, "rvb_reshade: " + std::to_string(nsurfaces) + " surfaces for a scene of " + std::to_string(ctx->nsurfaces));
-    if (check_source_counts(ctx, "rvb_reshade", ctx->npairs) != RVB_OK) return RVB_ERR_INVALID;
+    if (check_source_counts(ctx, "rvb_reshade", ctx->trace.npairs()) != RVB_OK) return RVB_ERR_INVALID;
     RVB_BIND(ctx);
     KeptTrace & kept = ctx->kept;
     TraceArgs a = for_record_pass(ctx, kept.args);   // the trace's own arguments; surfaces and air are the call's
@@ -124,8 +122,7 @@ int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces,
     ctx->reset_timings();
     int rc = reset_time_ranges(ctx, a);
     if (rc != RVB_OK) return rc;
-    ctx->void_fetched_results();
-    ctx->live_count_valid = false;                // (the re-shade kernels rewrite every volume and count nothing)
+    ctx->void_fetched_results();                  // (the re-shade kernels rewrite every volume and count nothing: no live count)
     ctx->begin_timing("reshade_kernel");
     rvb_launch_reshade(a, kept.dev.paths.as<const float4>(), ctx->stream);
     ctx->end_timing();
@@ -136,7 +133,6 @@ int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces,
     const SourceShading source = ctx->source.shading();
     if ((rc = apply_source_patterns(ctx, a, source)) != RVB_OK) return rc;
     kept.note_shading(a, source);
-    ctx->select_first_pair();
     return RVB_OK;
 }
 
@@ -147,14 +143,14 @@ int rvb_reshade_grad(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t 
     if (!d_weights || !grad_surfaces) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: null weights or null output");
     if (nbins == 0 || nbins >= (1ull << 32)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: no bins (or more than 32-bit bin numbers reach)");
     if (!std::isfinite(predelay) || !std::isfinite(sample_rate)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: predelay or sample rate is not finite");
-    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: nothing traced (or the scene or the directions have changed since)");
+    if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: nothing traced (or the scene or the directions have changed since)");
     if (!ctx->kept.valid) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: the last trace was made without rvb_keep_paths(ctx, 1)");
     if (!ctx->ir.configured()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: no IR configuration (rvb_ir_configure_speakers after the trace or re-shade)");
     if (ctx->ir.model.hrtf) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: the HRTF model is configured; this version takes the speaker model only");
     if (ctx->ir.which() != RVB_IR_DIFFUSE) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: configured with image sources; this version takes which == RVB_IR_DIFFUSE only");
     if (ctx->ir.model.nchannels > 8)
         return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: " + std::to_string(ctx->ir.model.nchannels) + " speaker channels configured; this version takes 1 to 8");
-    if (ctx->nreflections > RVB_RESHADE_GRAD_MAX_REFLECTIONS)
+    if (ctx->trace.nreflections() > RVB_RESHADE_GRAD_MAX_REFLECTIONS)
         return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad: more than " RVB_STR(RVB_RESHADE_GRAD_MAX_REFLECTIONS) " reflections");
     if (ctx->nsurfaces >= (1ull << 27)) return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad: too many surfaces");
     RVB_BIND(ctx);
@@ -199,7 +195,7 @@ int rvb_reshade_grad_map(rvb_ctx * ctx, float predelay, float sample_rate, uint6
     // (without a scene there is no count to hold against: nothing is traced then, the next refusal)
     if (ctx->have_scene && ntriangles != ctx->ntriangles)
         return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_map: a map of " + std::to_string(ntriangles) + " triangles for a scene of " + std::to_string(ctx->ntriangles));
-    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: nothing traced (or the scene or the directions have changed since)");
+    if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: nothing traced (or the scene or the directions have changed since)");
     if (!ctx->kept.valid || !ctx->kept.listener_valid)
         return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: the last trace was made without rvb_keep_paths(ctx, RVB_KEEP_MATERIALS | RVB_KEEP_LISTENER): "
                                         "a record's triangle is in its listener record");
@@ -214,9 +210,9 @@ int rvb_reshade_grad_map(rvb_ctx * ctx, float predelay, float sample_rate, uint6
         const uintptr_t w0 = (uintptr_t) d_weights, w1 = w0 + (uintptr_t) nbins * nchannels * 8 * sizeof(float);
         if (m0 < w1 && w0 < m1) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_map: the map overlaps the weights");
     }
-    if (ctx->nreflections > RVB_RESHADE_GRAD_MAX_REFLECTIONS)
+    if (ctx->trace.nreflections() > RVB_RESHADE_GRAD_MAX_REFLECTIONS)
         return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad_map: more than " RVB_STR(RVB_RESHADE_GRAD_MAX_REFLECTIONS) " reflections");
-    const uint64_t n = ctx->nrays * ctx->nreflections;              // records of the pair
+    const uint64_t n = ctx->nrays * ctx->trace.nreflections();              // records of the pair
     if (n >= (1ull << 32))
         return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad_map: nrays * nreflections reaches 2^32 (record numbers are 32-bit sort values)");
     if (ntriangles >= (1ull << 27)) return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad_map: too many triangles (2^27 or more)");

@@ -44,7 +44,6 @@ int check_source_counts(rvb_ctx * ctx, const char * who, uint64_t npairs)
 int apply_source_patterns(rvb_ctx * ctx, const TraceArgs & a, const SourceShading & source, bool gains_stand)
 {
     if (source.off()) return RVB_OK;
-    ctx->live_count_valid = false;              // (a gain may silence a record or turn it into NaNs: the count of the kernel before no longer bounds the live ones)
     if (source.table_orientations && !gains_stand) RVB_HIP(fail, ctx, ctx->source.gains.ensure((size_t) a.nrays * 8 * sizeof(float)));
     const int rc = reset_time_ranges(ctx, a);
     if (rc != RVB_OK) return rc;

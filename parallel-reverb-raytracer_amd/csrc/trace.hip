@@ -1,8 +1,8 @@
 // trace.hip — the trace of include/rvb_capi.h: buffers, fills and kernel arguments; the path kernel; everything after it; then what a
 // trace leaves for the host (diffuse impulses, direct path, image-source candidates) and the image-source merge (its rule on its own:
 // merge_image_winners, which images.hip shares).  The steps that a kept
-// trace replays (kept.hip) come first: they are declared in ctx.h.  The source directivity is source.hip's, the per-pair arrays of a
-// launch are PairLaunch's (ctx.h).
+// trace replays (kept.hip) come first: they are declared in ctx.h.  The source directivity is source.hip's; the stage's state, its
+// buffers and the per-pair arrays of a launch are TraceStage's (ctx.h, over trace_state.h).
 #include "ctx.h"
 
 #include <algorithm>
@@ -14,7 +14,7 @@
 int reset_time_ranges(rvb_ctx * ctx, const TraceArgs & a)
 {
     if (a.npairs > 1) {
-        RVB_HIP(fail, ctx, ctx->pairs.reset_ranges(a.npairs, ctx->stream));
+        RVB_HIP(fail, ctx, ctx->trace.pairs.reset_ranges(a.npairs, ctx->stream));
     } else {
         RVB_HIP(fail, ctx, hipMemsetAsync(a.time_range, 0xFF, 4, ctx->stream));
         RVB_HIP(fail, ctx, hipMemsetAsync(a.time_range + 1, 0, 4, ctx->stream));
@@ -34,7 +34,7 @@ int launch_images_beside(rvb_ctx * ctx, TraceArgs & a)
     rvb_launch_images(a, ctx->side_stream);
     ctx->end_timing(ctx->side_stream);
     RVB_HIP(fail, ctx, hipEventRecord(ctx->side_done, ctx->side_stream));
-    a.scene.stamps = ctx->stamps.as<unsigned long long>() + 16;
+    a.scene.stamps = ctx->trace.stamps.as<unsigned long long>() + 16;
     return RVB_OK;
 }
 
@@ -69,21 +69,11 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     const float * mic = mics, * source = sources;
     RVB_BIND(ctx);
     ctx->void_trace();                                // (until trace_finish: a failure below must not leave the last trace's results half reset)
-    ctx->live_count_valid = false;
+    TraceStage & trace = ctx->trace;
+    trace.begin();
     ctx->kept.void_all();
     const uint64_t nrays = ctx->nrays * npairs;       // rays of this launch
-    const size_t imp_bytes = (size_t) nrays * nreflections * sizeof(rvb_impulse);
-    const size_t early_bytes = (size_t) nrays * 9 * sizeof(uint32_t);
-    RVB_HIP(fail, ctx, ctx->impulses.ensure(imp_bytes));
-    RVB_HIP(fail, ctx, ctx->early.ensure(early_bytes));
-    RVB_HIP(fail, ctx, ctx->candidates.ensure((size_t) nrays * 9 * sizeof(rvb_image_candidate)));
-    RVB_HIP(fail, ctx, ctx->image_items.ensure(((size_t) nrays * 9 + npairs) * 3 * sizeof(uint32_t)));      // (ray, bounce) entries, then a state word each
-    const size_t stripe_bytes = (size_t) RVB_LIVE_STRIPES * npairs * sizeof(uint32_t);
-    if (stripe_bytes > ctx->live_stripes.cap) {
-        RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));          // (a launch that still adds to the old block)
-        RVB_HIP(fail, ctx, ctx->live_stripes.ensure(stripe_bytes));
-        RVB_HIP(fail, ctx, hipMemsetAsync(ctx->live_stripes.p, 0, stripe_bytes, ctx->stream));
-    }
+    RVB_HIP(fail, ctx, trace.ensure_launch(nrays, npairs, nreflections, ctx->stream));
     KeptTrace & kept = ctx->kept;
     if (kept.keep_paths) {                            // rvb_keep_paths: what rvb_reshade needs beside the results
         RVB_HIP(fail, ctx, kept.dev.paths.ensure((size_t) nrays * nreflections * sizeof(float4)));
@@ -96,31 +86,19 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     // impulse array itself (work record or zeros), so no 819 MB fill is needed here
     // (a probe that skips this 3.6 MB fill — the kernel trace of the pipeline shows it stretched to 0.7 ms beside a histogram's host copy, right in
     // front of the next path kernel — made the pipeline 2 % SLOWER, 4.52 -> 4.62 ms per IR, three alternating runs: the fills stay)
-    SmallBlock * small = ctx->small_dev();
-    if (early_bytes) RVB_HIP(fail, ctx, hipMemsetAsync(ctx->early.p, 0xFF, early_bytes, ctx->stream));
+    SmallBlock * small = trace.small_dev();
+    if (nrays) RVB_HIP(fail, ctx, hipMemsetAsync(trace.early.p, 0xFF, TraceStage::early_bytes(nrays), ctx->stream));
     RVB_HIP(fail, ctx, hipMemsetAsync(small, 0, sizeof(SmallBlock), ctx->stream));
     RVB_HIP(fail, ctx, hipMemsetAsync(&small->trace_range[0], 0xFF, 4, ctx->stream));
 
     TraceArgs & a = plan.a;
     a.scene = ctx->scene;
     a.directions = ctx->directions;
-    a.impulses = ctx->impulses.as<rvb_impulse>();
-    a.early = ctx->early.as<uint32_t>();
-    a.candidates = ctx->candidates.as<rvb_image_candidate>();
-    a.candidate_count = &small->candidate_count;
-    a.image_items = reinterpret_cast<ImageItem *>(ctx->image_items.p);
-    a.image_state = ctx->image_items.as<uint32_t>() + ((size_t) nrays * 9 + npairs) * 2;
-    a.image_item_count = &small->image_item_count;
-    a.direct = &small->direct;
+    trace.point(a, nrays, npairs);
     a.npairs = (uint32_t) npairs;
     a.rays_per_pair = (uint32_t) ctx->nrays;
-    a.pair_mics = nullptr;
-    a.pair_sources = nullptr;
-    a.executed = &small->executed;
-    a.time_range = small->trace_range;
     a.image_dist = kept.keep_paths ? kept.dev.image_dist.as<float>() : nullptr;
-    a.live_stripes = ctx->live_stripes.as<uint32_t>();
-    RVB_HIP(fail, ctx, ctx->pairs.stage(mics, sources, npairs, ctx->stream, a));        // several pairs per launch: the four above point to arrays per pair
+    RVB_HIP(fail, ctx, trace.pairs.stage(mics, sources, npairs, ctx->stream, a));       // several pairs per launch: four of them point to arrays per pair
     // record bucketing for coherent shadow rays (RVB_SHADOW_SORT=0 turns it off)
     static const bool sort_records = !(getenv("RVB_SHADOW_SORT") && getenv("RVB_SHADOW_SORT")[0] == '0');
     const uint64_t nrecords = nrays * nreflections;
@@ -130,21 +108,21 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     // The grouping only has to bring neighbouring triangles together: the top 16 bits of the leaf position are two
     // onesweep passes instead of three (C2, 17 key bits: grouping 0.66 -> 0.51 ms beside image_kernel, shadow_kernel +0.02 ms).
     if (sort_records && nrecords && nrecords < (1ull << 32) && ctx->scene.ntris) {
-        RVB_HIP(fail, ctx, ctx->sort_keys.ensure(nrecords * 4));
-        RVB_HIP(fail, ctx, ctx->sort_scratch.ensure(nrecords * 4));
-        RVB_HIP(fail, ctx, ctx->sort_order.ensure(nrecords * 4));
+        RVB_HIP(fail, ctx, trace.sort_keys.ensure(nrecords * 4));
+        RVB_HIP(fail, ctx, trace.sort_scratch.ensure(nrecords * 4));
+        RVB_HIP(fail, ctx, trace.sort_order.ensure(nrecords * 4));
         const size_t group_bytes = rvb_group_records_temp_bytes(ctx->nrays * nreflections);
         if (group_bytes == 0) return fail(ctx, RVB_ERR_HIP, "rvb_trace: radix sort size query failed");
-        RVB_HIP(fail, ctx, ctx->group_temp.ensure(group_bytes));
+        RVB_HIP(fail, ctx, trace.group_temp.ensure(group_bytes));
         // slots of escaped rays get key 0xFFFFFFFF from path_kernel: they land in the last bucket and the
         // shadow kernel skips them by their valid flag
         // 16-bit keys in 64-byte runs (the path stage, trace_kernels.hip: flush_key_run) whenever a ray's row divides into whole runs and rocPRIM sorts;
         // 32-bit keys, one store per record, otherwise (and for RVB_SORT=own)
         if (nreflections % 32 == 0 && !own_sort_enabled()) {
-            a.sort_keys16 = ctx->sort_keys.as<uint16_t>();
+            a.sort_keys16 = trace.sort_keys.as<uint16_t>();
             a.key_shift = (uint32_t) std::max(0, key_bits - 16);
         } else {
-            a.sort_keys = ctx->sort_keys.as<uint32_t>();
+            a.sort_keys = trace.sort_keys.as<uint32_t>();
         }
     }
     a.nrays = nrays;
@@ -154,20 +132,20 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     // (rays_in_flight: what a group launch carries in all; 0 = this trace alone, times the caller's hint)
     a.path_lanes = ctx->path_lanes ? ctx->path_lanes : (rays_in_flight ? rvb_path_lanes_for(rays_in_flight, 1) : rvb_path_lanes_for(nrays, ctx->concurrent_traces));
     a.ray_offset = ray_offset;
-    for (int i = 0; i < 3; ++i) { a.mic[i] = mic[i]; a.source[i] = source[i]; ctx->mic[i] = mic[i]; }
+    for (int i = 0; i < 3; ++i) { a.mic[i] = mic[i]; a.source[i] = source[i]; }
     for (int i = 0; i < 8; ++i) a.air[i] = air_coefficient[i];
 
     RVB_HIP(fail, ctx, ctx->source.upload(ctx->stream));
 
     // diagnostic builds (RVB_STAMPS): [0..15] path_kernel, [16..31] shadow_kernel
-    RVB_HIP(fail, ctx, ctx->stamps.ensure(32 * sizeof(unsigned long long)));
+    RVB_HIP(fail, ctx, trace.stamps.ensure(32 * sizeof(unsigned long long)));
     // (zeroed per trace only where a diagnostic build may write them: one tiny fill kernel less on the stream of every shipped trace)
     static const bool stamps_on = getenv("RVB_STAMPS") != nullptr;
-    if (stamps_on || !ctx->stamps_cleared) {
-        RVB_HIP(fail, ctx, hipMemsetAsync(ctx->stamps.p, 0, 32 * sizeof(unsigned long long), ctx->stream));
-        ctx->stamps_cleared = true;
+    if (stamps_on || !trace.stamps_cleared) {
+        RVB_HIP(fail, ctx, hipMemsetAsync(trace.stamps.p, 0, 32 * sizeof(unsigned long long), ctx->stream));
+        trace.stamps_cleared = true;
     }
-    a.scene.stamps = ctx->stamps.as<unsigned long long>();
+    a.scene.stamps = trace.stamps.as<unsigned long long>();
 
     ctx->reset_timings();
     plan.npairs = npairs;
@@ -197,7 +175,7 @@ int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
     }
     if (a.sort_keys || a.sort_keys16) {
         ctx->begin_timing("record_sort_kernels");
-        a.sort_order = ctx->sort_order.as<uint32_t>();
+        a.sort_order = ctx->trace.sort_order.as<uint32_t>();
         RVB_HIP(fail, ctx, hipGetLastError());
         // one grouping per pair (a pair's shadow rays share a microphone; records are [pair][ray][bounce])
         const uint64_t per_pair = ctx->nrays * nreflections;
@@ -205,33 +183,29 @@ int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
             if (a.sort_keys16) {
                 // key16 = leaf position >> key_shift: its top group_bits bits are bits [end - group_bits, end) with end = min(16, key_bits)
                 const int end = std::min(16, key_bits);
-                RVB_HIP(fail, ctx, rvb_group_records16(ctx->group_temp.p, ctx->group_temp.cap, a.sort_keys16 + p * per_pair,
-                                                       ctx->sort_scratch.as<uint16_t>() + p * per_pair, a.sort_order + p * per_pair, per_pair,
+                RVB_HIP(fail, ctx, rvb_group_records16(ctx->trace.group_temp.p, ctx->trace.group_temp.cap, a.sort_keys16 + p * per_pair,
+                                                       ctx->trace.sort_scratch.as<uint16_t>() + p * per_pair, a.sort_order + p * per_pair, per_pair,
                                                        (uint32_t) (p * per_pair), std::max(0, end - group_bits), end, ctx->stream));
             } else if (own_sort_enabled()) {
                 const int rc = own_sort(ctx, a.sort_keys + p * per_pair, (uint32_t) (p * per_pair), per_pair, std::max(0, key_bits - group_bits), key_bits,
-                                        ctx->sort_scratch.as<uint32_t>() + p * per_pair, a.sort_order + p * per_pair, false);
+                                        ctx->trace.sort_scratch.as<uint32_t>() + p * per_pair, a.sort_order + p * per_pair, false);
                 if (rc != RVB_OK) return rc;
             } else {
-                RVB_HIP(fail, ctx, rvb_group_records(ctx->group_temp.p, ctx->group_temp.cap, a.sort_keys + p * per_pair,
-                                                     ctx->sort_scratch.as<uint32_t>() + p * per_pair, a.sort_order + p * per_pair, per_pair,
+                RVB_HIP(fail, ctx, rvb_group_records(ctx->trace.group_temp.p, ctx->trace.group_temp.cap, a.sort_keys + p * per_pair,
+                                                     ctx->trace.sort_scratch.as<uint32_t>() + p * per_pair, a.sort_order + p * per_pair, per_pair,
                                                      (uint32_t) (p * per_pair), std::max(0, key_bits - group_bits), key_bits, ctx->stream));
             }
         }
         ctx->end_timing();
     }
     const SourceShading source = ctx->source.shading();
-    ctx->live_count_valid = true;               // the shadow stage leaves the count (a directivity pass behind it clears this: apply_source_patterns)
     if ((rc = launch_shadow_behind_images(ctx, a, source)) != RVB_OK) return rc;
     ctx->kept.take(a, source);
-    ctx->nreflections = nreflections;
-    ctx->traced = true;
-    ctx->void_fetched_results();
-    ctx->npairs = npairs;
-    ctx->traced_rays = nrays;
-    ctx->trace_ray_offset = a.ray_offset;
-    ctx->pairs.mics_host.assign(mics, mics + 3 * npairs);
-    ctx->select_first_pair();
+    // the shadow stage leaves the live count; a directivity pass behind it (apply_source_patterns) may silence a record or turn it
+    // into NaNs, and the count no longer bounds the live ones
+    ctx->trace.finished(npairs, nrays, nreflections, a.ray_offset, source.off());
+    ctx->ir.drop_configuration();
+    ctx->trace.pairs.mics_host.assign(mics, mics + 3 * npairs);
     return RVB_OK;
 }
 
@@ -257,21 +231,22 @@ bool by_ray_and_slot(const rvb_image_candidate & x, const rvb_image_candidate & 
 // one synchronising 128-byte read per trace serves candidate count, direct path, time range, bounce count
 int fetch_small(rvb_ctx * ctx)
 {
-    if (ctx->small_valid)
+    TraceStage & trace = ctx->trace;
+    if (trace.fetched())
         return RVB_OK;
-    RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->small_host, ctx->small.p, sizeof(SmallBlock), hipMemcpyDeviceToHost, ctx->stream));
-    if (ctx->traced_rays)      // capacity rays * 9 >= 32 entries unless there are fewer than 4 rays
-        RVB_HIP(fail, ctx, hipMemcpyAsync(ctx->first_candidates, ctx->candidates.p,
-                                          std::min(kFirstCandidates * sizeof(rvb_image_candidate), (size_t) ctx->traced_rays * 9 * sizeof(rvb_image_candidate)),
+    RVB_HIP(fail, ctx, hipMemcpyAsync(&trace.host->small, trace.small.p, sizeof(SmallBlock), hipMemcpyDeviceToHost, ctx->stream));
+    if (trace.rays())          // capacity rays * 9 >= 32 entries unless there are fewer than 4 rays
+        RVB_HIP(fail, ctx, hipMemcpyAsync(trace.host->first, trace.candidates.p,
+                                          std::min(sizeof(trace.host->first), (size_t) trace.rays() * 9 * sizeof(rvb_image_candidate)),
                                           hipMemcpyDeviceToHost, ctx->stream));
-    if (ctx->npairs > 1)       // per-pair direct paths and time ranges
-        RVB_HIP(fail, ctx, ctx->pairs.fetch(ctx->npairs, ctx->stream));
+    if (trace.npairs() > 1)    // per-pair direct paths and time ranges
+        RVB_HIP(fail, ctx, trace.pairs.fetch(trace.npairs(), ctx->stream));
     RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
-    if (*ctx->live_overflow_host) {            // (the lists behind this point are sound again: the word is reported once)
-        *ctx->live_overflow_host = 0;
+    if (trace.host->live_overflow) {           // (the lists behind this point are sound again: the word is reported once)
+        trace.host->live_overflow = 0;
         return fail(ctx, RVB_ERR_HIP, "internal error: an exact-mode list held more live impulses than the trace had counted; the histogram made from it lacks the excess");
     }
-    ctx->small_valid = true;
+    trace.small_fetched();
     return RVB_OK;
 }
 
@@ -393,24 +368,23 @@ int rvb_trace_pairs(rvb_ctx * ctx, const float * mics, const float * sources, ui
 int rvb_ir_select_pair(rvb_ctx * ctx, uint64_t pair)
 {
     if (!ctx) return RVB_ERR_INVALID;
-    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_ir_select_pair: nothing traced");
-    if (pair >= ctx->npairs) return fail(ctx, RVB_ERR_INVALID, "rvb_ir_select_pair: pair out of range");
-    ctx->ir_pair = pair;
+    if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_ir_select_pair: nothing traced");
+    if (pair >= ctx->trace.npairs()) return fail(ctx, RVB_ERR_INVALID, "rvb_ir_select_pair: pair out of range");
+    ctx->trace.select_pair(pair);
     ctx->ir.drop_configuration();             // (a prepared list names the records of the pair it was made for; the fold reads ir_diffuse)
-    for (int i = 0; i < 3; ++i) ctx->mic[i] = ctx->pairs.mic_of(pair)[i];
     return RVB_OK;
 }
 
 int rvb_get_diffuse(rvb_ctx * ctx, rvb_impulse * out)
 {
     if (!ctx) return RVB_ERR_INVALID;
-    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_get_diffuse: nothing traced");
+    if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_get_diffuse: nothing traced");
     RVB_BIND(ctx);
     RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
-    const size_t bytes = (size_t) ctx->traced_rays * ctx->nreflections * sizeof(rvb_impulse);
+    const size_t bytes = (size_t) ctx->trace.rays() * ctx->trace.nreflections() * sizeof(rvb_impulse);
     if (bytes) {
         if (!out) return fail(ctx, RVB_ERR_INVALID, "rvb_get_diffuse: null output");
-        return rvb_copy_to_host(ctx, out, ctx->impulses.p, bytes);
+        return rvb_copy_to_host(ctx, out, ctx->trace.impulses.p, bytes);
     }
     return RVB_OK;
 }
@@ -418,32 +392,31 @@ int rvb_get_diffuse(rvb_ctx * ctx, rvb_impulse * out)
 int rvb_diffuse_device(rvb_ctx * ctx, const void ** d_impulses, uint64_t * count)
 {
     if (!ctx) return RVB_ERR_INVALID;
-    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_diffuse_device: nothing traced");
-    if (d_impulses) *d_impulses = ctx->impulses.p;
-    if (count) *count = ctx->traced_rays * ctx->nreflections;
+    if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_diffuse_device: nothing traced");
+    if (d_impulses) *d_impulses = ctx->trace.impulses.p;
+    if (count) *count = ctx->trace.rays() * ctx->trace.nreflections();
     return RVB_OK;
 }
 
 int rvb_get_direct(rvb_ctx * ctx, rvb_impulse * out)
 {
     if (!ctx || !out) return RVB_ERR_INVALID;
-    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_get_direct: nothing traced");
+    if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_get_direct: nothing traced");
     RVB_BIND(ctx);
     int rc = fetch_small(ctx);
     if (rc != RVB_OK) return rc;
-    if (ctx->npairs > 1) *out = ctx->pairs.direct_of(ctx->ir_pair);      // of the pair chosen with rvb_ir_select_pair
-    else *out = ctx->small_host->direct;
+    *out = ctx->trace.direct();               // of the pair chosen with rvb_ir_select_pair
     return RVB_OK;
 }
 
 int rvb_get_image_candidates(rvb_ctx * ctx, rvb_image_candidate * out, uint64_t capacity, uint64_t * count)
 {
     if (!ctx || !count) return RVB_ERR_INVALID;
-    if (!ctx->traced) return fail(ctx, RVB_ERR_STATE, "rvb_get_image_candidates: nothing traced");
+    if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_get_image_candidates: nothing traced");
     RVB_BIND(ctx);
     int rc = fetch_small(ctx);
     if (rc != RVB_OK) return rc;
-    const uint32_t n = ctx->small_host->candidate_count;
+    const uint32_t n = ctx->trace.host->small.candidate_count;
     *count = n;
     if (!out)
         return RVB_OK;                       // size query
@@ -451,9 +424,9 @@ int rvb_get_image_candidates(rvb_ctx * ctx, rvb_image_candidate * out, uint64_t 
         return fail(ctx, RVB_ERR_CAPACITY, "rvb_get_image_candidates: capacity too small");
     if (n) {
         if (n <= kFirstCandidates)
-            std::memcpy(out, ctx->first_candidates, (size_t) n * sizeof(rvb_image_candidate));     // came with the small block
+            std::memcpy(out, ctx->trace.host->first, (size_t) n * sizeof(rvb_image_candidate));     // came with the small block
         else
-            RVB_HIP(fail, ctx, hipMemcpy(out, ctx->candidates.p, (size_t) n * sizeof(rvb_image_candidate), hipMemcpyDeviceToHost));
+            RVB_HIP(fail, ctx, hipMemcpy(out, ctx->trace.candidates.p, (size_t) n * sizeof(rvb_image_candidate), hipMemcpyDeviceToHost));
         std::sort(out, out + n, by_ray_and_slot);
     }
     return RVB_OK;

@@ -2,7 +2,8 @@
 
 LedgerContext has the method surface of capi.Context over the CPU oracle (in the manner of tests/oracle_tracer.py) and keeps the same
 caches and flags as rvb_ctx, function by function as csrc/ does: the fetched small block, the tenant of the sort buffers (the keys of a
-flatten size query or a prepared list: IrState of csrc/ir_state.h) beside what the buffers really hold, its own copy of the images, the
+flatten size query or a prepared list: IrState of csrc/ir_state.h) beside what the buffers really hold, the trace's flags and selected
+pair (TraceState of csrc/trace_state.h; its live count has no reader among the walks and is not modelled), its own copy of the images, the
 ear count of the table, the kept state, the selected pair.
 `forget=<site>` leaves out exactly one invalidation of the code.  The conditions below: the model and the complete stand-in agree on
 every walk; every forgotten invalidation is flagged by a directed sequence and by a quarter of the seeds; the seeds cover every
@@ -17,11 +18,11 @@ from context_model import Disagreement, Rec, Walk
 from parallel_reverb_raytracer_amd import capi
 from parallel_reverb_raytracer_amd.dtypes import IMPULSE
 
-# the invalidation sites of csrc/, "function:what it clears" or "function:the transition of IrState it calls"
+# the invalidation sites of csrc/, "function:what it clears" or "function:the transition of IrState / TraceState (or the composition of rvb_ctx) it calls"
 FORGETS = (
     "ensure_sort_buffers:tenant", "configure_common:exact.valid", "configure_common:range_pending",
     "set_one_ear_table:hrtf_table_ears", "set_one_ear_table:drop_configuration", "drop_configuration:configured", "drop_configuration:exact.valid",
-    "trace_finish:void_fetched_results", "trace_finish:select_first_pair", "trace_finish:kept", "reshade:void_fetched_results",
+    "trace_finish:not fetched", "trace_finish:pair 0", "trace_finish:kept", "reshade:void_fetched_results",
     "relisten:void_fetched_results", "set_scene:traced", "set_directions:traced", "void_trace:drop_configuration", "keep_paths(0):release",
     "select_pair:drop_configuration", "accumulate:exact.valid", "flatten_fill:keys consumed",
 )
@@ -87,9 +88,11 @@ class LedgerContext:
 
     # ---- trace.hip -------------------------------------------------------------------------------------------------------------------
     def void_fetched_results(self, site):
+        """rvb_ctx::void_fetched_results: TraceState::records_rewritten — not fetched, pair 0 — and the configuration dropped"""
         if self.forgot(site):
             return
         self.small_valid = False
+        self.ir_pair = 0
         self.drop_configuration()
 
     def _index(self, what, xyz):
@@ -115,10 +118,12 @@ class LedgerContext:
             self.kept_valid, self.listener_valid = self.keep, self.keep and self.keep_listener
             if self.kept_valid:
                 self.kept_rec = self.dev
-        self.traced = True
-        self.void_fetched_results("trace_finish:void_fetched_results")
+        self.traced = True                                                # TraceState::finished: traced, its sizes, not fetched, pair 0
         self.npairs = len(self.dev.mics)
-        if not self.forgot("trace_finish:select_first_pair"):
+        if not self.forgot("trace_finish:not fetched"):                   # (... and the configuration dropped, as void_trace has already)
+            self.small_valid = False
+            self.drop_configuration()
+        if not self.forgot("trace_finish:pair 0"):
             self.ir_pair = 0
 
     def select_pair(self, pair):
@@ -203,7 +208,6 @@ class LedgerContext:
         table = "own" if surfaces is None else next(t for t in cm.TABLES if self.w.table(self.scene, t) is surfaces)
         self.void_fetched_results("reshade:void_fetched_results")
         self.dev = self.kept_rec = self.kept_rec._replace(table=table, air=self._air(air), pattern=self.pattern)
-        self.ir_pair = 0
 
     def relisten(self, mics):
         if not self.traced:
@@ -214,7 +218,6 @@ class LedgerContext:
             self.fail(capi.ERR_INVALID, "rvb_relisten: microphone count")
         self.void_fetched_results("relisten:void_fetched_results")
         self.dev = self.kept_rec = self.kept_rec._replace(mics=tuple(self._index("mics", m) for m in mics))
-        self.ir_pair = 0
 
     # ---- sort.hip --------------------------------------------------------------------------------------------------------------------
     def ensure_sort_buffers(self, n):
