@@ -121,14 +121,15 @@ int rvb_set_scene(rvb_ctx * ctx, const rvb_triangle * triangles, uint64_t ntrian
     if (!err.empty())
         return fail(ctx, err.find("stack") != std::string::npos ? RVB_ERR_CAPACITY : RVB_ERR_INVALID, "rvb_set_scene: " + err);
     RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
-    ctx->have_scene = false;
+    ContextScene & scene = ctx->scene;
+    scene.drop();                                   // (until set() below: a failure midway leaves no scene)
     ctx->void_trace();
     // a store other contexts hold stays theirs: this context gets a new one (buffers it holds alone are reused)
-    if (!ctx->store || ctx->store.use_count() > 1) {
-        ctx->store = std::make_shared<SceneStore>();
-        ctx->store->device = ctx->device;
+    if (!scene.store || scene.store.use_count() > 1) {
+        scene.store = std::make_shared<SceneStore>();
+        scene.store->device = ctx->device;
     }
-    SceneStore & st = *ctx->store;
+    SceneStore & st = *scene.store;
     auto upload = [&](DevBuf & b, const void * src, size_t bytes) -> hipError_t {
         hipError_t e = b.ensure(bytes);
         if (e != hipSuccess || bytes == 0) return e;
@@ -142,22 +143,17 @@ int rvb_set_scene(rvb_ctx * ctx, const rvb_triangle * triangles, uint64_t ntrian
     RVB_HIP(fail, ctx, upload(st.shade, built.shade.data(), built.shade.size() * sizeof(TriShade)));
     RVB_HIP(fail, ctx, upload(st.corners, built.corners.data(), built.corners.size() * sizeof(TriCorners)));
     RVB_HIP(fail, ctx, upload(st.surfaces, surfaces, nsurfaces * sizeof(rvb_surface)));
-    ctx->scene.nodes = st.nodes.as<const BvhNode>();
-    ctx->scene.tris = st.tris.as<const BvhTri>();
-    ctx->scene.shade = st.shade.as<const TriShade>();
-    ctx->scene.corners = st.corners.as<const TriCorners>();
-    ctx->scene.surfaces = st.surfaces.as<const rvb_surface>();
-    ctx->scene.ntris = (uint32_t) built.tris.size();
+    SceneDev dev;
+    dev.nodes = st.nodes.as<const BvhNode>();
+    dev.tris = st.tris.as<const BvhTri>();
+    dev.shade = st.shade.as<const TriShade>();
+    dev.corners = st.corners.as<const TriCorners>();
+    dev.surfaces = st.surfaces.as<const rvb_surface>();
+    dev.ntris = (uint32_t) built.tris.size();
     // cull slack along the ray: the float distance of a triangle may differ from the exact one
-    ctx->scene.cull_abs = built.pad;
-    ctx->scene.cull_rel = 1e-4f;
-    ctx->nnodes = built.nodes.size();
-    ctx->kept_triangles = built.tris.size();
-    ctx->depth = built.depth;
-    ctx->stack_need = built.stack_need;
-    ctx->nsurfaces = nsurfaces;
-    ctx->ntriangles = ntriangles;
-    ctx->have_scene = true;
+    dev.cull_abs = built.pad;
+    dev.cull_rel = 1e-4f;
+    scene.set(dev, built.nodes.size(), built.tris.size(), built.depth, built.stack_need, nsurfaces, ntriangles);
     return RVB_OK;
 }
 
@@ -165,19 +161,11 @@ int rvb_share_scene(rvb_ctx * ctx, rvb_ctx * from)
 {
     if (!ctx || !from) return RVB_ERR_INVALID;
     if (ctx == from) return RVB_OK;
-    if (!from->have_scene || !from->store) return fail(ctx, RVB_ERR_STATE, "rvb_share_scene: the other context holds no scene");
+    if (!from->scene.have() || !from->scene.store) return fail(ctx, RVB_ERR_STATE, "rvb_share_scene: the other context holds no scene");
     if (from->device != ctx->device) return fail(ctx, RVB_ERR_INVALID, "rvb_share_scene: the contexts are on different devices (a scene is shared within one GPU's memory)");
     RVB_BIND(ctx);
     RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));        // nothing of this context reads its old scene any more
-    ctx->store = from->store;
-    ctx->scene = from->scene;
-    ctx->nnodes = from->nnodes;
-    ctx->kept_triangles = from->kept_triangles;
-    ctx->depth = from->depth;
-    ctx->stack_need = from->stack_need;
-    ctx->nsurfaces = from->nsurfaces;
-    ctx->ntriangles = from->ntriangles;
-    ctx->have_scene = true;
+    ctx->scene = from->scene;                                       // the store, where the kernels find it, every count
     ctx->void_trace();
     return RVB_OK;
 }
@@ -185,10 +173,10 @@ int rvb_share_scene(rvb_ctx * ctx, rvb_ctx * from)
 int rvb_scene_info(rvb_ctx * ctx, uint64_t * nodes, uint64_t * kept_triangles, uint32_t * depth)
 {
     if (!ctx) return RVB_ERR_INVALID;
-    if (!ctx->have_scene) return fail(ctx, RVB_ERR_STATE, "rvb_scene_info: no scene");
-    if (nodes) *nodes = ctx->nnodes;
-    if (kept_triangles) *kept_triangles = ctx->kept_triangles;
-    if (depth) *depth = ctx->depth;
+    if (!ctx->scene.have()) return fail(ctx, RVB_ERR_STATE, "rvb_scene_info: no scene");
+    if (nodes) *nodes = ctx->scene.nnodes;
+    if (kept_triangles) *kept_triangles = ctx->scene.kept_triangles;
+    if (depth) *depth = ctx->scene.depth;
     return RVB_OK;
 }
 

@@ -1,14 +1,16 @@
 // ctx.h — the context behind include/rvb_capi.h and what its translation units share:
-//   context.hip  life cycle, scene, directions, timings, diagnostics
+//   context.hip  life cycle, scene (ContextScene below), directions, timings, diagnostics
 //   trace.hip    the trace in three steps (TraceStage below, over trace_state.h), the tail steps a kept trace replays, its results, rvb_merge_images
 //   source.hip   source directivity (SourceDirectivity below, over source_state.h / source_state.hip): setters, upload, launches
-//   kept.hip     behind a kept trace: re-shading, its material gradients per surface and per triangle, a new microphone
+//   kept.hip     behind a kept trace (KeptTrace below, over kept_state.h): re-shading, its material gradients per surface and per
+//                triangle, a new microphone
 //   memory.hip   caller-owned device / pinned memory, staged host copies, the export stream
 //   sort.hip     the sorts the other stages call, their buffers (SortBuffers below), "sorted list and bin boundaries"
 //   ir.hip       the fused impulse-response stage (IrStage below, over ir_state.h): configure, time range, binning, download / export
 //   flatten.hip  the materialised steps of the reference: attenuate per channel, fix the predelay, flatten
 //   decay.hip    decay curves, reverberation times and the decay loss on the caller's device arrays
-//   images.hip   include/rvb_capi_images.h: the merged image list made on the device, the image-source part of the material gradient
+//   images.hip   include/rvb_capi_images.h: the merged image list made on the device (MergedImages below, over merged_state.h), the
+//                image-source part of the material gradient
 // No compute happens in them and nothing falls back to the CPU: every entry point that produces results launches HIP kernels:
 //   the trace         trace_kernels.hip, image_kernels.hip, shadow_kernels.hip, source_kernels.hip
 //   a kept trace      reshade_kernels.hip, reshade_grad_kernels.hip, relisten_kernels.hip (the three over kept_tiles.h),
@@ -21,7 +23,9 @@
 #include "../../include/rvb_capi.h"
 #include "hip_owned.h"
 #include "ir_state.h"
+#include "kept_state.h"
 #include "kernels.h"
+#include "merged_state.h"
 #include "source_state.h"
 #include "trace_state.h"
 
@@ -41,6 +45,31 @@ struct SceneStore {
     int device = 0;
     DevBuf nodes, tris, shade, corners, surfaces;
     ~SceneStore() { (void) hipSetDevice(device); }
+};
+
+// A context's scene as one value: the store it holds (its own after rvb_set_scene, another context's after rvb_share_scene, which
+// copies the whole value), where the kernels find it, and its counts.  Nothing of it is read while have() is false.
+struct ContextScene {
+    std::shared_ptr<SceneStore> store;
+    SceneDev dev;
+    uint64_t nnodes = 0, kept_triangles = 0;
+    uint32_t depth = 0;
+    uint32_t stack_need = RVB_BVH_STACK;
+    uint64_t nsurfaces = 0;
+    uint64_t ntriangles = 0;                     // as passed to rvb_set_scene: the index space of a record's triangle
+    bool have() const { return have_; }
+    // rvb_set_scene begins: no scene until set() — what a failure midway leaves.  The store stays, to be reused if held alone.
+    void drop() { have_ = false; }
+    // rvb_set_scene has uploaded into the store
+    void set(const SceneDev & on_device, uint64_t nodes, uint64_t kept, uint32_t tree_depth, uint32_t stack, uint64_t surfaces, uint64_t triangles)
+    {
+        dev = on_device;
+        nnodes = nodes; kept_triangles = kept; depth = tree_depth; stack_need = stack; nsurfaces = surfaces; ntriangles = triangles;
+        have_ = true;
+    }
+
+private:
+    bool have_ = false;
 };
 
 // The small result block of a trace: one per context on the device, fetched into its pinned host mirror once per trace (fetch_small).
@@ -261,19 +290,17 @@ struct TraceStage : TraceState {
 
 struct Timing { std::string name; hipEvent_t start, stop; };       // (events of the context's pool)
 
-// A kept trace (rvb_keep_paths; kept.hip works from it).  While keeping is on a trace leaves, beside its results, a 16-byte side record
-// per (ray, bounce) (SideRecord of csrc/kept_tiles.h) and the INIT_DIST of every image impulse (csrc/reshade_kernels.hip), and `args` remembers its kernel arguments:
+// A kept trace, the device half over KeptState (kept_state.h; rvb_keep_paths; kept.hip works from it).  While keeping is on a trace
+// leaves, beside its results, a 16-byte side record per (ray, bounce) (SideRecord of csrc/kept_tiles.h) and the INIT_DIST of every
+// image impulse (csrc/reshade_kernels.hip), and trace_args() remembers its kernel arguments:
 // microphones, sources, air, ray offset and every buffer of the launch.  With RVB_KEEP_LISTENER it leaves an 8-byte listener record per
 // (ray, bounce) too, {own-plane threshold, triangle} (csrc/relisten_kernels.hip).  The buffers exist only while keeping is on.
-// The kept state is valid while TraceState::traced() holds and nothing has voided it: a trace voids it first (void_all) and takes it last (take).
+// The kept state is valid while TraceState::traced() holds and nothing has voided it: a trace voids it first (trace_begins) and takes it last (take).
 // The grouping order of the records is kept where the trace left it: `sort_order` is written by the record grouping of a trace and by
 // nothing else (the binning stages sort in SortBuffers), and the next trace voids the kept state before it
-// regroups; args.sort_order points there (null: the trace grouped nothing).
-struct KeptTrace {
-    bool keep_paths = false, keep_listener = false;      // asked for: the buffers come with the next trace, sized for it
-    bool valid = false;                                  // the last trace was made with keeping on
-    bool listener_valid = false;                         // ... and with RVB_KEEP_LISTENER
-    TraceArgs args = {};
+// regroups; trace_args().sort_order points there (null: the trace grouped nothing).
+struct KeptTrace : KeptState {
+    static_assert(kListenerBit == RVB_KEEP_LISTENER, "KeptState::ask reads the listener bit of rvb_keep_paths");
     // everything on the device that keeping owns.  `surfaces` is the table of the last rvb_reshade: the scene (which may be shared)
     // keeps its own; uploaded in stream order through surfaces_stage, as the source patterns are.  `grad_scratch`: the result and the
     // partial tables of rvb_reshade_grad (csrc/reshade_grad_kernels.hip).  `map_scratch`: the term rows of rvb_reshade_grad_map, 64 bytes per
@@ -284,51 +311,73 @@ struct KeptTrace {
     } dev;
     static_assert(sizeof(Buffers) == 6 * sizeof(DevBuf), "any() names every buffer");
     StagedBlock surfaces_stage;
-    // what the records reflect right now — the kept trace's table, air and source directivity (pattern, table or nothing), or those of
-    // the last rvb_reshade —: where rvb_reshade_grad takes its derivatives and what rvb_relisten shades with
-    const rvb_surface * shaded_surfaces = nullptr;
-    float shaded_air[8] = {};
-    SourceShading shaded_source;
 
-    void void_all() { valid = false; listener_valid = false; }
+    // What a launch of nrays rays in npairs pairs keeps beside its results (nothing while keeping is off), and where its kernels put it.
+    hipError_t ensure_launch(uint64_t nrays, uint64_t npairs, uint64_t nreflections)
+    {
+        if (!keeping()) return hipSuccess;
+        hipError_t e;
+        if ((e = dev.paths.ensure((size_t) nrays * nreflections * sizeof(float4))) != hipSuccess) return e;
+        if ((e = dev.image_dist.ensure(TraceStage::image_entries(nrays, npairs) * sizeof(float))) != hipSuccess) return e;
+        return keeping_listener() ? dev.listen.ensure((size_t) nrays * nreflections * sizeof(uint2)) : hipSuccess;
+    }
+    float * image_dist_for_launch() const { return keeping() ? dev.image_dist.as<float>() : nullptr; }
+    uint2 * listen_for_launch() const { return keeping_listener() ? dev.listen.as<uint2>() : nullptr; }
+
     // `a` with `source` wrote the records last: a trace's shadow kernel, the re-shade kernels
     void note_shading(const TraceArgs & a, const SourceShading & source)
     {
-        shaded_surfaces = a.scene.surfaces;
-        for (int i = 0; i < 8; ++i) shaded_air[i] = a.air[i];
-        shaded_source = source;
+        shaded_surfaces_ = a.scene.surfaces;
+        for (int i = 0; i < 8; ++i) shaded_air_[i] = a.air[i];
+        shaded_source_ = source;
     }
     // a trace with the arguments `a` is complete
     void take(const TraceArgs & a, const SourceShading & source)
     {
-        valid = keep_paths;
-        listener_valid = keep_paths && keep_listener;
-        if (valid) { args = a; note_shading(a, source); }
+        trace_taken();
+        if (valid()) { args_ = a; note_shading(a, source); }
     }
-    // the kept trace's own arguments under the table and the air that the records reflect now
+    // rvb_relisten has rewritten the records for this microphone: "the kept trace stays valid and is now that of the new microphone(s)"
+    // (those of several pairs are in PairLaunch::geom)
+    void relistened(const float mic[3]) { for (int i = 0; i < 3; ++i) args_.mic[i] = mic[i]; }
+    // the kept trace's own arguments ...
+    const TraceArgs & trace_args() const { return args_; }
+    // ... and under the table and the air that the records reflect now
     TraceArgs shaded_args() const
     {
-        TraceArgs a = args;
-        a.scene.surfaces = shaded_surfaces;
-        for (int i = 0; i < 8; ++i) a.air[i] = shaded_air[i];
+        TraceArgs a = args_;
+        a.scene.surfaces = shaded_surfaces_;
+        for (int i = 0; i < 8; ++i) a.air[i] = shaded_air_[i];
         return a;
+    }
+    // the source directivity that the records reflect now (pattern, table or nothing) ...
+    const SourceShading & shaded_source() const { return shaded_source_; }
+    // ... and its pattern for pair `pair`: one pattern serves every pair, several are one per pair.  false: no pattern shaded the records.
+    bool shaded_pattern(uint64_t pair, SourcePatternDev & out) const
+    {
+        const std::vector<SourcePatternDev> & patterns = shaded_source_.patterns;
+        out = patterns.empty() ? SourcePatternDev{} : patterns[patterns.size() > 1 ? pair : 0];
+        return !patterns.empty();
     }
     // frees the device buffers (the caller has synchronised the streams whose work may still use them)
     void release() { Buffers freed(std::move(dev)); }
+
+private:
+    TraceArgs args_ = {};
+    // what the records reflect right now — the kept trace's table, air and source directivity, or those of the last rvb_reshade —:
+    // where rvb_reshade_grad takes its derivatives and what rvb_relisten shades with
+    const rvb_surface * shaded_surfaces_ = nullptr;
+    float shaded_air_[8] = {};
+    SourceShading shaded_source_;
 };
 
-// The merged image list made on the device (rvb_ir_configure_*_merged, images.hip).  Which candidate wins each key of rvb_merge_images
-// depends on geometry and microphone only: `winners` holds, per output impulse in the merge's order, the device position of the candidate
+// The merged image list made on the device, the device half over MergedState (merged_state.h; rvb_ir_configure_*_merged, images.hip).
+// Which candidate wins each key of rvb_merge_images depends on geometry and microphone only: `winners` holds, per output impulse in the merge's order, the device position of the candidate
 // it is copied from, or RVB_IMAGE_WINNER_DIRECT for the pair's direct slot.  Made once per (trace or relisten, pair, remove_direct) from
 // one download of the candidates, uploaded once; a re-shade, a source setter and rvb_ir_select_pair leave it alone.
-struct MergedImages {
-    bool valid = false;                          // `winners` describes the candidates on the device
-    uint64_t pair = 0;
-    bool remove_direct = false;
-    uint64_t count = 0;
-    DevBuf winners;                              // [count] uint32_t
+struct MergedImages : MergedState {
+    DevBuf winners;                              // [count()] uint32_t
     DevBuf grad_scratch;                         // rvb_reshade_grad_images: the term rows, then the result
-    void void_list() { valid = false; }
 };
 
 // The impulse-response stage, the device half over IrState (ir_state.h): the model and the image list of the configuration, the HRTF
@@ -368,15 +417,7 @@ struct rvb_ctx {
     int compute_units = 0;
     uint64_t hbm_bytes = 0;
 
-    // scene
-    bool have_scene = false;
-    std::shared_ptr<SceneStore> store;          // (its own after rvb_set_scene, another context's after rvb_share_scene)
-    SceneDev scene;
-    uint64_t nnodes = 0, kept_triangles = 0;
-    uint32_t depth = 0;
-    uint32_t stack_need = RVB_BVH_STACK;
-    uint64_t nsurfaces = 0;
-    uint64_t ntriangles = 0;                     // as passed to rvb_set_scene: the index space of a record's triangle
+    ContextScene scene;
 
     // rays + trace results
     DevBuf directions_own;
@@ -481,6 +522,8 @@ int launch_shadow_behind_images(rvb_ctx * ctx, const TraceArgs & a, const Source
 // source.hip: what a trace and a re-shade do about the source directivity (described where they are defined)
 int check_source_counts(rvb_ctx * ctx, const char * who, uint64_t npairs);
 int apply_source_patterns(rvb_ctx * ctx, const TraceArgs & a, const SourceShading & source, bool gains_stand = false);
+// kept.hip: the tail of a per-surface gradient — waits for the stream, then the nsurfaces * 16 + 8 floats at d_out into the caller's arrays
+int download_surface_gradient(rvb_ctx * ctx, const float * d_out, rvb_surface * grad_surfaces, float grad_air[8]);
 
 // trace.hip: the merge rule of rvb_merge_images on its own — per output impulse, in the merge's (std::map key) order, the position in
 // `candidates` of the candidate it is copied from, or RVB_IMAGE_WINNER_DIRECT for the direct slot.  RVB_ERR_INVALID for a slot out of range.

@@ -4,15 +4,13 @@
 #include "../../include/rvb_capi_images.h"
 #include "ctx.h"
 
-#include <cstring>
-
 namespace {
 
 // The winner list of the selected pair: from the cache, or made from one download of the candidates in device order and uploaded.
 int ensure_winners(rvb_ctx * ctx, bool remove_direct)
 {
     MergedImages & merged = ctx->merged;
-    if (merged.valid && merged.pair == ctx->trace.pair() && merged.remove_direct == remove_direct) return RVB_OK;
+    if (merged.serves(ctx->trace.pair(), remove_direct)) return RVB_OK;
     int rc = fetch_small(ctx);
     if (rc != RVB_OK) return rc;
     RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));        // the candidates are final, and no kernel reads the list that is about to be replaced
@@ -35,14 +33,11 @@ int ensure_winners(rvb_ctx * ctx, bool remove_direct)
         if (w != RVB_IMAGE_WINNER_DIRECT) w = position[w];
     // From here on the list on the device is no longer the one a configuration may have been made from: that configuration goes with
     // it (a failure above has left both as they were).
-    merged.valid = false;
+    merged.void_list();
     if (ctx->ir.from_merged_list()) ctx->ir.drop_configuration();
     RVB_HIP(fail, ctx, merged.winners.ensure(winners.size() * sizeof(uint32_t)));
     if (!winners.empty()) RVB_HIP(fail, ctx, hipMemcpy(merged.winners.p, winners.data(), winners.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    merged.count = winners.size();
-    merged.pair = ctx->trace.pair();
-    merged.remove_direct = remove_direct;
-    merged.valid = true;
+    merged.made(ctx->trace.pair(), remove_direct, winners.size());
     return RVB_OK;
 }
 
@@ -52,7 +47,7 @@ int configure_merged(rvb_ctx * ctx, int which, int remove_direct, uint64_t * nim
     int rc = ir_configure_refusals(ctx, which);
     if (rc != RVB_OK) return rc;
     if ((rc = ensure_winners(ctx, remove_direct != 0)) != RVB_OK) return rc;
-    const uint64_t n = ctx->merged.count;
+    const uint64_t n = ctx->merged.count();
     if ((rc = ir_configure_images(ctx, which, nullptr, n, true)) != RVB_OK) return rc;
     ctx->reset_timings();
     ctx->begin_timing("image_gather_kernel");
@@ -92,23 +87,23 @@ int rvb_reshade_grad_images(rvb_ctx * ctx, float predelay, float sample_rate, ui
     if (nbins == 0 || nbins >= (1ull << 32)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_images: no bins (or more than 32-bit bin numbers reach)");
     if (!std::isfinite(predelay) || !std::isfinite(sample_rate)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_images: predelay or sample rate is not finite");
     if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: nothing traced (or the scene or the directions have changed since)");
-    if (!ctx->kept.valid) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: the last trace was made without rvb_keep_paths(ctx, 1)");
+    if (!ctx->kept.valid()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: the last trace was made without rvb_keep_paths(ctx, 1)");
     if (!ctx->ir.configured())
         return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: no IR configuration (rvb_ir_configure_speakers_merged after the trace, re-shade or relisten)");
     if (ctx->ir.model.hrtf) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: the HRTF model is configured; this version takes the speaker model only");
-    if (!ctx->ir.from_merged_list() || !ctx->merged.valid)
+    if (!ctx->ir.from_merged_list() || !ctx->merged.valid())
         return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: the caller's list has lost its chains: configure with rvb_ir_configure_speakers_merged");
     if (ctx->ir.which() == RVB_IR_DIFFUSE)
         return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: configured with which == RVB_IR_DIFFUSE: no image takes part (rvb_reshade_grad has that gradient)");
     if (ctx->ir.model.nchannels > 8)
         return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: " + std::to_string(ctx->ir.model.nchannels) + " speaker channels configured; this version takes 1 to 8");
-    if (ctx->nsurfaces >= (1ull << 27)) return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad_images: too many surfaces");
+    if (ctx->scene.nsurfaces >= (1ull << 27)) return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad_images: too many surfaces");
     RVB_BIND(ctx);
     KeptTrace & kept = ctx->kept;
     MergedImages & merged = ctx->merged;
     TraceArgs a = kept.shaded_args();
     a.scene.stamps = nullptr;
-    const uint64_t n = ctx->ir.nimages(), entries = ctx->nsurfaces * 16 + 8;
+    const uint64_t n = ctx->ir.nimages(), entries = ctx->scene.nsurfaces * 16 + 8;
     // the term rows, then the result
     const size_t row_bytes = (size_t) n * RVB_IMAGE_GRAD_ROW * sizeof(uint32_t);
     RVB_HIP(fail, ctx, merged.grad_scratch.ensure(row_bytes + entries * sizeof(float)));
@@ -125,9 +120,8 @@ int rvb_reshade_grad_images(rvb_ctx * ctx, float predelay, float sample_rate, ui
     g.sample_rate = sample_rate;
     for (int i = 0; i < 3; ++i) g.mic[i] = ctx->trace.mic()[i];
     // the source directivity that the records reflect now, for the selected pair
-    const SourceShading & shaded = kept.shaded_source;
-    g.has_pattern = !shaded.patterns.empty();
-    if (g.has_pattern) g.pattern = shaded.patterns[shaded.patterns.size() > 1 ? ctx->trace.pair() : 0];
+    const SourceShading & shaded = kept.shaded_source();
+    g.has_pattern = kept.shaded_pattern(ctx->trace.pair(), g.pattern);
     if (shaded.table_orientations) {
         const SourceTableDev t = ctx->source.table_on_device(shaded.table_orientations);
         g.table = t.table;
@@ -138,16 +132,10 @@ int rvb_reshade_grad_images(rvb_ctx * ctx, float predelay, float sample_rate, ui
     rvb_launch_reshade_grad_images(a, ctx->ir.model, g, rows, ctx->stream);
     ctx->end_timing();
     ctx->begin_timing("reshade_grad_images_reduce_kernel");
-    rvb_launch_reshade_grad_images_reduce(rows, n, ctx->nsurfaces, d_out, ctx->stream);
+    rvb_launch_reshade_grad_images_reduce(rows, n, ctx->scene.nsurfaces, d_out, ctx->stream);
     ctx->end_timing();
     RVB_HIP(fail, ctx, hipGetLastError());
-    RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<float> host(entries);
-    const int rc = rvb_copy_to_host(ctx, host.data(), d_out, entries * sizeof(float));
-    if (rc != RVB_OK) return rc;
-    std::memcpy(grad_surfaces, host.data(), (size_t) ctx->nsurfaces * sizeof(rvb_surface));
-    if (grad_air) std::memcpy(grad_air, host.data() + ctx->nsurfaces * 16, 8 * sizeof(float));
-    return RVB_OK;
+    return download_surface_gradient(ctx, d_out, grad_surfaces, grad_air);
 }
 
 }  // extern "C"

@@ -11,7 +11,7 @@
 static TraceArgs for_record_pass(const rvb_ctx * ctx, TraceArgs a)
 {
     a.scene.stamps = nullptr;
-    a.lds_surfaces = rvb_reshade_lds_surfaces(ctx->nsurfaces);
+    a.lds_surfaces = rvb_reshade_lds_surfaces(ctx->scene.nsurfaces);
     return a;
 }
 
@@ -28,13 +28,23 @@ static ReshadeGradArgs grad_args(const rvb_ctx * ctx, float predelay, float samp
     g.first_ray = ctx->trace.pair() * ctx->nrays;
     g.nrays = (uint32_t) ctx->nrays;
     for (int i = 0; i < 3; ++i) g.mic[i] = ctx->trace.mic()[i];
-    const std::vector<SourcePatternDev> & shaded_patterns = kept.shaded_source.patterns;
-    g.has_pattern = !shaded_patterns.empty();
-    g.pattern = g.has_pattern ? shaded_patterns[shaded_patterns.size() > 1 ? ctx->trace.pair() : 0] : SourcePatternDev{};
+    g.has_pattern = kept.shaded_pattern(ctx->trace.pair(), g.pattern);
     // a table shaded the records: the pair's rows of the gains that launch left (source_table_rays_kernel)
-    g.ray_gains = kept.shaded_source.table_orientations ? ctx->source.gains_of_pair(ctx->trace.pair(), ctx->nrays) : nullptr;
-    g.nsurfaces = ctx->nsurfaces;
+    g.ray_gains = kept.shaded_source().table_orientations ? ctx->source.gains_of_pair(ctx->trace.pair(), ctx->nrays) : nullptr;
+    g.nsurfaces = ctx->scene.nsurfaces;
     return g;
+}
+
+int download_surface_gradient(rvb_ctx * ctx, const float * d_out, rvb_surface * grad_surfaces, float grad_air[8])
+{
+    const uint64_t nsurfaces = ctx->scene.nsurfaces, entries = nsurfaces * 16 + 8;
+    RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<float> host(entries);
+    const int rc = rvb_copy_to_host(ctx, host.data(), d_out, entries * sizeof(float));
+    if (rc != RVB_OK) return rc;
+    std::memcpy(grad_surfaces, host.data(), (size_t) nsurfaces * sizeof(rvb_surface));
+    if (grad_air) std::memcpy(grad_air, host.data() + nsurfaces * 16, 8 * sizeof(float));
+    return RVB_OK;
 }
 
 extern "C" {
@@ -43,11 +53,7 @@ int rvb_keep_paths(rvb_ctx * ctx, int keep)
 {
     if (!ctx) return RVB_ERR_INVALID;
     KeptTrace & kept = ctx->kept;
-    kept.keep_paths = keep != 0;                  // (the buffers come with the next trace, sized for it)
-    kept.keep_listener = (keep & RVB_KEEP_LISTENER) != 0;
-    if (keep) return RVB_OK;
-    kept.void_all();
-    if (kept.dev.any()) {
+    if (kept.ask(keep) && kept.dev.any()) {       // (asked to keep: the buffers come with the next trace, sized for it)
         RVB_BIND(ctx);
         RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));        // a keep pass or a re-shade may still use them
         RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->side_stream));
@@ -63,7 +69,7 @@ int rvb_relisten(rvb_ctx * ctx, const float * mics, uint64_t npairs)
     for (uint64_t i = 0; i < 3 * npairs; ++i)
         if (!std::isfinite(mics[i])) return fail(ctx, RVB_ERR_INVALID, "rvb_relisten: microphone " + std::to_string(i / 3) + " holds a coordinate that is not finite");
     if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_relisten: nothing traced (or the scene or the directions have changed since)");
-    if (!ctx->kept.listener_valid)
+    if (!ctx->kept.listener_valid())
         return fail(ctx, RVB_ERR_STATE, "rvb_relisten: the last trace was made without rvb_keep_paths(ctx, RVB_KEEP_MATERIALS | RVB_KEEP_LISTENER)");
     if (npairs != ctx->trace.npairs())
         return fail(ctx, RVB_ERR_INVALID, "rvb_relisten: " + std::to_string(npairs) + " microphone(s) for a kept trace of " + std::to_string(ctx->trace.npairs()) + " pair(s)");
@@ -92,9 +98,9 @@ int rvb_relisten(rvb_ctx * ctx, const float * mics, uint64_t npairs)
     ctx->end_timing();
     RVB_HIP(fail, ctx, hipGetLastError());
     if ((rc = launch_images_beside(ctx, a)) != RVB_OK) return rc;
-    if ((rc = launch_shadow_behind_images(ctx, a, kept.shaded_source, true)) != RVB_OK) return rc;
+    if ((rc = launch_shadow_behind_images(ctx, a, kept.shaded_source(), true)) != RVB_OK) return rc;
     // the kept trace is now that of the new microphone(s): later rvb_reshade, rvb_reshade_grad and rvb_relisten start from here
-    for (int i = 0; i < 3; ++i) kept.args.mic[i] = mics[i];
+    kept.relistened(mics);
     ctx->trace.pairs.mics_host.assign(mics, mics + 3 * npairs);
     return RVB_OK;
 }
@@ -104,18 +110,18 @@ int rvb_reshade(rvb_ctx * ctx, const rvb_surface * surfaces, uint64_t nsurfaces,
     if (!ctx) return RVB_ERR_INVALID;
     if (!air_coefficient) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade: null air coefficient");
     if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade: nothing traced (or the scene or the directions have changed since)");
-    if (!ctx->kept.valid) return fail(ctx, RVB_ERR_STATE, "rvb_reshade: the last trace was made without rvb_keep_paths(ctx, 1)");
-    if (surfaces && nsurfaces != ctx->nsurfaces)
-        return fail(ctx, RVB_ERR_INVALID, "rvb_reshade: " + std::to_string(nsurfaces) + " surfaces for a scene of " + std::to_string(ctx->nsurfaces));
+    if (!ctx->kept.valid()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade: the last trace was made without rvb_keep_paths(ctx, 1)");
+    if (surfaces && nsurfaces != ctx->scene.nsurfaces)
+        return fail(ctx, RVB_ERR_INVALID, "rvb_reshade: " + std::to_string(nsurfaces) + " surfaces for a scene of " + std::to_string(ctx->scene.nsurfaces));
     if (check_source_counts(ctx, "rvb_reshade", ctx->trace.npairs()) != RVB_OK) return RVB_ERR_INVALID;
     RVB_BIND(ctx);
     KeptTrace & kept = ctx->kept;
-    TraceArgs a = for_record_pass(ctx, kept.args);   // the trace's own arguments; surfaces and air are the call's
+    TraceArgs a = for_record_pass(ctx, kept.trace_args());   // the trace's own arguments; surfaces and air are the call's
     if (surfaces) {
         RVB_HIP(fail, ctx, kept.surfaces_stage.upload(kept.dev.surfaces, surfaces, (size_t) nsurfaces * sizeof(rvb_surface), ctx->stream));
         a.scene.surfaces = kept.dev.surfaces.as<const rvb_surface>();
     } else {
-        a.scene.surfaces = ctx->scene.surfaces;
+        a.scene.surfaces = ctx->scene.dev.surfaces;
     }
     for (int i = 0; i < 8; ++i) a.air[i] = air_coefficient[i];
     RVB_HIP(fail, ctx, ctx->source.upload(ctx->stream));
@@ -144,7 +150,7 @@ int rvb_reshade_grad(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t 
     if (nbins == 0 || nbins >= (1ull << 32)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: no bins (or more than 32-bit bin numbers reach)");
     if (!std::isfinite(predelay) || !std::isfinite(sample_rate)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: predelay or sample rate is not finite");
     if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: nothing traced (or the scene or the directions have changed since)");
-    if (!ctx->kept.valid) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: the last trace was made without rvb_keep_paths(ctx, 1)");
+    if (!ctx->kept.valid()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: the last trace was made without rvb_keep_paths(ctx, 1)");
     if (!ctx->ir.configured()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: no IR configuration (rvb_ir_configure_speakers after the trace or re-shade)");
     if (ctx->ir.model.hrtf) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: the HRTF model is configured; this version takes the speaker model only");
     if (ctx->ir.which() != RVB_IR_DIFFUSE) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: configured with image sources; this version takes which == RVB_IR_DIFFUSE only");
@@ -152,13 +158,13 @@ int rvb_reshade_grad(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t 
         return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: " + std::to_string(ctx->ir.model.nchannels) + " speaker channels configured; this version takes 1 to 8");
     if (ctx->trace.nreflections() > RVB_RESHADE_GRAD_MAX_REFLECTIONS)
         return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad: more than " RVB_STR(RVB_RESHADE_GRAD_MAX_REFLECTIONS) " reflections");
-    if (ctx->nsurfaces >= (1ull << 27)) return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad: too many surfaces");
+    if (ctx->scene.nsurfaces >= (1ull << 27)) return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad: too many surfaces");
     RVB_BIND(ctx);
     KeptTrace & kept = ctx->kept;
     const TraceArgs a = for_record_pass(ctx, kept.shaded_args());
     const uint32_t nchannels = ctx->ir.model.nchannels;
-    const uint64_t entries = ctx->nsurfaces * 16 + 8;
-    const uint32_t blocks = rvb_reshade_grad_blocks(ctx->nrays, ctx->nsurfaces);
+    const uint64_t entries = ctx->scene.nsurfaces * 16 + 8;
+    const uint32_t blocks = rvb_reshade_grad_blocks(ctx->nrays, ctx->scene.nsurfaces);
     // the weights in the accumulation image's layout go where that image goes; the result (floats), then the partial tables (doubles)
     const size_t out_bytes = (entries * sizeof(float) + 15) & ~(size_t) 15;
     RVB_HIP(fail, ctx, ctx->ir.acc.ensure((size_t) nbins * nchannels * 8 * sizeof(float)));
@@ -174,16 +180,10 @@ int rvb_reshade_grad(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t 
     rvb_launch_reshade_grad(a, kept.dev.paths.as<const float4>(), ctx->ir.model, g, partials, blocks, ctx->stream);
     ctx->end_timing();
     ctx->begin_timing("reshade_grad_reduce_kernel");
-    rvb_launch_reshade_grad_reduce(partials, blocks, ctx->nsurfaces, d_out, ctx->stream);
+    rvb_launch_reshade_grad_reduce(partials, blocks, ctx->scene.nsurfaces, d_out, ctx->stream);
     ctx->end_timing();
     RVB_HIP(fail, ctx, hipGetLastError());
-    RVB_HIP(fail, ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<float> host(entries);
-    const int rc = rvb_copy_to_host(ctx, host.data(), d_out, entries * sizeof(float));
-    if (rc != RVB_OK) return rc;
-    std::memcpy(grad_surfaces, host.data(), (size_t) ctx->nsurfaces * sizeof(rvb_surface));
-    if (grad_air) std::memcpy(grad_air, host.data() + ctx->nsurfaces * 16, 8 * sizeof(float));
-    return RVB_OK;
+    return download_surface_gradient(ctx, d_out, grad_surfaces, grad_air);
 }
 
 int rvb_reshade_grad_map(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins, const void * d_weights, void * d_map, uint64_t ntriangles)
@@ -193,10 +193,10 @@ int rvb_reshade_grad_map(rvb_ctx * ctx, float predelay, float sample_rate, uint6
     if (nbins == 0 || nbins >= (1ull << 32)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_map: no bins (or more than 32-bit bin numbers reach)");
     if (!std::isfinite(predelay) || !std::isfinite(sample_rate)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_map: predelay or sample rate is not finite");
     // (without a scene there is no count to hold against: nothing is traced then, the next refusal)
-    if (ctx->have_scene && ntriangles != ctx->ntriangles)
-        return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_map: a map of " + std::to_string(ntriangles) + " triangles for a scene of " + std::to_string(ctx->ntriangles));
+    if (ctx->scene.have() && ntriangles != ctx->scene.ntriangles)
+        return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_map: a map of " + std::to_string(ntriangles) + " triangles for a scene of " + std::to_string(ctx->scene.ntriangles));
     if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: nothing traced (or the scene or the directions have changed since)");
-    if (!ctx->kept.valid || !ctx->kept.listener_valid)
+    if (!ctx->kept.listener_valid())
         return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: the last trace was made without rvb_keep_paths(ctx, RVB_KEEP_MATERIALS | RVB_KEEP_LISTENER): "
                                         "a record's triangle is in its listener record");
     if (!ctx->ir.configured()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_map: no IR configuration (rvb_ir_configure_speakers after the trace or re-shade)");

@@ -61,7 +61,7 @@ struct TracePlan {
 int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint64_t npairs, uint64_t nreflections,
                   const float air_coefficient[8], uint64_t ray_offset, uint64_t rays_in_flight, TracePlan & plan)
 {
-    if (!ctx->have_scene) return fail(ctx, RVB_ERR_STATE, "rvb_trace: rvb_set_scene has not been called");
+    if (!ctx->scene.have()) return fail(ctx, RVB_ERR_STATE, "rvb_trace: rvb_set_scene has not been called");
     if (!ctx->directions && ctx->nrays) return fail(ctx, RVB_ERR_STATE, "rvb_trace: no directions");
     if (nreflections >= (1ull << 31) || ctx->nrays * npairs * 9 >= (1ull << 32))
         return fail(ctx, RVB_ERR_CAPACITY, "rvb_trace: too many reflections or rays for one context");
@@ -71,16 +71,11 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     ctx->void_trace();                                // (until trace_finish: a failure below must not leave the last trace's results half reset)
     TraceStage & trace = ctx->trace;
     trace.begin();
-    ctx->kept.void_all();
+    KeptTrace & kept = ctx->kept;
+    kept.trace_begins();
     const uint64_t nrays = ctx->nrays * npairs;       // rays of this launch
     RVB_HIP(fail, ctx, trace.ensure_launch(nrays, npairs, nreflections, ctx->stream));
-    KeptTrace & kept = ctx->kept;
-    if (kept.keep_paths) {                            // rvb_keep_paths: what rvb_reshade needs beside the results
-        RVB_HIP(fail, ctx, kept.dev.paths.ensure((size_t) nrays * nreflections * sizeof(float4)));
-        RVB_HIP(fail, ctx, kept.dev.image_dist.ensure(((size_t) nrays * 9 + npairs) * sizeof(float)));
-        if (kept.keep_listener)                       // RVB_KEEP_LISTENER: and what rvb_relisten needs beside those
-            RVB_HIP(fail, ctx, kept.dev.listen.ensure((size_t) nrays * nreflections * sizeof(uint2)));
-    }
+    RVB_HIP(fail, ctx, kept.ensure_launch(nrays, npairs, nreflections));       // rvb_keep_paths: what rvb_reshade and rvb_relisten need beside the results
 
     // reference rayverb.cpp:600-616: outputs start zero-filled — path_kernel writes every slot of the
     // impulse array itself (work record or zeros), so no 819 MB fill is needed here
@@ -92,22 +87,22 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     RVB_HIP(fail, ctx, hipMemsetAsync(&small->trace_range[0], 0xFF, 4, ctx->stream));
 
     TraceArgs & a = plan.a;
-    a.scene = ctx->scene;
+    a.scene = ctx->scene.dev;
     a.directions = ctx->directions;
     trace.point(a, nrays, npairs);
     a.npairs = (uint32_t) npairs;
     a.rays_per_pair = (uint32_t) ctx->nrays;
-    a.image_dist = kept.keep_paths ? kept.dev.image_dist.as<float>() : nullptr;
+    a.image_dist = kept.image_dist_for_launch();
     RVB_HIP(fail, ctx, trace.pairs.stage(mics, sources, npairs, ctx->stream, a));       // several pairs per launch: four of them point to arrays per pair
     // record bucketing for coherent shadow rays (RVB_SHADOW_SORT=0 turns it off)
     static const bool sort_records = !(getenv("RVB_SHADOW_SORT") && getenv("RVB_SHADOW_SORT")[0] == '0');
     const uint64_t nrecords = nrays * nreflections;
     a.sort_keys = nullptr; a.sort_keys16 = nullptr; a.key_shift = 0; a.sort_order = nullptr;
     int key_bits = 1;
-    while (key_bits < 32 && (1ull << key_bits) < ctx->scene.ntris) ++key_bits;
+    while (key_bits < 32 && (1ull << key_bits) < ctx->scene.dev.ntris) ++key_bits;
     // The grouping only has to bring neighbouring triangles together: the top 16 bits of the leaf position are two
     // onesweep passes instead of three (C2, 17 key bits: grouping 0.66 -> 0.51 ms beside image_kernel, shadow_kernel +0.02 ms).
-    if (sort_records && nrecords && nrecords < (1ull << 32) && ctx->scene.ntris) {
+    if (sort_records && nrecords && nrecords < (1ull << 32) && ctx->scene.dev.ntris) {
         RVB_HIP(fail, ctx, trace.sort_keys.ensure(nrecords * 4));
         RVB_HIP(fail, ctx, trace.sort_scratch.ensure(nrecords * 4));
         RVB_HIP(fail, ctx, trace.sort_order.ensure(nrecords * 4));
@@ -127,8 +122,8 @@ int trace_prepare(rvb_ctx * ctx, const float * mics, const float * sources, uint
     }
     a.nrays = nrays;
     a.nreflections = (uint32_t) nreflections;
-    a.stack_entries = ctx->stack_need;
-    a.lds_surfaces = rvb_lds_surfaces(ctx->stack_need, ctx->nsurfaces);
+    a.stack_entries = ctx->scene.stack_need;
+    a.lds_surfaces = rvb_lds_surfaces(ctx->scene.stack_need, ctx->scene.nsurfaces);
     // (rays_in_flight: what a group launch carries in all; 0 = this trace alone, times the caller's hint)
     a.path_lanes = ctx->path_lanes ? ctx->path_lanes : (rays_in_flight ? rvb_path_lanes_for(rays_in_flight, 1) : rvb_path_lanes_for(nrays, ctx->concurrent_traces));
     a.ray_offset = ray_offset;
@@ -166,10 +161,10 @@ int trace_finish(rvb_ctx * ctx, TracePlan & plan, const float * mics)
     // reads, waits for both.
     int rc = launch_images_beside(ctx, a);
     if (rc != RVB_OK) return rc;
-    if (ctx->kept.keep_paths) {
+    if (ctx->kept.keeping()) {
         // rvb_keep_paths: what the shadow kernel is about to overwrite, while the image kernels read the same records on the side stream
         ctx->begin_timing("path_keep_kernel");
-        rvb_launch_path_keep(a, ctx->kept.dev.paths.as<float4>(), ctx->kept.keep_listener ? ctx->kept.dev.listen.as<uint2>() : nullptr, ctx->stream);
+        rvb_launch_path_keep(a, ctx->kept.dev.paths.as<float4>(), ctx->kept.listen_for_launch(), ctx->stream);
         ctx->end_timing();
         RVB_HIP(fail, ctx, hipGetLastError());
     }

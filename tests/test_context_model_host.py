@@ -111,10 +111,10 @@ class LedgerContext:
             self.fail(capi.ERR_STATE, "rvb_trace: no directions")
         self.void_trace("trace_prepare:traced")                           # (no forget site: trace_finish sets it again)
         if not self.forgot("trace_finish:kept"):
-            self.kept_valid = self.listener_valid = False                 # kept.void_all()
+            self.kept_valid = self.listener_valid = False                 # KeptState::trace_begins
         self.dev = Rec(self.scene, "own", self._air(air), tuple(self._index("mics", m) for m in mics),
                        tuple(self._index("sources", s) for s in sources), self.nrays, int(nreflections), int(ray_offset), self.pattern)
-        if not self.forgot("trace_finish:kept"):                          # kept.take()
+        if not self.forgot("trace_finish:kept"):                          # kept.take(): KeptState::trace_taken
             self.kept_valid, self.listener_valid = self.keep, self.keep and self.keep_listener
             if self.kept_valid:
                 self.kept_rec = self.dev
