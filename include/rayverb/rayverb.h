@@ -167,10 +167,6 @@ public:
 
     // [channel][azimuth][elevation]; override to supply another table (reference tests/hrtf_tests.h:28).
     virtual const std::array<std::array<std::array<cl_float8, 180>, 360>, 2> & getHrtfData() const;
-
-private:
-    std::vector<AttenuatedImpulse> attenuate(const cl_float3 & mic_pos, unsigned long channel, const cl_float3 & facing,
-                                             const cl_float3 & up, const std::vector<Impulse> & impulses);
 };
 
 class SpeakerAttenuator : public Attenuator {
@@ -178,9 +174,6 @@ public:
     SpeakerAttenuator();
     // Outer vector: one entry per speaker.
     std::vector<std::vector<AttenuatedImpulse>> attenuate(const RaytracerResults & results, const std::vector<Speaker> & speakers);
-
-private:
-    std::vector<AttenuatedImpulse> attenuate(const cl_float3 & mic_pos, const Speaker & speaker, const std::vector<Impulse> & impulses);
 };
 
 // Read a file and parse it as JSON into `doc`; parse errors are reported through the document

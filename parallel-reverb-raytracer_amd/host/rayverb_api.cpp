@@ -3,14 +3,13 @@
 // the CPU except the reference's own host-side steps (bounds warnings, vector plumbing).
 #include "../../include/rayverb/rayverb.h"
 #include "../../include/rvb_capi.h"
+#include "resident_cache.h"
 #include "scene_loader.h"
 
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
-#include <list>
-#include <map>
 #include <mutex>
 #include <thread>
 
@@ -108,132 +107,28 @@ void parallel_ranges(size_t n, F f)
     for (std::thread & t : pool) t.join();
 }
 
-// ---- device copies of vectors this library handed out (OPT-IN: RVB_API_RESIDENT=1) ---------------------------------------
-// The reference's API moves every stage's result through std::vector and its implementation uploads whatever vector it is handed,
-// stage by stage (rayverb.cpp:863-875).  That is what this mirror does by default: every stage uploads the vector it receives.
-//
-// With RVB_API_RESIDENT=1 in the environment the CALLER PROMISES not to edit a vector this library returned between the
-// stages of the sequence Raytracer::getAllRaw -> Attenuator::attenuate -> fixPredelay -> flattenImpulses (cmd/main.cpp:241-298
-// does not).  The producer of a vector then remembers where its device copy lives, keyed by the vector's buffer (address,
-// element count), and the next stage uses that copy instead of uploading.  A changed length or address is caught by the key and a
-// sample of the contents (every kSampleStride-th element) is compared as a courtesy, but an in-place edit that misses the sample
-// is NOT seen — checking all of a 0.8 GB vector costs as much host-memory traffic as uploading it, which is why the mechanism
-// is a promise the caller opts into and not the default.
-const size_t kSampleStride = 251;
-const size_t kResidentByteCap = (size_t) 6 << 30;      // owned device copies kept at a time (bytes), oldest dropped first
-
-struct Resident {
-    const void * host = nullptr;      // the vector's buffer
-    size_t count = 0, elem = 0;       // elements, bytes per element
-    void * device = nullptr;          // device copy (of `device_count` leading elements)
-    size_t device_count = 0;
-    bool owned = false;               // allocated for this entry (freed with it) / borrowed from a tracing context
-    const rvb_ctx * owner = nullptr;  // borrowed: the context whose trace buffer this is (copies of a Raytracer share it) ...
-    uint64_t generation = 0;          // ... and that context's trace count when the entry was made: a later trace voids the entry
-    std::vector<unsigned char> sample;
-};
-
-std::mutex g_resident_mutex;
-std::list<Resident> g_resident;
-std::map<const rvb_ctx *, uint64_t> g_trace_generation;       // traces started per context (guarded by g_resident_mutex)
-
-bool resident_enabled()
+// the one ResidentCache of the process (resident_cache.h: the mechanism, the caller's promise and why it is opt-in).  Never
+// destroyed: whatever it still holds at exit is abandoned without a device call, as the shared context goes away beside it.
+ResidentCache & resident()
 {
-    static const bool on = std::getenv("RVB_API_RESIDENT") && std::getenv("RVB_API_RESIDENT")[0] == '1';
-    return on;
+    static ResidentCache * const cache = [] {
+        const char * e = std::getenv("RVB_API_RESIDENT");
+        return new ResidentCache(e && e[0] == '1', (size_t) 6 << 30, 251);
+    }();
+    return *cache;
 }
 
-std::vector<unsigned char> take_sample(const void * host, size_t count, size_t elem)
+// a device allocation of the shared context under an owner: freed when the last holder (the cache, a reader) lets go
+std::shared_ptr<void> owned_device(void * d_ptr)
 {
-    std::vector<unsigned char> s;
-    s.reserve((count / kSampleStride + 2) * elem);
-    const unsigned char * p = static_cast<const unsigned char *>(host);
-    for (size_t i = 0; i < count; i += kSampleStride) s.insert(s.end(), p + i * elem, p + (i + 1) * elem);
-    if (count) s.insert(s.end(), p + (count - 1) * elem, p + count * elem);
-    return s;
-}
-
-void release_entry(Resident & r)
-{
-    if (r.owned && r.device) (void) rvb_device_free(shared_context(), r.device);
-    r.device = nullptr;
-}
-
-// a context is about to trace (or goes away): its trace buffer no longer holds what the borrowed entries describe
-void resident_new_trace(const rvb_ctx * owner)
-{
-    std::lock_guard<std::mutex> lock(g_resident_mutex);
-    ++g_trace_generation[owner];
-    for (auto it = g_resident.begin(); it != g_resident.end();)
-        if (!it->owned && it->owner == owner) it = g_resident.erase(it); else ++it;
-}
-
-uint64_t resident_generation(const rvb_ctx * owner)
-{
-    std::lock_guard<std::mutex> lock(g_resident_mutex);
-    return g_trace_generation[owner];
-}
-
-// drops owned device copies, oldest first, until at most `keep_bytes` of them remain; returns whether anything was freed
-bool resident_evict(size_t keep_bytes)
-{
-    std::lock_guard<std::mutex> lock(g_resident_mutex);
-    size_t held = 0;
-    for (const Resident & r : g_resident) if (r.owned) held += r.device_count * r.elem;
-    bool freed = false;
-    while (held > keep_bytes && !g_resident.empty()) {
-        auto it = g_resident.end();
-        for (auto j = g_resident.begin(); j != g_resident.end(); ++j) if (j->owned) it = j;      // the last owned entry = the oldest
-        if (it == g_resident.end()) break;
-        held -= it->device_count * it->elem;
-        release_entry(*it);
-        g_resident.erase(it);
-        freed = true;
-    }
-    return freed;
-}
-
-void resident_remember(Resident r)
-{
-    if (!resident_enabled()) { release_entry(r); return; }
-    r.sample = take_sample(r.host, r.count, r.elem);
-    {
-        std::lock_guard<std::mutex> lock(g_resident_mutex);
-        for (auto it = g_resident.begin(); it != g_resident.end();)      // a buffer address names one vector at a time
-            if (it->host == r.host) { release_entry(*it); it = g_resident.erase(it); } else ++it;
-        g_resident.push_front(std::move(r));
-    }
-    (void) resident_evict(kResidentByteCap);
-}
-
-// the entry of (host, count) if the vector still reads as it did; stale entries are dropped
-bool resident_find(const void * host, size_t count, size_t elem, Resident & out)
-{
-    if (!resident_enabled() || !host) return false;
-    std::lock_guard<std::mutex> lock(g_resident_mutex);
-    for (auto it = g_resident.begin(); it != g_resident.end(); ++it) {
-        if (it->host != host) continue;
-        const bool current = it->owned || g_trace_generation[it->owner] == it->generation;
-        if (current && it->count == count && it->elem == elem && it->sample == take_sample(host, count, elem)) { out = *it; out.sample.clear(); return true; }
-        release_entry(*it);
-        g_resident.erase(it);
-        return false;
-    }
-    return false;
-}
-
-void resident_resample(const void * host, size_t count, size_t elem)
-{
-    std::lock_guard<std::mutex> lock(g_resident_mutex);
-    for (Resident & r : g_resident)
-        if (r.host == host && r.count == count && r.elem == elem) r.sample = take_sample(host, count, elem);
+    return std::shared_ptr<void>(d_ptr, [](void * p) { (void) rvb_device_free(shared_context(), p); });
 }
 
 // rvb_device_alloc that gives the resident cache's device copies back before it reports a failure
 int device_alloc_evicting(rvb_ctx * ctx, uint64_t bytes, void ** d_ptr)
 {
     int rc = rvb_device_alloc(ctx, bytes, d_ptr);
-    if (rc != RVB_OK && resident_evict(0))
+    if (rc != RVB_OK && resident().evict(0))
         rc = rvb_device_alloc(ctx, bytes, d_ptr);
     return rc;
 }
@@ -250,11 +145,7 @@ void throw_on(int rc, rvb_ctx * ctx, const char * where)
 
 ContextProvider::ContextProvider() : ctx_(make_context()) {}
 
-void ContextProvider::check(int rc, const char * where) const
-{
-    if (rc != RVB_OK)
-        throw cl::Error(rc, (std::string(where) + ": " + rvb_last_error(ctx_.get())).c_str());
-}
+void ContextProvider::check(int rc, const char * where) const { throw_on(rc, ctx_.get(), where); }
 
 void Raytracer::check_multi(int rc, const char * where) const
 {
@@ -283,19 +174,16 @@ std::vector<std::vector<float>> flattenImpulses(const std::vector<AttenuatedImpu
     rvb_ctx * ctx = shared_context();
     uint64_t nbins = 0;
     std::vector<float> flat;
-    Resident r;
-    if (resident_find(impulse.data(), impulse.size(), sizeof(AttenuatedImpulse), r) && r.device_count == impulse.size()) {
-        // the attenuator's device copy (kept in step by fixPredelay): no upload
-        throw_on(rvb_flatten_device(ctx, r.device, impulse.size(), samplerate, nullptr, 0, &nbins), ctx, "rvb_flatten_device");
-        flat.resize(8 * nbins);
-        // (the size query left the keys on the device; the second call redoes only them, not an upload)
-        throw_on(rvb_flatten_device(ctx, r.device, impulse.size(), samplerate, flat.data(), nbins, &nbins), ctx, "rvb_flatten_device");
-    } else {
-        const rvb_attenuated_impulse * in = reinterpret_cast<const rvb_attenuated_impulse *>(impulse.data());
-        throw_on(rvb_flatten(ctx, in, impulse.size(), samplerate, nullptr, 0, &nbins), ctx, "rvb_flatten");      // uploads once ...
-        flat.resize(8 * nbins);
-        throw_on(rvb_flatten(ctx, in, impulse.size(), samplerate, flat.data(), nbins, &nbins), ctx, "rvb_flatten");   // ... and fills from the device copy
-    }
+    const ResidentCache::Found r = resident().find(impulse.data(), impulse.size(), sizeof(AttenuatedImpulse));
+    const bool have = r && r.device_count == impulse.size();      // the attenuator's device copy (kept in step by fixPredelay): no upload
+    const rvb_attenuated_impulse * in = reinterpret_cast<const rvb_attenuated_impulse *>(impulse.data());
+    auto flatten = [&](float * out, uint64_t capacity) {
+        if (have) throw_on(rvb_flatten_device(ctx, r.device, impulse.size(), samplerate, out, capacity, &nbins), ctx, "rvb_flatten_device");
+        else throw_on(rvb_flatten(ctx, in, impulse.size(), samplerate, out, capacity, &nbins), ctx, "rvb_flatten");
+    };
+    flatten(nullptr, 0);                       // the size query: uploads once where nothing is resident, leaves array and keys on the device ...
+    flat.resize(8 * nbins);
+    flatten(flat.data(), nbins);               // ... and the fill works from them, not from another upload
     std::vector<std::vector<float>> flattened(sizeof(VolumeType) / sizeof(float));
     for (size_t b = 0; b < flattened.size(); ++b)
         flattened[b].assign(flat.begin() + (long) (b * nbins), flat.begin() + (long) ((b + 1) * nbins));
@@ -313,27 +201,17 @@ std::vector<std::vector<std::vector<float>>> flattenImpulses(const std::vector<s
 // reference rayverb.h:49-74: the smallest non-zero time, 0 if there is none (min is order-independent: threads may split the range)
 float findPredelay(const std::vector<AttenuatedImpulse> & ret)
 {
-    const size_t n = ret.size();
-    const size_t threads = n < (1u << 16) ? 1 : host_threads();
-    std::vector<float> part(threads, 0.0f);
-    const size_t per = threads ? (n + threads - 1) / threads : 0;
-    std::vector<std::thread> pool;
-    auto work = [&](size_t t) {
-        float a = 0.0f;
-        for (size_t i = t * per; i < std::min(n, (t + 1) * per); ++i) {
-            const float pd = ret[i].time;
-            if (pd != 0.0f && (a == 0.0f || pd < a)) a = pd;
-        }
-        part[t] = a;
-    };
-    if (threads <= 1) { if (threads) work(0); }
-    else {
-        for (size_t t = 0; t < threads; ++t) pool.emplace_back(work, t);
-        for (std::thread & t : pool) t.join();
-    }
+    std::mutex m;
     float a = 0.0f;
-    for (float pd : part)
-        if (pd != 0.0f && (a == 0.0f || pd < a)) a = pd;
+    parallel_ranges(ret.size(), [&](size_t lo, size_t hi) {
+        float part = 0.0f;                     // one partial per range
+        for (size_t i = lo; i < hi; ++i) {
+            const float pd = ret[i].time;
+            if (pd != 0.0f && (part == 0.0f || pd < part)) part = pd;
+        }
+        std::lock_guard<std::mutex> lock(m);
+        if (part != 0.0f && (a == 0.0f || part < a)) a = part;
+    });
     return a;
 }
 
@@ -351,8 +229,8 @@ float findPredelay(const std::vector<std::vector<AttenuatedImpulse>> & ret)
 void fixPredelay(std::vector<AttenuatedImpulse> & ret, float seconds)
 {
     // the device copy takes part only if the vector still reads as it did when the copy was made (sample comparison)
-    Resident r;
-    const bool have = resident_find(ret.data(), ret.size(), sizeof(AttenuatedImpulse), r) && r.owned && r.device_count == ret.size();
+    const ResidentCache::Found r = resident().find(ret.data(), ret.size(), sizeof(AttenuatedImpulse));
+    const bool have = r && r.owned && r.device_count == ret.size();
     AttenuatedImpulse * a = ret.data();
     parallel_ranges(ret.size(), [a, seconds](size_t lo, size_t hi) {
         for (size_t i = lo; i < hi; ++i) a[i].time = a[i].time > seconds ? a[i].time - seconds : 0;
@@ -360,7 +238,7 @@ void fixPredelay(std::vector<AttenuatedImpulse> & ret, float seconds)
     if (!have) return;
     rvb_ctx * ctx = shared_context();
     throw_on(rvb_fix_predelay_device(ctx, r.device, r.device_count, seconds), ctx, "rvb_fix_predelay_device");
-    resident_resample(ret.data(), ret.size(), sizeof(AttenuatedImpulse));
+    resident().resample(ret.data(), ret.size(), sizeof(AttenuatedImpulse));
 }
 
 void fixPredelay(std::vector<std::vector<AttenuatedImpulse>> & ret, float seconds)
@@ -450,13 +328,13 @@ Raytracer::~Raytracer()
 {
     // entries that borrow the context's trace buffer: void once the context may go away (copies of this object share the
     // context; treating every destruction as the end of the buffer only costs an upload)
-    resident_new_trace(context());
+    resident().owner_traces(context());
 }
 
 void Raytracer::raytrace(const cl_float3 & micpos, const cl_float3 & source, const std::vector<cl_float3> & directions, bool verbose)
 {
     storedMicpos = micpos;
-    resident_new_trace(context());             // the trace buffer is about to be overwritten (copies of this object share it)
+    resident().owner_traces(context());        // the trace buffer is about to be overwritten (copies of this object share it)
 
     // reference rayverb.cpp:547-583: warn when mic or source lie outside the model's bounding box
     const bool micinside = inside(bounds, micpos);
@@ -515,16 +393,12 @@ void Raytracer::fetchDiffuse(std::vector<Impulse> & out)
         check_multi(rvb_multi_get_diffuse(multi_.get(), reinterpret_cast<rvb_impulse *>(out.data())), "rvb_multi_get_diffuse");
         return;
     }
+    const uint64_t stamp = resident().trace_count(context());       // read before the buffer is: a trace meanwhile voids the entry
     check(rvb_get_diffuse(context(), reinterpret_cast<rvb_impulse *>(out.data())), "rvb_get_diffuse");
     const void * d = nullptr;
     uint64_t count = 0;
-    if (n && rvb_diffuse_device(context(), &d, &count) == RVB_OK && count == n) {
-        Resident r;
-        r.host = out.data(); r.count = out.size(); r.elem = sizeof(Impulse);
-        r.device = const_cast<void *>(d); r.device_count = n; r.owned = false; r.owner = context();
-        r.generation = resident_generation(context());
-        resident_remember(r);
-    }
+    if (n && rvb_diffuse_device(context(), &d, &count) == RVB_OK && count == n)
+        resident().remember_borrowed(out.data(), out.size(), sizeof(Impulse), const_cast<void *>(d), n, context(), stamp);
 }
 
 std::vector<Impulse> Raytracer::mergedImages(bool removeDirect)
@@ -632,10 +506,19 @@ struct DeviceImpulses {
     void * tail = nullptr;            // the rest (uploaded; owned)
     size_t ntail = 0;
     void * upload = nullptr;          // owned storage behind `head` when nothing was resident
+    std::shared_ptr<void> lease;      // the reader's reference to a resident `head`
     ~DeviceImpulses()
     {
         if (tail) (void) rvb_device_free(ctx, tail);
         if (upload) (void) rvb_device_free(ctx, upload);
+    }
+    // launch(input, count, output) on the head, then on the tail behind the head's results
+    template <class Launch>
+    int launch_parts(void * d_out, Launch launch) const
+    {
+        int rc = launch(head, nhead, d_out);
+        if (rc == RVB_OK && ntail) rc = launch(tail, ntail, static_cast<char *>(d_out) + nhead * sizeof(AttenuatedImpulse));
+        return rc;
     }
 };
 
@@ -643,10 +526,11 @@ void stage_impulses(const std::vector<Impulse> & impulses, DeviceImpulses & dev)
 {
     rvb_ctx * ctx = dev.ctx;
     const size_t n = impulses.size();
-    Resident r;
-    if (resident_find(impulses.data(), n, sizeof(Impulse), r) && !r.owned && r.device_count <= n) {
+    const ResidentCache::Found r = resident().find(impulses.data(), n, sizeof(Impulse));
+    if (r && !r.owned && r.device_count <= n) {
         // getRawDiffuse / getAllRaw: the diffuse impulses are still in the tracer's buffer; the few image impulses that
         // getAllRaw put behind them come from the host vector
+        dev.lease = r.lease;
         dev.head = r.device;
         dev.nhead = r.device_count;
         dev.ntail = n - r.device_count;
@@ -665,19 +549,19 @@ void stage_impulses(const std::vector<Impulse> & impulses, DeviceImpulses & dev)
 
 // one channel: kernel on the staged input, result downloaded into a fresh vector whose device copy is remembered
 template <class Launch>
-std::vector<AttenuatedImpulse> attenuate_channel(rvb_ctx * ctx, size_t n, Launch launch)
+std::vector<AttenuatedImpulse> attenuate_channel(const DeviceImpulses & dev, Launch launch)
 {
+    rvb_ctx * ctx = dev.ctx;
+    const size_t n = dev.nhead + dev.ntail;
     std::vector<AttenuatedImpulse> ret = uninitialized_vector<AttenuatedImpulse>(n);
     if (n == 0) return ret;
     void * d_out = nullptr;
     throw_on(device_alloc_evicting(ctx, n * sizeof(AttenuatedImpulse), &d_out), ctx, "rvb_device_alloc");
-    int rc = launch(d_out);
+    std::shared_ptr<void> out = owned_device(d_out);          // freed by whoever holds it last: this frame on an error or with the cache off
+    int rc = dev.launch_parts(d_out, launch);
     if (rc == RVB_OK) rc = rvb_copy_to_host(ctx, ret.data(), d_out, n * sizeof(AttenuatedImpulse));
-    if (rc != RVB_OK) { (void) rvb_device_free(ctx, d_out); throw_on(rc, ctx, "attenuate"); }
-    Resident r;
-    r.host = ret.data(); r.count = n; r.elem = sizeof(AttenuatedImpulse);
-    r.device = d_out; r.device_count = n; r.owned = true;
-    resident_remember(r);                       // (frees d_out itself when residency is off)
+    throw_on(rc, ctx, "attenuate");
+    resident().remember_owned(ret.data(), n, sizeof(AttenuatedImpulse), std::move(out));
     return ret;
 }
 }  // namespace
@@ -693,27 +577,11 @@ std::vector<std::vector<AttenuatedImpulse>> HrtfAttenuator::attenuate(const Rayt
         // [360][180] of cl_float8 is contiguous: exactly the flattened table of rayverb.cpp:774-780
         const float * table = reinterpret_cast<const float *>(getHrtfData()[ch].data());
         const cl_float3 mic = results.mic;
-        const size_t n = results.impulses.size();
-        attenuated[ch] = attenuate_channel(dev.ctx, n, [&](void * d_out) {
-            int rc = rvb_attenuate_hrtf_device(dev.ctx, mic.s, dev.head, dev.nhead, table, facing.s, up.s, ch, d_out);
-            if (rc == RVB_OK && dev.ntail)
-                rc = rvb_attenuate_hrtf_device(dev.ctx, mic.s, dev.tail, dev.ntail, table, facing.s, up.s, ch,
-                                               static_cast<char *>(d_out) + dev.nhead * sizeof(AttenuatedImpulse));
-            return rc;
+        attenuated[ch] = attenuate_channel(dev, [&](const void * in, size_t count, void * d_out) {
+            return rvb_attenuate_hrtf_device(dev.ctx, mic.s, in, count, table, facing.s, up.s, ch, d_out);
         });
     }
     return attenuated;
-}
-
-std::vector<AttenuatedImpulse> HrtfAttenuator::attenuate(const cl_float3 & mic_pos, unsigned long channel, const cl_float3 & facing,
-                                                         const cl_float3 & up, const std::vector<Impulse> & impulses)
-{
-    const float * table = reinterpret_cast<const float *>(getHrtfData()[channel].data());
-    std::vector<AttenuatedImpulse> ret(impulses.size());
-    check(rvb_attenuate_hrtf(context(), mic_pos.s, reinterpret_cast<const rvb_impulse *>(impulses.data()), impulses.size(), table,
-                             facing.s, up.s, channel, reinterpret_cast<rvb_attenuated_impulse *>(ret.data())),
-          "rvb_attenuate_hrtf");
-    return ret;
 }
 
 SpeakerAttenuator::SpeakerAttenuator() {}
@@ -724,25 +592,12 @@ std::vector<std::vector<AttenuatedImpulse>> SpeakerAttenuator::attenuate(const R
     DeviceImpulses dev(shared_context());
     stage_impulses(results.impulses, dev);
     std::vector<std::vector<AttenuatedImpulse>> attenuated(speakers.size());
-    const size_t n = results.impulses.size();
     for (size_t i = 0; i < speakers.size(); ++i) {
         const cl_float3 mic = results.mic;
         const rvb_speaker * sp = reinterpret_cast<const rvb_speaker *>(&speakers[i]);
-        attenuated[i] = attenuate_channel(dev.ctx, n, [&](void * d_out) {
-            int rc = rvb_attenuate_speaker_device(dev.ctx, mic.s, dev.head, dev.nhead, sp, d_out);
-            if (rc == RVB_OK && dev.ntail)
-                rc = rvb_attenuate_speaker_device(dev.ctx, mic.s, dev.tail, dev.ntail, sp, static_cast<char *>(d_out) + dev.nhead * sizeof(AttenuatedImpulse));
-            return rc;
+        attenuated[i] = attenuate_channel(dev, [&](const void * in, size_t count, void * d_out) {
+            return rvb_attenuate_speaker_device(dev.ctx, mic.s, in, count, sp, d_out);
         });
     }
     return attenuated;
-}
-
-std::vector<AttenuatedImpulse> SpeakerAttenuator::attenuate(const cl_float3 & mic_pos, const Speaker & speaker, const std::vector<Impulse> & impulses)
-{
-    std::vector<AttenuatedImpulse> ret(impulses.size());
-    check(rvb_attenuate_speaker(context(), mic_pos.s, reinterpret_cast<const rvb_impulse *>(impulses.data()), impulses.size(),
-                                reinterpret_cast<const rvb_speaker *>(&speaker), reinterpret_cast<rvb_attenuated_impulse *>(ret.data())),
-          "rvb_attenuate_speaker");
-    return ret;
 }
