@@ -149,6 +149,18 @@ _LIVE_SIGNATURES = {
     "rvb_ir_exact_list_info": (_i, _vp, _vp, _vp, _vp),
 }
 LIVE_SYMBOLS = list(_LIVE_SIGNATURES)
+# ... and of include/rvb_capi_window.h, the echo finder (tests/test_window_header_host.py), with its constants and structures
+_WINDOW_SIGNATURES = {
+    "rvb_window_select": (_i, _vp, _vp, _u64, _f, _f, _vp, _u64, _vp, _vp, _vp),
+    "rvb_window_paths": (_i, _vp, _f, _f, _vp, _u64, _u64, _vp, _vp, _vp, _vp),
+}
+WINDOW_SYMBOLS = list(_WINDOW_SIGNATURES)
+WINDOW_TILE = 1024
+WINDOW_MAX_PATHS = 1024
+WINDOW_ENTRY = np.dtype([("record", "<u8"), ("score", "<f4"), ("time", "<f4")])
+WINDOW_PATH = np.dtype([("ray", "<u8"), ("bounce", "<u4"), ("nhits", "<u4"), ("score", "<f4"), ("time", "<f4"), ("pad_", "<f4", (2,)),
+                        ("volume", "<f4", (NUM_BANDS,))])
+WINDOW_HIT = np.dtype([("position", "<f4", (3,)), ("triangle", "<u4")])
 _lib = None
 
 
@@ -174,7 +186,7 @@ def load_library():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _IMAGE_SIGNATURES, _LIVE_SIGNATURES):
+        for table in (_SIGNATURES, _IMAGE_SIGNATURES, _LIVE_SIGNATURES, _WINDOW_SIGNATURES):
             for name, (restype, *argtypes) in table.items():
                 function = getattr(lib, name)
                 function.restype, function.argtypes = restype, argtypes
@@ -661,6 +673,69 @@ class Context(_Handle):
         listed, live, valid = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int(0)
         self._check(self.lib.rvb_ir_exact_list_info(self.handle, ctypes.byref(listed), ctypes.byref(live), ctypes.byref(valid)))
         return listed.value, live.value, bool(valid.value)
+
+    # ---- the echo finder (include/rvb_capi_window.h) ---------------------------------------------------------------
+    @staticmethod
+    def _window_weights(weights):
+        return _f8(np.asarray(weights, dtype=np.float32).reshape(8)) if weights is not None else None
+
+    def _device_block(self, nbytes, fill=None):
+        """A device block of this context's library for a call's results, as a (pointer, free) pair."""
+        p = _vp()
+        self._check(self.lib.rvb_device_alloc(self.handle, max(int(nbytes), 16), ctypes.byref(p)))
+        if fill is not None:
+            self._check(self.lib.rvb_copy_to_device(self.handle, p, _ptr(fill), fill.nbytes))
+        return p, lambda: self.lib.rvb_device_free(self.handle, p)
+
+    def window_select(self, impulses, n=None, t_begin=0.0, t_end=float("inf"), weights=None, max_entries=WINDOW_MAX_PATHS):
+        """(entries, in_window): the strongest records behind the window [t_begin, t_end) of a device array of `n` impulses
+        (rvb_window_select) — a torch CUDA tensor (n defaults to its bytes / 64; the context's stream waits for torch's current stream) or
+        a device address.  entries is a WINDOW_ENTRY array of min(in_window, max_entries) rows by descending score, equal scores by
+        ascending record number; the score is sum_b (weights[b] * volume[b])^2, weights None = ones.  Synchronous."""
+        if hasattr(impulses, "data_ptr"):
+            assert impulses.is_cuda and impulses.is_contiguous()
+            if n is None:
+                n = impulses.numel() * impulses.element_size() // IMPULSE.itemsize
+            self.ir_accumulate_wait_for_torch()
+            impulses = impulses.data_ptr()
+        capacity = min(max(int(max_entries), 0), WINDOW_MAX_PATHS)           # (the library refuses what lies outside; nothing is written then)
+        d_entries, free = self._device_block(capacity * WINDOW_ENTRY.itemsize)
+        try:
+            count, inside = _u64(0), _u64(0)
+            self._check(self.lib.rvb_window_select(self.handle, impulses or None, int(n), t_begin, t_end, self._window_weights(weights), int(max_entries),
+                                                   d_entries, ctypes.byref(count), ctypes.byref(inside)))
+            entries = np.zeros(count.value, dtype=WINDOW_ENTRY)
+            if count.value:
+                self._check(self.lib.rvb_copy_to_host(self.handle, _ptr(entries), d_entries, entries.nbytes))
+        finally:
+            free()
+        return entries, inside.value
+
+    def window_paths(self, t_begin, t_end, weights=None, max_paths=64, max_hits=0):
+        """(paths, hits, in_window): the strongest diffuse paths of the selected pair behind the window [t_begin, t_end), from the records
+        as they stand now (rvb_window_paths).  paths is a WINDOW_PATH array of min(in_window, max_paths) rows; hits a WINDOW_HIT array
+        [rows][max_hits] whose row e holds the first min(paths[e].nhits, max_hits) hits of path e, the rest zero — or None with max_hits
+        0, which needs no kept trace (hits need keep_paths(True, listener=True)).  Synchronous."""
+        capacity = min(max(int(max_paths), 0), WINDOW_MAX_PATHS)
+        d_paths, free_paths = self._device_block(capacity * WINDOW_PATH.itemsize)
+        try:
+            zeros = np.zeros((capacity, int(max_hits)), dtype=WINDOW_HIT) if max_hits else None
+            d_hits, free_hits = self._device_block(zeros.nbytes, zeros) if max_hits else (None, lambda: None)
+            try:
+                count, inside = _u64(0), _u64(0)
+                self._check(self.lib.rvb_window_paths(self.handle, t_begin, t_end, self._window_weights(weights), int(max_paths), int(max_hits),
+                                                      d_paths, d_hits, ctypes.byref(count), ctypes.byref(inside)))
+                paths = np.zeros(count.value, dtype=WINDOW_PATH)
+                hits = np.zeros((count.value, int(max_hits)), dtype=WINDOW_HIT) if max_hits else None
+                if count.value:
+                    self._check(self.lib.rvb_copy_to_host(self.handle, _ptr(paths), d_paths, paths.nbytes))
+                    if max_hits:
+                        self._check(self.lib.rvb_copy_to_host(self.handle, _ptr(hits), d_hits, hits.nbytes))
+            finally:
+                free_hits()
+        finally:
+            free_paths()
+        return paths, hits, inside.value
 
     def export_tensor_to_host(self, tensor, pinned_host_tensor):
         """Enqueues, behind the binning, the copy of a device tensor (the histogram ir_accumulate_tensor filled) into a PINNED host

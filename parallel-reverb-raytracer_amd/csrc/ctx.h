@@ -11,6 +11,7 @@
 //   decay.hip    decay curves, reverberation times and the decay loss on the caller's device arrays
 //   images.hip   include/rvb_capi_images.h: the merged image list made on the device (MergedImages below, over merged_state.h), the
 //                image-source part of the material gradient
+//   window.hip   include/rvb_capi_window.h: the strongest records behind a time window and their paths (window_kernels.hip, over window_select.h)
 // No compute happens in them and nothing falls back to the CPU: every entry point that produces results launches HIP kernels:
 //   the trace         trace_kernels.hip, image_kernels.hip, shadow_kernels.hip, source_kernels.hip
 //   a kept trace      reshade_kernels.hip, reshade_grad_kernels.hip, relisten_kernels.hip (the three over kept_tiles.h),
@@ -432,6 +433,9 @@ struct rvb_ctx {
     // rvb_decay_* (csrc/decay.hip): per-tile sums and carries, per-row windows and results; nothing else lives here, so the decay calls
     // leave the sort buffers, the IR configuration and a prepared exact list alone
     DevBuf decay_scratch;
+    // rvb_window_* (csrc/window.hip): the select's state and tables, the listed entries, a key per record; a block of its own for the
+    // same reason
+    DevBuf window_scratch;
     std::vector<Timing> timings;
     std::vector<Event> event_pool;
     size_t events_used = 0;

@@ -6,6 +6,7 @@
 
 #include "../../include/rvb_capi.h"
 #include "../../include/rvb_capi_live.h"
+#include "../../include/rvb_capi_window.h"
 #include "bvh.h"
 
 struct SceneDev {                       // device pointers of the current scene
@@ -327,3 +328,20 @@ hipError_t rvb_radix_sort_pairs(void * temp, size_t temp_bytes, const uint32_t *
 size_t rvb_sort_temp_bytes(uint64_t n);
 void rvb_sort_pairs(void * temp, size_t temp_bytes, const uint32_t * keys_in, uint32_t * keys_out,
                     const uint32_t * values_in, uint32_t * values_out, uint64_t n, int key_bits, hipStream_t s);
+// The echo finder (window_kernels.hip; include/rvb_capi_window.h; the select's arithmetic: window_select.h).  `scratch` is one block of
+// rvb_window_scratch_bytes(n) bytes: the select's state and the gather's counter, the digit tables of the six passes, the gathered
+// composites, the entries of rvb_window_paths, then a key per record.  rvb_launch_window_begin zeroes its head (a memset node);
+// the others are one kernel each but rvb_launch_window_pass, which is window_histogram_kernel for digit `pass` (0..2: of the key — 0 is
+// counted by the score kernel, so only its walk runs —, 3..5: of ~record) and window_walk_kernel behind it.  The sort kernel writes entries
+// [0, want) and nothing else; the paths kernel reads them from the scratch.  listen: the pair's listener records, null with hits == null.
+struct WindowWeights { float w[8]; };
+size_t rvb_window_scratch_bytes(uint64_t n);
+rvb_window_entry * rvb_window_scratch_entries(void * scratch);
+const void * rvb_window_scratch_state(const void * scratch);             // window_select::State
+hipError_t rvb_launch_window_begin(void * scratch, hipStream_t s);
+void rvb_launch_window_score(const rvb_impulse * in, uint64_t n, float t_begin, float t_end, const WindowWeights & weights, void * scratch, hipStream_t s);
+void rvb_launch_window_pass(uint32_t pass, uint64_t n, uint64_t max_entries, void * scratch, hipStream_t s);
+void rvb_launch_window_gather(uint64_t n, void * scratch, hipStream_t s);
+void rvb_launch_window_sort(const rvb_impulse * in, void * scratch, rvb_window_entry * entries, hipStream_t s);
+void rvb_launch_window_paths(const rvb_impulse * in, const uint2 * listen, uint32_t nreflections, uint64_t max_paths, uint64_t max_hits,
+                             const void * scratch, rvb_window_path * paths, rvb_window_hit * hits, hipStream_t s);
