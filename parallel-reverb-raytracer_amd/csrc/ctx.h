@@ -517,6 +517,12 @@ inline int key_bits_for(uint64_t nbins)
     return bits;
 }
 
+// runs of 2^shift neighbouring keys ("coarse bins") that cover the keys 0 .. nkeys-1
+inline uint64_t coarse_keys(uint64_t nkeys, int shift)
+{
+    return (nkeys + (1ull << shift) - 1) >> shift;
+}
+
 // trace.hip: one synchronising 128-byte read per trace serves candidate count, direct path, time range, bounce count
 int fetch_small(rvb_ctx * ctx);
 // trace.hip: the steps of a trace that kept.hip replays (described where they are defined)
@@ -548,6 +554,6 @@ bool own_sort_enabled();
 int own_sort(rvb_ctx * ctx, const uint32_t * keys, uint32_t value_base, uint64_t n, int begin_bit, int end_bit,
              uint32_t * keys_out, uint32_t * values_out, bool want_keys);
 int ensure_sort_buffers(rvb_ctx * ctx, uint64_t n);
-int sort_and_bin(rvb_ctx * ctx, uint64_t n, uint64_t nkeys, int key_bits, bool may_sort_own);
+int sort_and_bin(rvb_ctx * ctx, uint64_t n, uint64_t nkeys, int key_bits, bool may_sort_own, int coarse_shift = 0);
 
 #pragma GCC visibility pop

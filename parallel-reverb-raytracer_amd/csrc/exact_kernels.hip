@@ -196,13 +196,27 @@ __global__ __launch_bounds__(64 * LIVE_WAVES) void live_compact_kernel(const uin
 // Where each bin's run starts in the sorted key list: starts[key] = first position of that key (entries of absent keys keep
 // the caller's 0xFFFFFFFF fill).  One coalesced pass over the keys replaces a 23-step binary search per bin — 19 M dependent
 // random reads at workload C2, which made the summation kernel fetch 3 GB for 0.5 GB of impulses.
-__global__ __launch_bounds__(256) void bin_starts_kernel(const uint32_t * __restrict__ keys, uint64_t n, uint64_t nbins, uint32_t * __restrict__ starts,
-                                                         uint32_t * __restrict__ ends)
+// shift > 0: the list is ordered on key >> shift only (sort_and_bin), and starts / ends are those of key >> shift, "coarse bins".
+// Entries whose whole key is >= nbins count for nothing, and they may stand anywhere in the last coarse bin's run (a live impulse
+// behind the histogram's end keeps its place among the others; the list's sentinel tail follows them all): the run reaches from its
+// first entry below nbins to behind its last one, taken with atomicMin / atomicMax over every entry that has no such neighbour in
+// its run (ends pre-filled with 0).  A coarse bin with no entry below nbins keeps starts = 0xFFFFFFFF.
+__global__ __launch_bounds__(256) void bin_starts_kernel(const uint32_t * __restrict__ keys, uint64_t n, uint64_t nbins, uint32_t shift,
+                                                         uint32_t * __restrict__ starts, uint32_t * __restrict__ ends)
 {
     for (uint64_t k = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (uint64_t) gridDim.x * blockDim.x) {
         const uint32_t key = keys[k];
         if (key >= nbins)
             continue;
+        if (shift) {
+            const uint32_t run = key >> shift;
+            const uint32_t before = k == 0 ? 0xFFFFFFFFu : keys[k - 1], after = k + 1 == n ? 0xFFFFFFFFu : keys[k + 1];
+            if (before >= nbins || (before >> shift) != run)
+                atomicMin(starts + run, (uint32_t) k);
+            if (after >= nbins || (after >> shift) != run)
+                atomicMax(ends + run, (uint32_t) (k + 1));
+            continue;
+        }
         if (k == 0 || keys[k - 1] != key)
             starts[key] = (uint32_t) k;
         if (k + 1 == n || keys[k + 1] != key)     // (with both ends known the summation loop has no data-dependent exit: its gathers overlap)
@@ -269,6 +283,114 @@ __global__ __launch_bounds__(64) void ordered_sum_kernel(ModelDev m, uint32_t fi
 #pragma unroll
         for (int b = 0; b < 4; ++b)
             hist[hist_row(first_channel + c, half, b, nbins) + bin] = sum[c][b];
+}
+
+// The speaker fold over a list ordered by coarse bin only (sort_and_bin with RVB_COARSE_SHIFT: one radix pass less at workload C2).
+// A wave owns one coarse bin, the run [starts, ends) of its RVB_COARSE_BINS = 32 bins; lane pair p owns bin 32 * coarse + p, the even
+// lane bands 0-3 and the odd lane bands 4-7 as in ordered_sum_kernel.  The wave walks the run in rounds of COARSE_CHUNK = 64 entries:
+//   * every lane holds one entry: its key and value come with one coalesced load each, its 64-byte record with the lane's own gather
+//     (64 records in flight per wave; the next round's keys, values and records are requested before this round's are consumed);
+//   * the lane evaluates the record's channel gains — once per record and channel, not once per lane of a pair — and leaves volume
+//     and gains in LDS; an entry that no bin of this launch matches (a key at or past nbins or outside [bin_begin, bin_end)) is
+//     neither gathered nor stored;
+//   * behind a workgroup barrier (one wave: the LDS writes of the producer lanes are done before a consumer lane reads), each pair
+//     takes the positions of the round's entries with its bin's key as a ballot mask and adds them lowest position first.
+// Why the sums are bit for bit ordered_sum_kernel<false, NCH>'s: the list goes into a stable sort in impulse order, so within the
+// run the entries of one bin stand in impulse order, and rounds and mask bits are taken in list order; the gain is speaker_gain of
+// attenuation.h on the same record position and channel; the add is the same `sum[c][b] += vol[b] * g` (one multiply, one add, no
+// contraction) on top of what the histogram holds; nothing else touches a value, and a bin without entries is not written.
+// A second barrier ends the round: the next round's producers overwrite the LDS.
+#define COARSE_CHUNK 64
+static_assert(COARSE_CHUNK == 64 && RVB_COARSE_BINS * 2 == 64, "an entry per lane, a lane pair per bin");
+template <int NCH>
+__global__ __launch_bounds__(64)       // LDS per wave: 64 x (32 + 4 NCH) bytes — 2.5 KiB at two channels, 3 KiB at four
+void ordered_sum_coarse_kernel(ModelDev m, uint32_t first_channel, const rvb_impulse * __restrict__ diffuse, uint64_t ndiffuse,
+                               const rvb_impulse * __restrict__ images, const uint32_t * __restrict__ keys,
+                               const uint32_t * __restrict__ values, const uint32_t * __restrict__ starts,
+                               const uint32_t * __restrict__ ends, uint64_t nbins, uint64_t bin_begin, uint64_t bin_end,
+                               float * __restrict__ hist)
+{
+    __shared__ float4 s_vol[COARSE_CHUNK][2];
+    __shared__ float s_gain[COARSE_CHUNK][NCH];
+    const uint32_t lane = threadIdx.x;
+    const uint64_t coarse = (bin_begin >> RVB_COARSE_SHIFT) + blockIdx.x;
+    const uint64_t lo = starts[coarse];
+    if (lo == 0xFFFFFFFFull)
+        return;                               // nothing lands in these bins: the histogram keeps what it holds (the whole wave leaves)
+    const uint64_t hi = ends[coarse];
+    const uint32_t half = lane & 1u, pair = lane >> 1;
+    const uint32_t first_bin = (uint32_t) (coarse << RVB_COARSE_SHIFT);
+    const uint64_t bin = (uint64_t) first_bin + pair;
+    const bool mine = bin >= bin_begin && bin < bin_end;          // (bin_end <= nbins: fold_range)
+    float sum[NCH][4];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+            sum[c][b] = mine ? hist[hist_row(first_channel + c, half, b, nbins) + bin] : 0.0f;
+    bool touched = false;
+
+    // the lane's entry of a round: its key (0xFFFFFFFF behind the run) and value, then its record where a bin of this launch takes it
+    uint32_t key, value, next_key, next_value;
+    float4 v0, v1, p;
+#define COARSE_ENTRY(K, KEY, VALUE) do { const uint64_t at_ = (K) + lane; const bool in_ = at_ < hi; \
+                                         KEY = in_ ? keys[at_] : 0xFFFFFFFFu; VALUE = in_ ? values[at_] : 0u; } while (0)
+#define COARSE_TAKEN(KEY) ((KEY) >= bin_begin && (KEY) < bin_end)
+#define COARSE_GATHER() do { if (COARSE_TAKEN(key)) { \
+                                 const float4 * r_ = reinterpret_cast<const float4 *>(value < ndiffuse ? diffuse + value : images + (value - ndiffuse)); \
+                                 v0 = r_[0]; v1 = r_[1]; p = r_[2]; } } while (0)
+    v0 = v1 = p = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    COARSE_ENTRY(lo, key, value);
+    COARSE_GATHER();
+    COARSE_ENTRY(lo + COARSE_CHUNK, next_key, next_value);
+    for (uint64_t k = lo; k < hi; k += COARSE_CHUNK) {
+        const bool taken = COARSE_TAKEN(key);
+        const uint32_t slot = taken ? key - first_bin : 0xFFFFFFFFu;      // which pair's bin: 0 .. 31
+        if (taken) {
+            s_vol[lane][0] = v0;
+            s_vol[lane][1] = v1;
+            const v3 pos = mk3(p.x, p.y, p.z);                  // (keyed into a bin: the volume is non-zero)
+#pragma unroll
+            for (int c = 0; c < NCH; ++c)
+                s_gain[lane][c] = speaker_gain(m, first_channel + c, pos);
+        }
+        key = next_key;
+        value = next_value;
+        COARSE_GATHER();
+        COARSE_ENTRY(k + 2 * COARSE_CHUNK, next_key, next_value);
+        __syncthreads();
+        unsigned long long todo = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < RVB_COARSE_BINS; ++q) {
+            const unsigned long long holders = __ballot(slot == q);
+            if (pair == q) todo = holders;
+        }
+        if (!mine) todo = 0;
+        while (todo) {                                           // the adds stay in impulse order
+            const uint32_t e = (uint32_t) __ffsll((long long) todo) - 1u;
+            todo &= todo - 1;
+            const float4 v = s_vol[e][half];
+            const float vol[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                const float g = s_gain[e][c];
+#pragma unroll
+                for (int b = 0; b < 4; ++b) sum[c][b] += vol[b] * g;
+            }
+            touched = true;
+        }
+        __syncthreads();
+    }
+#undef COARSE_ENTRY
+#undef COARSE_TAKEN
+#undef COARSE_GATHER
+    if (touched) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                hist[hist_row(first_channel + c, half, b, nbins) + bin] = sum[c][b];
+    }
 }
 
 // The HRTF model's ordered sum, both ears in ONE launch over the combined list of bin_keys_hrtf_kernel: two lanes per (bin, ear) —
@@ -464,10 +586,10 @@ void rvb_launch_bin_keys_hrtf(const AttenuationModel & m, const rvb_impulse * in
                        predelay, sample_rate, nbins, keys, values);
 }
 
-void rvb_launch_bin_starts(const uint32_t * sorted_keys, uint64_t n, uint64_t nbins, uint32_t * starts, uint32_t * ends, hipStream_t s)
+void rvb_launch_bin_starts(const uint32_t * sorted_keys, uint64_t n, uint64_t nbins, uint32_t * starts, uint32_t * ends, hipStream_t s, int shift)
 {
     if (n == 0) return;
-    hipLaunchKernelGGL(bin_starts_kernel, dim3(stream_blocks(n, 256)), dim3(256), 0, s, sorted_keys, n, nbins, starts, ends);
+    hipLaunchKernelGGL(bin_starts_kernel, dim3(stream_blocks(n, 256)), dim3(256), 0, s, sorted_keys, n, nbins, (uint32_t) shift, starts, ends);
 }
 
 size_t rvb_live_scratch_bytes(uint64_t n)
@@ -499,13 +621,18 @@ void rvb_launch_live_list(const AttenuationModel & m, const rvb_impulse * diffus
 void rvb_launch_ordered_sum(const AttenuationModel & m, uint32_t first_channel, uint32_t nchannels, const rvb_impulse * diffuse,
                             uint64_t ndiffuse, const rvb_impulse * images,
                             const uint32_t * sorted_values, const uint32_t * starts, const uint32_t * ends, uint64_t n,
-                            uint64_t nbins, float * hist, hipStream_t s, uint64_t bin_begin, uint64_t bin_end)
+                            uint64_t nbins, float * hist, hipStream_t s, uint64_t bin_begin, uint64_t bin_end, const uint32_t * coarse_keys)
 {
     if (!fold_range(nbins, bin_begin, bin_end) || n == 0) return;
-    const dim3 grid((unsigned) ((2 * (bin_end - bin_begin) + 63) / 64)), block(64);      // two lanes per bin
+    const bool coarse = coarse_keys != nullptr && !m.hrtf;
+    // two lanes per bin; by coarse bin: a wave for each one that [bin_begin, bin_end) cuts
+    const dim3 grid(coarse ? (unsigned) (((bin_end - 1) >> RVB_COARSE_SHIFT) - (bin_begin >> RVB_COARSE_SHIFT) + 1)
+                           : (unsigned) ((2 * (bin_end - bin_begin) + 63) / 64)), block(64);
     const ModelDev md = make_model(m);
-#define RVB_SUM(HRTF, NCH) hipLaunchKernelGGL((ordered_sum_kernel<HRTF, NCH>), grid, block, 0, s, md, first_channel, diffuse, ndiffuse, \
-                                              images, sorted_values, starts, ends, nbins, bin_begin, bin_end, hist)
+#define RVB_SUM(HRTF, NCH) do { if (coarse) hipLaunchKernelGGL((ordered_sum_coarse_kernel<NCH>), grid, block, 0, s, md, first_channel, diffuse, ndiffuse, \
+                                                               images, coarse_keys, sorted_values, starts, ends, nbins, bin_begin, bin_end, hist); \
+                                else hipLaunchKernelGGL((ordered_sum_kernel<HRTF, NCH>), grid, block, 0, s, md, first_channel, diffuse, ndiffuse, \
+                                                        images, sorted_values, starts, ends, nbins, bin_begin, bin_end, hist); } while (0)
     if (m.hrtf) { RVB_SUM(true, 1); return; }
     switch (nchannels) {                       // speaker channels of one sorted list
     case 1: RVB_SUM(false, 1); break;
@@ -515,7 +642,8 @@ void rvb_launch_ordered_sum(const AttenuationModel & m, uint32_t first_channel, 
     default:                                   // more than four: in groups (64 accumulators per lane would spill)
         for (uint32_t c = 0; c < nchannels; c += 4) {
             const uint32_t k = nchannels - c < 4 ? nchannels - c : 4;
-            rvb_launch_ordered_sum(m, first_channel + c, k, diffuse, ndiffuse, images, sorted_values, starts, ends, n, nbins, hist, s, bin_begin, bin_end);
+            rvb_launch_ordered_sum(m, first_channel + c, k, diffuse, ndiffuse, images, sorted_values, starts, ends, n, nbins, hist, s, bin_begin, bin_end,
+                                   coarse_keys);
         }
     }
 #undef RVB_SUM

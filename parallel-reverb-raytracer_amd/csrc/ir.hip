@@ -180,6 +180,13 @@ int exact_list(rvb_ctx * ctx, const ExactList & in, uint32_t channel, float pred
     return sort_and_bin(ctx, in.n, nbins, key_bits_for(nbins), may_sort_own);
 }
 
+// RVB_EXACT_COARSE=0, the measurement switch (tools/README.md): the speaker fold keeps the list ordered by bin and ordered_sum_kernel.
+bool coarse_list_enabled()
+{
+    static const bool on = !(getenv("RVB_EXACT_COARSE") && std::strcmp(getenv("RVB_EXACT_COARSE"), "0") == 0);
+    return on;
+}
+
 // Exact mode, step 1 (everything that does not depend on what the histogram holds): per-impulse bin keys, the radix sort, where each
 // bin's run starts and ends.  Speaker channels keep the input time (kernel.cpp:530-533) and share ONE sorted list; the two HRTF ears
 // shift the arrival time differently (kernel.cpp:616-622) and are keyed in one pass into ONE list of 2 n entries (bin_keys_hrtf_kernel).
@@ -198,7 +205,10 @@ int exact_prepare(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbi
     } else if (own_sort_enabled()) {
         rc = exact_list(ctx, in, 0, predelay, sample_rate, nbins, true);          // identity values: the list of every impulse
     } else {
-        if ((rc = live_list(ctx, in, predelay, sample_rate, nbins)) == RVB_OK) rc = sort_and_bin(ctx, in.listed, nbins, key_bits_for(nbins), false);
+        // up to 8 speakers: the fold works by coarse bin (ordered_sum_coarse_kernel) and the sort leaves the low key bits alone
+        in.coarse_shift = m.nchannels <= 8 && coarse_list_enabled() ? RVB_COARSE_SHIFT : 0;
+        if ((rc = live_list(ctx, in, predelay, sample_rate, nbins)) == RVB_OK)
+            rc = sort_and_bin(ctx, in.listed, nbins, key_bits_for(nbins), false, in.coarse_shift);
     }
     if (rc != RVB_OK) return rc;
     RVB_HIP(fail, ctx, hipGetLastError());
@@ -222,8 +232,10 @@ int exact_fold(rvb_ctx * ctx, uint64_t b0, uint64_t b1, float * hist)
         rvb_launch_ordered_sum_wide(m, ir_diffuse(ctx), e.ndiffuse, ctx->ir.images.as<rvb_impulse>(), ctx->sort.vals_b.as<uint32_t>(),
                                     ctx->sort.bin_starts.as<uint32_t>(), ctx->sort.bin_starts.as<uint32_t>() + e.nbins, e.listed, e.nbins, hist, ctx->stream, b0, b1);
     } else {
+        const uint64_t nruns = coarse_keys(e.nbins, e.coarse_shift);
         rvb_launch_ordered_sum(m, 0, m.nchannels, ir_diffuse(ctx), e.ndiffuse, ctx->ir.images.as<rvb_impulse>(), ctx->sort.vals_b.as<uint32_t>(),
-                               ctx->sort.bin_starts.as<uint32_t>(), ctx->sort.bin_starts.as<uint32_t>() + e.nbins, e.listed, e.nbins, hist, ctx->stream, b0, b1);
+                               ctx->sort.bin_starts.as<uint32_t>(), ctx->sort.bin_starts.as<uint32_t>() + nruns, e.listed, e.nbins, hist, ctx->stream, b0, b1,
+                               e.coarse_shift ? ctx->sort.keys_b.as<uint32_t>() : nullptr);
     }
     RVB_HIP(fail, ctx, hipGetLastError());
     return RVB_OK;

@@ -20,11 +20,14 @@ struct FlattenQuery {
 // Exact mode in two steps (rvb_ir_exact_prepare / rvb_ir_exact_fold): what the sorted list in keys_b / vals_b / bin_starts was prepared for.
 // `listed` entries per ear: the impulses that carry volume and a tail that matches no bin (live_list, ir.hip), listed <= n; the full
 // list of RVB_SORT=own has listed == n and !compacted.  count_valid: the trace's live count sized the list.
+// coarse_shift: 0 for a list ordered by bin with boundaries per bin; s > 0 for one ordered by bin >> s only, with boundaries per run of
+// 2^s bins (sort_and_bin) — the fold takes the form from here, so it never reads boundaries of the other kind.
 struct ExactList {
     bool hrtf_combined = false;
     uint64_t nbins = 0, n = 0, ndiffuse = 0, nimages = 0;
     uint64_t listed = 0;
     bool count_valid = false, compacted = false;
+    int coarse_shift = 0;
 };
 
 class IrState {

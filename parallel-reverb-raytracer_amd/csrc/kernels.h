@@ -285,7 +285,13 @@ void rvb_launch_bin_keys(const AttenuationModel & m, uint32_t channel, const rvb
 void rvb_launch_ordered_sum(const AttenuationModel & m, uint32_t first_channel, uint32_t nchannels, const rvb_impulse * diffuse,
                             uint64_t ndiffuse, const rvb_impulse * images,
                             const uint32_t * sorted_values, const uint32_t * starts, const uint32_t * ends, uint64_t n,
-                            uint64_t nbins, float * hist, hipStream_t s, uint64_t bin_begin = 0, uint64_t bin_end = ~0ull);   // bins [bin_begin, bin_end) only
+                            uint64_t nbins, float * hist, hipStream_t s, uint64_t bin_begin = 0, uint64_t bin_end = ~0ull,   // bins [bin_begin, bin_end) only
+                            const uint32_t * coarse_keys = nullptr);
+// coarse_keys: the list is ordered by coarse bin only (sort_and_bin with coarse_shift = RVB_COARSE_SHIFT: runs of RVB_COARSE_BINS
+// neighbouring bins, every bin's entries in impulse order within its run) — its whole keys, and starts / ends are per coarse bin.
+// The same sums then come from ordered_sum_coarse_kernel, a wave per coarse bin.
+#define RVB_COARSE_SHIFT 5
+#define RVB_COARSE_BINS (1u << RVB_COARSE_SHIFT)
 // The same fold for more than 8 speaker channels (ordered_sum_wide_kernel): ALL m.nchannels channels of bins [bin_begin, bin_end) in one
 // launch, the speaker table read from m.speaker_table, every record gathered from HBM once.
 void rvb_make_speaker_table(const rvb_speaker * speakers, uint64_t nspeakers, float4 * table);      // host: the entries of speaker_table
@@ -310,8 +316,10 @@ void rvb_launch_live_list(const AttenuationModel & m, const rvb_impulse * diffus
                           float predelay, float sample_rate, uint32_t nbins, uint64_t listed, uint32_t * raw, void * scratch,
                           uint32_t * keys, uint32_t * values, uint32_t * overflow, hipStream_t s);
 // starts[key] / ends[key] = first position of `key` in the sorted list / one past its last (starts[] pre-filled with 0xFFFFFFFF by
-// the caller, nbins entries each; ends[] is only read where starts[] was written)
-void rvb_launch_bin_starts(const uint32_t * sorted_keys, uint64_t n, uint64_t nbins, uint32_t * starts, uint32_t * ends, hipStream_t s);
+// the caller, nbins entries each; ends[] is only read where starts[] was written).  With shift > 0 the list is ordered on
+// key >> shift only and the boundaries are those of key >> shift, (nbins + 2^shift - 1) >> shift entries each: from the first to
+// behind the last entry of the run whose whole key is below nbins (ends[] pre-filled with 0 by the caller).
+void rvb_launch_bin_starts(const uint32_t * sorted_keys, uint64_t n, uint64_t nbins, uint32_t * starts, uint32_t * ends, hipStream_t s, int shift = 0);
 // flattenImpulses of already attenuated impulses (rayverb.cpp:48-77): keys + ordered sum
 void rvb_launch_flat_keys(const rvb_attenuated_impulse * in, uint64_t n, float sample_rate, uint32_t * keys, uint32_t * values,
                           uint32_t * max_time_bits, hipStream_t s);
@@ -324,10 +332,11 @@ hipError_t rvb_radix_sort_pairs(void * temp, size_t temp_bytes, const uint32_t *
                                 uint32_t * keys_a, uint32_t * values_a, uint32_t * keys_b, uint32_t * values_b, uint64_t n,
                                 int begin_bit, int end_bit, bool want_keys, const uint32_t ** keys_sorted, const uint32_t ** values_sorted,
                                 hipStream_t s);
-// stable sort of (key, value) pairs by key (rocPRIM's device radix sort, rocprim_sort.hip); temp storage managed by the caller
+// stable sort of (key, value) pairs on key bits [begin_bit, key_bits) (rocPRIM's device radix sort, rocprim_sort.hip); the keys come
+// out whole; temp storage managed by the caller
 size_t rvb_sort_temp_bytes(uint64_t n);
 void rvb_sort_pairs(void * temp, size_t temp_bytes, const uint32_t * keys_in, uint32_t * keys_out,
-                    const uint32_t * values_in, uint32_t * values_out, uint64_t n, int key_bits, hipStream_t s);
+                    const uint32_t * values_in, uint32_t * values_out, uint64_t n, int begin_bit, int key_bits, hipStream_t s);
 // The echo finder (window_kernels.hip; include/rvb_capi_window.h; the select's arithmetic: window_select.h).  `scratch` is one block of
 // rvb_window_scratch_bytes(n) bytes: the select's state and the gather's counter, the digit tables of the six passes, the gathered
 // composites, the entries of rvb_window_paths, then a key per record.  rvb_launch_window_begin zeroes its head (a memset node);

@@ -17,10 +17,11 @@ size_t rvb_sort_temp_bytes(uint64_t n)
 }
 
 void rvb_sort_pairs(void * temp, size_t temp_bytes, const uint32_t * keys_in, uint32_t * keys_out,
-                    const uint32_t * values_in, uint32_t * values_out, uint64_t n, int key_bits, hipStream_t s)
+                    const uint32_t * values_in, uint32_t * values_out, uint64_t n, int begin_bit, int key_bits, hipStream_t s)
 {
     if (n == 0) return;
-    (void) rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, values_in, values_out, (size_t) n, 0, (unsigned) key_bits, s);
+    (void) rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, values_in, values_out, (size_t) n, (unsigned) begin_bit,
+                                     (unsigned) key_bits, s);
 }
 
 // Grouping of the trace's work records by spatial bucket: sort (bucket key, record index) pairs on the

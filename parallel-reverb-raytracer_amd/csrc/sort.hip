@@ -54,19 +54,28 @@ int ensure_sort_buffers(rvb_ctx * ctx, uint64_t n)
 // The (key, value) list of n entries in keys_a / vals_a, keys below nkeys in key_bits bits -> the sorted list in keys_b / vals_b and
 // bin_starts[2 * nkeys]: where each key's run starts, then where it ends.  RVB_SORT=own takes identity values only: it may serve the
 // sort (may_sort_own) where the key pass wrote the entry numbers 0 .. n-1 as values; every other list is rocPRIM's.
-int sort_and_bin(rvb_ctx * ctx, uint64_t n, uint64_t nkeys, int key_bits, bool may_sort_own)
+// coarse_shift > 0 (rocPRIM's sort only): the list is ordered on key bits [coarse_shift, key_bits) alone — stable, so every run of
+// 2^coarse_shift neighbouring keys is contiguous and each key's entries keep their order within it; keys_b holds the whole keys and
+// the boundaries are those of key >> coarse_shift, coarse_keys(nkeys, coarse_shift) of them.  Keys that fit into coarse_shift bits
+// are one run: the list is copied.
+int sort_and_bin(rvb_ctx * ctx, uint64_t n, uint64_t nkeys, int key_bits, bool may_sort_own, int coarse_shift)
 {
     SortBuffers & b = ctx->sort;
-    RVB_HIP(fail, ctx, b.bin_starts.ensure(nkeys * 8));
+    const uint64_t nruns = coarse_keys(nkeys, coarse_shift);
+    RVB_HIP(fail, ctx, b.bin_starts.ensure(nruns * 8));
     uint32_t * starts = b.bin_starts.as<uint32_t>();
-    if (may_sort_own && own_sort_enabled()) {
+    if (coarse_shift > 0 && key_bits <= coarse_shift) {
+        RVB_HIP(fail, ctx, hipMemcpyAsync(b.keys_b.p, b.keys_a.p, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        RVB_HIP(fail, ctx, hipMemcpyAsync(b.vals_b.p, b.vals_a.p, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    } else if (coarse_shift == 0 && may_sort_own && own_sort_enabled()) {
         const int rc = own_sort(ctx, b.keys_a.as<uint32_t>(), 0u, n, 0, key_bits, b.keys_b.as<uint32_t>(), b.vals_b.as<uint32_t>(), true);
         if (rc != RVB_OK) return rc;
     } else {
         rvb_sort_pairs(b.temp.p, b.temp.cap, b.keys_a.as<uint32_t>(), b.keys_b.as<uint32_t>(),
-                       b.vals_a.as<uint32_t>(), b.vals_b.as<uint32_t>(), n, key_bits, ctx->stream);
+                       b.vals_a.as<uint32_t>(), b.vals_b.as<uint32_t>(), n, coarse_shift, key_bits, ctx->stream);
     }
-    RVB_HIP(fail, ctx, hipMemsetAsync(starts, 0xFF, nkeys * 4, ctx->stream));
-    rvb_launch_bin_starts(b.keys_b.as<uint32_t>(), n, nkeys, starts, starts + nkeys, ctx->stream);
+    RVB_HIP(fail, ctx, hipMemsetAsync(starts, 0xFF, nruns * 4, ctx->stream));
+    if (coarse_shift > 0) RVB_HIP(fail, ctx, hipMemsetAsync(starts + nruns, 0, nruns * 4, ctx->stream));
+    rvb_launch_bin_starts(b.keys_b.as<uint32_t>(), n, nkeys, starts, starts + nruns, ctx->stream, coarse_shift);
     return RVB_OK;
 }
