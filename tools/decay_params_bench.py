@@ -22,25 +22,21 @@ child process under its own `timeout -k 10`; the table is written (--out) only w
     python tools/decay_params_bench.py [--rows 16,512] [--bins N] [--repeats R] [--parent ROOT] [--out FILE]
 """
 import argparse
-import json
 import os
-import shlex
 import statistics
-import subprocess
 import sys
-import tempfile
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import benchsteps
+from benchsteps import Samples, Table
+
 HBM_TBS = 6.6
 LEVELS = ((0.0, -10.0), (-5.0, -25.0), (-5.0, -35.0))
 
 
 def step(args):
     """The GPU process of one shape and one build: appends one JSON line of raw samples to the work file."""
-    sys.path.insert(0, args.root)
-    import rvb_import
-    rvb_import.load()
+    sys.path.insert(0, args.root)          # the build under test: this checkout's, or the one of --parent
+    benchsteps.load_library()
     import numpy as np
     import torch
     from parallel_reverb_raytracer_amd import capi
@@ -64,19 +60,10 @@ def step(args):
     del level
     pinned = torch.empty((nrows, nbins), dtype=torch.float32).pin_memory()
     torch.cuda.synchronize()
-    samples = {}
-
-    def note(name, value):
-        samples.setdefault(name, []).append(float(value))
+    s = Samples()
 
     def timed(name, call, kernels=True, wait=ctx.synchronize):
-        t0 = time.perf_counter()
-        call()
-        wait()
-        note(name, (time.perf_counter() - t0) * 1e3)
-        if kernels:
-            for k, v in ctx.last_timings():
-                note(name + ":" + k, v)
+        s.timed(name, call, wait, ctx.last_timings if kernels else None)
 
     h, e, t, m, w = (x.data_ptr() for x in (hist, curve, target, mask, weights))
     ctx.decay_curve(h, nrows, nbins, e)
@@ -87,9 +74,7 @@ def step(args):
         has = np.isfinite(params) & (params != 0)
         safe = np.where(has, params, 1.0).astype(np.float64)
         targets, pweights = (safe * 1.25).astype(np.float32), np.where(has, 1.0 / (safe * safe), 0.0).astype(np.float32)
-    for rep in range(args.warmup + args.repeats):
-        if rep == args.warmup:
-            samples.clear()
+    for rep in s.repetitions(args.warmup, args.repeats):
         if not new:
             timed("curve", lambda: ctx.decay_curve(h, nrows, nbins, e))
             timed("times", lambda: ctx.decay_times(e, nrows, nbins, sr, -5.0, -35.0))
@@ -102,99 +87,74 @@ def step(args):
         timed("download", lambda: pinned.copy_(curve, non_blocking=True), kernels=False, wait=torch.cuda.synchronize)
         timed("params_loss", lambda: checks.__setitem__("ploss", ctx.decay_params_loss(h, e, nrows, nbins, sr, targets, pweights, w)[0]))
         timed("params_loss_only", lambda: checks.__setitem__("ploss_only", ctx.decay_params_loss(h, e, nrows, nbins, sr, targets, pweights, None)[0]))
-    rec = {"side": args.step, "nrows": nrows, "nbins": nbins, "samples": samples, "loss": float(checks["loss"].sum())}
+    rec = {"side": args.step, "nrows": nrows, "nbins": nbins, "loss": float(checks["loss"].sum())}
     if new:
         assert all(checks["params"][:, p].tobytes() == checks["three"][p].tobytes() for p in range(3)), "the times differ from rvb_decay_times"
         assert checks["ploss"].tobytes() == checks["ploss_only"].tobytes()
         rec.update(params0=[float(x) for x in checks["params"][0]], params_loss=float(checks["ploss"].sum()))
     ctx.close()
-    with open(args.work, "a") as f:
-        f.write(json.dumps(rec) + "\n")
+    s.dump(args.work, **rec)
 
 
 def report(args):
-    lines = ["decay params bench: rows x %d bins of float32, one context, one MI355X; median ms [min .. max] (n)" % args.bins,
-             "calls: host clock to the synchronisation; kernels: HIP events of rvb_last_timings; floors at %.1f TB/s" % HBM_TBS]
-    records = [json.loads(raw) for raw in open(args.work).read().splitlines()]
+    t = Table()
+    t.line("decay params bench: rows x %d bins of float32, one context, one MI355X; median ms [min .. max] (n)" % args.bins)
+    t.line("calls: host clock to the synchronisation; kernels: HIP events of rvb_last_timings; floors at %.1f TB/s" % HBM_TBS)
+    records = benchsteps.records(args.work)
     for nrows in sorted({r["nrows"] for r in records}):
-        merged = {"new": {}, "this": {}, "parent": {}}
-        for r in records:
-            if r["nrows"] == nrows:
-                for k, v in r["samples"].items():
-                    merged[r["side"]].setdefault(k, []).extend(v)
-        first = next(r for r in records if r["nrows"] == nrows and r["side"] == "new")
-        s, array = merged["new"], nrows * args.bins * 4
+        mine = [r for r in records if r["nrows"] == nrows]
+        t.samples = benchsteps.merge(mine, key=lambda rec, k: (rec["side"], k))
+        first = next(r for r in mine if r["side"] == "new")
+        array = nrows * args.bins * 4
         floor = array / (HBM_TBS * 1e12) * 1e3
-        med = lambda key, side="new": statistics.median(merged[side][key])
-        lines.append("%d x %d (%.1f MB per array); EDT T20 T30 C50 C80 D50 Ts of row 0: %s; params loss %.6g, decay loss %.6g" %
-                     (nrows, args.bins, array / 1e6, " ".join("%.4g" % x for x in first["params0"]), first["params_loss"], first["loss"]))
-
-        def row(label, key, side="new", floor_ms=None):
-            v = merged[side][key]
-            tail = "" if floor_ms is None else "   floor %.3f ms: %.2f x" % (floor_ms, statistics.median(v) / floor_ms)
-            lines.append("  %-58s %8.3f [%.3f .. %.3f] (%d)%s" % (label, statistics.median(v), min(v), max(v), len(v), tail))
-
+        med = lambda key, side="new": t.med((side, key))
+        t.line("%d x %d (%.1f MB per array); EDT T20 T30 C50 C80 D50 Ts of row 0: %s; params loss %.6g, decay loss %.6g" %
+               (nrows, args.bins, array / 1e6, " ".join("%.4g" % x for x in first["params0"]), first["params_loss"], first["loss"]))
         floors = {"decay_params_find_kernel": floor, "decay_params_sums_kernel": floor, "decay_params_adjoint_sums_kernel": floor,
                   "decay_params_adjoint_scan_kernel": 3 * floor}
         for name, label in (("params", "rvb_decay_params"), ("params_loss", "rvb_decay_params_loss with weights"),
                             ("params_loss_only", "rvb_decay_params_loss, loss only")):
-            row(label, name)
-            for k in sorted(k for k in s if k.startswith(name + ":")):
-                row("      " + k.split(":", 1)[1], k, floor_ms=floors.get(k.split(":", 1)[1]))
-        row("three rvb_decay_times calls (EDT, T20, T30)", "three_times")
-        row("pinned download of the curve", "download")
-        row("rvb_decay_loss with weights", "loss")
-        row("rvb_decay_loss, loss only", "loss_only")
-        kernels = lambda name: sum(statistics.median(s[k]) for k in s if k.startswith(name + ":"))
-        lines.append("  params: %.3f ms against %.3f ms for the three calls and the download (%.1f x); kernels %.3f ms against a floor of %.3f ms "
-                     "(E twice)" % (med("params"), med("three_times") + med("download"), (med("three_times") + med("download")) / med("params"),
-                                    kernels("params"), 2 * floor))
-        lines.append("  params loss with weights: %.3f ms against rvb_decay_loss' %.3f ms; loss only %.3f ms against %.3f ms; adjoint kernels %.3f ms "
-                     "against a floor of %.3f ms (E twice, H once, w once)" %
-                     (med("params_loss"), med("loss"), med("params_loss_only"), med("loss_only"), sum(statistics.median(v) for k, v in s.items() if k.startswith("params_loss:decay_params_adjoint")),
-                      4 * floor))
-        if merged["parent"]:
-            lines.append("  this build against the parent build, the same three calls in alternating processes:")
+            t.row(label, ("new", name))
+            for k in t.kernels("new", name):
+                t.row("      " + k, ("new", name + ":" + k), tail="   floor %.3f ms: %.2f x" % (floors[k], med(name + ":" + k) / floors[k]) if k in floors else "")
+        t.row("three rvb_decay_times calls (EDT, T20, T30)", ("new", "three_times"))
+        t.row("pinned download of the curve", ("new", "download"))
+        t.row("rvb_decay_loss with weights", ("new", "loss"))
+        t.row("rvb_decay_loss, loss only", ("new", "loss_only"))
+        kernels = lambda name, start="": sum(med(name + ":" + k) for k in t.kernels("new", name) if k.startswith(start))
+        t.line("  params: %.3f ms against %.3f ms for the three calls and the download (%.1f x); kernels %.3f ms against a floor of %.3f ms "
+               "(E twice)" % (med("params"), med("three_times") + med("download"), (med("three_times") + med("download")) / med("params"),
+                              kernels("params"), 2 * floor))
+        t.line("  params loss with weights: %.3f ms against rvb_decay_loss' %.3f ms; loss only %.3f ms against %.3f ms; adjoint kernels %.3f ms "
+               "against a floor of %.3f ms (E twice, H once, w once)" %
+               (med("params_loss"), med("loss"), med("params_loss_only"), med("loss_only"), kernels("params_loss", "decay_params_adjoint"), 4 * floor))
+        if any(r["side"] == "parent" for r in mine):
+            t.line("  this build against the parent build, the same three calls in alternating processes:")
             for name, label in (("curve", "rvb_decay_curve"), ("times", "rvb_decay_times, -5 .. -35 dB"), ("loss", "rvb_decay_loss with weights")):
-                row("    %s, this build" % label, name, side="this")
-                row("    %s, parent" % label, name, side="parent")
-                runs = [statistics.median(r["samples"][name]) for r in records if r["nrows"] == nrows and r["side"] == "parent"]
-                lines.append("      difference of the medians %+.4f ms; the parent's own processes: medians %s, samples %.3f .. %.3f" %
-                             (med(name, "this") - med(name, "parent"), " / ".join("%.4f" % x for x in runs), min(merged["parent"][name]), max(merged["parent"][name])))
-    text = "\n".join(lines)
-    print(text, flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+                t.row("    %s, this build" % label, ("this", name))
+                t.row("    %s, parent" % label, ("parent", name))
+                runs = [statistics.median(r["samples"][name]) for r in mine if r["side"] == "parent"]
+                t.line("      difference of the medians %+.4f ms; the parent's own processes: medians %s, samples %.3f .. %.3f" %
+                       (med(name, "this") - med(name, "parent"), " / ".join("%.4f" % x for x in runs), min(t.samples[("parent", name)]), max(t.samples[("parent", name)])))
+    t.emit(args.out)
+
+
+def build_steps(args):
+    sides = [("new", benchsteps.ROOT)] + ([("this", benchsteps.ROOT), ("parent", os.path.abspath(args.parent))] * 2 if args.parent else [])
+    return (benchsteps.shape(args, "bins", "repeats", "warmup"),
+            [(side, ["--root", root, "--nrows", str(int(n))], None) for n in args.rows.split(",") for side, root in sides])
 
 
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--rows", default="16,512")
     p.add_argument("--bins", type=int, default=846741)
-    p.add_argument("--repeats", type=int, default=21)
-    p.add_argument("--warmup", type=int, default=3)
-    p.add_argument("--step-timeout", type=int, default=240)
+    benchsteps.add_common_arguments(p, repeats=21, warmup=3, step_timeout=240)
     p.add_argument("--parent", default=None, help="root of a built checkout of the commit to compare the unchanged calls with")
-    p.add_argument("--out", default=None)
-    p.add_argument("--step", default=None, help=argparse.SUPPRESS)
-    p.add_argument("--root", default=ROOT, help=argparse.SUPPRESS)
+    p.add_argument("--root", default=benchsteps.ROOT, help=argparse.SUPPRESS)
     p.add_argument("--nrows", type=int, default=0, help=argparse.SUPPRESS)
-    p.add_argument("--work", default=None, help=argparse.SUPPRESS)
     args = p.parse_args()
-    if args.step == "report":
-        return report(args)
-    if args.step:
-        return step(args)
-    work = os.path.join(tempfile.mkdtemp(prefix="decay_params_bench_"), "samples.json")
-    shape = ["--bins", str(args.bins), "--repeats", str(args.repeats), "--warmup", str(args.warmup), "--work", work]
-    me = [sys.executable, os.path.abspath(__file__)]
-    sides = [("new", ROOT)] + ([("this", ROOT), ("parent", os.path.abspath(args.parent))] * 2 if args.parent else [])
-    parts = ["timeout -k 10 %d %s && echo 'decay_params_bench: %s rows, %s build done' >&2" %
-             (args.step_timeout, " ".join(shlex.quote(x) for x in me + shape + ["--step", side, "--root", root, "--nrows", str(int(n))]), int(n), side)
-             for n in args.rows.split(",") for side, root in sides]
-    parts.append(" ".join(shlex.quote(x) for x in me + shape + ["--step", "report"] + (["--out", args.out] if args.out else [])))
-    return subprocess.call(["bash", "-c", " && ".join(parts)])
+    return benchsteps.run(args, dict.fromkeys(("new", "this", "parent"), step), report, build_steps)
 
 
 if __name__ == "__main__":

@@ -22,30 +22,15 @@ step is a child process under its own `timeout -k 10`; the table is written (--o
     python tools/early_fit_bench.py [--rays N] [--repeats R] [--parent-lib FILE] [--out FILE]
 """
 import argparse
-import json
 import os
-import shlex
-import statistics
-import subprocess
 import sys
-import tempfile
 import time
 
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchsteps
+from benchsteps import Samples, Table
 
 SPEAKERS = ([(-1, 0, -1), (1, 0, -1)], [0.5, 0.5])
 WORKLOADS = {"cathedral": 128, "room": 12}
-
-
-def other_surfaces(surfaces):
-    rng = np.random.default_rng(11)
-    b = surfaces.copy()
-    b["specular"] = rng.uniform(0.3, 0.9, b["specular"].shape).astype(np.float32)
-    b["diffuse"] = rng.uniform(0.3, 0.9, b["diffuse"].shape).astype(np.float32)
-    return b
 
 
 def workload(args, name):
@@ -54,37 +39,19 @@ def workload(args, name):
     if name == "cathedral":
         scene, info = scenes.cathedral(args.triangles)
         return scene, info["mic"], info["source"], WORKLOADS[name]
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, os.path.join(benchsteps.ROOT, "tests"))
     import image_edges
     return image_edges.room(), image_edges.PAIRS[0][0], image_edges.PAIRS[0][1], WORKLOADS[name]
 
 
-class Samples:
-    def __init__(self, ctx):
-        self.ctx, self.samples = ctx, {}
-
-    def note(self, name, value):
-        self.samples.setdefault(name, []).append(float(value))
-
-    def timed(self, name, call, kernels=True):
-        t0 = time.perf_counter()
-        call()
-        self.ctx.synchronize()
-        self.note(name, (time.perf_counter() - t0) * 1e3)
-        if kernels:
-            for k, v in self.ctx.last_timings():
-                self.note(name + ":" + k, v)
-
-
 def step_forward(args):
-    """(a) and (b) for one workload: writes one JSON line of raw samples to the work file."""
-    import rvb_import
-    rvb_import.load()
+    """(a) and (b) for one workload: writes one JSON line of raw samples to that workload's work file."""
+    benchsteps.load_library()
     import torch
     from parallel_reverb_raytracer_amd import capi, dtypes, scenes
     air = dtypes.AIR_COEFFICIENTS
     scene, mic, src, nrefl = workload(args, args.workload)
-    table = other_surfaces(scene[2])
+    table = benchsteps.other_surfaces(scene[2])
     ctx = capi.Context(0)
     ctx.set_scene(scene)
     ctx.set_directions(scenes.sphere_directions(args.rays, seed=1))
@@ -98,8 +65,11 @@ def step_forward(args):
     weights = torch.randn((2, 8, nbins), dtype=torch.float32, device="cuda", generator=torch.Generator(device="cuda").manual_seed(5))
     hist = torch.zeros((2, 8, nbins), dtype=torch.float32, device="cuda")
     torch.cuda.synchronize()
-    s = Samples(ctx)
+    s = Samples()
     sr = args.sample_rate
+
+    def timed(name, call, kernels=True):
+        s.timed(name, call, ctx.synchronize, ctx.last_timings if kernels else None)
 
     def configure_host():
         t0 = time.perf_counter()
@@ -117,36 +87,32 @@ def step_forward(args):
             ctx.reshade(table, air)
             s.note(name + ":configure (host clock, not synchronised)", configure())
             ctx.ir_accumulate(predelay, sr, nbins, capi.IR_EXACT, hist.data_ptr())
-        s.timed(name, call, kernels=False)
+        timed(name, call, kernels=False)
 
-    for rep in range(args.warmup + args.repeats):
-        if rep == args.warmup:
-            s.samples.clear()
+    for rep in s.repetitions(args.warmup, args.repeats):
         forward("host", configure_host)
         ctx.relisten(mic)                                   # the same microphone: the same results, the list void
         ctx.synchronize()
         forward("merged_first", configure_merged)
         forward("merged_later", configure_merged)
-        s.timed("grad_images", lambda: ctx.reshade_grad_images(predelay, sr, nbins, weights.data_ptr()))
+        timed("grad_images", lambda: ctx.reshade_grad_images(predelay, sr, nbins, weights.data_ptr()))
         ctx.ir_configure_speakers(mic, SPEAKERS[0], SPEAKERS[1], capi.IR_DIFFUSE, None)
-        s.timed("grad", lambda: ctx.reshade_grad(predelay, sr, nbins, weights.data_ptr()))
+        timed("grad", lambda: ctx.reshade_grad(predelay, sr, nbins, weights.data_ptr()))
     ctx.close()
-    with open(args.work, "w") as f:
-        f.write(json.dumps({"samples": s.samples, "nbins": nbins, "nsurfaces": int(scene[2].shape[0]), "nimages": int(nimages),
-                            "ncandidates": ncandidates, "reflections": nrefl, "triangles": int(scene[0].shape[0])}) + "\n")
+    s.dump(args.work + "." + args.workload, nbins=nbins, nsurfaces=int(scene[2].shape[0]), nimages=int(nimages), ncandidates=ncandidates,
+           reflections=nrefl, triangles=int(scene[0].shape[0]))
 
 
 def step_turn(args):
-    """(c), one turn of one library (RVB_LIB decides which): appends one JSON line of raw samples to the work file."""
-    import rvb_import
-    rvb_import.load()
+    """(c), one turn of one library (RVB_LIB decides which): appends one JSON line of raw samples to the work file of the turns."""
+    benchsteps.load_library()
     import torch
     from parallel_reverb_raytracer_amd import capi, dtypes, scenes
     air = dtypes.AIR_COEFFICIENTS
     if args.label == "parent":
         capi._IMAGE_SIGNATURES.clear()          # the parent's library has no entry point of rvb_capi_images.h: nothing of that table to apply
     scene, mic, src, nrefl = workload(args, "cathedral")
-    table = other_surfaces(scene[2])
+    table = benchsteps.other_surfaces(scene[2])
     ctx = capi.Context(0)
     ctx.set_scene(scene)
     ctx.set_directions(scenes.sphere_directions(args.rays, seed=1))
@@ -157,65 +123,56 @@ def step_turn(args):
     nbins = ctx.ir_bins(latest, predelay, args.sample_rate)
     weights = torch.randn((2, 8, nbins), dtype=torch.float32, device="cuda", generator=torch.Generator(device="cuda").manual_seed(5))
     torch.cuda.synchronize()
-    s = Samples(ctx)
-    for rep in range(args.warmup + args.repeats):
-        if rep == args.warmup:
-            s.samples.clear()
-        s.timed("trace", lambda: ctx.trace(mic, src, nrefl, air), kernels=False)
-        s.timed("reshade", lambda: ctx.reshade(table, air), kernels=False)
+    s = Samples()
+    for rep in s.repetitions(args.warmup, args.repeats):
+        s.timed("trace", lambda: ctx.trace(mic, src, nrefl, air), ctx.synchronize)
+        s.timed("reshade", lambda: ctx.reshade(table, air), ctx.synchronize)
         ctx.ir_configure_speakers(mic, SPEAKERS[0], SPEAKERS[1], capi.IR_DIFFUSE, None)
-        s.timed("grad", lambda: ctx.reshade_grad(predelay, args.sample_rate, nbins, weights.data_ptr()), kernels=False)
+        s.timed("grad", lambda: ctx.reshade_grad(predelay, args.sample_rate, nbins, weights.data_ptr()), ctx.synchronize)
     ctx.close()
-    with open(args.work, "a") as f:
-        f.write(json.dumps({"lib": args.label, "samples": s.samples}) + "\n")
-
-
-def fmt(v):
-    return "%8.3f [%.3f .. %.3f] (%d)" % (statistics.median(v), min(v), max(v), len(v))
+    s.dump(args.work + ".turns", lib=args.label)
 
 
 def report(args):
-    lines = ["early fit bench: %d rays, 2 speakers, %.0f Hz, one context; median ms [min .. max] (n); calls: host clock to rvb_synchronize; "
-             "kernels: HIP events of rvb_last_timings" % (args.rays, args.sample_rate)]
+    t = Table()          # (rows a level deeper than the other benches': two more spaces in front of every label)
+    t.line("early fit bench: %d rays, 2 speakers, %.0f Hz, one context; median ms [min .. max] (n); calls: host clock to rvb_synchronize; "
+           "kernels: HIP events of rvb_last_timings" % (args.rays, args.sample_rate))
     for name in WORKLOADS:
-        rec = json.loads(open(args.work + "." + name).read())
-        s = rec["samples"]
-        lines.append("%s: %d triangles, %d surfaces, %d rays x %d reflections, %d candidates -> %d images, %d bins" %
-                     (name, rec["triangles"], rec["nsurfaces"], args.rays, rec["reflections"], rec["ncandidates"], rec["nimages"], rec["nbins"]))
-        lines.append("  (a) one forward evaluation, RVB_IR_ALL: rvb_reshade + configure + rvb_ir_accumulate(RVB_IR_EXACT)")
+        rec, = benchsteps.records(args.work + "." + name)
+        t.samples = rec["samples"]
+        t.line("%s: %d triangles, %d surfaces, %d rays x %d reflections, %d candidates -> %d images, %d bins" %
+               (name, rec["triangles"], rec["nsurfaces"], args.rays, rec["reflections"], rec["ncandidates"], rec["nimages"], rec["nbins"]))
+        t.line("  (a) one forward evaluation, RVB_IR_ALL: rvb_reshade + configure + rvb_ir_accumulate(RVB_IR_EXACT)")
         for key, label in (("host", "through the host merge (baseline)"), ("merged_first", "rvb_ir_configure_speakers_merged, first call"),
                            ("merged_later", "rvb_ir_configure_speakers_merged, later calls")):
-            lines.append("    %-56s %s" % (label, fmt(s[key])))
-            lines.append("    %-56s %s" % ("      its configure step", fmt(s[key + ":configure (host clock, not synchronised)"])))
-        host, later, first = (statistics.median(s[k]) for k in ("host", "merged_later", "merged_first"))
-        spread = max(s["host"]) - min(s["host"])
-        lines.append("    host / later = %.2f x, host / first = %.2f x; host - later = %.3f ms, the host path's repetitions spread over %.3f ms: %s" %
-                     (host / later, host / first, host - later, spread,
-                      "later calls are faster beyond that spread" if host - later > spread else
-                      "NOT faster beyond that spread (the evaluation is bound by the re-shade and the exact binning of the diffuse records)"))
-        lines.append("  (b) the gradients")
+            t.row("  " + label, key)
+            t.row("        its configure step", key + ":configure (host clock, not synchronised)")
+        host, later, first = (t.med(k) for k in ("host", "merged_later", "merged_first"))
+        spread = t.spread("host")
+        t.line("    host / later = %.2f x, host / first = %.2f x; host - later = %.3f ms, the host path's repetitions spread over %.3f ms: %s" %
+               (host / later, host / first, host - later, spread,
+                "later calls are faster beyond that spread" if host - later > spread else
+                "NOT faster beyond that spread (the evaluation is bound by the re-shade and the exact binning of the diffuse records)"))
+        t.line("  (b) the gradients")
         for key, label in (("grad_images", "rvb_reshade_grad_images"), ("grad", "rvb_reshade_grad")):
-            lines.append("    %-56s %s" % (label, fmt(s[key])))
-            for k in sorted(k for k in s if k.startswith(key + ":")):
-                lines.append("    %-56s %s" % ("      " + k.split(":", 1)[1], fmt(s[k])))
+            t.row("  " + label, key)
+            t.kernel_rows(None, key, indent="        ")
     if args.parent_lib:
-        turns = [json.loads(line) for line in open(args.work + ".turns")]
-        lines.append("(c) cathedral, this build and the parent commit's in processes that take turns (%d turns each, every sample of a library pooled)" % args.turns)
-        pooled = {}
-        for t in turns:
-            for k, v in t["samples"].items():
-                pooled.setdefault((t["lib"], k), []).extend(v)
+        t.samples = benchsteps.merge(benchsteps.records(args.work + ".turns"), key=lambda rec, k: (rec["lib"], k))
+        t.line("(c) cathedral, this build and the parent commit's in processes that take turns (%d turns each, every sample of a library pooled)" % args.turns)
         for key, label in (("trace", "rvb_trace, keeping on"), ("reshade", "rvb_reshade"), ("grad", "rvb_reshade_grad")):
-            for lib in ("parent", "this"):
-                lines.append("    %-56s %s" % ("%s, %s" % (label, lib), fmt(pooled[(lib, key)])))
-            p, t = pooled[("parent", key)], pooled[("this", key)]
-            diff, spread = statistics.median(t) - statistics.median(p), max(p) - min(p)
-            lines.append("      this - parent = %+.3f ms, the parent's own spread %.3f ms: %s" % (diff, spread, "inside" if abs(diff) <= spread else "OUTSIDE"))
-    text = "\n".join(lines)
-    print(text, flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+            parent, this = (t.row("  %s, %s" % (label, lib), (lib, key)) for lib in ("parent", "this"))
+            diff, spread = this - parent, t.spread(("parent", key))
+            t.line("      this - parent = %+.3f ms, the parent's own spread %.3f ms: %s" % (diff, spread, "inside" if abs(diff) <= spread else "OUTSIDE"))
+    t.emit(args.out)
+
+
+def build_steps(args):
+    steps = [("forward", ["--workload", name], None) for name in WORKLOADS]
+    if args.parent_lib:
+        steps += [("turn", ["--label", "parent"], args.parent_lib), ("turn", ["--label", "this"], None)] * args.turns
+    return (benchsteps.shape(args, "rays", "triangles", "sample_rate", "repeats", "warmup", "turns") +
+            (["--parent-lib", args.parent_lib] if args.parent_lib else []), steps)          # (the report asks whether there were turns)
 
 
 def main():
@@ -223,36 +180,12 @@ def main():
     p.add_argument("--rays", type=int, default=100000)
     p.add_argument("--triangles", type=int, default=75000)
     p.add_argument("--sample-rate", type=float, default=44100.0)
-    p.add_argument("--repeats", type=int, default=21)
-    p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--turns", type=int, default=3)
-    p.add_argument("--parent-lib", default=None)
-    p.add_argument("--step-timeout", type=int, default=240)
-    p.add_argument("--out", default=None)
-    p.add_argument("--step", default=None, help=argparse.SUPPRESS)
+    benchsteps.add_common_arguments(p, repeats=21, warmup=3, step_timeout=240, parent_lib=True, help={})
     p.add_argument("--workload", default=None, help=argparse.SUPPRESS)
     p.add_argument("--label", default=None, help=argparse.SUPPRESS)
-    p.add_argument("--work", default=None, help=argparse.SUPPRESS)
     args = p.parse_args()
-    if args.step == "report":
-        return report(args)
-    if args.step == "forward":
-        return step_forward(args)
-    if args.step == "turn":
-        return step_turn(args)
-    work = os.path.join(tempfile.mkdtemp(prefix="early_fit_bench_"), "samples")
-    shape = ["--rays", str(args.rays), "--triangles", str(args.triangles), "--sample-rate", str(args.sample_rate), "--repeats", str(args.repeats),
-             "--warmup", str(args.warmup), "--turns", str(args.turns)]
-    me = " ".join(shlex.quote(x) for x in [sys.executable, os.path.abspath(__file__)] + shape)
-    limit = "timeout -k 10 %d " % args.step_timeout
-    parts = ["%s%s --step forward --workload %s --work %s" % (limit, me, name, shlex.quote(work + "." + name)) for name in WORKLOADS]
-    if args.parent_lib:
-        for _ in range(args.turns):
-            parts.append("RVB_LIB=%s %s%s --step turn --label parent --work %s" % (shlex.quote(os.path.abspath(args.parent_lib)), limit, me, shlex.quote(work + ".turns")))
-            parts.append("%s%s --step turn --label this --work %s" % (limit, me, shlex.quote(work + ".turns")))
-    parts.append("%s --step report --work %s%s%s" % (me, shlex.quote(work), " --parent-lib " + shlex.quote(args.parent_lib) if args.parent_lib else "",
-                                                     " --out " + shlex.quote(args.out) if args.out else ""))
-    return subprocess.call(["bash", "-c", " && ".join(parts)])
+    return benchsteps.run(args, {"forward": step_forward, "turn": step_turn}, report, build_steps)
 
 
 if __name__ == "__main__":

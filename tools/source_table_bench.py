@@ -16,17 +16,10 @@ them ended well.
     python tools/source_table_bench.py [--parent-lib PATH] [--rays N] [--reflections K] [--triangles T] [--repeats R] [--rounds M] [--out FILE]
 """
 import argparse
-import json
-import os
-import shlex
-import statistics
-import subprocess
 import sys
-import tempfile
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchsteps
+from benchsteps import Samples, Table
 
 FACING, UP = (0.6, 0.0, 0.8), (0.0, 1.0, 0.0)
 
@@ -34,25 +27,13 @@ FACING, UP = (0.6, 0.0, 0.8), (0.0, 1.0, 0.0)
 def step(args):
     """One GPU process: --step this | parent.  Appends one JSON line of raw samples to the work file."""
     import numpy as np
-    import rvb_import
-    rvb_import.load()
+    benchsteps.load_library()
     from parallel_reverb_raytracer_amd import capi, dtypes, scenes
     air = dtypes.AIR_COEFFICIENTS
     scene, info = scenes.cathedral(args.triangles)
     mic, src = info["mic"], info["source"]
     dirs = scenes.sphere_directions(args.rays, seed=1)
-    samples = {}
-
-    def note(name, value):
-        samples.setdefault(name, []).append(float(value))
-
-    def timed(ctx, prefix):
-        t0 = time.perf_counter()
-        ctx.trace(mic, src, args.reflections, air)
-        ctx.synchronize()
-        note(prefix, (time.perf_counter() - t0) * 1e3)
-        for k, v in ctx.last_timings():
-            note(prefix + ":" + k, v)
+    s = Samples()
 
     off = capi.Context(0)
     off.set_scene(scene)
@@ -68,72 +49,47 @@ def step(args):
         pattern.set_source_pattern(FACING, shape)
         table.set_source_table(directivity.table_from_function(directivity.polar_pattern(shape)), FACING, UP)
         variants += [("p", pattern), ("t", table)]
-    for rep in range(args.warmup + args.repeats):
-        if rep == args.warmup:
-            samples.clear()
+    for rep in s.repetitions(args.warmup, args.repeats):
         for name, c in variants:
-            timed(c, name)
+            s.timed(name, lambda: c.trace(mic, src, args.reflections, air), c.synchronize, c.last_timings)
     for _, c in reversed(variants):
         c.close()
-    with open(args.work, "a") as f:
-        f.write(json.dumps({"step": args.step, "lib": capi.LIB_PATH, "samples": samples}) + "\n")
+    s.dump(args.work, step=args.step, lib=capi.LIB_PATH)
 
 
 def report(args):
-    merged = {}
-    for line in open(args.work):
-        rec = json.loads(line)
-        for k, v in rec["samples"].items():
-            merged.setdefault((rec["step"], k), []).extend(v)
+    t = Table.load(args.work)
     nrecords = args.rays * args.reflections
-    lines = ["source table bench: %d rays x %d reflections = %d records (%.0f MB of records, %.1f MB of per-ray gains), cathedral %d triangles, "
-             "one context per variant" % (args.rays, args.reflections, nrecords, nrecords * 64 / 1e6, args.rays * 32 / 1e6, args.triangles),
-             "median ms [min .. max] (n); calls: host clock to rvb_synchronize; kernels: HIP events of rvb_last_timings"]
-
-    def med(key):
-        return statistics.median(merged[key]) if key in merged else None
-
-    def spread(key):
-        return max(merged[key]) - min(merged[key])
-
-    def row(label, key):
-        if key not in merged:
-            lines.append("  %-58s not measured" % label)
-            return
-        v = merged[key]
-        lines.append("  %-58s %8.3f [%.3f .. %.3f] (%d)" % (label, statistics.median(v), min(v), max(v), len(v)))
-
-    row("(a) rvb_trace, directivity off, this library", ("this", "a"))
-    row("(a) rvb_trace, directivity off, parent library", ("parent", "a"))
-    for k in sorted(k for s, k in merged if s == "this" and k.startswith("a:")):
-        row("      " + k[2:] + " (this)", ("this", k))
-        row("      " + k[2:] + " (parent)", ("parent", k))
-    row("(p) rvb_trace, polar pattern", ("this", "p"))
-    row("      source_pattern_kernel", ("this", "p:source_pattern_kernel"))
-    row("(t) rvb_trace, table", ("this", "t"))
-    row("      source_table_rays_kernel", ("this", "t:source_table_rays_kernel"))
-    row("      source_table_kernel", ("this", "t:source_table_kernel"))
-    lines.append("bars:")
-    a, ap = med(("this", "a")), med(("parent", "a"))
+    t.line("source table bench: %d rays x %d reflections = %d records (%.0f MB of records, %.1f MB of per-ray gains), cathedral %d triangles, "
+           "one context per variant" % (args.rays, args.reflections, nrecords, nrecords * 64 / 1e6, args.rays * 32 / 1e6, args.triangles))
+    t.line("median ms [min .. max] (n); calls: host clock to rvb_synchronize; kernels: HIP events of rvb_last_timings")
+    t.row("(a) rvb_trace, directivity off, this library", ("this", "a"))
+    t.row("(a) rvb_trace, directivity off, parent library", ("parent", "a"))
+    for k in t.kernels("this", "a"):
+        t.row("      " + k + " (this)", ("this", "a:" + k))
+        t.row("      " + k + " (parent)", ("parent", "a:" + k))
+    t.row("(p) rvb_trace, polar pattern", ("this", "p"))
+    t.row("      source_pattern_kernel", ("this", "p:source_pattern_kernel"))
+    t.row("(t) rvb_trace, table", ("this", "t"))
+    t.row("      source_table_rays_kernel", ("this", "t:source_table_rays_kernel"))
+    t.row("      source_table_kernel", ("this", "t:source_table_kernel"))
+    t.line("bars:")
+    a, ap = t.med(("this", "a")), t.med(("parent", "a"))
     if a is not None and ap is not None:
-        s = spread(("parent", "a"))
-        lines.append("  directivity off against the parent: %.3f ms against %.3f ms, difference %+.3f ms, %s the spread of the parent's repetitions, "
-                     "%.3f ms (max - min)" % (a, ap, a - ap, "within" if abs(a - ap) <= s else "OUTSIDE", s))
-    kp, kt, kr = med(("this", "p:source_pattern_kernel")), med(("this", "t:source_table_kernel")), med(("this", "t:source_table_rays_kernel"))
+        s = t.spread(("parent", "a"))
+        t.line("  directivity off against the parent: %.3f ms against %.3f ms, difference %+.3f ms, %s the spread of the parent's repetitions, "
+               "%.3f ms (max - min)" % (a, ap, a - ap, "within" if abs(a - ap) <= s else "OUTSIDE", s))
+    kp, kt, kr = (t.med(("this", k)) for k in ("p:source_pattern_kernel", "t:source_table_kernel", "t:source_table_rays_kernel"))
     if kp is not None and kt is not None:
-        s = spread(("this", "p:source_pattern_kernel"))
-        lines.append("  source_table_kernel against source_pattern_kernel: %.3f ms against %.3f ms, difference %+.3f ms; spread of the pattern kernel "
-                     "%.3f ms (max - min): the table pass is %s" % (kt, kp, kt - kp, s, "SLOWER by more than the spread" if kt - kp > s else "not slower by more than the spread"))
-        lines.append("  both move 128 B per record (64 read, 64 written): pattern %.2f TB/s, table %.2f TB/s; the row selections of all rays take %.3f ms" %
-                     (nrecords * 128 / (kp * 1e-3) / 1e12, nrecords * 128 / (kt * 1e-3) / 1e12, kr))
-    p, t = med(("this", "p")), med(("this", "t"))
-    if a is not None and p is not None and t is not None:
-        lines.append("  a directivity costs a trace: pattern %+.3f ms, table %+.3f ms" % (p - a, t - a))
-    text = "\n".join(lines)
-    print(text, flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+        s = t.spread(("this", "p:source_pattern_kernel"))
+        t.line("  source_table_kernel against source_pattern_kernel: %.3f ms against %.3f ms, difference %+.3f ms; spread of the pattern kernel "
+               "%.3f ms (max - min): the table pass is %s" % (kt, kp, kt - kp, s, "SLOWER by more than the spread" if kt - kp > s else "not slower by more than the spread"))
+        t.line("  both move 128 B per record (64 read, 64 written): pattern %.2f TB/s, table %.2f TB/s; the row selections of all rays take %.3f ms" %
+               (nrecords * 128 / (kp * 1e-3) / 1e12, nrecords * 128 / (kt * 1e-3) / 1e12, kr))
+    p, tb = t.med(("this", "p")), t.med(("this", "t"))
+    if a is not None and p is not None and tb is not None:
+        t.line("  a directivity costs a trace: pattern %+.3f ms, table %+.3f ms" % (p - a, tb - a))
+    t.emit(args.out)
 
 
 def main():
@@ -141,33 +97,11 @@ def main():
     p.add_argument("--rays", type=int, default=100000)
     p.add_argument("--reflections", type=int, default=128)
     p.add_argument("--triangles", type=int, default=75000)
-    p.add_argument("--repeats", type=int, default=12, help="per round and library (>= 20 in all with the default two rounds)")
-    p.add_argument("--warmup", type=int, default=3)
-    p.add_argument("--rounds", type=int, default=2)
-    p.add_argument("--parent-lib", default=None, help="librvb_hip.so built from the commit before the feature")
-    p.add_argument("--step-timeout", type=int, default=240)
-    p.add_argument("--out", default=None)
-    p.add_argument("--step", default=None, help=argparse.SUPPRESS)
-    p.add_argument("--work", default=None, help=argparse.SUPPRESS)
+    benchsteps.add_common_arguments(p, repeats=12, warmup=3, step_timeout=240, parent_lib=True, rounds=2,
+                                    help=dict(benchsteps.HELP, repeats="per round and library (>= 20 in all with the default two rounds)"))
     args = p.parse_args()
-    if args.step == "report":
-        return report(args)
-    if args.step:
-        return step(args)
-    work = os.path.join(tempfile.mkdtemp(prefix="source_table_bench_"), "samples.jsonl")
-    shape = ["--rays", str(args.rays), "--reflections", str(args.reflections), "--triangles", str(args.triangles),
-             "--repeats", str(args.repeats), "--warmup", str(args.warmup), "--work", work]
-    me = [sys.executable, os.path.abspath(__file__)]
-    steps = []
-    for _ in range(args.rounds):
-        steps.append(("", "this"))
-        if args.parent_lib:
-            steps.append(("RVB_LIB=%s " % shlex.quote(os.path.abspath(args.parent_lib)), "parent"))
-    parts = []
-    for env, name in steps:      # every GPU step under a time limit of its own; a step that fails ends the chain
-        parts.append("%stimeout -k 10 %d %s" % (env, args.step_timeout, " ".join(shlex.quote(x) for x in me + shape + ["--step", name])))
-    parts.append(" ".join(shlex.quote(x) for x in me + shape + ["--step", "report"] + (["--out", args.out] if args.out else [])))
-    return subprocess.call(["bash", "-c", " && ".join(parts)])
+    return benchsteps.run(args, dict.fromkeys(("this", "parent"), step), report, lambda args: (
+        benchsteps.shape(args, "rays", "reflections", "triangles", "repeats", "warmup"), benchsteps.in_turn(args.rounds, args.parent_lib)))
 
 
 if __name__ == "__main__":

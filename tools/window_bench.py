@@ -19,16 +19,11 @@ the steps are chained with &&, and the table is written (--out) only when all of
 import argparse
 import ctypes
 import json
-import os
-import shlex
-import statistics
-import subprocess
 import sys
-import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchsteps
+from benchsteps import Samples, Table
 
 OTHER_MIC = (-10.28, 3.85, -2.24)
 HBM_TBS = 6.6                 # the streaming rate the floor of the score pass is taken at
@@ -37,8 +32,7 @@ HBM_TBS = 6.6                 # the streaming rate the floor of the score pass i
 def step(args):
     """One GPU process: --step window | routes | this | parent.  Appends one JSON line of raw samples to the work file."""
     import numpy as np
-    import rvb_import
-    rvb_import.load()
+    benchsteps.load_library()
     from parallel_reverb_raytracer_amd import capi, dtypes, scenes
     if args.step == "parent":
         capi._WINDOW_SIGNATURES.clear()                                     # (the parent's library does not export them)
@@ -46,29 +40,19 @@ def step(args):
     scene, info = scenes.cathedral(args.triangles)
     mic, src = info["mic"], info["source"]
     dirs = scenes.sphere_directions(args.rays, seed=1)
-    samples, facts = {}, {}
-
-    def note(name, value):
-        samples.setdefault(name, []).append(float(value))
+    s, facts = Samples(), {}
+    note = s.note
 
     ctx = capi.Context(0)
     ctx.set_scene(scene)
     ctx.set_directions(dirs)
     ctx.keep_paths(True, listener=True)
 
-    def timed(prefix, call, sync=True):
-        t0 = time.perf_counter()
-        call()
-        if sync:
-            ctx.synchronize()
-        note(prefix, (time.perf_counter() - t0) * 1e3)
-        for k, v in ctx.last_timings():
-            note(prefix + ":" + k, v)
+    def timed(name, call):
+        s.timed(name, call, ctx.synchronize, ctx.last_timings)
 
     if args.step in ("this", "parent"):
-        for rep in range(args.warmup + args.repeats):
-            if rep == args.warmup:
-                samples.clear()
+        for rep in s.repetitions(args.warmup, args.repeats):
             timed("trace", lambda: ctx.trace(mic, src, args.reflections, air))
             timed("reshade", lambda: ctx.reshade(None, air))
             timed("relisten", lambda: ctx.relisten(OTHER_MIC))
@@ -94,12 +78,12 @@ def step(args):
             count, inside = ctypes.c_uint64(0), ctypes.c_uint64(0)
             for name, (t0, t1) in windows.items():
                 for k in (64, 1024):
-                    for rep in range(args.warmup + args.repeats):
-                        if rep == args.warmup:
-                            for key in [key for key in samples if key.startswith("w %s %d" % (name, k))]:
-                                del samples[key]
-                        timed("w %s %d" % (name, k), lambda: ctx._check(ctx.lib.rvb_window_paths(
-                            ctx.handle, t0, t1, None, k, args.reflections, d_paths, d_hits, ctypes.byref(count), ctypes.byref(inside))), sync=False)
+                    part = Samples()                                        # a warm-up per window and list length; the call is synchronous
+                    for rep in part.repetitions(args.warmup, args.repeats):
+                        part.timed("w %s %d" % (name, k), lambda: ctx._check(ctx.lib.rvb_window_paths(
+                            ctx.handle, t0, t1, None, k, args.reflections, d_paths, d_hits, ctypes.byref(count), ctypes.byref(inside))),
+                            lambda: None, ctx.last_timings)
+                    s.samples.update(part.samples)
                     facts["in_window %s" % name] = inside.value
                     facts["count %s %d" % (name, k)] = count.value
                     if (name, k) == ("q25_q75", 1024):                      # the list the routes step makes on the host
@@ -153,72 +137,54 @@ def step(args):
                     note("t", (time.perf_counter() - t) * 1e3)
             facts["torch_top_set_equals_host"] = sorted(int(i) for i in out.indices.cpu()) == sorted(facts["host_top"])
     ctx.close()
-    with open(args.work, "a") as f:
-        f.write(json.dumps({"step": args.step, "lib": capi.LIB_PATH, "samples": samples, "facts": facts}) + "\n")
+    s.dump(args.work, step=args.step, lib=capi.LIB_PATH, facts=facts)
 
 
 def report(args):
-    merged, facts = {}, {}
-    for line in open(args.work):
-        rec = json.loads(line)
+    recs, facts = benchsteps.records(args.work), {}
+    for rec in recs:
         facts.setdefault(rec["step"], {}).update(rec["facts"])
-        for k, v in rec["samples"].items():
-            merged.setdefault((rec["step"], k), []).extend(v)
+    t = Table(benchsteps.merge(recs), label=66, value=9)
     nrecords = args.rays * args.reflections
-    lines = ["window bench: %d rays x %d reflections = %d records (%.0f MB), cathedral %d triangles, one context, trace kept with RVB_KEEP_LISTENER"
-             % (args.rays, args.reflections, nrecords, nrecords * 64 / 1e6, args.triangles),
-             "median ms [min .. max] (n); calls: host clock around the call (window calls are synchronous, the others run to rvb_synchronize); "
-             "kernels: HIP events of rvb_last_timings",
-             "floor of the score pass: %.0f MB at %.1f TB/s = %.3f ms" % (nrecords * 64 / 1e6, HBM_TBS, nrecords * 64 / (HBM_TBS * 1e12) * 1e3)]
-
-    def row(label, key):
-        if key not in merged:
-            lines.append("  %-66s not measured" % label)
-            return None
-        v = merged[key]
-        lines.append("  %-66s %9.3f [%.3f .. %.3f] (%d)" % (label, statistics.median(v), min(v), max(v), len(v)))
-        return statistics.median(v)
-
+    t.line("window bench: %d rays x %d reflections = %d records (%.0f MB), cathedral %d triangles, one context, trace kept with RVB_KEEP_LISTENER"
+           % (args.rays, args.reflections, nrecords, nrecords * 64 / 1e6, args.triangles))
+    t.line("median ms [min .. max] (n); calls: host clock around the call (window calls are synchronous, the others run to rvb_synchronize); "
+           "kernels: HIP events of rvb_last_timings")
+    t.line("floor of the score pass: %.0f MB at %.1f TB/s = %.3f ms" % (nrecords * 64 / 1e6, HBM_TBS, nrecords * 64 / (HBM_TBS * 1e12) * 1e3))
     w = facts.get("window", {})
     if w:
-        lines.append("records %d, live %d; windows %s" % (w["records"], w["live"], json.dumps(w["windows"])))
+        t.line("records %d, live %d; windows %s" % (w["records"], w["live"], json.dumps(w["windows"])))
     for name in ("50ms", "q25_q75", "whole"):
         for k in (64, 1024):
             prefix = "w %s %d" % (name, k)
-            if ("window", prefix) not in merged:
+            if ("window", prefix) not in t.samples:
                 continue
-            row("(w) rvb_window_paths, %s, max_paths %d (in window %s, listed %s)" % (name, k, w.get("in_window %s" % name), w.get("count %s %d" % (name, k))),
-                ("window", prefix))
-            kernels = sorted((key for step_, key in merged if step_ == "window" and key.startswith(prefix + ":")),
-                             key=lambda key: -statistics.median(merged[("window", key)]))
-            for key in kernels:
-                row("      " + key[len(prefix) + 1:], ("window", key))
+            t.row("(w) rvb_window_paths, %s, max_paths %d (in window %s, listed %s)" % (name, k, w.get("in_window %s" % name), w.get("count %s %d" % (name, k))),
+                  ("window", prefix))
+            kernels = sorted(t.kernels("window", prefix), key=lambda kernel: -t.med(("window", prefix + ":" + kernel)))       # the longest first
+            for kernel in kernels:
+                t.row("      " + kernel, ("window", prefix + ":" + kernel))
             if kernels:
-                top = kernels[0]
-                score = statistics.median(merged[("window", prefix + ":window_score_kernel")])
-                lines.append("      bound by %s; the score pass streams %.2f TB/s" % (top[len(prefix) + 1:], nrecords * 64 / (score * 1e-3) / 1e12))
+                t.line("      bound by %s; the score pass streams %.2f TB/s" %
+                       (kernels[0], nrecords * 64 / (t.med(("window", prefix + ":window_score_kernel")) * 1e-3) / 1e12))
     r = facts.get("routes", {})
     if r:
-        lines.append("the same query ([q25, q75), 1024 entries) without the feature:")
-        row("(t) torch: score, mask, torch.topk over %s" % r.get("torch_input"), ("routes", "t"))
-        row("(h) rvb_get_diffuse + numpy (argpartition, sort of the winners)", ("routes", "h"))
-        row("      of which the copy of the records to the host", ("routes", "h copy"))
-        lines.append("  torch's 1024 are the host's 1024 as a set: %s" % r.get("torch_top_set_equals_host"))
+        t.line("the same query ([q25, q75), 1024 entries) without the feature:")
+        t.row("(t) torch: score, mask, torch.topk over %s" % r.get("torch_input"), ("routes", "t"))
+        t.row("(h) rvb_get_diffuse + numpy (argpartition, sort of the winners)", ("routes", "h"))
+        t.row("      of which the copy of the records to the host", ("routes", "h copy"))
+        t.line("  torch's 1024 are the host's 1024 as a set: %s" % r.get("torch_top_set_equals_host"))
         if "gpu_top" in w and "host_top" in r:
-            lines.append("  rvb_window_paths' 1024 are the host's 1024, in the same order: %s" % (w["gpu_top"] == r["host_top"]))
-    if any(step_ == "parent" for step_, _ in merged):
-        lines.append("unchanged paths against a build of the parent commit (processes in turn):")
+            t.line("  rvb_window_paths' 1024 are the host's 1024, in the same order: %s" % (w["gpu_top"] == r["host_top"]))
+    if any(step_ == "parent" for step_, _ in t.samples):
+        t.line("unchanged paths against a build of the parent commit (processes in turn):")
         for call in ("trace", "reshade", "relisten"):
-            a, b = row("(a) rvb_%s, this library" % call, ("this", call)), row("(a) rvb_%s, parent library" % call, ("parent", call))
+            a, b = t.row("(a) rvb_%s, this library" % call, ("this", call)), t.row("(a) rvb_%s, parent library" % call, ("parent", call))
             if a is not None and b is not None:
-                spread = max(merged[("parent", call)]) - min(merged[("parent", call)])
-                lines.append("      %.3f against %.3f ms, difference %+.3f ms; spread of the parent's repetitions %.3f ms (max - min): %s" %
-                             (a, b, a - b, spread, "inside" if abs(a - b) <= spread else "OUTSIDE"))
-    text = "\n".join(lines)
-    print(text, flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+                spread = t.spread(("parent", call))
+                t.line("      %.3f against %.3f ms, difference %+.3f ms; spread of the parent's repetitions %.3f ms (max - min): %s" %
+                       (a, b, a - b, spread, "inside" if abs(a - b) <= spread else "OUTSIDE"))
+    t.emit(args.out)
 
 
 def main():
@@ -226,33 +192,11 @@ def main():
     p.add_argument("--rays", type=int, default=100000)
     p.add_argument("--reflections", type=int, default=128)
     p.add_argument("--triangles", type=int, default=75000)
-    p.add_argument("--repeats", type=int, default=21)
-    p.add_argument("--warmup", type=int, default=3)
-    p.add_argument("--rounds", type=int, default=2)
-    p.add_argument("--parent-lib", default=None, help="librvb_hip.so built from the commit before the feature")
-    p.add_argument("--step-timeout", type=int, default=240)
-    p.add_argument("--out", default=None)
-    p.add_argument("--step", default=None, help=argparse.SUPPRESS)
-    p.add_argument("--work", default=None, help=argparse.SUPPRESS)
+    benchsteps.add_common_arguments(p, repeats=21, warmup=3, step_timeout=240, parent_lib=True, rounds=2)
     args = p.parse_args()
-    if args.step == "report":
-        return report(args)
-    if args.step:
-        return step(args)
-    work = os.path.join(tempfile.mkdtemp(prefix="window_bench_"), "samples.jsonl")
-    shape = ["--rays", str(args.rays), "--reflections", str(args.reflections), "--triangles", str(args.triangles),
-             "--repeats", str(args.repeats), "--warmup", str(args.warmup), "--work", work]
-    me = [sys.executable, os.path.abspath(__file__)]
-    steps = [("", "window"), ("", "routes")]
-    if args.parent_lib:
-        for _ in range(args.rounds):
-            steps.append(("", "this"))
-            steps.append(("RVB_LIB=%s " % shlex.quote(os.path.abspath(args.parent_lib)), "parent"))
-    parts = []
-    for env, name in steps:      # every GPU step under a time limit of its own; a step that fails ends the chain
-        parts.append("%stimeout -k 10 %d %s" % (env, args.step_timeout, " ".join(shlex.quote(x) for x in me + shape + ["--step", name])))
-    parts.append(" ".join(shlex.quote(x) for x in me + shape + ["--step", "report"] + (["--out", args.out] if args.out else [])))
-    return subprocess.call(["bash", "-c", " && ".join(parts)])
+    return benchsteps.run(args, dict.fromkeys(("window", "routes", "this", "parent"), step), report, lambda args: (
+        benchsteps.shape(args, "rays", "reflections", "triangles", "repeats", "warmup"),
+        [("window", [], None), ("routes", [], None)] + (benchsteps.in_turn(args.rounds, args.parent_lib) if args.parent_lib else [])))
 
 
 if __name__ == "__main__":
