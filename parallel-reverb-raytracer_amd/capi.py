@@ -161,6 +161,16 @@ WINDOW_ENTRY = np.dtype([("record", "<u8"), ("score", "<f4"), ("time", "<f4")])
 WINDOW_PATH = np.dtype([("ray", "<u8"), ("bounce", "<u4"), ("nhits", "<u4"), ("score", "<f4"), ("time", "<f4"), ("pad_", "<f4", (2,)),
                         ("volume", "<f4", (NUM_BANDS,))])
 WINDOW_HIT = np.dtype([("position", "<f4", (3,)), ("triangle", "<u4")])
+# ... and of include/rvb_capi_speech.h, modulation transfer and the speech transmission index (tests/test_speech_header_host.py)
+_SPEECH_SIGNATURES = {
+    "rvb_mtf": (_i, _vp, _vp, _u64, _u64, _f, _vp, _u64, _vp, _vp),
+    "rvb_mtf_adjoint": (_i, _vp, _vp, _u64, _u64, _f, _vp, _u64, _vp, _vp),
+    "rvb_speech_index": (_i, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp),
+}
+SPEECH_SYMBOLS = list(_SPEECH_SIGNATURES)
+MTF_MAX_FREQS = 16
+STI_BANDS = 7
+STI_FREQS = 14
 _lib = None
 
 
@@ -186,7 +196,7 @@ def load_library():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _IMAGE_SIGNATURES, _LIVE_SIGNATURES, _WINDOW_SIGNATURES):
+        for table in (_SIGNATURES, _IMAGE_SIGNATURES, _LIVE_SIGNATURES, _WINDOW_SIGNATURES, _SPEECH_SIGNATURES):
             for name, (restype, *argtypes) in table.items():
                 function = getattr(lib, name)
                 function.restype, function.argtypes = restype, argtypes
@@ -296,6 +306,25 @@ def merge_images(candidates, direct, remove_direct):
     d = np.ascontiguousarray(direct, dtype=IMPULSE) if direct is not None else None
     return _query_then_fill(_merge_check, lib.rvb_merge_images, (_ptr(cand), cand.shape[0], _ptr(d), int(remove_direct)),
                             lambda count: np.zeros(count, dtype=IMPULSE))
+
+
+def speech_index(mtf, alpha, beta, snr_db=None, want_derivative=False):
+    """(sti, mti float64 [7]) or, with want_derivative, (sti, mti, dSTI/dmtf float64 [7][nfreqs]) of a matrix mtf [7][nfreqs] of modulation
+    transfer values, band k in row k (rvb_speech_index: host arithmetic in binary64, no context and no GPU).  alpha [7] and beta [6] are
+    the band weights and the redundancy weights, snr_db [7] the signal-to-noise ratios in dB (None: noiseless, +inf for a band likewise).
+    A NaN in mtf gives a NaN index."""
+    mtf = np.ascontiguousarray(mtf, dtype=np.float64)
+    assert mtf.ndim == 2 and mtf.shape[0] == STI_BANDS, "mtf: float64 [7][nfreqs]"
+    alpha = np.ascontiguousarray(alpha, dtype=np.float64).reshape(STI_BANDS)
+    beta = np.ascontiguousarray(beta, dtype=np.float64).reshape(STI_BANDS - 1)
+    snr = None if snr_db is None else np.ascontiguousarray(snr_db, dtype=np.float64).reshape(STI_BANDS)
+    sti = ctypes.c_double(0.0)
+    mti = np.zeros(STI_BANDS, dtype=np.float64)
+    derivative = np.zeros(mtf.shape, dtype=np.float64) if want_derivative else None
+    rc = load_library().rvb_speech_index(_ptr(mtf), mtf.shape[1], _ptr(snr), _ptr(alpha), _ptr(beta), ctypes.byref(sti), _ptr(mti), _ptr(derivative))
+    if rc != OK:
+        raise RvbError(rc, "rvb_speech_index: a required array is missing, or nfreqs is 0 or above %d" % MTF_MAX_FREQS)
+    return (sti.value, mti, derivative) if want_derivative else (sti.value, mti)
 
 
 class _Handle:
@@ -736,6 +765,26 @@ class Context(_Handle):
         finally:
             free_paths()
         return paths, hits, inside.value
+
+    # ---- modulation transfer (include/rvb_capi_speech.h): device arrays of nrows rows of nbins floats, the caller's own -------------
+    def mtf(self, device_histogram_pointer, nrows, nbins, sample_rate, mod_freqs, want_sums=False):
+        """float64 [nrows][nfreqs]: m(F) = |sum_j H_j^2 exp(-2 pi i F j / fs)| / sum_j H_j^2 of every row at the modulation frequencies
+        mod_freqs in Hz (rvb_mtf): binary64 sums in a fixed order, NaN in an all-zero row.  With want_sums (mtf, sums), sums float64
+        [nrows][1 + 2 nfreqs] = S, A_0, B_0, A_1, ...  Synchronous."""
+        freqs = np.ascontiguousarray(mod_freqs, dtype=np.float64).reshape(-1)
+        out = np.zeros((int(nrows), freqs.shape[0]), dtype=np.float64)
+        sums = np.zeros((int(nrows), 1 + 2 * freqs.shape[0]), dtype=np.float64) if want_sums else None
+        self._check(self.lib.rvb_mtf(self.handle, device_histogram_pointer or None, int(nrows), int(nbins), sample_rate, _ptr(freqs), freqs.shape[0],
+                                     _ptr(out), _ptr(sums)))
+        return (out, sums) if want_sums else out
+
+    def mtf_adjoint(self, device_histogram_pointer, nrows, nbins, sample_rate, mod_freqs, coeffs, device_weights_pointer):
+        """w = dL/dH in H's layout at device_weights_pointer (float32 [nrows][nbins], every entry written) for a loss with coeffs
+        [nrows][nfreqs] = dL/dm (rvb_mtf_adjoint): what reshade_grad, reshade_grad_images and reshade_grad_map take.  Synchronous."""
+        freqs = np.ascontiguousarray(mod_freqs, dtype=np.float64).reshape(-1)
+        coeffs = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(int(nrows), freqs.shape[0])
+        self._check(self.lib.rvb_mtf_adjoint(self.handle, device_histogram_pointer or None, int(nrows), int(nbins), sample_rate, _ptr(freqs),
+                                             freqs.shape[0], _ptr(coeffs), device_weights_pointer or None))
 
     def export_tensor_to_host(self, tensor, pinned_host_tensor):
         """Enqueues, behind the binning, the copy of a device tensor (the histogram ir_accumulate_tensor filled) into a PINNED host

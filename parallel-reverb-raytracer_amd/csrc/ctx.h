@@ -11,6 +11,7 @@
 //   decay.hip    decay curves, reverberation times and the decay loss on the caller's device arrays
 //   images.hip   include/rvb_capi_images.h: the merged image list made on the device (MergedImages below, over merged_state.h), the
 //                image-source part of the material gradient
+//   speech.hip   include/rvb_capi_speech.h: modulation transfer, its adjoint and the speech transmission index (speech_kernels.hip, speech_index.h)
 //   window.hip   include/rvb_capi_window.h: the strongest records behind a time window and their paths (window_kernels.hip, over window_select.h)
 // No compute happens in them and nothing falls back to the CPU: every entry point that produces results launches HIP kernels:
 //   the trace         trace_kernels.hip, image_kernels.hip, shadow_kernels.hip, source_kernels.hip
@@ -436,6 +437,8 @@ struct rvb_ctx {
     // rvb_window_* (csrc/window.hip): the select's state and tables, the listed entries, a key per record; a block of its own for the
     // same reason
     DevBuf window_scratch;
+    // rvb_mtf* (csrc/speech.hip): per-tile sums, per-row results and coefficients; a block of its own for the same reason
+    DevBuf speech_scratch;
     std::vector<Timing> timings;
     std::vector<Event> event_pool;
     size_t events_used = 0;

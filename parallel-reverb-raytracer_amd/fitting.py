@@ -1,4 +1,5 @@
-"""Fitting materials to a measured decay — a decay curve (fit_decay) or a table of room acoustic parameters (fit_params): the loop a user of rvb_reshade / rvb_reshade_grad would otherwise write (include/rvb_capi.h).
+"""Fitting materials to a measured decay — a decay curve (fit_decay), a table of room acoustic parameters (fit_params) or a target speech
+transmission index (fit_sti): the loop a user of rvb_reshade / rvb_reshade_grad would otherwise write (include/rvb_capi.h).
 
 One evaluation never leaves the device but for a few floats per row:
 
@@ -8,6 +9,7 @@ One evaluation never leaves the device but for a few floats per row:
     decay_curve(H) -> E                          Schroeder integral
     decay_loss(H, E, target, mask) -> L, w       w = dL/dH in H's layout
       or decay_params_loss(H, E, targets, param_weights) -> L, w, params      against measured EDT, T20, T30, C50, C80, D50, Ts
+      or mtf(H) -> speech_index -> L, dL/dm -> mtf_adjoint(H, dL/dm) -> w   against a target speech transmission index (fit_sti)
     reshade_grad(w) -> dL/dtable, dL/dair        chain rule through the binning
     (reshade_grad_map(w) -> dL/dtable per TRIANGLE: decay_sensitivity_map, "where on the walls"; needs keep_paths(True, listener=True))
 
@@ -22,7 +24,7 @@ with which=IR_ALL the whole response; the per-triangle map takes IR_DIFFUSE only
 (numpy arrays are uploaded): the target a decay curve in linear energy, the mask >= 0 and zero outside the evaluation range."""
 import numpy as np
 
-from . import capi
+from . import capi, speech
 from .dtypes import SURFACE, aligned_copy
 
 
@@ -239,3 +241,83 @@ def fit_params(ctx, table, air, mic, speakers, targets, param_weights, sample_ra
     return _fit(ctx, table, air, free, steps, lower, upper,
                 lambda candidate: _evaluate_params(ctx, candidate, *args, True, which, remove_direct)[:2],
                 lambda candidate: _evaluate_params(ctx, candidate, *args, False, which, remove_direct)[0])
+
+
+# ---- fitting to a target speech transmission index (include/rvb_capi_speech.h) --------------------------------------------------------
+
+def _histogram(ctx, table, air, mic, speakers, sample_rate, predelay, nbins, which, remove_direct):
+    """_histogram_and_curve without the curve: re-shade, bin exactly."""
+    import torch
+    assert which in (capi.IR_DIFFUSE, capi.IR_IMAGES, capi.IR_ALL)
+    ctx.reshade(table, air)
+    _configure(ctx, mic, speakers, which, remove_direct)
+    hist = torch.zeros((ctx.nchannels, 8, int(nbins)), dtype=torch.float32, device="cuda")
+    ctx.ir_accumulate_tensor(predelay, sample_rate, nbins, capi.IR_EXACT, hist)      # (waits for torch's stream: the zero fill)
+    return hist
+
+
+def _sti_forward(ctx, table, air, mic, speakers, targets, channel_weights, sample_rate, predelay, nbins, snr_db, want_weights, which, remove_direct):
+    """(loss, sti, hist, weights): L = sum_c channel_weights_c (STI_c - targets_c)^2 and, if wanted, w = dL/dH as a tensor of H's shape:
+    dL/dm = 2 weight (STI - target) dSTI/dm per channel (rvb_speech_index), then rvb_mtf_adjoint."""
+    import torch
+    hist = _histogram(ctx, table, air, mic, speakers, sample_rate, predelay, nbins, which, remove_direct)
+    m = speech.mtf_rows(ctx, hist, sample_rate)
+    targets = np.asarray(targets, dtype=np.float64).reshape(ctx.nchannels)
+    channel_weights = np.asarray(channel_weights, dtype=np.float64).reshape(ctx.nchannels)
+    if not want_weights:
+        sti = speech.index_of_rows(m, snr_db)
+        return float((channel_weights * (sti - targets) ** 2).sum()), sti, hist, None
+    sti, derivative = speech.index_of_rows(m, snr_db, want_derivative=True)
+    coeffs = (2.0 * channel_weights * (sti - targets))[:, None, None] * derivative.reshape(ctx.nchannels, 8, -1)
+    weights = torch.empty_like(hist)
+    ctx.mtf_adjoint(hist.data_ptr(), ctx.nchannels * 8, nbins, sample_rate, speech.STI_FREQS, coeffs, weights.data_ptr())
+    return float((channel_weights * (sti - targets) ** 2).sum()), sti, hist, weights
+
+
+def _evaluate_sti(ctx, table, air, mic, speakers, targets, channel_weights, sample_rate, predelay, nbins, snr_db, want_grad, which, remove_direct):
+    loss, sti, _, weights = _sti_forward(ctx, table, air, mic, speakers, targets, channel_weights, sample_rate, predelay, nbins, snr_db, want_grad,
+                                         which, remove_direct)
+    if not want_grad:
+        return loss, None, None, sti
+    grads, grad_air = _gradient(ctx, mic, speakers, predelay, sample_rate, nbins, weights, which, remove_direct)
+    return loss, grads, grad_air, sti
+
+
+def sti_loss_and_grad(ctx, table, air, mic, speakers, targets, channel_weights, sample_rate, predelay, nbins, snr_db=None, which=capi.IR_ALL,
+                      remove_direct=False):
+    """(loss, grad_surfaces, grad_air, sti) of the kept trace in `ctx` under the surface table `table` and the air coefficients `air`:
+    loss = sum_c channel_weights_c (STI_c - targets_c)^2 over the channels, STI_c the speech transmission index of channel c
+    (speech.sti: male-speech weights, snr_db seven signal-to-noise ratios in dB or None), its gradient as a SURFACE array and a
+    float32[8], and the model's indices float64 [nchannels].  The chain: dSTI/dm (rvb_speech_index), rvb_mtf_adjoint, then the
+    gradient of params_loss_and_grad.  The whole response by default (which=IR_ALL): an index without the direct sound is not the
+    seat's.  A channel with an empty band has a NaN index and makes the loss NaN.  Leaves the context re-shaded with `table`.
+    SCOPE: see the module text."""
+    return _evaluate_sti(ctx, table, air, mic, speakers, targets, channel_weights, sample_rate, predelay, nbins, snr_db, True, which, remove_direct)
+
+
+def sti_loss(ctx, table, air, mic, speakers, targets, channel_weights, sample_rate, predelay, nbins, snr_db=None, which=capi.IR_ALL,
+             remove_direct=False):
+    """The loss of sti_loss_and_grad alone (no weights, no gradient), bit for bit: what a line search evaluates."""
+    return _evaluate_sti(ctx, table, air, mic, speakers, targets, channel_weights, sample_rate, predelay, nbins, snr_db, False, which, remove_direct)[0]
+
+
+def fit_sti(ctx, table, air, mic, speakers, targets, channel_weights, sample_rate, predelay, nbins, free, steps, lower=0.01, upper=0.99,
+            snr_db=None, which=capi.IR_ALL, remove_direct=False):
+    """fit_decay's loop — projected gradient descent with Armijo steps on the coefficients that `free` marks, the same record — on the
+    loss of sti_loss_and_grad: materials toward a target speech transmission index.  Returns (table, record).  The air is held fixed."""
+    args = (air, mic, speakers, targets, channel_weights, sample_rate, predelay, nbins, snr_db)
+    return _fit(ctx, table, air, free, steps, lower, upper,
+                lambda candidate: _evaluate_sti(ctx, candidate, *args, True, which, remove_direct)[:2],
+                lambda candidate: _evaluate_sti(ctx, candidate, *args, False, which, remove_direct)[0])
+
+
+def sti_sensitivity_map(ctx, table, air, mic, speakers, targets, channel_weights, sample_rate, predelay, nbins, snr_db=None, which=capi.IR_DIFFUSE):
+    """(loss, map): the loss of sti_loss_and_grad(which=IR_DIFFUSE), bit for bit, and its gradient per TRIANGLE (rvb_reshade_grad_map) as
+    a SURFACE array [ntriangles] — where on the walls treatment buys intelligibility at this microphone.  Needs a trace kept with
+    keep_paths(True, listener=True).  The map is that of the diffuse records: ValueError for which != IR_DIFFUSE."""
+    if which != capi.IR_DIFFUSE:
+        raise ValueError("sti_sensitivity_map: which must be IR_DIFFUSE (rvb_reshade_grad_map takes the diffuse records only)")
+    loss, _, _, weights = _sti_forward(ctx, table, air, mic, speakers, targets, channel_weights, sample_rate, predelay, nbins, snr_db, True,
+                                       capi.IR_DIFFUSE, False)
+    per_triangle = ctx.reshade_grad_map(predelay, sample_rate, nbins, weights.data_ptr())
+    return loss, np.ascontiguousarray(per_triangle.cpu().numpy()).view(SURFACE).reshape(-1)
