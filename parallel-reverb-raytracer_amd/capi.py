@@ -171,6 +171,12 @@ SPEECH_SYMBOLS = list(_SPEECH_SIGNATURES)
 MTF_MAX_FREQS = 16
 STI_BANDS = 7
 STI_FREQS = 14
+# ... and of include/rvb_capi_source_grad.h, the source-end gradients of a kept trace (tests/test_source_grad_header_host.py)
+_SOURCE_GRAD_SIGNATURES = {
+    "rvb_source_grad": (_i, _vp, _f, _f, _u64, _vp, _vp, _vp, _vp),
+    "rvb_source_grad_images": (_i, _vp, _f, _f, _u64, _vp, _vp, _vp, _vp, _vp),
+}
+SOURCE_GRAD_SYMBOLS = list(_SOURCE_GRAD_SIGNATURES)
 _lib = None
 
 
@@ -196,7 +202,7 @@ def load_library():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _IMAGE_SIGNATURES, _LIVE_SIGNATURES, _WINDOW_SIGNATURES, _SPEECH_SIGNATURES):
+        for table in (_SIGNATURES, _IMAGE_SIGNATURES, _LIVE_SIGNATURES, _WINDOW_SIGNATURES, _SPEECH_SIGNATURES, _SOURCE_GRAD_SIGNATURES):
             for name, (restype, *argtypes) in table.items():
                 function = getattr(lib, name)
                 function.restype, function.argtypes = restype, argtypes
@@ -266,6 +272,12 @@ def make_source_patterns(directions, shapes):
         out[i].direction[:3] = [float(x) for x in d[i]]
         out[i].shape[:] = [float(x) for x in per[i]]
     return out
+
+
+class SourcePatternGrad(ctypes.Structure):
+    """rvb_source_pattern_grad of include/rvb_capi_source_grad.h: dL/dshape per band, and dL/ddirection with the direction taken as a free
+    3-vector (direction[3] = 0)."""
+    _fields_ = [("shape", ctypes.c_float * 8), ("direction", ctypes.c_float * 4)]
 
 
 class SourceOrientation(ctypes.Structure):
@@ -370,6 +382,7 @@ class Context(_Handle):
         self.nchannels = 0
         self.nsurfaces = 0
         self.ntriangles = 0
+        self.nimages = 0
         self._keep = []
         self._events = collections.deque(maxlen=2)     # the torch events of the last TWO waits, whichever method made them
 
@@ -488,6 +501,43 @@ class Context(_Handle):
         grad_air = np.zeros(8, dtype=np.float32)
         self._check(self.lib.rvb_reshade_grad_images(self.handle, predelay, sample_rate, nbins, device_weights_pointer, _ptr(grads), _ptr(grad_air)))
         return grads, grad_air
+
+    def _source_grad_outputs(self, n, want_grad, want_rows, want_pattern, extra=None):
+        """The torch CUDA tensors of a source-gradient call for n rays or images, and its host pattern structure; None where not asked for."""
+        import torch
+        grad = torch.empty((n, 8), dtype=torch.float32, device="cuda") if want_grad else None
+        rows = torch.empty((n,), dtype=torch.int32, device="cuda") if want_rows else None
+        more = torch.empty((n, extra), dtype=torch.float32, device="cuda") if extra else None
+        pattern = SourcePatternGrad() if want_pattern else None
+        torch.cuda.synchronize()                     # (the allocator may hand out memory that work on torch's stream still reads)
+        return grad, rows, more, pattern
+
+    @staticmethod
+    def _pattern_grad(pattern):
+        return None if pattern is None else {"shape": np.array(pattern.shape[:], dtype=np.float32), "direction": np.array(pattern.direction[:3], dtype=np.float32)}
+
+    def source_grad(self, predelay, sample_rate, nbins, device_weights_pointer, want_grad=True, want_rows=False, want_pattern=False):
+        """dL/d(source gain) of L = sum w * H per ray (rvb_source_grad of include/rvb_capi_source_grad.h): L, w and the state exactly as
+        reshade_grad takes them.  Returns a dict: "grad" a float32 CUDA tensor [nrays][8] (want_grad), "rows" an int32 CUDA tensor [nrays]
+        of source-table rows (want_rows; the records must reflect a table), "pattern" {"shape": float32 [8], "direction": float32 [3]},
+        the derivatives with respect to the polar pattern that the records reflect, the direction taken as a free vector (want_pattern).
+        Synchronous."""
+        grad, rows, _, pattern = self._source_grad_outputs(self.nrays, want_grad, want_rows, want_pattern)
+        self._check(self.lib.rvb_source_grad(self.handle, predelay, sample_rate, nbins, device_weights_pointer,
+                                             grad.data_ptr() if grad is not None else None, rows.data_ptr() if rows is not None else None,
+                                             ctypes.byref(pattern) if pattern is not None else None))
+        return {"grad": grad, "rows": rows, "pattern": self._pattern_grad(pattern)}
+
+    def source_grad_images(self, predelay, sample_rate, nbins, device_weights_pointer, nimages=None, want_grad=True, want_depart=False, want_rows=False,
+                           want_pattern=False):
+        """The same per image of a configuration made with ir_configure_speakers_merged (rvb_source_grad_images), `nimages` its length (None:
+        what that call returned):
+        "grad" [nimages][8] in the merged list's order, "depart" [nimages][4] the departure unit vectors the gain uses, "rows", "pattern"."""
+        grad, rows, depart, pattern = self._source_grad_outputs(int(self.nimages if nimages is None else nimages), want_grad, want_rows, want_pattern, extra=4 if want_depart else None)
+        self._check(self.lib.rvb_source_grad_images(self.handle, predelay, sample_rate, nbins, device_weights_pointer,
+                                                    grad.data_ptr() if grad is not None else None, depart.data_ptr() if depart is not None else None,
+                                                    rows.data_ptr() if rows is not None else None, ctypes.byref(pattern) if pattern is not None else None))
+        return {"grad": grad, "depart": depart, "rows": rows, "pattern": self._pattern_grad(pattern)}
 
     def reshade_grad_map(self, predelay, sample_rate, nbins, device_weights_pointer, out=None):
         """The gradient of reshade_grad per TRIANGLE (rvb_reshade_grad_map): a float32 CUDA tensor [ntriangles][16], row t the derivatives of
@@ -637,6 +687,7 @@ class Context(_Handle):
         nimages = _u64(0)
         self._check(self.lib.rvb_ir_configure_speakers_merged(self.handle, _f3(mic), _ptr(sp), sp.shape[0], which, int(remove_direct), ctypes.byref(nimages)))
         self.nchannels = sp.shape[0]
+        self.nimages = nimages.value                   # (source_grad_images sizes its outputs by it)
         return nimages.value
 
     def ir_configure_hrtf_merged(self, mic, table, facing, up, which=IR_ALL, remove_direct=False):

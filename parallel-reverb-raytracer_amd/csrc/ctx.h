@@ -307,11 +307,13 @@ struct KeptTrace : KeptState {
     // keeps its own; uploaded in stream order through surfaces_stage, as the source patterns are.  `grad_scratch`: the result and the
     // partial tables of rvb_reshade_grad (csrc/reshade_grad_kernels.hip).  `map_scratch`: the term rows of rvb_reshade_grad_map, 64 bytes per
     // record of a pair, and behind them the fold's partials (csrc/reshade_grad_map_kernels.hip); allocated by its first call.
+    // `source_scratch`: the binary64 sums, departure vectors, partials and result of rvb_source_grad / rvb_source_grad_images
+    // (csrc/source_grad.hip); allocated by the first call that asks for a pattern gradient or takes images.
     struct Buffers {
-        DevBuf paths, image_dist, listen, surfaces, grad_scratch, map_scratch;
-        bool any() const { return paths.p || image_dist.p || listen.p || surfaces.p || grad_scratch.p || map_scratch.p; }
+        DevBuf paths, image_dist, listen, surfaces, grad_scratch, map_scratch, source_scratch;
+        bool any() const { return paths.p || image_dist.p || listen.p || surfaces.p || grad_scratch.p || map_scratch.p || source_scratch.p; }
     } dev;
-    static_assert(sizeof(Buffers) == 6 * sizeof(DevBuf), "any() names every buffer");
+    static_assert(sizeof(Buffers) == 7 * sizeof(DevBuf), "any() names every buffer");
     StagedBlock surfaces_stage;
 
     // What a launch of nrays rays in npairs pairs keeps beside its results (nothing while keeping is off), and where its kernels put it.
@@ -535,6 +537,14 @@ int launch_shadow_behind_images(rvb_ctx * ctx, const TraceArgs & a, const Source
 // source.hip: what a trace and a re-shade do about the source directivity (described where they are defined)
 int check_source_counts(rvb_ctx * ctx, const char * who, uint64_t npairs);
 int apply_source_patterns(rvb_ctx * ctx, const TraceArgs & a, const SourceShading & source, bool gains_stand = false);
+// kept.hip: what the gradient passes over the kept records share (described where they are defined) — `a` for such a pass, what a pass
+// takes beside it, and the refusals of rvb_reshade_grad under the name of the call `who` (its own null arguments are that call's to refuse)
+TraceArgs for_record_pass(const rvb_ctx * ctx, TraceArgs a);
+ReshadeGradArgs grad_args(const rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins);
+int reshade_grad_refusals(rvb_ctx * ctx, const char * who, float predelay, float sample_rate, uint64_t nbins);
+// images.hip: the same for rvb_reshade_grad_images — its refusals, and what its kernel takes (the weights read in place)
+int reshade_grad_images_refusals(rvb_ctx * ctx, const char * who, float predelay, float sample_rate, uint64_t nbins);
+ImageGradArgs image_grad_args(const rvb_ctx * ctx, const TraceArgs & a, float predelay, float sample_rate, uint64_t nbins, const void * d_weights);
 // kept.hip: the tail of a per-surface gradient — waits for the stream, then the nsurfaces * 16 + 8 floats at d_out into the caller's arrays
 int download_surface_gradient(rvb_ctx * ctx, const float * d_out, rvb_surface * grad_surfaces, float grad_air[8]);
 

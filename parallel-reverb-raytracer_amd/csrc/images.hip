@@ -61,6 +61,53 @@ int configure_merged(rvb_ctx * ctx, int which, int remove_direct, uint64_t * nim
 
 }  // namespace
 
+// What rvb_reshade_grad_images refuses of the binning and of the context's state, before any device is touched, under the name of the
+// call `name`: rvb_source_grad_images (source_grad.hip) has the same preconditions.
+int reshade_grad_images_refusals(rvb_ctx * ctx, const char * name, float predelay, float sample_rate, uint64_t nbins)
+{
+    const std::string who = name;
+    if (nbins == 0 || nbins >= (1ull << 32)) return fail(ctx, RVB_ERR_INVALID, who + ": no bins (or more than 32-bit bin numbers reach)");
+    if (!std::isfinite(predelay) || !std::isfinite(sample_rate)) return fail(ctx, RVB_ERR_INVALID, who + ": predelay or sample rate is not finite");
+    if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, who + ": nothing traced (or the scene or the directions have changed since)");
+    if (!ctx->kept.valid()) return fail(ctx, RVB_ERR_STATE, who + ": the last trace was made without rvb_keep_paths(ctx, 1)");
+    if (!ctx->ir.configured())
+        return fail(ctx, RVB_ERR_STATE, who + ": no IR configuration (rvb_ir_configure_speakers_merged after the trace, re-shade or relisten)");
+    if (ctx->ir.model.hrtf) return fail(ctx, RVB_ERR_STATE, who + ": the HRTF model is configured; this version takes the speaker model only");
+    if (!ctx->ir.from_merged_list() || !ctx->merged.valid())
+        return fail(ctx, RVB_ERR_STATE, who + ": the caller's list has lost its chains: configure with rvb_ir_configure_speakers_merged");
+    if (ctx->ir.which() == RVB_IR_DIFFUSE)
+        return fail(ctx, RVB_ERR_STATE, who + ": configured with which == RVB_IR_DIFFUSE: no image takes part (rvb_reshade_grad has that gradient)");
+    if (ctx->ir.model.nchannels > 8)
+        return fail(ctx, RVB_ERR_STATE, who + ": " + std::to_string(ctx->ir.model.nchannels) + " speaker channels configured; this version takes 1 to 8");
+    if (ctx->scene.nsurfaces >= (1ull << 27)) return fail(ctx, RVB_ERR_CAPACITY, who + ": too many surfaces");
+    return RVB_OK;
+}
+
+// what an image gradient kernel takes beside `a` (the kept trace's arguments under what the records reflect now): the merged list, the
+// binning, the weights in place, and the source directivity that the records reflect, for the selected pair
+ImageGradArgs image_grad_args(const rvb_ctx * ctx, const TraceArgs & a, float predelay, float sample_rate, uint64_t nbins, const void * d_weights)
+{
+    const KeptTrace & kept = ctx->kept;
+    ImageGradArgs g = {};
+    g.winners = ctx->merged.winners.as<const uint32_t>();
+    g.images = ctx->ir.images.as<const rvb_impulse>();
+    g.n = ctx->ir.nimages();
+    g.direct_dist = a.nrays * (RVB_NUM_IMAGE_SOURCE - 1) + ctx->trace.pair();
+    g.weights = reinterpret_cast<const float *>(d_weights);
+    g.nbins = nbins;
+    g.predelay = predelay;
+    g.sample_rate = sample_rate;
+    for (int i = 0; i < 3; ++i) g.mic[i] = ctx->trace.mic()[i];
+    const SourceShading & shaded = kept.shaded_source();
+    g.has_pattern = kept.shaded_pattern(ctx->trace.pair(), g.pattern);
+    if (shaded.table_orientations) {
+        const SourceTableDev t = ctx->source.table_on_device(shaded.table_orientations);
+        g.table = t.table;
+        g.table_basis = t.bases + ctx->trace.pair() * t.basis_stride;
+    }
+    return g;
+}
+
 extern "C" {
 
 int rvb_ir_configure_speakers_merged(rvb_ctx * ctx, const float mic[3], const rvb_speaker * speakers, uint64_t nspeakers,
@@ -84,20 +131,8 @@ int rvb_reshade_grad_images(rvb_ctx * ctx, float predelay, float sample_rate, ui
 {
     if (!ctx) return RVB_ERR_INVALID;
     if (!d_weights || !grad_surfaces) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_images: null weights or null output");
-    if (nbins == 0 || nbins >= (1ull << 32)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_images: no bins (or more than 32-bit bin numbers reach)");
-    if (!std::isfinite(predelay) || !std::isfinite(sample_rate)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad_images: predelay or sample rate is not finite");
-    if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: nothing traced (or the scene or the directions have changed since)");
-    if (!ctx->kept.valid()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: the last trace was made without rvb_keep_paths(ctx, 1)");
-    if (!ctx->ir.configured())
-        return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: no IR configuration (rvb_ir_configure_speakers_merged after the trace, re-shade or relisten)");
-    if (ctx->ir.model.hrtf) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: the HRTF model is configured; this version takes the speaker model only");
-    if (!ctx->ir.from_merged_list() || !ctx->merged.valid())
-        return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: the caller's list has lost its chains: configure with rvb_ir_configure_speakers_merged");
-    if (ctx->ir.which() == RVB_IR_DIFFUSE)
-        return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: configured with which == RVB_IR_DIFFUSE: no image takes part (rvb_reshade_grad has that gradient)");
-    if (ctx->ir.model.nchannels > 8)
-        return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad_images: " + std::to_string(ctx->ir.model.nchannels) + " speaker channels configured; this version takes 1 to 8");
-    if (ctx->scene.nsurfaces >= (1ull << 27)) return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad_images: too many surfaces");
+    const int refused = reshade_grad_images_refusals(ctx, "rvb_reshade_grad_images", predelay, sample_rate, nbins);
+    if (refused != RVB_OK) return refused;
     RVB_BIND(ctx);
     KeptTrace & kept = ctx->kept;
     MergedImages & merged = ctx->merged;
@@ -109,24 +144,7 @@ int rvb_reshade_grad_images(rvb_ctx * ctx, float predelay, float sample_rate, ui
     RVB_HIP(fail, ctx, merged.grad_scratch.ensure(row_bytes + entries * sizeof(float)));
     uint32_t * rows = merged.grad_scratch.as<uint32_t>();
     float * d_out = reinterpret_cast<float *>(merged.grad_scratch.as<char>() + row_bytes);
-    ImageGradArgs g = {};
-    g.winners = merged.winners.as<const uint32_t>();
-    g.images = ctx->ir.images.as<const rvb_impulse>();
-    g.n = n;
-    g.direct_dist = a.nrays * (RVB_NUM_IMAGE_SOURCE - 1) + ctx->trace.pair();
-    g.weights = reinterpret_cast<const float *>(d_weights);
-    g.nbins = nbins;
-    g.predelay = predelay;
-    g.sample_rate = sample_rate;
-    for (int i = 0; i < 3; ++i) g.mic[i] = ctx->trace.mic()[i];
-    // the source directivity that the records reflect now, for the selected pair
-    const SourceShading & shaded = kept.shaded_source();
-    g.has_pattern = kept.shaded_pattern(ctx->trace.pair(), g.pattern);
-    if (shaded.table_orientations) {
-        const SourceTableDev t = ctx->source.table_on_device(shaded.table_orientations);
-        g.table = t.table;
-        g.table_basis = t.bases + ctx->trace.pair() * t.basis_stride;
-    }
+    const ImageGradArgs g = image_grad_args(ctx, a, predelay, sample_rate, nbins, d_weights);
     ctx->reset_timings();
     ctx->begin_timing("reshade_grad_images_kernel");
     rvb_launch_reshade_grad_images(a, ctx->ir.model, g, rows, ctx->stream);

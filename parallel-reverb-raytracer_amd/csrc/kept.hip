@@ -8,7 +8,7 @@
 
 // `a` for a pass over the kept records (reshade_kernels.hip, reshade_grad_kernels.hip, relisten_kernels.hip): no stamps, and the share
 // of the surface table that those kernels stage in LDS
-static TraceArgs for_record_pass(const rvb_ctx * ctx, TraceArgs a)
+TraceArgs for_record_pass(const rvb_ctx * ctx, TraceArgs a)
 {
     a.scene.stamps = nullptr;
     a.lds_surfaces = rvb_reshade_lds_surfaces(ctx->scene.nsurfaces);
@@ -17,7 +17,7 @@ static TraceArgs for_record_pass(const rvb_ctx * ctx, TraceArgs a)
 
 // what a gradient pass takes beside `a`: the selected pair's rays and microphone, the binning, the weights where the accumulation image
 // goes (rvb_launch_reshade_grad_weights puts them there), and the source directivity that the records reflect now
-static ReshadeGradArgs grad_args(const rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins)
+ReshadeGradArgs grad_args(const rvb_ctx * ctx, float predelay, float sample_rate, uint64_t nbins)
 {
     const KeptTrace & kept = ctx->kept;
     ReshadeGradArgs g;
@@ -33,6 +33,26 @@ static ReshadeGradArgs grad_args(const rvb_ctx * ctx, float predelay, float samp
     g.ray_gains = kept.shaded_source().table_orientations ? ctx->source.gains_of_pair(ctx->trace.pair(), ctx->nrays) : nullptr;
     g.nsurfaces = ctx->scene.nsurfaces;
     return g;
+}
+
+// What rvb_reshade_grad refuses of the binning and of the context's state, before any device is touched, under the name of the call
+// `name`: rvb_source_grad (source_grad.hip) has the same preconditions.
+int reshade_grad_refusals(rvb_ctx * ctx, const char * name, float predelay, float sample_rate, uint64_t nbins)
+{
+    const std::string who = name;
+    if (nbins == 0 || nbins >= (1ull << 32)) return fail(ctx, RVB_ERR_INVALID, who + ": no bins (or more than 32-bit bin numbers reach)");
+    if (!std::isfinite(predelay) || !std::isfinite(sample_rate)) return fail(ctx, RVB_ERR_INVALID, who + ": predelay or sample rate is not finite");
+    if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, who + ": nothing traced (or the scene or the directions have changed since)");
+    if (!ctx->kept.valid()) return fail(ctx, RVB_ERR_STATE, who + ": the last trace was made without rvb_keep_paths(ctx, 1)");
+    if (!ctx->ir.configured()) return fail(ctx, RVB_ERR_STATE, who + ": no IR configuration (rvb_ir_configure_speakers after the trace or re-shade)");
+    if (ctx->ir.model.hrtf) return fail(ctx, RVB_ERR_STATE, who + ": the HRTF model is configured; this version takes the speaker model only");
+    if (ctx->ir.which() != RVB_IR_DIFFUSE) return fail(ctx, RVB_ERR_STATE, who + ": configured with image sources; this version takes which == RVB_IR_DIFFUSE only");
+    if (ctx->ir.model.nchannels > 8)
+        return fail(ctx, RVB_ERR_STATE, who + ": " + std::to_string(ctx->ir.model.nchannels) + " speaker channels configured; this version takes 1 to 8");
+    if (ctx->trace.nreflections() > RVB_RESHADE_GRAD_MAX_REFLECTIONS)
+        return fail(ctx, RVB_ERR_CAPACITY, who + ": more than " RVB_STR(RVB_RESHADE_GRAD_MAX_REFLECTIONS) " reflections");
+    if (ctx->scene.nsurfaces >= (1ull << 27)) return fail(ctx, RVB_ERR_CAPACITY, who + ": too many surfaces");
+    return RVB_OK;
 }
 
 int download_surface_gradient(rvb_ctx * ctx, const float * d_out, rvb_surface * grad_surfaces, float grad_air[8])
@@ -147,18 +167,8 @@ int rvb_reshade_grad(rvb_ctx * ctx, float predelay, float sample_rate, uint64_t 
 {
     if (!ctx) return RVB_ERR_INVALID;
     if (!d_weights || !grad_surfaces) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: null weights or null output");
-    if (nbins == 0 || nbins >= (1ull << 32)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: no bins (or more than 32-bit bin numbers reach)");
-    if (!std::isfinite(predelay) || !std::isfinite(sample_rate)) return fail(ctx, RVB_ERR_INVALID, "rvb_reshade_grad: predelay or sample rate is not finite");
-    if (!ctx->trace.traced()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: nothing traced (or the scene or the directions have changed since)");
-    if (!ctx->kept.valid()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: the last trace was made without rvb_keep_paths(ctx, 1)");
-    if (!ctx->ir.configured()) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: no IR configuration (rvb_ir_configure_speakers after the trace or re-shade)");
-    if (ctx->ir.model.hrtf) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: the HRTF model is configured; this version takes the speaker model only");
-    if (ctx->ir.which() != RVB_IR_DIFFUSE) return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: configured with image sources; this version takes which == RVB_IR_DIFFUSE only");
-    if (ctx->ir.model.nchannels > 8)
-        return fail(ctx, RVB_ERR_STATE, "rvb_reshade_grad: " + std::to_string(ctx->ir.model.nchannels) + " speaker channels configured; this version takes 1 to 8");
-    if (ctx->trace.nreflections() > RVB_RESHADE_GRAD_MAX_REFLECTIONS)
-        return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad: more than " RVB_STR(RVB_RESHADE_GRAD_MAX_REFLECTIONS) " reflections");
-    if (ctx->scene.nsurfaces >= (1ull << 27)) return fail(ctx, RVB_ERR_CAPACITY, "rvb_reshade_grad: too many surfaces");
+    const int refused = reshade_grad_refusals(ctx, "rvb_reshade_grad", predelay, sample_rate, nbins);
+    if (refused != RVB_OK) return refused;
     RVB_BIND(ctx);
     KeptTrace & kept = ctx->kept;
     const TraceArgs a = for_record_pass(ctx, kept.shaded_args());

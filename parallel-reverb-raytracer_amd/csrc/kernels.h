@@ -195,6 +195,28 @@ struct ImageGradArgs {
 };
 void rvb_launch_reshade_grad_images(const TraceArgs & a, const AttenuationModel & model, const ImageGradArgs & g, uint32_t * rows, hipStream_t s);
 void rvb_launch_reshade_grad_images_reduce(const uint32_t * rows, uint64_t n, uint64_t nsurfaces, float * out, hipStream_t s);
+// Source-end gradients from the kept trace (source_grad_kernels.hip; include/rvb_capi_source_grad.h): L = sum w * H of rvb_reshade_grad
+// (rays: `g` as that launch takes it, the weights transposed) and of rvb_reshade_grad_images (images: `g` as that launch takes it, the
+// weights read in place), differentiated with respect to the source gain of every ray or image.  What a launch leaves per item (each may
+// be null): grad[n][8] the sums rounded once, lambda[n][8] the binary64 sums before the rounding (the pattern kernel's input), rows[n] the
+// row of the source table for the item's departure vector under table_basis (three float4; read with rows only).  The images kernel also
+// leaves departures[n] = mic - position (w = 0) and, where asked, units[n] = normalize3(normalize3(departure)).
+// The pattern pair: a partial of eleven binary64 sums (shape[8], direction[3]) per tile of RVB_SOURCE_GRAD_TILE items in `partials`, then
+// out[12] floats, rvb_source_pattern_grad's layout.  Bit-identical from run to run.
+struct SourceGradOut {
+    float * grad;
+    double * lambda;
+    uint32_t * rows;
+    const float4 * table_basis;
+};
+#define RVB_SOURCE_GRAD_TILE 256
+inline uint64_t rvb_source_grad_tiles(uint64_t n) { return (n + RVB_SOURCE_GRAD_TILE - 1) / RVB_SOURCE_GRAD_TILE; }
+void rvb_launch_source_grad_rays(const TraceArgs & a, const float4 * kept, const AttenuationModel & model, const ReshadeGradArgs & g, const SourceGradOut & o,
+                                 hipStream_t s);
+void rvb_launch_source_grad_images(const TraceArgs & a, const AttenuationModel & model, const ImageGradArgs & g, const SourceGradOut & o, float4 * departures,
+                                   float4 * units, hipStream_t s);
+void rvb_launch_source_grad_pattern(const float4 * vectors, const double * lambda, uint64_t n, const SourcePatternDev & pattern, double * partials, hipStream_t s);
+void rvb_launch_source_grad_pattern_fold(const double * partials, uint64_t n, float * out, hipStream_t s);
 // Decay curves (decay_kernels.hip; rvb_decay_curve / rvb_decay_times / rvb_decay_loss of include/rvb_capi.h) on nrows rows of nbins floats.
 // Every phase is a launch of its own — a value per tile of RVB_DECAY_TILE bins, one wave per row over the row's tiles, the tile again on
 // top of its carry —; `tiles` is [nrows][rvb_decay_tiles(nbins)] doubles (three such planes for the loss: m d^2, 2 m d, g), `first`

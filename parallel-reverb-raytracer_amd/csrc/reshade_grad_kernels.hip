@@ -25,17 +25,13 @@
 //                                 terms P_k a_k behind the eight specular ones -P_{k-1} B_k —, staged per tile in LDS where the table
 //                                 stands otherwise and stored as whole 64-byte rows, a ray's run of a tile in one piece; beside it the
 //                                 record's sort key (its triangle, ntriangles for a slot without a record) and its number.
-#include "kept_tiles.h"
-#include "attenuation.h"
+#include "grad_tiles.h"
 
 #include <algorithm>
 
 namespace {
 
-#define GRAD_TILE 16u                // bounces per tile
-typedef KeptRows<GRAD_TILE> GradRows;    // eight rays per wave, a ray's row of staged records padded by one
-#define GRAD_BIN_WORD 3u             // a staged record is the side record with dist for newDist and, in this word, the bin (NONE: adds nothing)
-#define GRAD_GATHER 8u               // weight gathers of a lane in flight together
+// (GRAD_TILE, GradRows, GRAD_BIN_WORD, GRAD_GATHER, GRAD_STAGE_WORDS: grad_tiles.h, shared with source_grad_kernels.hip)
 #define GRAD_WINDOW 64u             // surfaces per table in LDS (8 KiB of binary64 sums)
 #define GRAD_MAX_BLOCKS 16384u       // (4096 left every wave three or four groups of rays at workload C2: 1.87 ms against 1.71 ms, profiles/reshade_grad_n1.txt)
 #define GRAD_PARTIAL_BYTES (64ull << 20)        // the partial tables of a launch stay below this (or at 64 tables)
@@ -62,7 +58,6 @@ struct GradDev {
 #define GRAD_TERM_RAY_WORDS (GRAD_TILE * 16u + 8u)
 #define GRAD_TERM_WORDS (GradRows::RAYS * GRAD_TERM_RAY_WORDS)
 __host__ __device__ __forceinline__ uint32_t grad_table_words(uint32_t window, bool map = false) { return map ? GRAD_TERM_WORDS : (window * 16u + 8u) * 2u; }
-#define GRAD_STAGE_WORDS (GradRows::RECORDS * 4u)
 __host__ __device__ __forceinline__ uint32_t grad_surfaces_at(uint32_t window, uint32_t ntiles, bool map = false)
 {
     return grad_table_words(window, map) + 2u * GRAD_STAGE_WORDS + 2u * GRAD_TILE * WAVE + ntiles * WAVE;

@@ -91,3 +91,22 @@ def normalised(v):
     n = np.linalg.norm(v, axis=-1, keepdims=True)
     assert (n > 0).all() and np.isfinite(n).all(), "a vector of zero length"
     return (v / n).astype(np.float32)
+
+
+def balloon_gradient(grad, rows):
+    """The float64 [360][180][8] sums by table row of per-ray or per-image gain derivatives: grad [n][8] (dL/dg of capi.Context.source_grad
+    or source_grad_images) and rows [n] (their table rows) as numpy arrays or torch tensors.  Entry [a][e][b] is dL/dtable[a][e][b] of the
+    source table that the records reflect; a row of 64800 or above — the zero row behind the table — belongs to no cell and adds nothing.
+    Added in binary64 in the order of the rays (images)."""
+    if hasattr(grad, "cpu"):
+        grad = grad.cpu().numpy()
+    if hasattr(rows, "cpu"):
+        rows = rows.cpu().numpy()
+    grad = np.asarray(grad, dtype=np.float64).reshape(-1, 8)
+    rows = np.asarray(rows).reshape(-1).astype(np.int64) & 0xFFFFFFFF      # (an int32 tensor holds the unsigned row)
+    assert grad.shape[0] == rows.shape[0], "balloon_gradient: a row per gradient entry"
+    out = np.zeros((360 * 180, 8), dtype=np.float64)
+    inside = rows < 360 * 180
+    np.add.at(out, rows[inside], grad[inside])
+    return out.reshape(360, 180, 8)
+

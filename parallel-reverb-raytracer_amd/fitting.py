@@ -18,6 +18,10 @@ ir_configure_speakers_merged(which) — the merged image list made on the device
 is reshade_grad_images(w), for IR_ALL plus reshade_grad(w) under an IR_DIFFUSE configuration: L is a sum over impulses, the two are
 added in binary64 and rounded to float once, for surfaces and air alike.
 
+The same losses also have a gradient at the SOURCE end (include/rvb_capi_source_grad.h): source_gradient(w) is dL/d(source gain) per ray
+and per image, and with a polar pattern on the source dL/d(direction, shapes) — aim_loss_and_grad, fit_aim ("where to point the
+loudspeaker") —, with a source table dL/d(table cell) — sti_source_balloon.  A trial there is set_source_pattern + the same evaluation.
+
 SCOPE: that of rvb_reshade_grad and rvb_reshade_grad_images — a context that holds a trace made with keep_paths(True), the speaker model
 with at most 8 channels, no HRTF; by default the diffuse records only (which=IR_DIFFUSE, the calls of earlier versions one for one),
 with which=IR_ALL the whole response; the per-triangle map takes IR_DIFFUSE only.  The target and the mask are float32 CUDA tensors [nchannels][8][nbins]
@@ -143,27 +147,22 @@ ARMIJO_C = 1e-4
 MAX_HALVINGS = 30
 
 
-def _fit(ctx, table, air, free, steps, lower, upper, loss_and_grad, loss_only):
-    """The projected-gradient / Armijo loop of fit_decay and fit_params: loss_and_grad(table) -> (loss, grad_surfaces),
-    loss_only(table) -> loss."""
-    table = aligned_copy(np.ascontiguousarray(table, dtype=SURFACE))
-    free = np.asarray(free, dtype=bool).reshape(table.shape[0], 16)
+def _armijo(state, steps, loss_and_grad, loss_only, steepest_of, trial_of):
+    """The Armijo loop that every fit here runs, on a state the caller moves: loss_and_grad(state) -> (loss, g), loss_only(state) -> loss,
+    steepest_of(g) the largest |g|, trial_of(state, g, t) -> (trial state, descent = g.(theta - theta(t))).  A trial is accepted when
+    descent > 0 and L(trial) <= L - c descent, c = 1e-4; t halves until then, at most 30 times, and a step that is never accepted ends
+    the loop.  The first t is 0.25 / steepest; later steps start from twice the last accepted t.  Returns (state, record)."""
     record = []
     t = None
     for _ in range(int(steps)):
-        loss, grads = loss_and_grad(table)
-        theta = coefficients(table)
-        g = np.where(free, coefficients(np.ascontiguousarray(grads)), np.float32(0.0)).astype(np.float64)
-        steepest = np.abs(g).max()
+        loss, g = loss_and_grad(state)
+        steepest = steepest_of(g)
         if not steepest > 0 or not np.isfinite(steepest):
             break
         t = 0.25 / steepest if t is None else 2.0 * t
         accepted = None
         for halvings in range(MAX_HALVINGS + 1):
-            trial = aligned_copy(table)
-            moved = np.clip(theta.astype(np.float64) - t * g, lower, upper).astype(np.float32)
-            coefficients(trial)[free] = moved[free]
-            descent = float((g * (theta.astype(np.float64) - coefficients(trial).astype(np.float64))).sum())
+            trial, descent = trial_of(state, g, t)
             trial_loss = loss_only(trial)
             if descent > 0 and trial_loss <= loss - ARMIJO_C * descent:
                 accepted = (trial, trial_loss, descent, halvings)
@@ -171,8 +170,29 @@ def _fit(ctx, table, air, free, steps, lower, upper, loss_and_grad, loss_only):
             t *= 0.5
         if accepted is None:
             break
-        table = accepted[0]
+        state = accepted[0]
         record.append({"loss_before": loss, "loss": accepted[1], "step": t, "halvings": accepted[3], "descent": accepted[2]})
+    return state, record
+
+
+def _fit(ctx, table, air, free, steps, lower, upper, loss_and_grad, loss_only):
+    """The projected-gradient / Armijo loop of fit_decay and fit_params: loss_and_grad(table) -> (loss, grad_surfaces),
+    loss_only(table) -> loss."""
+    table = aligned_copy(np.ascontiguousarray(table, dtype=SURFACE))
+    free = np.asarray(free, dtype=bool).reshape(table.shape[0], 16)
+
+    def masked(candidate):
+        loss, grads = loss_and_grad(candidate)
+        return loss, np.where(free, coefficients(np.ascontiguousarray(grads)), np.float32(0.0)).astype(np.float64)
+
+    def trial_of(current, g, t):
+        theta = coefficients(current)
+        trial = aligned_copy(current)
+        moved = np.clip(theta.astype(np.float64) - t * g, lower, upper).astype(np.float32)
+        coefficients(trial)[free] = moved[free]
+        return trial, float((g * (theta.astype(np.float64) - coefficients(trial).astype(np.float64))).sum())
+
+    table, record = _armijo(table, steps, masked, loss_only, lambda g: np.abs(g).max(), trial_of)
     ctx.reshade(table, air)
     return table, record
 
@@ -195,20 +215,27 @@ def fit_decay(ctx, table, air, mic, speakers, target, mask, sample_rate, predela
 
 # ---- fitting to a table of measured room acoustic parameters (rvb_decay_params_loss) ------------------------------------------------
 
-def _evaluate_params(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, want_grad, which=capi.IR_DIFFUSE,
-                     remove_direct=False):
+def _params_forward(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, want_weights, which=capi.IR_DIFFUSE,
+                    remove_direct=False):
+    """The evaluation up to the loss: (loss, params, weights), weights = dL/dH as a tensor [nchannels][8][nbins], or None."""
     import torch
     hist, curve = _histogram_and_curve(ctx, table, air, mic, speakers, sample_rate, predelay, nbins, which, remove_direct)
-    weights = torch.empty_like(hist) if want_grad else None
+    weights = torch.empty_like(hist) if want_weights else None
     shape = (ctx.nchannels * 8, capi.DECAY_NPARAMS)
     loss_rows, params = ctx.decay_params_loss(hist.data_ptr(), curve.data_ptr(), ctx.nchannels * 8, nbins, sample_rate,
                                               np.asarray(targets, dtype=np.float32).reshape(shape),
-                                              np.asarray(param_weights, dtype=np.float32).reshape(shape), weights.data_ptr() if want_grad else None)
-    params = params.reshape(ctx.nchannels, 8, capi.DECAY_NPARAMS)
+                                              np.asarray(param_weights, dtype=np.float32).reshape(shape), weights.data_ptr() if want_weights else None)
+    return float(loss_rows.sum()), params.reshape(ctx.nchannels, 8, capi.DECAY_NPARAMS), weights
+
+
+def _evaluate_params(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, want_grad, which=capi.IR_DIFFUSE,
+                     remove_direct=False):
+    loss, params, weights = _params_forward(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, want_grad, which,
+                                            remove_direct)
     if not want_grad:
-        return float(loss_rows.sum()), None, None, params
+        return loss, None, None, params
     grads, grad_air = _gradient(ctx, mic, speakers, predelay, sample_rate, nbins, weights, which, remove_direct)
-    return float(loss_rows.sum()), grads, grad_air, params
+    return loss, grads, grad_air, params
 
 
 def params_loss_and_grad(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, which=capi.IR_DIFFUSE,
@@ -321,3 +348,116 @@ def sti_sensitivity_map(ctx, table, air, mic, speakers, targets, channel_weights
                                        capi.IR_DIFFUSE, False)
     per_triangle = ctx.reshade_grad_map(predelay, sample_rate, nbins, weights.data_ptr())
     return loss, np.ascontiguousarray(per_triangle.cpu().numpy()).view(SURFACE).reshape(-1)
+
+
+# ---- the source end: aim and polar pattern (include/rvb_capi_source_grad.h) ------------------------------------------------------------
+
+def source_gradient(ctx, weights, mic, speakers, sample_rate, predelay, nbins, which=capi.IR_DIFFUSE, want_pattern=False, want_rows=False):
+    """dL/d(source gain) of L = sum weights * H for the configuration that an evaluation here left (the context configured with `which`,
+    weights = dL/dH a float32 CUDA tensor [nchannels][8][nbins]): a dict with "rays" — capi.Context.source_grad's result, "grad" [nrays][8]
+    and, if asked, "rows" — for the diffuse part (None for which=IR_IMAGES), "images" — source_grad_images' result with "depart" — for
+    which != IR_DIFFUSE (None otherwise), and "pattern" {"shape" float64 [8], "direction" float64 [3]}: the parts' pattern gradients added in
+    binary64 (want_pattern; the direction is the derivative for a free 3-vector).  For IR_ALL the image part is taken first, under the
+    merged configuration; the context is left configured with IR_DIFFUSE then, as the material gradients leave it."""
+    out = {"rays": None, "images": None, "pattern": None}
+    parts = []
+    if which != capi.IR_DIFFUSE:
+        out["images"] = ctx.source_grad_images(predelay, sample_rate, nbins, weights.data_ptr(), want_depart=True, want_rows=want_rows, want_pattern=want_pattern)
+        parts.append(out["images"]["pattern"])
+        if which == capi.IR_ALL:
+            ctx.ir_configure_speakers(mic, speakers[0], speakers[1], capi.IR_DIFFUSE, None)
+    if which != capi.IR_IMAGES:
+        out["rays"] = ctx.source_grad(predelay, sample_rate, nbins, weights.data_ptr(), want_rows=want_rows, want_pattern=want_pattern)
+        parts.append(out["rays"]["pattern"])
+    if want_pattern:
+        out["pattern"] = {k: sum(p[k].astype(np.float64) for p in parts) for k in ("shape", "direction")}
+    return out
+
+
+def _aim_forward(ctx, kind, direction, shapes, table, air, mic, speakers, loss_args, sample_rate, predelay, nbins, want_weights, which, remove_direct):
+    """set_source_pattern + the evaluation of loss `kind` up to the loss, through the forward of the material fits: (loss, weights, extra),
+    extra the times' place holder None ("decay"), the parameters ("params") or the indices ("sti")."""
+    ctx.set_source_pattern(direction, shapes)
+    if kind == "decay":
+        target, mask, normalised = loss_args
+        loss, _, weights = _forward(ctx, table, air, mic, speakers, target, mask, sample_rate, predelay, nbins, normalised, want_weights, which, remove_direct)
+        return loss, weights, None
+    if kind == "params":
+        targets, param_weights = loss_args
+        loss, params, weights = _params_forward(ctx, table, air, mic, speakers, targets, param_weights, sample_rate, predelay, nbins, want_weights, which,
+                                                remove_direct)
+        return loss, weights, params
+    if kind == "sti":
+        targets, channel_weights, snr_db = loss_args
+        loss, sti, _, weights = _sti_forward(ctx, table, air, mic, speakers, targets, channel_weights, sample_rate, predelay, nbins, snr_db, want_weights,
+                                             which, remove_direct)
+        return loss, weights, sti
+    raise ValueError("aim: kind must be 'decay', 'params' or 'sti'")
+
+
+def aim_loss(ctx, kind, direction, shapes, table, air, mic, speakers, loss_args, sample_rate, predelay, nbins, which=capi.IR_ALL, remove_direct=False):
+    """The loss of aim_loss_and_grad alone, bit for bit: what a line search evaluates."""
+    return _aim_forward(ctx, kind, direction, shapes, table, air, mic, speakers, loss_args, sample_rate, predelay, nbins, False, which, remove_direct)[0]
+
+
+def aim_loss_and_grad(ctx, kind, direction, shapes, table, air, mic, speakers, loss_args, sample_rate, predelay, nbins, which=capi.IR_ALL,
+                      remove_direct=False):
+    """(loss, grad_direction float64 [3], grad_shapes float64 [8], extra) of the kept trace in `ctx` with the polar pattern (direction,
+    shapes — a scalar or eight values) on the source, under the table `table` and the air `air`.  kind and loss_args name the loss:
+    "decay" (target, mask, normalised) — decay_loss_and_grad's —, "params" (targets, param_weights) — params_loss_and_grad's —, "sti"
+    (targets, channel_weights, snr_db) — sti_loss_and_grad's; extra is None, the parameters or the indices.  grad_direction is the
+    derivative for the pattern's unit vector taken as a free 3-vector (rvb_source_pattern_grad): project it onto the tangent plane of the
+    direction to turn the source.  One evaluation costs the forward and one or two gradient sweeps, whatever the number of free
+    parameters.  Leaves the pattern set and the context re-shaded with it."""
+    loss, weights, extra = _aim_forward(ctx, kind, direction, shapes, table, air, mic, speakers, loss_args, sample_rate, predelay, nbins, True, which,
+                                        remove_direct)
+    pattern = source_gradient(ctx, weights, mic, speakers, sample_rate, predelay, nbins, which, want_pattern=True)["pattern"]
+    return loss, pattern["direction"], pattern["shape"], extra
+
+
+def _unit(v):
+    v = np.asarray(v, dtype=np.float64).reshape(3)
+    return v / np.sqrt((v * v).sum())
+
+
+def fit_aim(ctx, kind, direction, shapes, table, air, mic, speakers, loss_args, sample_rate, predelay, nbins, steps, free_direction=True,
+            free_shapes=False, which=capi.IR_ALL, remove_direct=False):
+    """Projected gradient descent with fit_decay's Armijo loop on the polar pattern of the source: the direction (free_direction) moves
+    along the gradient's projection onto its tangent plane and is renormalised after each step, the shapes (free_shapes) are clipped to
+    [0, 1].  Each trial is set_source_pattern + reshade + the loss of aim_loss_and_grad.  Returns (direction float64 [3], shapes float64
+    [8], record), the record as fit_decay's; leaves the fitted pattern set and the context re-shaded with it."""
+    args = (table, air, mic, speakers, loss_args, sample_rate, predelay, nbins, which, remove_direct)
+    state = (_unit(direction), np.broadcast_to(np.asarray(shapes, dtype=np.float64).reshape(-1), (8,)).copy())
+
+    def loss_and_grad(current):
+        n, shape = current
+        loss, gd, gs, _ = aim_loss_and_grad(ctx, kind, n, shape, *args)
+        tangent = gd - (gd * n).sum() * n if free_direction else np.zeros(3)
+        return loss, np.concatenate([tangent, gs if free_shapes else np.zeros(8)])
+
+    def trial_of(current, g, t):
+        n, shape = current
+        trial = (_unit(n - t * g[:3]), np.clip(shape - t * g[3:], 0.0, 1.0))
+        return trial, float((g[:3] * (n - trial[0])).sum() + (g[3:] * (shape - trial[1])).sum())
+
+    (n, shape), record = _armijo(state, steps, loss_and_grad, lambda current: aim_loss(ctx, kind, current[0], current[1], *args),
+                                 lambda g: np.abs(g).max(), trial_of)
+    aim_loss(ctx, kind, n, shape, *args)
+    return n, shape, record
+
+
+def sti_source_balloon(ctx, table, air, mic, speakers, targets, channel_weights, sample_rate, predelay, nbins, snr_db=None, which=capi.IR_ALL,
+                       remove_direct=False):
+    """(loss, sti, balloon): the loss and the indices of sti_loss_and_grad for a source with the TABLE set on the context
+    (set_source_table), and balloon float64 [360][180][8] = dL/dtable[a][e][b]: what a change of the loudspeaker's gain in every departure
+    cell and band does to the loss (targets of 1 make it "which cells carry the intelligibility of this seat").  The rays' and the images'
+    gain derivatives are added up by table row (directivity.balloon_gradient); cells that no ray or image leaves through are 0."""
+    from .directivity import balloon_gradient
+    loss, sti, _, weights = _sti_forward(ctx, table, air, mic, speakers, targets, channel_weights, sample_rate, predelay, nbins, snr_db, True, which,
+                                         remove_direct)
+    parts = source_gradient(ctx, weights, mic, speakers, sample_rate, predelay, nbins, which, want_rows=True)
+    balloon = np.zeros((360, 180, 8), dtype=np.float64)
+    for part in (parts["images"], parts["rays"]):
+        if part is not None:
+            balloon += balloon_gradient(part["grad"], part["rows"])
+    return loss, sti, balloon
